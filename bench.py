@@ -10,9 +10,15 @@ resident in HBM:
 Frames are splitmix64 of the global byte index (seed 0x5EED0001 / 0x5EED0003, uflow_amd/synth.py),
 trailers sealed on the GPU, one bit flipped in every 1000th frame.  Results are checked against
 the CPU oracle (N = 1: every frame; N > 1: the valid flags of every frame and a sample of every
-rank's CRC words on rank 0); a mismatch makes the run fail.
+rank's CRC words on rank 0) in a --full run; a mismatch makes that run fail.
 
-Launch:  python bench.py [--gpus 1 --steps 50 --warmup 10]
+A plain run does only what the headline figure needs: it makes the frames, settles, warms up, times
+--steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the line.
+--full adds everything else the line can carry, each after the timed region: the oracle check, the
+read-only streaming ceiling (roofline.ceiling_GBs), cpu_baseline, and n1_sharded_ref at N > 1
+(--no-ceiling, --no-cpu-baseline and --no-n1-ref leave single parts of it out).
+
+Launch:  python bench.py [--gpus 1 --steps 50 --warmup 10] [--full] [--dump-outputs DIR]
          python bench.py --gpus N ...   (N > 1: starts its N ranks itself with torch.distributed.run,
                                          makes no GPU call, forwards rank 0's JSON line)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
@@ -41,6 +47,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU oracle "
+                         "check of the results, the read-only streaming ceiling probe, the CPU baseline and, at "
+                         "N > 1, n1_sharded_ref (a plain run skips all of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed, as rank 0 holds it in "
+                         "global frame order: DIR/crc.npy (the CRC words, float64) and DIR/valid.npy (the valid "
+                         "flags, float32); of a batch too large for 64 MB a fixed seeded sample, its frame "
+                         "indices in DIR/sample_index.npy (float64)")
     ap.add_argument("--frames-per-gpu", type=int, default=None,
                     help="weak scaling: frames per GPU (default: N = 1 -> 1M, config 2)")
     ap.add_argument("--global-frames", type=int, default=None,
@@ -62,12 +77,16 @@ def parse():
                          "transport, each rank told it is on its own host via NCCL_HOSTID)")
     ap.add_argument("--fake-worker", action="store_true",
                     help="launcher test (CPU): each rank joins a gloo group and rank 0 prints the rank count")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip the read-only streaming ceiling probe")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-ceiling", action="store_true",
+                    help="--full: skip the read-only streaming ceiling probe")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="target wall time of each CPU baseline leg")
     ap.add_argument("--no-n1-ref", action="store_true",
-                    help="N > 1: skip n1_sharded_ref (rank 0 alone gating the whole batch on its GPU)")
-    return ap.parse_args()
+                    help="--full, N > 1: skip n1_sharded_ref (rank 0 alone gating the whole batch on its GPU)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 class _StdoutToStderr:
@@ -345,6 +364,31 @@ def read_ceiling(eng, buf, stream, groups=5, per_group=10):
     return nbytes / (ms * 1e-3) / 1e9, ms, nbytes
 
 
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs may write (64 MB less room for the headers)
+DUMP_SEED = 0x5EED0D0D
+
+
+def dump_outputs(dirpath, crc, valid):
+    """The CRC words (int32 tensor, read as uint32) and valid flags of one step as DIR/crc.npy
+    (float64: every 32-bit word is exact) and DIR/valid.npy (float32).  A batch over the budget is
+    sampled: the batch is cut into k runs of consecutive frames and one frame taken from each, its
+    place in the run drawn from a fixed seed; the frame indices go to DIR/sample_index.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    n = crc.numel()
+    idx = None
+    if n * 12 > DUMP_BUDGET:
+        k = DUMP_BUDGET // 20
+        edges = np.arange(k + 1, dtype=np.int64) * n // k  # k runs of n / k frames that cover the batch
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = edges[:-1] + rng.integers(0, np.diff(edges), dtype=np.int64)
+        sel = torch.from_numpy(idx).to(crc.device)
+        crc, valid = crc[sel], valid[sel]
+        np.save(os.path.join(dirpath, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirpath, "crc.npy"), crc.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(dirpath, "valid.npy"), valid.cpu().numpy().astype(np.float32))
+    return n if idx is None else len(idx)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -492,15 +536,22 @@ def main():
         dist.all_gather(every, mine)
         split = [[float(x) for x in t.cpu()] for t in every]
 
+    # ---- what the last timed step left in its slot, as the caller holds it (rank 0: the whole batch) ----
+    dumped = None
+    if rank == 0 and a.dump_outputs:
+        dumped = dump_outputs(a.dump_outputs, *slots[last])
+
     # ---- read-only streaming ceiling, after the timed region, on rank 0 ----
     ceiling = None
-    if rank == 0 and not a.no_ceiling:
+    if rank == 0 and a.full and not a.no_ceiling:
         ceiling = read_ceiling(eng, frames[: min(n, 1 << 22) * L], compute)
 
-    # ---- correctness (after the timed region) ----
+    # ---- correctness (after the timed region; --full) ----
     crc, valid = slots[last]
     ok, parity = True, ""
-    if not sharded:
+    if not a.full:
+        parity = "not checked"
+    elif not sharded:
         import oracle
         h_valid = valid.cpu().numpy()
         ok = bool(np.array_equal(h_valid, expected_valid(0, total, a.flip_every)))
@@ -549,7 +600,7 @@ def main():
     # on an RCCL barrier: with --one-device the RCCL barrier's kernels would share rank 0's GPU while it
     # times the reference (2545 GiB/s there against 5940 alone).
     n1_ref = None
-    if sharded and world > 1 and not a.no_n1_ref:
+    if a.full and sharded and world > 1 and not a.no_n1_ref:
         torch.cuda.synchronize(dev)
         dist.barrier(group=host_group)  # every rank idle on the GPU before rank 0 starts timing
         if rank == 0:
@@ -582,7 +633,10 @@ def main():
             "vs_baseline": None,
             "dtype": "u8",
             "data": f"synthetic: splitmix64 of the global byte index (seed {seed:#x}), BE CRC trailers sealed on "
-                    f"the GPU, 1 bit flipped in every {a.flip_every}th frame; {parity}; valid flags as planted: {ok}",
+                    f"the GPU, 1 bit flipped in every {a.flip_every}th frame; "
+                    + (f"{parity}; valid flags as planted: {ok}" if a.full else
+                       "results not checked in this run (--full checks them against the CPU oracle and the "
+                       "planted flips)"),
             "config": {
                 "workload": cfg_name,
                 "frames_per_gpu": n, "frame_len": L, "global_frames": total,
@@ -615,6 +669,8 @@ def main():
                                            "host_call_ms: host time per step inside ufc_crc_sharded, which "
                                            "blocks until every peer has joined the call's status agreement "
                                            "(the gates and transfers themselves are enqueued asynchronously)")
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": a.dump_outputs, "frames": dumped, "of": total}
         if n1_ref is not None:
             result["n1_sharded_ref"] = n1_ref
         if ceiling is not None:
@@ -624,7 +680,7 @@ def main():
                 "ceiling_source": f"ufc_hbm_read_probe (hbm_probe.hip): a plain read-only stream of {probe_bytes} B "
                                   f"of the same frame buffer, 16 B per lane, 4 KiB per wave in flight, 8 waves per "
                                   f"CU; HIP events around 5 groups of 10 launches, {probe_ms:.4f} ms per launch"})
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             if sharded:  # rank 0's own frames: a bounded sample of the same workload
                 host = frames[: min(n, 1_000_000) * L].cpu().numpy()
             result["cpu_baseline"] = cpu_baseline(host, min(n, 1_000_000), L, a.cpu_seconds)

@@ -21,11 +21,11 @@ step() {  # step <name> <seconds> <cmd...>
   echo "$name ok"
 }
 step bench_ktrace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_ktrace -o run -- \
-    python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 step bench_fetch 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/bench_fetch -o run -- \
-    python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline
+    python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 step bench_write 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/bench_write -o run -- \
-    python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline
+    python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 step cfg_ktrace 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_ktrace -o run -- \
     python3 $R/tools/bench_configs.py --only $ONLY --reps 10
 step cfg_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/cfg_fetch -o run -- \
@@ -34,6 +34,6 @@ step cfg_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/cfg_wr
     python3 $R/tools/bench_configs.py --only $ONLY --reps 3
 step configs 600 python3 $R/tools/bench_configs.py --reps 20
 cat $OUT/configs.log
-timeout -k 10 300 python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 echo done

@@ -23,7 +23,7 @@ step() {  # step <name> <seconds> <cmd...>
 }
 for w in $WL; do
   if [ $w = bench ]; then
-    run=(python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline)
+    run=(python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline)
     pmc=(python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --settle-ms 50 --no-ceiling)
   else
     run=(python3 $R/tools/bench_configs.py --only $w --reps 20)
