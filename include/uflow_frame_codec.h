@@ -14,6 +14,11 @@
  *   ufc_parse_batch_host       <- the receive loops' Frame::read of every datagram (src/server/mod.rs:
  *                                 591-602, src/client/mod.rs:615-623), after the batched CRC gate
  *   ufc_parse_batch_varlen     <- the same parse on the GPU, device-resident frames
+ *   ufc_build_sizes_host, ufc_build_batch_host, ufc_build_sizes_varlen, ufc_build_batch_varlen
+ *                              <- the emitters' Frame::write of every data and ack frame they send
+ *                                 (src/half_connection/emit.rs:47-125, 170-211 over build.rs:55-162,
+ *                                 192-247) and write_* (serial/mod.rs:437-657), batched from the parse's
+ *                                 records, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -162,6 +167,61 @@ int ufc_parse_batch_host(const uint8_t* bytes, const uint64_t* offsets, size_t n
 int ufc_parse_batch_varlen(ufc_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, size_t n,
                            const uint8_t* d_valid, ufc_frame_info* d_infos, ufc_item* d_items, size_t items_cap,
                            uint64_t* d_items_used, void* stream);
+
+/* ---- batched builds: Frame::write of every frame of a batch, from the parse's records ----
+ * The inverse of the batched parses.  Input is their output format:
+ *   infos[n]        kind, ok, aux, f[], item_count and item_first are used; crc_ok is ignored.
+ *   items[n_items]  datagram: id, channel_id, window_parent_lead, channel_parent_lead, fragment_id,
+ *                   fragment_id_last, data_len, and data_offset = the payload's offset relative to the
+ *                   frame's source base; ack group: id = base_id, data_offset = bitfield, channel_id != 0 =
+ *                   nonce.  form and flags are ignored: the header form is chosen as DataFrameBuilder::add
+ *                   does (build.rs:81-122), so a datagram with fragment_id_last == 0 takes the micro or
+ *                   small form when its sizes allow and its fragment_id is then not encoded.
+ *   src_base[n]     (nullable: all zero) the byte offset in `payload` that frame i's data_offsets are
+ *                   relative to.  Passing a parsed batch's own offsets and bytes as src_base and payload
+ *                   re-emits that batch with no copy in between.
+ * Output is a CSR batch: frame i = out_bytes[out_offsets[i] .. out_offsets[i+1]), byte for byte what
+ * Frame::write gives (handshake_syn zero-padded to UFC_MAX_FRAME_SIZE).  MAX_FRAME_SIZE is NOT enforced:
+ * the reference enforces it in the emitter (emit.rs:69), not in the builder, and so does the caller here.
+ *
+ * Per-frame status: */
+#define UFC_BUILD_OK 0
+#define UFC_BUILD_SKIPPED 1   /* infos[i].ok == 0: nothing to write */
+#define UFC_BUILD_BAD_FIELD 2 /* what build.rs:74-77, 146 debug-assert, and records that describe no frame: an
+                                 unknown kind; item_first + item_count > n_items; data: item_count > 127, aux > 1,
+                                 channel_id >= 64, id >= 2^20, data_len > 65535; ack: item_count > 65535; sync:
+                                 aux > 3; handshake_error: aux > 2 */
+#define UFC_BUILD_BAD_SRC 3   /* a payload range leaves [0, payload_len) */
+/* Sizes: out_offsets[n + 1] (CSR: [0] = 0, [n] = total bytes) and status[n] (nullable).  Frames whose
+ * status is not UFC_BUILD_OK get length 0. */
+int ufc_build_sizes_host(const ufc_frame_info* infos, const ufc_item* items, size_t n_items, const uint64_t* src_base,
+                         size_t payload_len, size_t n, uint64_t* out_offsets, uint8_t* status, int nthreads);
+/* Write: frame i into out_bytes[out_offsets[i] .. out_offsets[i+1]), with the BE32 CRC as trailer if
+ * seal != 0, else 4 zero bytes (for a later batched seal).  The call stands alone (it needs nothing a
+ * sizes call left behind) and trusts out_offsets as the other CSR entry points trust theirs: frame i is
+ * written only when its span's length equals the frame's size and the span lies inside
+ * [out_offsets[0], out_offsets[n]) and ends at or before out_len; otherwise its span is left untouched (a
+ * length-0 span is the way to skip a frame).  Nothing outside [out_offsets[0], out_offsets[n]) is written.
+ * crc_out[n] (nullable, seal != 0 only): the CRC words of the frames written. */
+int ufc_build_batch_host(const ufc_frame_info* infos, const ufc_item* items, size_t n_items, const uint64_t* src_base,
+                         const uint8_t* payload, size_t payload_len, size_t n, const uint64_t* out_offsets,
+                         uint8_t* out_bytes, size_t out_len, int seal, uint32_t* crc_out, int nthreads);
+/* The same two on the GPU (gfx950 kernels, frame_build.hip): every pointer device memory, any alignment
+ * of d_out_bytes and d_payload, asynchronous on `stream`, nothing allocated per call (scan temporaries and
+ * the per-item destination offsets live in the context's per-stream scratch), n and n_items < 2^31 - 1,
+ * n == 0 returns UFC_OK whatever the pointers.  With seal != 0 the write is followed, on the same stream, by
+ * the variable-length seal of ufc_seal_batch_varlen over (d_out_bytes, d_out_offsets), which treats every
+ * span of 4 bytes or more as a frame: give a frame that is to be skipped a length-0 span.  These replace the
+ * per-frame assembly of the reference's emitters, src/half_connection/emit.rs:47-125, 170-211 over
+ * src/frame/serial/build.rs:55-162, 192-247; packing datagrams into frames (emit.rs:47-112) stays with
+ * the caller. */
+int ufc_build_sizes_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items,
+                           const uint64_t* d_src_base, size_t payload_len, size_t n, uint64_t* d_out_offsets,
+                           uint8_t* d_status, void* stream);
+int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items,
+                           const uint64_t* d_src_base, const uint8_t* d_payload, size_t payload_len, size_t n,
+                           const uint64_t* d_out_offsets, uint8_t* d_out_bytes, size_t out_len, int seal,
+                           uint32_t* d_crc_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -11,6 +11,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
   parse    Frame::read past the gate on the device (ufc_parse_batch_varlen): 1M real uflow frames from
            the reference's test generators (38 % longer than MAX_FRAME_SIZE).
   parse_mtu  the same with frames <= MAX_FRAME_SIZE only (what a uflow receiver gets).
+  build    Frame::write on the device (ufc_build_sizes_varlen / ufc_build_batch_varlen): the parse_mtu batch
+           gated and parsed, then built again from its records with the batch itself as payload source;
+           the sizes call, the write call (seal = 0) and the seal that follows timed separately, and a
+           device-to-device copy of the same output bytes as the floor.  Run with --only build.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -313,6 +317,55 @@ def parse(eng, dev, reps, n=1_000_000, mtu=False):
 
 def parse_mtu(eng, dev, reps):
     return parse(eng, dev, reps, mtu=True)
+
+
+def build(eng, dev, reps, n=1_000_000):
+    """The send-side mirror of parse_mtu: gate and parse the parse_mtu batch (1M frames <= MAX_FRAME_SIZE),
+    then build it again from the records, datagram payloads gathered from the parsed batch's own bytes.
+    Timed separately (events around groups of launches, after a settle): ufc_build_sizes_varlen,
+    ufc_build_batch_varlen with seal = 0 (item sizes + scan + frame check + the write kernel),
+    ufc_seal_batch_varlen over the built batch, and a device-to-device hipMemcpyAsync of the same byte
+    count (the floor: it reads and writes each output byte once)."""
+    import ctypes
+    from uflow_amd import _native as N
+    data, offsets, lens = parse_batch(n, True)
+    d = torch.from_numpy(data).to(dev)
+    o = torch.from_numpy(offsets).to(dev)
+    _, valid = eng.crc_varlen(d, o)
+    infos, items, used = eng.parse_varlen(d, o, valid)
+    torch.cuda.synchronize()
+    k = int(used.cpu()[0])
+    out, off, status = eng.build_varlen(infos, items, d, src_base=o, n_items=k)
+    torch.cuda.synchronize()
+    total = int(off[-1])
+    extra = {"all_ok": bool((status == 0).all())}
+    if CHECK:  # every frame of this batch is canonical (written by the oracle): the build re-emits it
+        extra["equals_source_batch"] = bool(total == d.numel() and torch.equal(out, d) and torch.equal(off, o))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    off2 = torch.empty_like(off)
+    status2 = torch.empty_like(status)
+    f_sizes = lambda: lib.ufc_build_sizes_varlen(ctx, p(infos), p(items), k, p(o), d.numel(), n, p(off2), p(status2), st)  # noqa: E731
+    f_write = lambda: lib.ufc_build_batch_varlen(ctx, p(infos), p(items), k, p(o), p(d), d.numel(), n, p(off), p(out),  # noqa: E731
+                                                 total, 0, None, st)
+    f_seal = lambda: eng.seal_varlen(out, off)  # noqa: E731
+    dst = torch.empty_like(out)
+    f_copy = lambda: dst.copy_(out)  # noqa: E731
+    res = {}
+    for name, fn in (("sizes", f_sizes), ("write", f_write), ("seal", f_seal), ("copy", f_copy)):
+        settle(fn, 500)
+        res[name] = timed(fn, reps)
+    payload_bytes = int(items[:k, 20:24].contiguous().view(torch.int32).sum())  # (every item here is a datagram or an ack group: data_len)
+    algo = payload_bytes + total + 24 * k + 32 * n + 8 * (n + 1) + 8 * n
+    w = res["write"][0]
+    return {"config": "f4: device build of 1M uflow frames <= MAX_FRAME_SIZE from their parsed records",
+            "frames": n, "items": k, "out_bytes": total, "payload_bytes": payload_bytes,
+            "sizes_ms": round(res["sizes"][0], 4), "write_ms": round(w, 4), "write_mean_ms": round(res["write"][1], 4),
+            "seal_ms": round(res["seal"][0], 4), "d2d_copy_ms": round(res["copy"][0], 4),
+            "write_over_copy": round(w / res["copy"][0], 3), "algorithmic_bytes": algo,
+            "write_algo_GB_s": round(algo / w / 1e-3 / 1e9, 1), "frac_of_8TBs": round(algo / (w * 1e-3) / 8e12, 4),
+            "frames_per_s": round(n / w * 1e3), **extra}
 
 
 def host(eng, reps=5, n=1_000_000, L=1472):

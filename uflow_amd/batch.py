@@ -187,6 +187,54 @@ class FrameCrcEngine:
               "ufc_parse_batch_varlen")
         return infos, items, used
 
+    # ---- Frame::write of a batch, on the device (uflow_frame_codec.h) ----
+    def build_sizes_varlen(self, infos, items, payload_len, src_base=None, n_items=None, stream=None):
+        """ufc_build_sizes_varlen: (out_offsets int64[n + 1], status uint8[n]) of the frames the records
+        describe (infos uint8[n, 32], items uint8[*, 24]: what parse_varlen returns)."""
+        n = infos.shape[0]
+        n_items = items.shape[0] if n_items is None else int(n_items)
+        self._check("infos", infos, (torch.uint8,), 32 * n)
+        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._check("src_base", src_base, (torch.int64,), n)
+        # (no fill kernel on torch's current stream: the call writes all n + 1 offsets on `stream`)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device) if n else \
+            torch.zeros(1, dtype=torch.int64, device=self.device)
+        status = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib().ufc_build_sizes_varlen(self._ctx, _ptr(infos), _ptr(items) if n_items else None, n_items,
+                                           _ptr(src_base), int(payload_len), n, _ptr(offsets), _ptr(status),
+                                           self._stream(stream)), "ufc_build_sizes_varlen")
+        return offsets, status
+
+    def build_varlen(self, infos, items, payload, src_base=None, seal=True, out=None, stream=None, n_items=None,
+                     crc_out=None):
+        """Batched Frame::write: the frames that `infos` / `items` describe (the tensors parse_varlen
+        returns; n_items = how many item rows are in use, default all) as a CSR batch, datagram payloads
+        gathered from `payload` (uint8) at src_base[i] + data_offset (src_base int64[n], default zeros;
+        a parsed batch's own offsets and bytes re-emit it).  Returns (out_bytes, out_offsets int64[n + 1],
+        status uint8[n]); frames whose status is not UFC_BUILD_OK have length 0.  seal: write the CRC
+        trailers (else 4 zero bytes each); crc_out (int32[n]) receives the CRC words then.  `out`: a
+        uint8 tensor to write into (at least out_offsets[n] bytes), else one is allocated.  Reads
+        out_offsets[n] on the host between the sizes and the write call (one synchronisation)."""
+        n = infos.shape[0]
+        n_items = items.shape[0] if n_items is None else int(n_items)
+        self._check("payload", payload, (torch.uint8,), 0)
+        self._check_outputs(n, crc_out)
+        offsets, status = self.build_sizes_varlen(infos, items, payload.numel(), src_base, n_items, stream)
+        if n == 0:
+            return (out if out is not None else torch.empty(0, dtype=torch.uint8, device=self.device)), offsets, status
+        if stream is not None:
+            stream.synchronize()
+        total = int(offsets[n].item())
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=self.device)
+        self._check("out", out, (torch.uint8,), total)
+        check(lib().ufc_build_batch_varlen(self._ctx, _ptr(infos), _ptr(items) if n_items else None, n_items,
+                                           _ptr(src_base), _ptr(payload) if payload.numel() else None, payload.numel(),
+                                           n, _ptr(offsets), _ptr(out) if out.numel() else None, out.numel(),
+                                           1 if seal else 0, _ptr(crc_out), self._stream(stream)),
+              "ufc_build_batch_varlen")
+        return out, offsets, status
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

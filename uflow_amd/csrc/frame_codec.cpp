@@ -40,6 +40,20 @@ inline void trailer(uint8_t* f, size_t body, int seal) {
 
 constexpr uint32_t kPacketIdMask = (1u << 20) - 1;  // src/packet_id.rs
 
+// ---- batched host build (the encode of frame_codec_core.hpp, shared with frame_build.hip) ----
+template <class F>
+void for_ranges(size_t n, int nthreads, const F& body) {  // body(a, b) over contiguous frame ranges
+  int T = nthreads > 0 ? nthreads : 1;
+  T = (int)std::min<size_t>((size_t)T, (n + 1023) / 1024);
+  if (T < 1) T = 1;
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; t++) th.emplace_back([&, t] { body(n * t / T, n * (t + 1) / T); });
+  body(0, n / T);
+  for (auto& x : th) x.join();
+}
+inline void put_packed(uint8_t* out, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t nbytes) {
+  for (uint32_t j = 0; j < nbytes; j++) out[j] = (uint8_t)ufc_codec::packed_byte(w0, w1, w2, j);
+}
 }  // namespace
 
 extern "C" {
@@ -288,6 +302,71 @@ int ufc_parse_batch_host(const uint8_t* bytes, const uint64_t* offsets, size_t n
   pass2(0);
   for (auto& x : th) x.join();
   return (items && !fill) ? UFC_ERR_NOMEM : UFC_OK;
+}
+
+// ---- batched host build ----
+int ufc_build_sizes_host(const ufc_frame_info* infos, const ufc_item* items, size_t n_items, const uint64_t* src_base,
+                         size_t payload_len, size_t n, uint64_t* out_offsets, uint8_t* status, int nthreads) {
+  if (n == 0) return UFC_OK;
+  if (!infos || !out_offsets || (!items && n_items) || n >= ((size_t)1 << 31) || n_items >= ((size_t)1 << 31))
+    return UFC_ERR_INVALID_ARG;
+  for_ranges(n, nthreads, [&](size_t a, size_t b) {
+    for (size_t i = a; i < b; i++) {
+      uint64_t size;
+      const uint8_t st = ufc_codec::check_frame(infos[i], items, n_items, src_base ? src_base[i] : 0, payload_len, size);
+      out_offsets[i + 1] = size;  // lengths first, summed below
+      if (status) status[i] = st;
+    }
+  });
+  out_offsets[0] = 0;
+  for (size_t i = 0; i < n; i++) out_offsets[i + 1] += out_offsets[i];
+  return UFC_OK;
+}
+
+int ufc_build_batch_host(const ufc_frame_info* infos, const ufc_item* items, size_t n_items, const uint64_t* src_base,
+                         const uint8_t* payload, size_t payload_len, size_t n, const uint64_t* out_offsets,
+                         uint8_t* out_bytes, size_t out_len, int seal, uint32_t* crc_out, int nthreads) {
+  if (n == 0) return UFC_OK;
+  if (!infos || !out_offsets || (!items && n_items) || (!payload && payload_len) || (!out_bytes && out_len) ||
+      n >= ((size_t)1 << 31) || n_items >= ((size_t)1 << 31))
+    return UFC_ERR_INVALID_ARG;
+  const uint64_t first = out_offsets[0], last = out_offsets[n];
+  for_ranges(n, nthreads, [&](size_t a, size_t b) {
+    for (size_t i = a; i < b; i++) {
+      const ufc_frame_info& info = infos[i];
+      const uint64_t base = src_base ? src_base[i] : 0;
+      uint64_t size;
+      const uint8_t st = ufc_codec::check_frame(info, items, n_items, base, payload_len, size);
+      if (!ufc_codec::span_matches(st, size, out_offsets[i], out_offsets[i + 1], first, last, out_len)) continue;
+      uint8_t* f = out_bytes + out_offsets[i];
+      uint64_t w0, w1, w2;
+      const uint32_t head = ufc_codec::encode_frame_head(info, w0, w1, w2);
+      put_packed(f, w0, w1, w2, head);
+      size_t pos = head;
+      if (info.kind == UFC_FRAME_DATA) {
+        for (uint32_t k = 0; k < info.item_count; k++) {
+          const ufc_item& d = items[(size_t)info.item_first + k];
+          const uint32_t hs = ufc_codec::datagram_header_size(d);
+          ufc_codec::encode_datagram_header(d, hs, w0, w1);
+          put_packed(f + pos, w0, w1, 0, hs);
+          if (d.data_len) std::memcpy(f + pos + hs, payload + base + d.data_offset, d.data_len);
+          pos += hs + d.data_len;
+        }
+      } else if (info.kind == UFC_FRAME_ACK) {
+        for (uint32_t k = 0; k < info.item_count; k++) {
+          ufc_codec::encode_ack_group(items[(size_t)info.item_first + k], w0, w1);
+          put_packed(f + pos, w0, w1, 0, UFC_ACK_GROUP_SIZE);
+          pos += UFC_ACK_GROUP_SIZE;
+        }
+      } else if (pos < size - 4) {  // handshake_syn's zero padding (:463)
+        std::memset(f + pos, 0, (size_t)size - 4 - pos);
+        pos = (size_t)size - 4;
+      }
+      trailer(f, pos, seal);
+      if (seal && crc_out) crc_out[i] = ufc::host_extend(0u, f, pos);
+    }
+  });
+  return UFC_OK;
 }
 
 }  // extern "C"

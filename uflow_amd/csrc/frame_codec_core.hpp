@@ -236,4 +236,177 @@ UFC_HD bool read_frame(const Rd& rd, uint32_t len, bool crc_ok, ufc_frame_info& 
   return read_frame_to(rd, len, crc_ok, info, PtrSink{items}, cap);
 }
 
+// ---- encode: Frame::write from the parse's records, for the batched builds (host and GPU) ----
+//
+// Restates write_* (serial/mod.rs:437-657), DataFrameBuilder::{new, add, encoded_size} (build.rs:55-143,
+// 172-183) and AckFrameBuilder::{new, add} (build.rs:192-228).  A header is produced as packed
+// little-endian words (byte j of the header = bits 8 (j & 7) of word j >> 3), so that a writer that owns
+// an arbitrary byte range of the output (the GPU's 16-byte pieces) takes any byte of it without a buffer.
+constexpr uint32_t kPacketIdMask = (1u << 20) - 1;  // src/packet_id.rs
+constexpr uint32_t kDataHead = 1 + kDataPayloadHeader;  // frame id + sequence id + nonce | count
+constexpr uint32_t kAckHead = 1 + kAckPayloadHeader;    // frame id + two base ids + count
+
+// Byte j (j < 24) of three packed words; every shift amount in range.
+UFC_HD uint32_t packed_byte(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t j) {
+  const uint32_t q = (j >> 3) & 3u;
+  const uint64_t w = q == 0 ? w0 : (q == 1 ? w1 : w2);
+  return (uint32_t)(w >> (8 * (j & 7u))) & 0xFFu;
+}
+UFC_HD uint64_t pk(uint32_t j, uint32_t v) { return (uint64_t)(v & 0xFFu) << (8 * (j & 7u)); }
+UFC_HD uint64_t pk_be32(uint32_t j, uint32_t v) {  // four bytes inside one word (j & 7 <= 4)
+  return pk(j, v >> 24) | pk(j + 1, v >> 16) | pk(j + 2, v >> 8) | pk(j + 3, v);
+}
+UFC_HD uint64_t pk_be16(uint32_t j, uint32_t v) { return pk(j, v >> 8) | pk(j + 1, v); }
+
+// The header form DataFrameBuilder::add chooses (build.rs:81-122): 6 micro, 9 small, 14 large.
+// ufc_item.form and .flags play no part.
+UFC_HD uint32_t datagram_header_size(const ufc_item& d) {
+  if (d.fragment_id_last == 0) {
+    if (d.data_len < 64 && d.window_parent_lead < 128 && d.channel_parent_lead < 256) return 6;
+    if (d.data_len < 256) return 9;
+  }
+  return 14;
+}
+// DataFrameBuilder::encoded_size (build.rs:172-183).
+UFC_HD uint64_t datagram_encoded_size(const ufc_item& d) { return (uint64_t)datagram_header_size(d) + d.data_len; }
+// What build.rs:74-77 debug-asserts of a datagram.
+UFC_HD bool datagram_fields_ok(const ufc_item& d) {
+  return d.channel_id < UFC_MAX_CHANNELS && d.id <= kPacketIdMask && d.data_len <= 0xFFFFu;
+}
+
+// The datagram header of hs = datagram_header_size(d) bytes (build.rs:84-143).
+UFC_HD void encode_datagram_header(const ufc_item& d, uint32_t hs, uint64_t& w0, uint64_t& w1) {
+  const uint32_t dl = d.data_len, ch = d.channel_id, seq = d.id;
+  const uint32_t w = d.window_parent_lead, h = d.channel_parent_lead;
+  if (hs == 6) {  // micro, :84-100
+    w0 = pk(0, dl | ((ch & 0x10) << 2)) | pk(1, ((seq >> 12) & 0xF0) | (ch & 0x0F)) | pk(2, seq >> 8) | pk(3, seq) |
+         pk(4, w | ((ch & 0x20) << 2)) | pk(5, h);
+    w1 = 0;
+  } else if (hs == 9) {  // small, :101-119
+    w0 = pk(0, ch | 0x80) | pk(1, dl) | pk(2, seq >> 16) | pk(3, seq >> 8) | pk(4, seq) | pk_be16(5, w) | pk(7, h >> 8);
+    w1 = pk(8, h);
+  } else {  // large, :123-143
+    w0 = pk(0, ch | 0xC0) | pk_be16(1, dl) | pk(3, seq >> 16) | pk(4, seq >> 8) | pk(5, seq) | pk_be16(6, w);
+    w1 = pk_be16(8, h) | pk_be16(10, d.fragment_id) | pk_be16(12, d.fragment_id_last);
+  }
+}
+
+// An ack group's UFC_ACK_GROUP_SIZE bytes (build.rs:213-228): id = base_id, data_offset = bitfield,
+// channel_id != 0 = nonce.
+UFC_HD void encode_ack_group(const ufc_item& g, uint64_t& w0, uint64_t& w1) {
+  w0 = pk_be32(0, g.id) | pk_be32(4, g.data_offset);
+  w1 = pk(8, g.channel_id != 0 ? 1u : 0u);
+}
+
+// How many bytes encode_frame_head gives for a frame of this kind.
+UFC_HD uint32_t frame_head_size(uint32_t kind) {
+  switch (kind) {
+    case UFC_FRAME_HANDSHAKE_SYN: return 18;
+    case UFC_FRAME_HANDSHAKE_SYN_ACK: return 21;
+    case UFC_FRAME_HANDSHAKE_ACK: return 5;
+    case UFC_FRAME_HANDSHAKE_ERROR: return 6;
+    case UFC_FRAME_DATA: return kDataHead;
+    case UFC_FRAME_SYNC: return 10;
+    case UFC_FRAME_ACK: return kAckHead;
+    default: return 1;
+  }
+}
+
+// The bytes a frame starts with: the whole body of a fixed-size frame (handshake_syn: the 18 bytes
+// before its zero padding), the data frame's 6 and the ack frame's 11.  Returns their count.
+UFC_HD uint32_t encode_frame_head(const ufc_frame_info& info, uint64_t& w0, uint64_t& w1, uint64_t& w2) {
+  const uint32_t* f = info.f;
+  w0 = pk(0, info.kind);
+  w1 = w2 = 0;
+  switch (info.kind) {
+    case UFC_FRAME_HANDSHAKE_SYN:  // :437-473
+      w0 |= pk(1, info.aux) | pk_be32(2, f[0]) | pk_be16(6, f[1] >> 16);
+      w1 = pk_be16(8, f[1]) | pk_be32(10, f[2]) | pk_be16(14, f[3] >> 16);
+      w2 = pk_be16(16, f[3]);
+      return 18;
+    case UFC_FRAME_HANDSHAKE_SYN_ACK:  // :475-514
+      w0 |= pk_be32(1, f[0]) | pk(5, f[1] >> 24) | pk(6, f[1] >> 16) | pk(7, f[1] >> 8);
+      w1 = pk(8, f[1]) | pk_be32(9, f[2]) | pk(13, f[3] >> 24) | pk(14, f[3] >> 16) | pk(15, f[3] >> 8);
+      w2 = pk(16, f[3]) | pk_be32(17, f[4]);
+      return 21;
+    case UFC_FRAME_HANDSHAKE_ACK:  // :516-539
+      w0 |= pk_be32(1, f[0]);
+      return 5;
+    case UFC_FRAME_HANDSHAKE_ERROR:  // :541-569
+      w0 |= pk_be32(1, f[0]) | pk(5, info.aux);
+      return 6;
+    case UFC_FRAME_DATA:  // DataFrameBuilder::new and the count patched by build, build.rs:56-66, 148-149
+      w0 |= pk_be32(1, f[0]) | pk(5, ((info.aux & 1u) << 7) | (info.item_count & 0x7Fu));
+      return kDataHead;
+    case UFC_FRAME_SYNC: {  // :623-657
+      const uint32_t mode = info.aux & 3u;
+      const uint32_t a = (mode & 1u) ? f[0] : 0u, b = (mode & 2u) ? f[1] : 0u;
+      w0 |= pk(1, mode) | pk_be32(2, a) | pk_be16(6, b >> 16);
+      w1 = pk_be16(8, b);
+      return 10;
+    }
+    case UFC_FRAME_ACK:  // AckFrameBuilder::new and the count patched by build, build.rs:192-205, 231-234
+      w0 |= pk_be32(1, f[0]) | pk(5, f[1] >> 24) | pk(6, f[1] >> 16) | pk(7, f[1] >> 8);
+      w1 = pk(8, f[1]) | pk_be16(9, info.item_count);
+      return kAckHead;
+    default:  // disconnect, disconnect_ack (:571-611)
+      return 1;
+  }
+}
+
+// Status and encoded size (trailer included) of the frame `info` describes; `items` is the batch's item
+// array of n_items records, src_base the offset in the payload buffer (payload_len bytes) that the
+// frame's data_offsets are relative to.  size is 0 unless the status is UFC_BUILD_OK.
+UFC_HD uint8_t check_frame(const ufc_frame_info& info, const ufc_item* items, uint64_t n_items, uint64_t src_base,
+                           uint64_t payload_len, uint64_t& size) {
+  size = 0;
+  if (!info.ok) return UFC_BUILD_SKIPPED;
+  switch (info.kind) {
+    case UFC_FRAME_HANDSHAKE_SYN: size = kMaxFrameSize; return UFC_BUILD_OK;
+    case UFC_FRAME_HANDSHAKE_SYN_ACK: size = 25; return UFC_BUILD_OK;
+    case UFC_FRAME_HANDSHAKE_ACK: size = 9; return UFC_BUILD_OK;
+    case UFC_FRAME_HANDSHAKE_ERROR:  // HandshakeErrorType has three values (:551-555)
+      if (info.aux > 2) return UFC_BUILD_BAD_FIELD;
+      size = 10;
+      return UFC_BUILD_OK;
+    case UFC_FRAME_DISCONNECT:
+    case UFC_FRAME_DISCONNECT_ACK: size = 5; return UFC_BUILD_OK;
+    case UFC_FRAME_SYNC:
+      if (info.aux > 3) return UFC_BUILD_BAD_FIELD;
+      size = 14;
+      return UFC_BUILD_OK;
+    case UFC_FRAME_ACK:
+      if (info.item_count > 0xFFFFu || (uint64_t)info.item_first + info.item_count > n_items) return UFC_BUILD_BAD_FIELD;
+      size = kAckHead + (uint64_t)UFC_ACK_GROUP_SIZE * info.item_count + 4;
+      return UFC_BUILD_OK;
+    case UFC_FRAME_DATA: {
+      if (info.item_count > UFC_DATA_FRAME_MAX_DATAGRAM_COUNT || info.aux > 1 ||
+          (uint64_t)info.item_first + info.item_count > n_items)
+        return UFC_BUILD_BAD_FIELD;
+      bool bad_field = false, bad_src = false;
+      uint64_t s = kDataHead + 4;
+      for (uint32_t k = 0; k < info.item_count; k++) {
+        const ufc_item d = items[(uint64_t)info.item_first + k];
+        bad_field = bad_field || !datagram_fields_ok(d);
+        // the payload range [src_base + data_offset, + data_len) inside [0, payload_len)
+        bad_src = bad_src || src_base > payload_len || (uint64_t)d.data_offset + d.data_len > payload_len - src_base;
+        s += datagram_encoded_size(d);
+      }
+      if (bad_field) return UFC_BUILD_BAD_FIELD;
+      if (bad_src) return UFC_BUILD_BAD_SRC;
+      size = s;
+      return UFC_BUILD_OK;
+    }
+    default:
+      return UFC_BUILD_BAD_FIELD;  // unknown kind
+  }
+}
+
+// Whether the build writes frame i: its status is OK, its span has the frame's size and lies inside
+// both the batch's range [first, last) and the output buffer.
+UFC_HD bool span_matches(uint8_t status, uint64_t size, uint64_t a, uint64_t b, uint64_t first, uint64_t last,
+                         uint64_t out_len) {
+  return status == UFC_BUILD_OK && b >= a && b - a == size && a >= first && b <= last && b <= out_len;
+}
+
 }  // namespace ufc_codec

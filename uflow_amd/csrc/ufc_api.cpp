@@ -16,6 +16,7 @@
 #include "../../include/uflow_frame_codec.h"
 #include "../../include/uflow_frame_crc.h"
 #include "crc_math.hpp"
+#include "frame_build.hpp"
 #include "frame_crc_kernels.hpp"
 #include "frame_parse.hpp"
 #include "ufc_internal.hpp"
@@ -64,7 +65,14 @@ constexpr uint32_t kCtrSlots = 64;
 
 namespace {
 
-enum ScratchKind { kScratchParse = 0, kScratchAsyncSlots = 2, kScratchSealCrc = 3, kScratchDeferList = 4, kScratchDeferCounts = 5 };
+enum ScratchKind {
+  kScratchParse = 0,
+  kScratchAsyncSlots = 2,
+  kScratchSealCrc = 3,
+  kScratchDeferList = 4,
+  kScratchDeferCounts = 5,
+  kScratchBuild = 6
+};
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
 // queued on that stream (the only user of the old buffer) before freeing it.  *fresh (if given): the
@@ -876,6 +884,62 @@ int ufc_parse_batch_varlen(ufc_ctx* ctx, const uint8_t* d_bytes, const uint64_t*
                        d_items_used};
   if ((e = ufc_dev::parse_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
+}
+
+// ---- batched build (frame_build.hip) ----
+namespace {
+// Arguments both build calls check; n and n_items + 1 are scanned with 32-bit counts.
+bool build_args_ok(const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items, size_t n,
+                   const uint64_t* d_out_offsets) {
+  return d_infos && d_out_offsets && (d_items || n_items == 0) && n < ((size_t)1 << 31) - 1 &&
+         n_items < ((size_t)1 << 31) - 1;
+}
+}  // namespace
+
+int ufc_build_sizes_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items,
+                           const uint64_t* d_src_base, size_t payload_len, size_t n, uint64_t* d_out_offsets,
+                           uint8_t* d_status, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  if (!build_args_ok(d_infos, d_items, n_items, n, d_out_offsets)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::build_scratch_bytes(n, n_items, 0);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchBuild, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
+  ufc_dev::BuildArgs a{d_infos, d_items, (uint64_t)n_items, d_src_base, nullptr, (uint64_t)payload_len, (uint64_t)n,
+                       d_out_offsets, d_status, nullptr, 0};
+  if ((e = ufc_dev::build_sizes(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items,
+                           const uint64_t* d_src_base, const uint8_t* d_payload, size_t payload_len, size_t n,
+                           const uint64_t* d_out_offsets, uint8_t* d_out_bytes, size_t out_len, int seal,
+                           uint32_t* d_crc_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  if (!build_args_ok(d_infos, d_items, n_items, n, d_out_offsets) || (!d_payload && payload_len) ||
+      (!d_out_bytes && out_len))
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::build_scratch_bytes(n, n_items, out_len);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchBuild, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
+  ufc_dev::BuildArgs a{d_infos, d_items, (uint64_t)n_items, d_src_base, d_payload, (uint64_t)payload_len, (uint64_t)n,
+                       const_cast<uint64_t*>(d_out_offsets), nullptr, d_out_bytes, (uint64_t)out_len};
+  if ((e = ufc_dev::build_write(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if (!seal || !d_out_bytes) return UFC_OK;
+  // The trailers: the variable-length seal over the batch just written, next on the stream (spans shorter
+  // than 4 bytes, the skipped frames' length-0 ones among them, get none: frame_crc_varlen8.hip).
+  ufc_dev::KernelParams kp{};
+  kp.bytes = d_out_bytes;
+  kp.wbytes = d_out_bytes;
+  kp.offsets = d_out_offsets;
+  kp.nframes = n;
+  kp.crc_out = d_crc_out;
+  return launch_varlen_any(ctx, true, false, kp, (hipStream_t)stream);
 }
 
 }  // extern "C"

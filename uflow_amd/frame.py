@@ -304,3 +304,33 @@ def parse_batch_host(data: np.ndarray, offsets: np.ndarray, valid: Optional[np.n
                                     items.ctypes.data, items.size, ctypes.byref(used), nthreads)
     check(rc, "ufc_parse_batch_host")
     return infos, items
+
+
+def build_batch_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarray, src_base: Optional[np.ndarray] = None,
+                     seal: bool = True, nthreads: int = 1):
+    """Frame::write of every frame the records describe (what parse_batch_host returns), in host memory:
+    ufc_build_sizes_host then ufc_build_batch_host.  Datagram payloads come from `payload` at
+    src_base[i] + data_offset (src_base uint64[n], default zeros; a parsed batch's own offsets and bytes
+    re-emit it).  Returns (out_bytes uint8, out_offsets uint64[n + 1], status uint8[n], crc uint32[n]);
+    frames whose status is not UFC_BUILD_OK have length 0; seal=False leaves 4 zero bytes as trailers."""
+    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
+    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    n = infos.size
+    sb = None
+    if src_base is not None:
+        src_base = np.ascontiguousarray(src_base, dtype=np.uint64)
+        if src_base.size < n:
+            raise ValueError("src_base must hold one offset per frame")
+        sb = src_base.ctypes.data
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    crc = np.zeros(n, dtype=np.uint32)
+    ip = items.ctypes.data if items.size else None
+    check(lib().ufc_build_sizes_host(infos.ctypes.data, ip, items.size, sb, payload.size, n, offsets.ctypes.data,
+                                     status.ctypes.data, nthreads), "ufc_build_sizes_host")
+    out = np.zeros(int(offsets[n]), dtype=np.uint8)
+    check(lib().ufc_build_batch_host(infos.ctypes.data, ip, items.size, sb, payload.ctypes.data if payload.size else None,
+                                     payload.size, n, offsets.ctypes.data, out.ctypes.data if out.size else None, out.size,
+                                     1 if seal else 0, crc.ctypes.data, nthreads), "ufc_build_batch_host")
+    return out, offsets, status, crc
