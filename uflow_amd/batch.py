@@ -140,14 +140,14 @@ class FrameCrcEngine:
                                           self._stream(stream)), "ufc_seal_batch_varlen")
         return crc_out
 
-    def crc_pairs(self, data, pairs, crc_out=None, valid_out=None, stream=None):
+    def crc_pairs(self, data, pairs, crc_out=None, valid_out=None, want_crc=True, want_valid=True, stream=None):
         """pairs: int64 tensor [n, 2] of (start, end) byte offsets into data (any gapped layout)."""
         if pairs.dim() != 2 or pairs.shape[1] != 2:
             raise ValueError("pairs must have shape [n, 2]")
         n = pairs.shape[0]
-        if crc_out is None:
+        if crc_out is None and want_crc:
             crc_out = torch.empty(n, dtype=torch.int32, device=self.device)
-        if valid_out is None:
+        if valid_out is None and want_valid:
             valid_out = torch.empty(n, dtype=torch.uint8, device=self.device)
         self._check("pairs", pairs, (torch.int64,), 2 * n)
         self._check("data", data, (torch.uint8,), 0)
@@ -243,6 +243,20 @@ class FrameCrcEngine:
         crc = np.empty(max(n, 0), dtype=np.uint32)
         check(lib().ufc_seal_host_varlen(self._ctx, data.ctypes.data, offsets.ctypes.data, n, crc.ctypes.data),
               "ufc_seal_host_varlen")
+        return crc
+
+    def seal_host_slots(self, slots: np.ndarray, slot_stride: int, lens: np.ndarray):
+        """Seal every datagram of a host slots batch in place (lens[i] >= 4 bytes at the start of slot i;
+        GPU CRC, host trailer write); returns the CRCs."""
+        if slots.dtype != np.uint8 or not slots.flags.c_contiguous or not slots.flags.writeable:
+            raise ValueError("slots must be a writable contiguous uint8 array")
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = lens.size
+        if n and slots.size < (n - 1) * slot_stride + int(lens[-1]):
+            raise ValueError("slots must hold slot n - 1 and its datagram")
+        crc = np.empty(n, dtype=np.uint32)
+        check(lib().ufc_seal_host_slots(self._ctx, slots.ctypes.data, slot_stride, lens.ctypes.data, n,
+                                        crc.ctypes.data), "ufc_seal_host_slots")
         return crc
 
     def validate_host_slots(self, slots: np.ndarray, slot_stride: int, lens: np.ndarray):

@@ -27,7 +27,8 @@ struct KernelParams {
   uint32_t front_ok;          // lean fixed kernel: the pad bytes before frame 0 are readable
   // Variable-length kernel: frames longer than its 13-line fast path (and in range) are left to a
   // second launch (frame_crc_long8_kernel): their indices go to defer_list (workgroup b's from entry
-  // 64 * its first run on), workgroup b's count to defer_counts[b].  Null: they take the byte path.
+  // 64 * its first run on), workgroup b's count to defer_counts[b].  Both are required: the kernel
+  // writes through them without a null check (launch_varlen8 always supplies per-stream scratch).
   uint32_t* defer_list;
   uint32_t* defer_counts;
 };
