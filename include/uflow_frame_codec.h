@@ -19,6 +19,10 @@
  *                                 (src/half_connection/emit.rs:47-125, 170-211 over build.rs:55-162,
  *                                 192-247) and write_* (serial/mod.rs:437-657), batched from the parse's
  *                                 records, on the host and on the GPU
+ *   ufc_pack_host, ufc_pack_varlen
+ *                              <- the emitters' push / finalize loop that cuts a flush's datagrams or ack
+ *                                 groups into frames (src/half_connection/emit.rs:47-125, 170-211), many
+ *                                 flushes per call, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -213,8 +217,8 @@ int ufc_build_batch_host(const ufc_frame_info* infos, const ufc_item* items, siz
  * the variable-length seal of ufc_seal_batch_varlen over (d_out_bytes, d_out_offsets), which treats every
  * span of 4 bytes or more as a frame: give a frame that is to be skipped a length-0 span.  These replace the
  * per-frame assembly of the reference's emitters, src/half_connection/emit.rs:47-125, 170-211 over
- * src/frame/serial/build.rs:55-162, 192-247; packing datagrams into frames (emit.rs:47-112) stays with
- * the caller. */
+ * src/frame/serial/build.rs:55-162, 192-247; packing datagrams into frames (emit.rs:47-112) is the
+ * batched pack below, whose records these calls take as they are. */
 int ufc_build_sizes_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_item* d_items, size_t n_items,
                            const uint64_t* d_src_base, size_t payload_len, size_t n, uint64_t* d_out_offsets,
                            uint8_t* d_status, void* stream);
@@ -222,6 +226,67 @@ int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const uf
                            const uint64_t* d_src_base, const uint8_t* d_payload, size_t payload_len, size_t n,
                            const uint64_t* d_out_offsets, uint8_t* d_out_bytes, size_t out_len, int seal,
                            uint32_t* d_crc_out, void* stream);
+
+/* ---- batched pack: the emitters' push / finalize, many flushes per call ----
+ * A flush is one connection's datagrams (or ack groups) in push order, with the limits its emitter was made
+ * with; each flush is cut into frames exactly as DataFrameEmitter / AckFrameEmitter cut it
+ * (src/half_connection/emit.rs:47-125, 170-211).  The output is the ufc_frame_info records of the frames,
+ * ready for ufc_build_sizes_* / ufc_build_batch_* over the same item array with no step in between.
+ *
+ * Per flush: alloc = flush_alloc, no frame in progress, frames = 0; H = 10 and at most 127 items per frame
+ * for data, H = 15 and no count limit for ack; e = the item's encoded size (a datagram's as
+ * DataFrameBuilder::encoded_size, build.rs:172-183, from data_len, the leads and fragment_id_last; an ack
+ * group's UFC_ACK_GROUP_SIZE).  For each item in order:
+ *   1. with a frame in progress of size s (H + its items): if alloc - s < 0, finalize and stop
+ *      SIZE_LIMITED; else if s + e > UFC_MAX_FRAME_SIZE or the frame holds its maximum count, finalize and
+ *      go on with 2; else add the item and take the next one;
+ *   2. if alloc < 0, stop SIZE_LIMITED;
+ *   3. data only: if frames >= window_room, stop WINDOW_LIMITED;
+ *   4. start a frame with this item (no size check: a datagram larger than a frame gets a frame of its own).
+ * After the last item, finalize.  Finalize: emit the frame, frames += 1, alloc -= s.
+ * The pack judges no field value (that stays UFC_BUILD_BAD_FIELD in the build); an ack flush with no groups
+ * yields no frame (push_dud stays with the caller); a kind other than UFC_FRAME_ACK packs as data. */
+typedef struct ufc_flush {        /* 24 bytes */
+  int64_t  flush_alloc;           /* the emitter's flush_alloc in bytes; may be negative */
+  uint32_t kind;                  /* UFC_FRAME_DATA or UFC_FRAME_ACK */
+  uint32_t window_room;           /* data: frames the frame queue still takes, window.size - (next_id - base_id);
+                                     ack: ignored */
+  uint32_t id0;                   /* data: frame_queue.next_id() of the first frame; ack: frame_window_base_id */
+  uint32_t id1;                   /* ack: packet_window_base_id */
+} ufc_flush;
+
+#define UFC_PACK_DONE 0           /* every item packed */
+#define UFC_PACK_SIZE_LIMITED 1   /* DataPushError::SizeLimited / the ack emitter's Err(()) */
+#define UFC_PACK_WINDOW_LIMITED 2 /* DataPushError::WindowLimited */
+#define UFC_PACK_BAD_RANGE 3      /* the flush's item range is reversed or leaves [0, n_items): nothing packed */
+typedef struct ufc_flush_result { /* 24 bytes */
+  uint32_t frame_first, frame_count; /* its frames: infos[frame_first .. frame_first + frame_count) */
+  uint32_t items_packed;             /* items that went into those frames; the push of the next one failed */
+  uint32_t stop;
+  int64_t  alloc_left;               /* flush_alloc after the last finalize */
+} ufc_flush_result;
+
+/* Flush j owns items[flush_first[j] .. flush_first[j + 1]) (CSR, n_flushes + 1 entries).  Frames come out in flush order and within a flush in emit order:
+ * frame_first is the exclusive sum of frame_count, *frames_used the total.  Frames at index >= frames_cap
+ * are not written (compare *frames_used with frames_cap, as with the parse's items_cap); frames_cap =
+ * n_items is always enough.  Every written info has kind set, ok = 1, crc_ok = 0, item_first and item_count
+ * into the same item array (a frame's items are consecutive: nothing is permuted), f[] and aux zero except:
+ *   data  f[0] = id0 + k (wrapping) for the flush's k-th frame; aux = bit g % 32 of nonce_bits[g / 32] for the
+ *         batch's g-th frame (nonce_bits NULL: 0; else one bit per frame below frames_cap)
+ *   ack   f[0] = id0, f[1] = id1
+ * n_items and n_flushes < 2^31 - 1; n_flushes == 0 returns UFC_OK whatever the pointers; a NULL flush_first,
+ * flushes, results or frames_used, NULL items with n_items != 0, or NULL infos with frames_cap != 0, is
+ * UFC_ERR_INVALID_ARG. */
+int ufc_pack_host(const ufc_item* items, size_t n_items, const uint64_t* flush_first, const ufc_flush* flushes,
+                  size_t n_flushes, const uint32_t* nonce_bits, ufc_frame_info* infos, size_t frames_cap,
+                  ufc_flush_result* results, uint64_t* frames_used, int nthreads);
+/* The same on the GPU (gfx950 kernels, frame_pack.hip): every pointer device memory, asynchronous on
+ * `stream`, nothing allocated per call (the items' size prefix sums, one hop byte per item, two words per
+ * flush and the scan temporaries live in the context's per-stream scratch). */
+int ufc_pack_varlen(ufc_ctx* ctx, const ufc_item* d_items, size_t n_items, const uint64_t* d_flush_first,
+                    const ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_nonce_bits,
+                    ufc_frame_info* d_infos, size_t frames_cap, ufc_flush_result* d_results,
+                    uint64_t* d_frames_used, void* stream);
 
 #ifdef __cplusplus
 }

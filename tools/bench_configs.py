@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -15,6 +15,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            gated and parsed, then built again from its records with the batch itself as payload source;
            the sizes call, the write call (seal = 0) and the seal that follows timed separately, and a
            device-to-device copy of the same output bytes as the floor.  Run with --only build.
+  pack     the emitters' push / finalize on the device (ufc_pack_varlen): the parse_mtu batch's datagram
+           records regrouped into many short and into a few thousand long flushes; the pack, ufc_pack_host
+           with 1 and 16 threads on the same records and the build's write call over the packed frames, one
+           line per grouping.  Run with --only pack.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -368,6 +372,92 @@ def build(eng, dev, reps, n=1_000_000):
             "frames_per_s": round(n / w * 1e3), **extra}
 
 
+def pack(eng, dev, reps, n=1_000_000):
+    """The step before the build: the parse_mtu batch gated and parsed, its datagram records (ack groups left
+    out) regrouped into flushes with no limit that bites, and packed into frames again (ufc_pack_varlen).
+    Two groupings: many short flushes (10 datagrams each) and a few thousand long ones (4096 each).  Per
+    grouping one JSON line: the pack's time per batch (events around groups of launches, after a settle),
+    ufc_pack_host on the same records with 1 and 16 threads (wall clock, median of 5), every record of the
+    GPU pack against the host's, and the existing build's write call (seal = 0) over the frames the pack
+    gave, in the same process, for scale.  Run with --only pack."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import FLUSH_DTYPE, FLUSH_RESULT_DTYPE, FRAME_INFO_DTYPE, ITEM_DTYPE, pack_host
+    data, offsets, lens = parse_batch(n, True)
+    d = torch.from_numpy(data).to(dev)
+    o = torch.from_numpy(offsets).to(dev)
+    _, valid = eng.crc_varlen(d, o)
+    infos0, items0, used0 = eng.parse_varlen(d, o, valid)
+    torch.cuda.synchronize()
+    k0 = int(used0.cpu()[0])
+    h_infos0 = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
+    h_items = items0[:k0].cpu().numpy().view(ITEM_DTYPE).reshape(-1).copy()
+    del infos0, items0
+    # payload offsets relative to the whole batch (one source base, 0, for every new frame), then the datagrams alone
+    frame_of = np.repeat(np.arange(n), h_infos0["item_count"])
+    h_items["data_offset"] = (h_items["data_offset"] + offsets[frame_of]).astype(np.uint32)
+    h_items = np.ascontiguousarray(h_items[h_items["form"] != 3])
+    k = h_items.size
+    d_items = torch.from_numpy(h_items.view(np.uint8).reshape(-1, 24)).to(dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    out = []
+    for name, per in (("short", 10), ("long", 4096)):
+        first = np.minimum(np.arange(0, k + per, per), k).astype(np.uint64)
+        nf = first.size - 1
+        flushes = np.zeros(nf, dtype=FLUSH_DTYPE)
+        flushes["kind"], flushes["flush_alloc"], flushes["window_room"] = 10, 1 << 50, 0xFFFFFFFF
+        flushes["id0"] = np.arange(nf, dtype=np.uint32) * 7
+        d_first = torch.from_numpy(first.astype(np.int64)).to(dev)
+        d_flushes = torch.from_numpy(flushes.view(np.uint8).reshape(-1, 24)).to(dev)
+        infos = torch.zeros((k, 32), dtype=torch.uint8, device=dev)
+        res = torch.zeros((nf, 24), dtype=torch.uint8, device=dev)
+        used = torch.zeros(1, dtype=torch.int64, device=dev)
+        f_pack = lambda: lib.ufc_pack_varlen(ctx, p(d_items), k, p(d_first), p(d_flushes), nf, None, p(infos), k,  # noqa: E731
+                                             p(res), p(used), st)
+        assert f_pack() == 0
+        torch.cuda.synchronize()
+        frames = int(used.cpu()[0])
+        settle(f_pack, 500)
+        med, mean = timed(f_pack, reps)
+        host_ms = {}
+        h_out = np.zeros(k, dtype=FRAME_INFO_DTYPE)
+        for T in (1, 16):
+            ts = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                h_infos, h_res, h_used = pack_host(h_items, first, flushes, nthreads=T, infos=h_out)
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        extra = {}
+        if CHECK:
+            g_infos = infos[:frames].cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
+            g_res = res.cpu().numpy().view(FLUSH_RESULT_DTYPE).reshape(-1)
+            extra["equals_host_pack"] = bool(frames == h_used and np.array_equal(g_infos, h_infos[:frames]) and
+                                             np.array_equal(g_res, h_res))
+        # the build's write over these frames
+        bi = infos[:frames]
+        boff, bstatus = eng.build_sizes_varlen(bi, d_items, d.numel())
+        torch.cuda.synchronize()
+        total = int(boff[-1])
+        bout = torch.empty(total, dtype=torch.uint8, device=dev)
+        f_write = lambda: lib.ufc_build_batch_varlen(ctx, p(bi), p(d_items), k, None, p(d), d.numel(), frames, p(boff),  # noqa: E731
+                                                     p(bout), total, 0, None, st)
+        assert f_write() == 0
+        settle(f_write, 500)
+        w, _ = timed(f_write, reps)
+        out.append({"config": f"f5: device pack of the parse_mtu batch's datagrams, {name} flushes ({per} items each)",
+                    "items": k, "flushes": nf, "frames": frames, "pack_ms": round(med, 4), "pack_mean_ms": round(mean, 4),
+                    "ns_per_item": round(med * 1e6 / k, 4), "host_pack_1t_ms": round(host_ms[1], 2),
+                    "host_pack_16t_ms": round(host_ms[16], 2), "host_1t_over_gpu": round(host_ms[1] / med, 1),
+                    "host_16t_over_gpu": round(host_ms[16] / med, 1), "build_write_ms": round(w, 4),
+                    "build_all_ok": bool((bstatus == 0).all()), "out_bytes": total,
+                    "pack_over_build_write": round(med / w, 3), **extra})
+        del infos, res, bout, boff, bstatus
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -416,6 +506,9 @@ def main():
     for what in a.only.split(","):
         if what == "host":
             for r in host(eng):
+                print(json.dumps(r), flush=True)
+        elif what == "pack":
+            for r in pack(eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:
             print(json.dumps(globals()[what](eng, dev, a.reps)), flush=True)

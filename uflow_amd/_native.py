@@ -34,6 +34,8 @@ UFC_VARLEN_BLOCKSTREAM, UFC_VARLEN_SORTED8, UFC_VARLEN_STREAM = 5, 6, 7
 UFC_OPT_SEAL_KERNEL, UFC_SEAL_INLINE, UFC_SEAL_TWO_PASS = 3, 0, 1
 # per-frame status of the batched builds (include/uflow_frame_codec.h)
 UFC_BUILD_OK, UFC_BUILD_SKIPPED, UFC_BUILD_BAD_FIELD, UFC_BUILD_BAD_SRC = 0, 1, 2, 3
+# why a flush of the batched packs stopped (include/uflow_frame_codec.h)
+UFC_PACK_DONE, UFC_PACK_SIZE_LIMITED, UFC_PACK_WINDOW_LIMITED, UFC_PACK_BAD_RANGE = 0, 1, 2, 3
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -128,6 +130,12 @@ _SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "ufc_pack_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "ufc_pack_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -143,6 +151,16 @@ class Item(ctypes.Structure):
                 ("window_parent_lead", ctypes.c_uint16), ("channel_parent_lead", ctypes.c_uint16),
                 ("fragment_id", ctypes.c_uint16), ("fragment_id_last", ctypes.c_uint16), ("flags", ctypes.c_uint16),
                 ("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32)]
+
+
+class Flush(ctypes.Structure):
+    _fields_ = [("flush_alloc", ctypes.c_int64), ("kind", ctypes.c_uint32), ("window_room", ctypes.c_uint32),
+                ("id0", ctypes.c_uint32), ("id1", ctypes.c_uint32)]
+
+
+class FlushResult(ctypes.Structure):
+    _fields_ = [("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32), ("items_packed", ctypes.c_uint32),
+                ("stop", ctypes.c_uint32), ("alloc_left", ctypes.c_int64)]
 
 
 class Builder(ctypes.Structure):

@@ -17,6 +17,10 @@ import torch
 from ._native import lib, check
 
 
+# Items of a flush whose frame chain one wave of the pack resolves in LDS at a time (kPackTile, csrc/frame_pack.hpp).
+PACK_TILE = 256
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -234,6 +238,36 @@ class FrameCrcEngine:
                                            1 if seal else 0, _ptr(crc_out), self._stream(stream)),
               "ufc_build_batch_varlen")
         return out, offsets, status
+
+    # ---- the emitters' push / finalize of many flushes, on the device (uflow_frame_codec.h) ----
+    def pack_flushes(self, items, flush_first, flushes, frames_cap=None, nonce_bits=None, stream=None):
+        """ufc_pack_varlen: cut every flush's items into frames as DataFrameEmitter / AckFrameEmitter do
+        (src/half_connection/emit.rs:47-125, 170-211).  items uint8[n_items, 24] (ufc_item records, what
+        parse_varlen returns), flush_first int64[n_flushes + 1] (CSR over the items), flushes uint8[n_flushes, 24]
+        (ufc_flush records, uflow_amd.frame.FLUSH_DTYPE), nonce_bits int32 words (bit g: the nonce of the batch's
+        g-th frame; default 0).  Returns (infos uint8[frames_cap, 32], results uint8[n_flushes, 24], frames_used
+        int64[1]) device tensors; frames_cap defaults to n_items, which is always enough.  infos is one that
+        build_varlen takes as is: the rows from frames_used on are zero, which the build skips (or pass
+        infos[:frames_used])."""
+        n_items = items.shape[0]
+        n = flushes.shape[0]
+        if frames_cap is None:
+            frames_cap = n_items
+        frames_cap = int(frames_cap)
+        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._check("flush_first", flush_first, (torch.int64,), n + 1)
+        self._check("flushes", flushes, (torch.uint8,), 24 * n)
+        self._check("nonce_bits", nonce_bits, (torch.int32, torch.uint32), (frames_cap + 31) // 32)
+        # (the outputs are zeroed on the stream the pack is queued on)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            infos = torch.zeros((frames_cap, 32), dtype=torch.uint8, device=self.device)
+            results = torch.zeros((n, 24), dtype=torch.uint8, device=self.device)
+            used = torch.zeros(1, dtype=torch.int64, device=self.device)
+        check(lib().ufc_pack_varlen(self._ctx, _ptr(items) if n_items else None, n_items, _ptr(flush_first),
+                                    _ptr(flushes) if n else None, n, _ptr(nonce_bits),
+                                    _ptr(infos) if frames_cap else None, frames_cap, _ptr(results) if n else None,
+                                    _ptr(used), self._stream(stream)), "ufc_pack_varlen")
+        return infos, results, used
 
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):

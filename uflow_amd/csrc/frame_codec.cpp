@@ -369,4 +369,85 @@ int ufc_build_batch_host(const ufc_frame_info* infos, const ufc_item* items, siz
   return UFC_OK;
 }
 
+// ---- batched host pack ----
+namespace {
+// One flush, item by item (emit.rs:47-125, 170-211 through the core's predicates).  infos null: the result
+// only; else its frames into infos[r.frame_first ..], those below frames_cap.
+void pack_flush(const ufc_item* items, uint64_t n_items, uint64_t first, uint64_t end, const ufc_flush& fl,
+                const uint32_t* nonce_bits, ufc_frame_info* infos, uint64_t frames_cap, ufc_flush_result& r) {
+  const uint32_t frame_first = r.frame_first;
+  r = ufc_flush_result{frame_first, 0, 0, UFC_PACK_DONE, fl.flush_alloc};
+  if (first > end || end > n_items) {
+    r.stop = UFC_PACK_BAD_RANGE;
+    return;
+  }
+  const bool ack = ufc_codec::pack_is_ack(fl);
+  const uint32_t H = ufc_codec::pack_overhead(ack), max_count = ufc_codec::pack_max_count(ack);
+  uint64_t spent = 0, s = 0, start = first;  // finalized bytes; the frame in progress: size (0: none), first item
+  uint32_t c = 0, frames = 0;
+  auto finalize = [&](uint64_t upto) {
+    if (s == 0) return;
+    const uint64_t g = (uint64_t)frame_first + frames;
+    if (infos && g < frames_cap)
+      infos[g] = ufc_codec::pack_frame_info(fl, ack, frames, g, nonce_bits, start, (uint32_t)(upto - start));
+    frames++;
+    spent += s;
+    s = 0;
+  };
+  uint64_t i = first;
+  for (; i < end; i++) {
+    const uint64_t e = ack ? (uint64_t)UFC_ACK_GROUP_SIZE : ufc_codec::datagram_encoded_size(items[i]);
+    const bool is_start = s == 0 || !ufc_codec::pack_frame_takes(s, c, e, max_count);
+    const uint32_t why = ufc_codec::pack_stop(fl, ack, spent + s, is_start, frames + (s ? 1u : 0u));
+    if (why != UFC_PACK_DONE) {
+      r.stop = why;
+      break;
+    }
+    if (is_start) {
+      finalize(i);
+      start = i;
+      s = H + e;
+      c = 1;
+    } else {
+      s += e;
+      c++;
+    }
+  }
+  finalize(i);
+  r.frame_count = frames;
+  r.items_packed = (uint32_t)(i - first);
+  r.alloc_left = fl.flush_alloc - (int64_t)spent;
+}
+}  // namespace
+
+int ufc_pack_host(const ufc_item* items, size_t n_items, const uint64_t* flush_first, const ufc_flush* flushes,
+                  size_t n_flushes, const uint32_t* nonce_bits, ufc_frame_info* infos, size_t frames_cap,
+                  ufc_flush_result* results, uint64_t* frames_used, int nthreads) {
+  if (n_flushes == 0) return UFC_OK;
+  if (!flush_first || !flushes || !results || !frames_used || (!items && n_items) || (!infos && frames_cap) ||
+      n_flushes >= ((size_t)1 << 31) - 1 || n_items >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  // Pass 1: every flush's result; then frame_first, their exclusive sum; pass 2: the frames.
+  for_ranges(n_flushes, nthreads, [&](size_t a, size_t b) {
+    for (size_t j = a; j < b; j++) {
+      results[j].frame_first = 0;
+      pack_flush(items, n_items, flush_first[j], flush_first[j + 1], flushes[j], nullptr, nullptr, 0, results[j]);
+    }
+  });
+  uint64_t total = 0;
+  for (size_t j = 0; j < n_flushes; j++) {
+    results[j].frame_first = (uint32_t)total;
+    total += results[j].frame_count;
+  }
+  *frames_used = total;
+  if (!infos) return UFC_OK;
+  for_ranges(n_flushes, nthreads, [&](size_t a, size_t b) {
+    for (size_t j = a; j < b; j++)
+      if (results[j].frame_count)
+        pack_flush(items, n_items, flush_first[j], flush_first[j + 1], flushes[j], nonce_bits, infos, frames_cap,
+                   results[j]);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

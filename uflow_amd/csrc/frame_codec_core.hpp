@@ -1,5 +1,7 @@
 // frame_codec_core.hpp -- the payload parse of Frame::read (everything after the CRC gate), written
-// once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip).
+// once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip); further down the
+// encode for the batched builds (frame_build.hip) and the emitters' arithmetic for the batched packs
+// (frame_pack.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -407,6 +409,70 @@ UFC_HD uint8_t check_frame(const ufc_frame_info& info, const ufc_item* items, ui
 UFC_HD bool span_matches(uint8_t status, uint64_t size, uint64_t a, uint64_t b, uint64_t first, uint64_t last,
                          uint64_t out_len) {
   return status == UFC_BUILD_OK && b >= a && b - a == size && a >= first && b <= last && b <= out_len;
+}
+
+// ---- pack: DataFrameEmitter / AckFrameEmitter push and finalize (src/half_connection/emit.rs:47-125,
+// 170-211), for the batched packs (host and GPU) ----
+//
+// A flush's frames are a greedy chain over its items' encoded sizes; flush_alloc and the frame window only
+// cut that chain at one item, the stop.  With `starts` = the frames begun before item i and `bytes` = the
+// encoded sizes of the flush's items before i, the emitter has spent (or, for the frame in progress, will
+// have spent once it is finalized)
+//   F(i) = H * starts + bytes
+// when item i is pushed: `flush_alloc - frame_size < 0` of emit.rs:64, 176 and `flush_alloc < 0` of :83, 191
+// are both flush_alloc < F(i).  F never decreases along a flush.
+constexpr uint32_t kDataFrameOverhead = kDataHead + 4;  // DATA_FRAME_OVERHEAD: head + trailer
+constexpr uint32_t kAckFrameOverhead = kAckHead + 4;    // ACK_FRAME_OVERHEAD
+// Groups in a full ack frame, the ack chain's constant hop.
+constexpr uint32_t kAckFrameMaxGroups = (kMaxFrameSize - kAckFrameOverhead) / UFC_ACK_GROUP_SIZE;
+
+UFC_HD bool pack_is_ack(const ufc_flush& fl) { return fl.kind == UFC_FRAME_ACK; }  // any other kind packs as data
+UFC_HD uint32_t pack_overhead(bool ack) { return ack ? kAckFrameOverhead : kDataFrameOverhead; }
+// max_packet_count of emit.rs:61-62 (packet_id::SPAN / (2 MAX_FRAME_WINDOW_SIZE) = 2^20 / 8192 = 128, so
+// DataFrameBuilder::MAX_COUNT decides); the ack emitter counts nothing.
+UFC_HD uint32_t pack_max_count(bool ack) { return ack ? 0xFFFFFFFFu : (uint32_t)UFC_DATA_FRAME_MAX_DATAGRAM_COUNT; }
+// Whether the frame in progress (size s with its overhead, c items) takes an item of e more bytes
+// (emit.rs:69, 180).
+UFC_HD bool pack_frame_takes(uint64_t s, uint32_t c, uint64_t e, uint32_t max_count) {
+  return s + e <= kMaxFrameSize && c < max_count;
+}
+// The push of item i: UFC_PACK_DONE when it goes through, else why the flush stops there.  is_start: the item
+// would begin a frame (the first item, or the frame in progress does not take it); F as above.
+UFC_HD uint32_t pack_stop(const ufc_flush& fl, bool ack, uint64_t F, bool is_start, uint32_t starts) {
+  if (fl.flush_alloc < (int64_t)F) return UFC_PACK_SIZE_LIMITED;                       // :64-68, :83-87, :176-179, :191-194
+  if (is_start && !ack && starts >= fl.window_room) return UFC_PACK_WINDOW_LIMITED;  // :89-92, frame_queue.can_push()
+  return UFC_PACK_DONE;
+}
+// The items a data frame that starts at item i takes when the flush does not end first: the largest m in
+// 1..127 (and <= n_items - i) whose items fit a frame, at least the first item alone (emit.rs:94-109 makes no
+// size check on it).  P(k) = the encoded sizes of items [0, k) summed, k <= n_items.
+template <class Psum>
+UFC_HD uint32_t pack_data_hop(const Psum& P, uint64_t i, uint64_t n_items) {
+  const uint64_t left = n_items - i;
+  uint32_t lo = 1, hi = left < UFC_DATA_FRAME_MAX_DATAGRAM_COUNT ? (uint32_t)left : (uint32_t)UFC_DATA_FRAME_MAX_DATAGRAM_COUNT;
+  const uint64_t limit = P(i) + (kMaxFrameSize - kDataFrameOverhead);
+  while (lo < hi) {  // at most 7 steps
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (P(i + mid) <= limit) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// The record of a flush's k-th frame, g-th of the batch, holding items [item_first, item_first + item_count).
+UFC_HD ufc_frame_info pack_frame_info(const ufc_flush& fl, bool ack, uint32_t k, uint64_t g, const uint32_t* nonce_bits,
+                                      uint64_t item_first, uint32_t item_count) {
+  ufc_frame_info info{};
+  info.kind = ack ? UFC_FRAME_ACK : UFC_FRAME_DATA;
+  info.ok = 1;
+  if (ack) {
+    info.f[0] = fl.id0;
+    info.f[1] = fl.id1;
+  } else {
+    info.f[0] = fl.id0 + k;  // frame_queue.next_id() of each frame in turn
+    info.aux = nonce_bits ? (uint8_t)((nonce_bits[g >> 5] >> (g & 31u)) & 1u) : (uint8_t)0;
+  }
+  info.item_count = item_count;
+  info.item_first = (uint32_t)item_first;
+  return info;
 }
 
 }  // namespace ufc_codec

@@ -18,6 +18,7 @@
 #include "crc_math.hpp"
 #include "frame_build.hpp"
 #include "frame_crc_kernels.hpp"
+#include "frame_pack.hpp"
 #include "frame_parse.hpp"
 #include "ufc_internal.hpp"
 
@@ -71,7 +72,8 @@ enum ScratchKind {
   kScratchSealCrc = 3,
   kScratchDeferList = 4,
   kScratchDeferCounts = 5,
-  kScratchBuild = 6
+  kScratchBuild = 6,
+  kScratchPack = 7
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -940,6 +942,28 @@ int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const uf
   kp.nframes = n;
   kp.crc_out = d_crc_out;
   return launch_varlen_any(ctx, true, false, kp, (hipStream_t)stream);
+}
+
+// ---- batched pack (frame_pack.hip) ----
+int ufc_pack_varlen(ufc_ctx* ctx, const ufc_item* d_items, size_t n_items, const uint64_t* d_flush_first,
+                    const ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_nonce_bits,
+                    ufc_frame_info* d_infos, size_t frames_cap, ufc_flush_result* d_results,
+                    uint64_t* d_frames_used, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n_flushes == 0) return UFC_OK;
+  // (n_items + 1 sizes and n_flushes + 1 frame counts are scanned with 32-bit counts)
+  if (!d_flush_first || !d_flushes || !d_results || !d_frames_used || (!d_items && n_items) ||
+      (!d_infos && frames_cap) || n_flushes >= ((size_t)1 << 31) - 1 || n_items >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::pack_scratch_bytes(n_flushes, n_items);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchPack, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
+  ufc_dev::PackArgs a{d_items, (uint64_t)n_items, d_flush_first, d_flushes, (uint64_t)n_flushes, d_nonce_bits,
+                      d_infos, (uint64_t)frames_cap, d_results, d_frames_used};
+  if ((e = ufc_dev::pack_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
 }
 
 }  // extern "C"

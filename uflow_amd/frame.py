@@ -7,6 +7,8 @@ Mirrors the reference (lowquark/uflow v0.7.1):
     DataFrameBuilder, AckFrameBuilder          <- src/frame/serial/build.rs:47-256
 and the batched receive-side parse that follows the batched CRC gate:
     parse_batch_host(bytes, offsets, valid)    <- Frame::read of every received datagram
+    pack_host(items, flush_first, flushes)     <- DataFrameEmitter / AckFrameEmitter push + finalize,
+                                                  src/half_connection/emit.rs:47-125, 170-211
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -19,7 +21,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import Builder, DatagramRef, FrameInfo, Item, check, lib, UFC_ERR_NOMEM
+from ._native import Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, check, lib, UFC_ERR_NOMEM
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -35,6 +37,13 @@ ITEM_DTYPE = np.dtype([("id", "<u4"), ("channel_id", "u1"), ("form", "u1"), ("wi
                        ("flags", "<u2"), ("data_offset", "<u4"), ("data_len", "<u4")])
 assert FRAME_INFO_DTYPE.itemsize == ctypes.sizeof(FrameInfo) == 32
 assert ITEM_DTYPE.itemsize == ctypes.sizeof(Item) == 24
+# ufc_flush / ufc_flush_result (batched packs)
+FLUSH_DTYPE = np.dtype([("flush_alloc", "<i8"), ("kind", "<u4"), ("window_room", "<u4"), ("id0", "<u4"), ("id1", "<u4")])
+FLUSH_RESULT_DTYPE = np.dtype([("frame_first", "<u4"), ("frame_count", "<u4"), ("items_packed", "<u4"), ("stop", "<u4"),
+                               ("alloc_left", "<i8")])
+assert FLUSH_DTYPE.itemsize == ctypes.sizeof(Flush) == 24
+assert FLUSH_RESULT_DTYPE.itemsize == ctypes.sizeof(FlushResult) == 24
+PACK_DONE, PACK_SIZE_LIMITED, PACK_WINDOW_LIMITED, PACK_BAD_RANGE = 0, 1, 2, 3
 
 
 @dataclass
@@ -334,3 +343,39 @@ def build_batch_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarray, 
                                      payload.size, n, offsets.ctypes.data, out.ctypes.data if out.size else None, out.size,
                                      1 if seal else 0, crc.ctypes.data, nthreads), "ufc_build_batch_host")
     return out, offsets, status, crc
+
+
+def pack_host(items: np.ndarray, flush_first: np.ndarray, flushes: np.ndarray, frames_cap: Optional[int] = None,
+              nonce_bits: Optional[np.ndarray] = None, nthreads: int = 1, infos: Optional[np.ndarray] = None):
+    """The emitters' push / finalize of many flushes in host memory (ufc_pack_host): flush j owns
+    items[flush_first[j] : flush_first[j + 1]] (ITEM_DTYPE records in push order, flush_first uint64[n + 1]) with
+    the limits of flushes[j] (FLUSH_DTYPE).  Returns (infos, results, frames_used): the frames' FRAME_INFO_DTYPE
+    records in flush order, as build_batch_host takes them (rows from frames_used on stay as they were: zero,
+    which the builds skip), one FLUSH_RESULT_DTYPE record per flush, and the number of frames.  frames_cap
+    (default: the number of items, always enough) bounds the records written; nonce_bits: uint32 words, bit g
+    the nonce of the batch's g-th frame (default 0); infos: an array to write into."""
+    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+    flush_first = np.ascontiguousarray(flush_first, dtype=np.uint64)
+    flushes = np.ascontiguousarray(flushes, dtype=FLUSH_DTYPE)
+    n = flushes.size
+    if flush_first.size < n + 1:
+        raise ValueError("flush_first must hold one more entry than there are flushes")
+    if frames_cap is None:
+        frames_cap = items.size if infos is None else infos.size
+    if infos is None:
+        infos = np.zeros(frames_cap, dtype=FRAME_INFO_DTYPE)
+    elif infos.dtype != FRAME_INFO_DTYPE or not infos.flags.c_contiguous or infos.size < frames_cap:
+        raise ValueError("infos must be a contiguous FRAME_INFO_DTYPE array of at least frames_cap records")
+    nb = None
+    if nonce_bits is not None:
+        nonce_bits = np.ascontiguousarray(nonce_bits, dtype=np.uint32)
+        if nonce_bits.size * 32 < frames_cap:
+            raise ValueError("nonce_bits must hold one bit per frame below frames_cap")
+        nb = nonce_bits.ctypes.data
+    results = np.zeros(n, dtype=FLUSH_RESULT_DTYPE)
+    used = ctypes.c_uint64(0)
+    check(lib().ufc_pack_host(items.ctypes.data if items.size else None, items.size, flush_first.ctypes.data,
+                              flushes.ctypes.data if n else None, n, nb, infos.ctypes.data if frames_cap else None,
+                              frames_cap, results.ctypes.data if n else None, ctypes.byref(used), nthreads),
+          "ufc_pack_host")
+    return infos, results, used.value
