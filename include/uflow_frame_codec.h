@@ -23,6 +23,12 @@
  *                              <- the emitters' push / finalize loop that cuts a flush's datagrams or ack
  *                                 groups into frames (src/half_connection/emit.rs:47-125, 170-211), many
  *                                 flushes per call, on the host and on the GPU
+ *   ufc_emit_packets_host, ufc_emit_packets_varlen
+ *                              <- PacketSender::emit_packet (src/half_connection/packet_sender.rs:149-238),
+ *                                 PendingPacket::new / datagram (pending_packet.rs:23-42, 84-103) and the
+ *                                 new-packet loop of emit_data_frames (half_connection/mod.rs:385-427): queued
+ *                                 packets into the datagram items the packs take, many senders per call, on
+ *                                 the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -287,6 +293,117 @@ int ufc_pack_varlen(ufc_ctx* ctx, const ufc_item* d_items, size_t n_items, const
                     const ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_nonce_bits,
                     ufc_frame_info* d_infos, size_t frames_cap, ufc_flush_result* d_results,
                     uint64_t* d_frames_used, void* stream);
+
+/* ---- batched packet emit: queued packets into datagram items, many senders per call ----
+ * The step in front of the pack: PacketSender::emit_packet (src/half_connection/packet_sender.rs:149-238),
+ * PendingPacket::new / datagram (pending_packet.rs:23-42, 84-103) and the new-packet loop of emit_data_frames
+ * (half_connection/mod.rs:385-427).  A sender is one connection's PacketSender state plus its queued packets
+ * in queue order; the output is the ufc_item records of the packets' fragments, ready for ufc_pack_* (with
+ * the flush_first this call writes) and ufc_build_* (src_base NULL: data_offset is absolute in the payload
+ * arena).
+ *
+ * Per sender, for the packets i = 0, 1, ... of its range, the first min(take, range) only:
+ *   1. channel_id >= 64, mode > 3 or data_len > UFC_MAX_PACKET_SIZE: stop BAD_PACKET at i (what
+ *      enqueue_packet debug-asserts, :139-141);
+ *   2. mode == TIME_SENSITIVE and packet.flush_id != sender.flush_id: the packet is dropped (:150-162), its
+ *      length counted in bytes_dropped; next packet;
+ *   3. (next_id - base_id) & 0xFFFFF >= window_size: stop WINDOW_LIMITED (:165-167);
+ *   4. a = the packet's alloc_size (:16-22: a length over 1448 rounded up to a multiple of 1448); alloc + a >
+ *      max_alloc rounded up to a multiple of 1448 (PacketSender::new, :100; saturating): stop ALLOC_LIMITED
+ *      (:169-173);
+ *   5. emit: seq = next_id; each parent lead = (seq - parent) & 0xFFFFF truncated to 16 bits as the
+ *      reference's `as u16`, 0 without a parent; next_id = (next_id + 1) & 0xFFFFF; alloc += a; a RELIABLE
+ *      packet becomes the window parent and its channel's parent; resend = mode >= PERSISTENT; the packet
+ *      yields last + 1 items, last = max(ceil(data_len / 1448), 1) - 1, fragment f with data_offset + 1448 f
+ *      and 1448 bytes, the last one the rest (an empty packet: one empty datagram).
+ * A stopped sender consumes nothing at or after the stopping packet; stale packets in front of it are
+ * dropped.  When the range (or take) ends first the stop is DONE.
+ *
+ * Every item has id = seq, channel_id, the two leads, fragment_id, fragment_id_last, data_offset, data_len,
+ * form = the header form DataFrameBuilder::add will choose (build.rs:81-122) and flags = UFC_ITEM_VALID when
+ * datagram_is_valid holds (always for consistent sender state; parents the caller made up may break it, which
+ * is data, not an error): what the parse gives back for the built frame, data_offset apart. */
+#define UFC_SEND_TIME_SENSITIVE 0 /* SendMode order, src/lib.rs:304-323 */
+#define UFC_SEND_UNRELIABLE 1
+#define UFC_SEND_PERSISTENT 2
+#define UFC_SEND_RELIABLE 3
+#define UFC_NO_PARENT 0xFFFFFFFFu
+#define UFC_MAX_PACKET_SIZE (UFC_MAX_FRAGMENT_SIZE * 65536u) /* MAX_PACKET_SIZE, src/lib.rs:300 */
+
+typedef struct ufc_packet {          /* 16 bytes */
+  uint32_t data_offset, data_len;    /* in the payload arena (< 2^32 bytes) */
+  uint32_t flush_id;                 /* the flush it was enqueued in */
+  uint8_t channel_id, mode;
+  uint16_t reserved;
+} ufc_packet;
+
+typedef struct ufc_sender {          /* 304 bytes; in and out */
+  uint32_t base_id, next_id, window_size, flush_id;
+  uint64_t alloc, max_alloc;
+  uint32_t window_parent_id;         /* UFC_NO_PARENT = None */
+  uint32_t take;                     /* look at the first min(take, range) packets only */
+  uint32_t reserve_items;            /* item slots left untouched in front of this sender's new items */
+  uint32_t reserved;
+  uint32_t channel_parent_id[UFC_MAX_CHANNELS]; /* UFC_NO_PARENT = None */
+} ufc_sender;
+
+#define UFC_PACKET_NOT_REACHED 0
+#define UFC_PACKET_EMITTED 1
+#define UFC_PACKET_DROPPED 2
+typedef struct ufc_packet_result {   /* 16 bytes, one per packet; all zero unless emitted or dropped */
+  uint32_t sequence_id;              /* emitted packets only, as item_first and item_count */
+  uint32_t item_first, item_count;   /* its fragments: items[item_first .. item_first + item_count) */
+  uint8_t status;                    /* UFC_PACKET_* */
+  uint8_t resend;                    /* emitted: mode >= PERSISTENT (the fragments go to the resend queue) */
+  uint16_t reserved;
+} ufc_packet_result;
+
+#define UFC_EMIT_DONE 0           /* the range (or take) ended */
+#define UFC_EMIT_WINDOW_LIMITED 1 /* the transfer window is full */
+#define UFC_EMIT_ALLOC_LIMITED 2  /* the receiver's allocation limit */
+#define UFC_EMIT_BAD_PACKET 3     /* a record enqueue_packet would not have taken */
+#define UFC_EMIT_BAD_RANGE 4      /* the packet range is reversed or leaves [0, n_packets): nothing done */
+typedef struct ufc_sender_result {   /* 32 bytes */
+  uint32_t item_first, item_count;   /* its item range, reserved slots included */
+  uint32_t packets_consumed;         /* emitted + dropped: the stopping packet's index in the range */
+  uint32_t packets_emitted, packets_dropped, stop;
+  uint64_t bytes_dropped;
+} ufc_sender_result;
+
+/* Sender s owns packets[packet_first[s] .. packet_first[s + 1]) (CSR, n_senders + 1 entries).  Outputs:
+ *   items, items_cap   sender s's items at items[flush_first[s] + reserve_items ..), packets in order and
+ *                      each packet's fragments in order; items at an index >= items_cap are not written
+ *                      (compare *items_used with items_cap, as with the parse; items_cap = 0 gives the records
+ *                      and the state alone).  The reserve_items slots in front of a sender's new items are
+ *                      never written: the caller puts the flush's resent and leftover fragments there, as the
+ *                      reference sends them first (mod.rs:351-383 before :385).
+ *   flush_first        [n_senders + 1], the exclusive sum of the senders' item counts, reserved slots
+ *                      included: what ufc_pack_* takes as its flush_first.  *items_used = flush_first[n_senders].
+ *   packet_results     [n_packets], nullable.  Every packet of a sender's range gets a record; packets that
+ *                      no sender owns are left as they were.
+ *   sender_results     [n_senders].
+ *   senders_out        [n_senders], nullable, may be `senders` itself: the state after the consumed prefix
+ *                      (next_id, alloc, window_parent_id, channel_parent_id updated, everything else copied).
+ * A BAD_RANGE sender gets item_count 0 (no reserved slots either), an unchanged state and no packet records.
+ * The ranges of the other senders must not overlap (in a CSR they cannot, unless an entry in between is out
+ * of order); where they do, the records and items of the packets they share are unspecified.
+ * n_packets, n_senders and the item total < 2^31 - 1 (the host call returns UFC_ERR_INVALID_ARG for an item
+ * total beyond it, with flush_first and *items_used written; the device call leaves that to the caller);
+ * n_senders == 0 returns UFC_OK whatever the pointers; a NULL packet_first, senders, flush_first,
+ * sender_results or items_used, NULL packets with n_packets != 0, or NULL items with items_cap != 0, is
+ * UFC_ERR_INVALID_ARG. */
+int ufc_emit_packets_host(const ufc_packet* packets, size_t n_packets, const uint64_t* packet_first,
+                          const ufc_sender* senders, size_t n_senders, ufc_item* items, size_t items_cap,
+                          uint64_t* flush_first, ufc_packet_result* packet_results, ufc_sender_result* sender_results,
+                          ufc_sender* senders_out, uint64_t* items_used, int nthreads);
+/* The same on the GPU (gfx950 kernels, packet_emit.hip): every pointer device memory, asynchronous on
+ * `stream`, nothing allocated per call (12 bytes per packet, 8 per sender and the scan temporaries live in
+ * the context's per-stream scratch). */
+int ufc_emit_packets_varlen(ufc_ctx* ctx, const ufc_packet* d_packets, size_t n_packets,
+                            const uint64_t* d_packet_first, const ufc_sender* d_senders, size_t n_senders,
+                            ufc_item* d_items, size_t items_cap, uint64_t* d_flush_first,
+                            ufc_packet_result* d_packet_results, ufc_sender_result* d_sender_results,
+                            ufc_sender* d_senders_out, uint64_t* d_items_used, void* stream);
 
 #ifdef __cplusplus
 }

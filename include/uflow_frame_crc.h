@@ -88,7 +88,7 @@ int ufc_ctx_destroy(ufc_ctx* ctx);
  * frames over 13 lines (1532 B) handed to their second launch, 4 B per frame of the largest launch
  * (< 2^29 frames) + 256 B, and 4 B per CU of counts; batch build: 8 B per item, 1 B per frame, 4 B per
  * 16 KiB of output and the scan temporaries; batch pack: 9 B per item, 8 B per flush and the scan
- * temporaries).  A caller that retires a stream releases its scratch
+ * temporaries; batch packet emit: 12 B per packet, 8 B per sender and the scan temporaries).  A caller that retires a stream releases its scratch
  * here, BEFORE destroying the stream: waits for the work queued on it, then frees its buffers. */
 int ufc_ctx_release_stream(ufc_ctx* ctx, void* stream);
 const char* ufc_error_string(int code);

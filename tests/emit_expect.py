@@ -1,0 +1,413 @@
+"""Expected results of the batched packet emit (ufc_emit_packets_host / ufc_emit_packets_varlen), and the cases
+both test modules share (test infrastructure, not a test module).
+
+`Tx` restates PacketSender (src/half_connection/packet_sender.rs: new :89-119, emit_packet :149-238, acknowledge
+:242-275) and `fragments` PendingPacket::new / datagram (pending_packet.rs:23-42, 84-103) in plain Python, one
+packet at a time.  An item's header form and validity come from the codec oracle (oracle/codec.py
+`datagram_header`, `datagram_is_valid`).  Nothing of the product is used except the record dtypes.
+"""
+import random
+
+import numpy as np
+
+from oracle import codec as C
+from uflow_amd.frame import ITEM_DTYPE, PACKET_DTYPE, PACKET_RESULT_DTYPE, SENDER_DTYPE, SENDER_RESULT_DTYPE
+
+ID_MASK = 0xFFFFF                        # src/packet_id.rs
+MAX_FRAGMENT_SIZE = 1448                 # src/lib.rs:297
+MAX_PACKET_SIZE = MAX_FRAGMENT_SIZE * 65536  # src/lib.rs:300
+MAX_PACKET_WINDOW_SIZE = 4096
+CHANNEL_COUNT = 64
+TIME_SENSITIVE, UNRELIABLE, PERSISTENT, RELIABLE = 0, 1, 2, 3  # SendMode, src/lib.rs:304-323
+NO_PARENT = 0xFFFFFFFF
+DONE, WINDOW_LIMITED, ALLOC_LIMITED, BAD_PACKET, BAD_RANGE = 0, 1, 2, 3, 4
+NOT_REACHED, EMITTED, DROPPED = 0, 1, 2
+FILL = 0xA5  # the pattern reserved and unused item slots are pre-filled with
+
+
+def alloc_size(packet_size):  # packet_sender.rs:16-22
+    if packet_size > MAX_FRAGMENT_SIZE:
+        return (packet_size + MAX_FRAGMENT_SIZE - 1) // MAX_FRAGMENT_SIZE * MAX_FRAGMENT_SIZE
+    return packet_size
+
+
+def sub(a, b):  # packet_id::sub
+    return (a - b) & ID_MASK
+
+
+class Tx:
+    """PacketSender without its queue: the queue is the caller's list of packets."""
+
+    def __init__(self, window_size=MAX_PACKET_WINDOW_SIZE, base_id=0, max_alloc=10000):
+        self.base_id = self.next_id = base_id
+        self.window_size = window_size
+        self.window = {}  # sequence id -> (alloc_size, channel_id)
+        self.window_parent_id = None
+        self.channel_parent_id = [None] * CHANNEL_COUNT
+        self.max_alloc_given = max_alloc
+        self.max_alloc = min((max_alloc + MAX_FRAGMENT_SIZE - 1) // MAX_FRAGMENT_SIZE * MAX_FRAGMENT_SIZE, 2**64 - 1)  # :100
+        self.alloc = 0
+
+    @classmethod
+    def from_record(cls, r):
+        t = cls(int(r["window_size"]), int(r["base_id"]), int(r["max_alloc"]))
+        t.next_id, t.alloc = int(r["next_id"]), int(r["alloc"])
+        opt = lambda v: None if int(v) == NO_PARENT else int(v)  # noqa: E731
+        t.window_parent_id = opt(r["window_parent_id"])
+        t.channel_parent_id = [opt(v) for v in r["channel_parent_id"]]
+        return t
+
+    def to_record(self, r):
+        """Writes the state into a SENDER_DTYPE record (flush_id, take, reserve_items are the caller's)."""
+        r["base_id"], r["next_id"], r["window_size"] = self.base_id, self.next_id, self.window_size
+        r["alloc"], r["max_alloc"] = self.alloc, self.max_alloc_given
+        r["window_parent_id"] = NO_PARENT if self.window_parent_id is None else self.window_parent_id
+        r["channel_parent_id"] = [NO_PARENT if v is None else v for v in self.channel_parent_id]
+
+    def emit_packet(self, size, channel_id, mode):
+        """emit_packet's second half (:164-234) for the packet at the queue's front, stale ones already dropped:
+        WINDOW_LIMITED, ALLOC_LIMITED, or (sequence_id, window_parent_lead, channel_parent_lead, resend)."""
+        if sub(self.next_id, self.base_id) >= self.window_size:
+            return WINDOW_LIMITED
+        a = alloc_size(size)
+        if self.alloc + a > self.max_alloc:
+            return ALLOC_LIMITED
+        seq = self.next_id
+        lead = lambda parent: 0 if parent is None else sub(seq, parent) & 0xFFFF  # `as u16`  # noqa: E731
+        wl, cl = lead(self.window_parent_id), lead(self.channel_parent_id[channel_id])
+        self.window[seq] = (a, channel_id)
+        self.next_id = (self.next_id + 1) & ID_MASK
+        self.alloc += a
+        if mode == RELIABLE:
+            self.window_parent_id = self.channel_parent_id[channel_id] = seq
+        return seq, wl, cl, mode in (PERSISTENT, RELIABLE)
+
+    def acknowledge(self, receiver_base_id):  # :242-275
+        if sub(receiver_base_id, self.base_id) > sub(self.next_id, self.base_id):
+            return
+        while self.base_id != receiver_base_id:
+            a, ch = self.window.pop(self.base_id)
+            if self.window_parent_id == self.base_id:
+                self.window_parent_id = None
+            if self.channel_parent_id[ch] == self.base_id:
+                self.channel_parent_id[ch] = None
+            self.alloc -= a
+            self.base_id = (self.base_id + 1) & ID_MASK
+
+
+def fragments(size):
+    """PendingPacket::new's last_fragment_id and datagram()'s ranges: [(offset in the packet, length)]."""
+    num = (size + MAX_FRAGMENT_SIZE - 1) // MAX_FRAGMENT_SIZE + (1 if size == 0 else 0)
+    return [(f * MAX_FRAGMENT_SIZE, MAX_FRAGMENT_SIZE if f < num - 1 else size - f * MAX_FRAGMENT_SIZE) for f in range(num)]
+
+
+def _form_flags(channel_id, seq, wl, cl, f, last, length):
+    dg = dict(sequence_id=seq, channel_id=channel_id, window_parent_lead=wl, channel_parent_lead=cl, fragment_id=f,
+              fragment_id_last=last, data=bytes(length))
+    return {6: 0, 9: 1, 14: 2}[len(C.datagram_header(dg))], 1 if C.datagram_is_valid(dg) else 0
+
+
+def packet_items(pk, seq, wl, cl):
+    """The ITEM_DTYPE records of an emitted packet's fragments."""
+    frs = fragments(int(pk["data_len"]))
+    last = len(frs) - 1
+    out = np.zeros(len(frs), dtype=ITEM_DTYPE)
+    out["id"], out["channel_id"], out["window_parent_lead"], out["channel_parent_lead"] = seq, pk["channel_id"], wl, cl
+    out["fragment_id"], out["fragment_id_last"] = np.arange(len(frs)), last
+    out["data_offset"] = (int(pk["data_offset"]) + np.array([o for o, _ in frs], dtype=np.int64)) & 0xFFFFFFFF
+    out["data_len"] = [n for _, n in frs]
+    # every fragment but the last has fragment 0's form and validity
+    ch = int(pk["channel_id"])
+    out["form"], out["flags"] = _form_flags(ch, seq, wl, cl, 0, last, frs[0][1])
+    out["form"][last], out["flags"][last] = _form_flags(ch, seq, wl, cl, last, last, frs[last][1])
+    return out
+
+
+class Expected:
+    pass
+
+
+def expect(packets, packet_first, senders, txs=None):
+    """What an emit of these senders must give, every item listed (no cap): .items (slots no packet owns hold
+    FILL bytes), .flush_first, .packet_results, .sender_results, .senders_out, .items_used.  txs: Tx objects to
+    use (and advance) instead of ones made from the sender records."""
+    n = len(senders)
+    e = Expected()
+    e.packet_results = np.zeros(len(packets), dtype=PACKET_RESULT_DTYPE)
+    e.sender_results = np.zeros(n, dtype=SENDER_RESULT_DTYPE)
+    e.senders_out = senders.copy()
+    e.flush_first = np.zeros(n + 1, dtype=np.uint64)
+    chunks, total = [], 0
+
+    def reserve(k):
+        nonlocal total
+        if k:
+            chunks.append(np.frombuffer(bytes([FILL]) * (ITEM_DTYPE.itemsize * k), dtype=ITEM_DTYPE))
+            total += k
+
+    for s in range(n):
+        sd, r = senders[s], e.sender_results[s]
+        e.flush_first[s] = r["item_first"] = total
+        a, b = int(packet_first[s]), int(packet_first[s + 1])
+        if a > b or b > len(packets):
+            r["stop"] = BAD_RANGE
+            continue
+        tx = txs[s] if txs is not None else Tx.from_record(sd)
+        reserve(int(sd["reserve_items"]))
+        stop, i = DONE, 0
+        upto = min(b - a, int(sd["take"]))
+        while i < upto:
+            pk = packets[a + i]
+            size, ch, mode = int(pk["data_len"]), int(pk["channel_id"]), int(pk["mode"])
+            if ch >= CHANNEL_COUNT or mode > RELIABLE or size > MAX_PACKET_SIZE:  # enqueue_packet's asserts
+                stop = BAD_PACKET
+                break
+            if mode == TIME_SENSITIVE and int(pk["flush_id"]) != int(sd["flush_id"]):  # :150-162
+                e.packet_results[a + i]["status"] = DROPPED
+                r["packets_dropped"] += 1
+                r["bytes_dropped"] += size
+                i += 1
+                continue
+            got = tx.emit_packet(size, ch, mode)
+            if got in (WINDOW_LIMITED, ALLOC_LIMITED):
+                stop = got
+                break
+            seq, wl, cl, resend = got
+            its = packet_items(pk, seq, wl, cl)
+            pr = e.packet_results[a + i]
+            pr["sequence_id"], pr["item_first"], pr["item_count"] = seq, total, len(its)
+            pr["status"], pr["resend"] = EMITTED, resend
+            chunks.append(its)
+            total += len(its)
+            r["packets_emitted"] += 1
+            i += 1
+        r["packets_consumed"], r["stop"] = i, stop
+        r["item_count"] = total - int(r["item_first"])
+        tx.to_record(e.senders_out[s])
+    e.flush_first[n] = e.items_used = total
+    e.items = np.concatenate(chunks) if chunks else np.zeros(0, ITEM_DTYPE)
+    return e
+
+
+def check(got, exp, items_cap=None):
+    """got = (items, flush_first, packet_results, sender_results, senders_out, items_used) of an emit, host
+    arrays, the items pre-filled with FILL bytes: every field of every record against exp = expect(...), the
+    items below min(items_used, items_cap), and FILL in every slot behind them."""
+    items, flush_first, packet_results, sender_results, senders_out, used = got
+    assert int(used) == exp.items_used, (int(used), exp.items_used)
+    assert np.array_equal(np.asarray(flush_first).astype(np.uint64), exp.flush_first)
+
+    def same(name, a, dtype, b):
+        a = np.asarray(a).view(dtype).reshape(-1)
+        assert a.size == b.size, (name, a.size, b.size)
+        for fld in dtype.names:
+            ne = a[fld] != b[fld]
+            bad = np.nonzero(ne.any(axis=1) if ne.ndim > 1 else ne)[0]
+            assert bad.size == 0, f"{name}[{bad[0]}].{fld}: {a[fld][bad[0]]} != {b[fld][bad[0]]}"
+
+    same("sender_results", sender_results, SENDER_RESULT_DTYPE, exp.sender_results)
+    same("senders_out", senders_out, SENDER_DTYPE, exp.senders_out)
+    if packet_results is not None:
+        same("packet_results", packet_results, PACKET_RESULT_DTYPE, exp.packet_results)
+    m = exp.items_used if items_cap is None else min(exp.items_used, items_cap)
+    items = np.asarray(items).view(ITEM_DTYPE).reshape(-1)
+    assert items.size >= m
+    same("items", items[:m], ITEM_DTYPE, exp.items[:m])
+    assert (items[m:].view(np.uint8) == FILL).all(), "wrote an item slot past the total or the cap"
+
+
+# ---- inputs ----
+
+def pkt(size, channel=0, mode=UNRELIABLE, flush_id=0, offset=None):
+    p = np.zeros((), dtype=PACKET_DTYPE)
+    p["data_len"], p["channel_id"], p["mode"], p["flush_id"] = size, channel, mode, flush_id
+    p["data_offset"] = 0xFFFFFFFF if offset is None else offset  # (None: laid out by Senders.arrays)
+    return p, offset is None
+
+
+class Senders:
+    """A batch under construction: add(packets, ...) appends one sender that owns the packets given."""
+
+    def __init__(self):
+        self.packets, self.first, self.senders, self.names = [], [0], [], []
+        self.arena = 0
+
+    def add(self, packets, name="", tx=None, flush_id=0, take=0xFFFFFFFF, reserve_items=0, **state):
+        """tx: a Tx to take the state from; else Tx(window_size, base_id, max_alloc) with next_id, alloc,
+        window_parent_id, channel_parents={channel: id} set as given."""
+        if tx is None:
+            tx = Tx(state.pop("window_size", MAX_PACKET_WINDOW_SIZE), state.pop("base_id", 0),
+                    state.pop("max_alloc", 1 << 40))
+            tx.next_id = state.pop("next_id", tx.base_id)
+            tx.alloc = state.pop("alloc", 0)
+            tx.window_parent_id = state.pop("window_parent_id", None)
+            for ch, v in state.pop("channel_parents", {}).items():
+                tx.channel_parent_id[ch] = v
+        assert not state, state
+        for p, lay in packets:
+            p = p.copy()
+            if lay:
+                p["data_offset"] = self.arena
+                if int(p["data_len"]) <= MAX_PACKET_SIZE:  # (a bad packet takes no room)
+                    self.arena += int(p["data_len"])
+            self.packets.append(p)
+        self.first.append(len(self.packets))
+        sd = np.zeros((), dtype=SENDER_DTYPE)
+        tx.to_record(sd)
+        sd["flush_id"], sd["take"], sd["reserve_items"] = flush_id, take, reserve_items
+        self.senders.append(sd)
+        self.names.append(name)
+        return self
+
+    def index(self, name):
+        return self.names.index(name)
+
+    def arrays(self):
+        packets = np.array(self.packets, dtype=PACKET_DTYPE) if self.packets else np.zeros(0, PACKET_DTYPE)
+        return packets, np.array(self.first, dtype=np.uint64), np.array(self.senders, dtype=SENDER_DTYPE)
+
+
+def reference_cases():
+    """packet_sender.rs's own tests `basic` and `parent_leads`: (Senders, [per sender: the (sequence_id,
+    channel_id, window_parent_lead, channel_parent_lead, resend) tuples its asserts list])."""
+    U, R = UNRELIABLE, RELIABLE
+    b = Senders()
+    b.add([pkt(4, 0, TIME_SENSITIVE), pkt(4, 0, U), pkt(4, 0, PERSISTENT), pkt(4, 0, R)], "basic", max_alloc=10000)
+    b.add([pkt(4, 1, U), pkt(4, 1, R), pkt(4, 1, U), pkt(4, 0, R), pkt(4, 0, U), pkt(4, 0, U), pkt(4, 0, R), pkt(4, 1, R)],
+          "parent_leads", max_alloc=10000)
+    want = [[(0, 0, 0, 0, False), (1, 0, 0, 0, False), (2, 0, 0, 0, True), (3, 0, 0, 0, True)],
+            [(0, 1, 0, 0, False), (1, 1, 0, 0, True), (2, 1, 1, 1, False), (3, 0, 2, 0, True), (4, 0, 1, 1, False),
+             (5, 0, 2, 2, False), (6, 0, 3, 3, True), (7, 1, 1, 6, True)]]
+    return b, want
+
+
+ACK_ROUND = [(1, UNRELIABLE), (1, RELIABLE), (1, UNRELIABLE), (0, RELIABLE), (0, UNRELIABLE), (0, RELIABLE), (1, RELIABLE)]
+# (channel, window_parent_lead, channel_parent_lead, resend) after sequence id ref_id + k
+ACK_ROUND_WANT = [(1, 0, 0, False), (1, 0, 0, True), (1, 1, 1, False), (0, 2, 0, True), (0, 1, 1, False), (0, 2, 2, True),
+                  (1, 1, 5, True)]
+ALLOC_SIZE_TABLE = [(0, 0), (1, 1), (MAX_FRAGMENT_SIZE - 1, MAX_FRAGMENT_SIZE - 1), (MAX_FRAGMENT_SIZE, MAX_FRAGMENT_SIZE),
+                    (MAX_FRAGMENT_SIZE + 1, 2 * MAX_FRAGMENT_SIZE), (2 * MAX_FRAGMENT_SIZE - 1, 2 * MAX_FRAGMENT_SIZE),
+                    (2 * MAX_FRAGMENT_SIZE, 2 * MAX_FRAGMENT_SIZE), (2 * MAX_FRAGMENT_SIZE + 1, 3 * MAX_FRAGMENT_SIZE)]
+EDGE_LENGTHS = (0, 1, 1447, 1448, 1449, 2896, 2897)
+
+
+def edge_cases():
+    """The single edge cases as one batch (each sender one case, found by name)."""
+    U, R, T, P = UNRELIABLE, RELIABLE, TIME_SENSITIVE, PERSISTENT
+    F = MAX_FRAGMENT_SIZE
+    b = Senders()
+    b.add([pkt(n, k % 3, (U, R, P)[k % 3]) for k, n in enumerate(EDGE_LENGTHS)], "lengths")
+    b.add([pkt(0), pkt(F), pkt(F + 1)], "fragment_emission")
+    b.add([pkt(5), pkt(MAX_PACKET_SIZE + 1, offset=0), pkt(5)], "too_long")
+    # ids wrap at 2^20, with parents before the wrap
+    b.add([pkt(3, 2, U), pkt(3, 2, R), pkt(3, 2, U), pkt(3, 5, U), pkt(3, 2, U)], "id_wrap", base_id=0xFFFFA,
+          next_id=0xFFFFE, window_parent_id=0xFFFFD, channel_parents={2: 0xFFFFB, 5: 0xFFFFD})
+    b.add([pkt(1), pkt(1)], "window_size_1", window_size=1, base_id=77, next_id=77)
+    b.add([pkt(1)] * 10, "window_size_4096", window_size=4096, base_id=100, next_id=100 + 4090)
+    for k in (2, 3, 4):  # room for three more packets
+        b.add([pkt(1, mode=R)] * k, f"window_{k}_of_3", window_size=8, base_id=0xFFFFE, next_id=3)
+    b.add([pkt(1)], "window_full", window_size=8, base_id=10, next_id=18)
+    b.add([pkt(1)], "window_overfull", window_size=8, base_id=10, next_id=30)
+    # max_alloc 2 * 1448 (given as 1449, rounded up), 1000 bytes in use: room for exactly 1896 more
+    for n in (1895, 1896, 1897):
+        b.add([pkt(448), pkt(n - 448), pkt(0)], f"alloc_{n}_of_1896", max_alloc=F + 1, alloc=1000)
+    b.add([pkt(F + 1)], "alloc_rounded_fragment_fits", max_alloc=2 * F, alloc=0)       # a = 2 * 1448
+    b.add([pkt(F + 1)], "alloc_rounded_fragment_limited", max_alloc=2 * F, alloc=1)
+    b.add([pkt(1)], "alloc_over_max", max_alloc=F, alloc=5 * F)
+    b.add([pkt(9), pkt(5, mode=T, flush_id=5), pkt(7, mode=T, flush_id=4), pkt(8, mode=T, flush_id=6), pkt(9), pkt(9)],
+          "stale_before_window_stop", flush_id=5, window_size=2)
+    b.add([pkt(7, mode=T, flush_id=4), pkt(9000), pkt(9)], "stale_before_alloc_stop", flush_id=5, max_alloc=F)
+    b.add([pkt(1), pkt(7, channel=64, mode=T, flush_id=4), pkt(1)], "stale_and_bad", flush_id=5)
+    b.add([pkt(1), pkt(7, mode=4), pkt(1)], "bad_mode")
+    b.add([pkt(7, channel=200)], "bad_first")
+    b.add([pkt(c + 1, c, R) for c in range(64)] + [pkt(2, 63 - c, U) for c in range(64)], "all_channels_reliable")
+    b.add([pkt(1, 3), pkt(1, 4)], "made_up_parents", next_id=50, window_parent_id=None, channel_parents={3: 40})
+    b.add([pkt(1, 3)], "made_up_parents_2", next_id=50, window_parent_id=45, channel_parents={3: 48})
+    b.add([pkt(1, 3)], "far_parents", next_id=0x20005, window_parent_id=3, channel_parents={3: 1})  # leads over 2^16
+    for take in (0, 2, 4, 9):
+        b.add([pkt(10 + k, mode=R) for k in range(4)], f"take_{take}", take=take)
+    b.add([pkt(7, mode=T, flush_id=1), pkt(3), pkt(7, mode=T, flush_id=1), pkt(4)], "take_ends_on_stale", take=3)
+    b.add([pkt(3000), pkt(2)], "reserve_3", reserve_items=3)
+    b.add([], "reserve_only", reserve_items=2)
+    b.add([pkt(2)], "reserve_take_0", reserve_items=4, take=0)
+    b.add([], "empty")
+    b.add([pkt(2, mode=T, flush_id=9)] * 3, "all_stale")
+    return b
+
+
+def tile_cases(tile=64):
+    """The smallest shapes where one lane per packet, `tile` packets at a time, can go wrong."""
+    U, R, T = UNRELIABLE, RELIABLE, TIME_SENSITIVE
+    rng = random.Random(17)
+    b = Senders()
+
+    def mixed(n):
+        return [pkt(rng.choice((0, 5, 300, 1448, 1449, 4000)), rng.randrange(4), rng.choice((T, U, U, PERSISTENT, R)),
+                    flush_id=rng.choice((0, 0, 1))) for _ in range(n)]
+
+    for n in (1, tile - 1, tile, tile + 1, 2 * tile, 2 * tile + 1, 200):
+        b.add(mixed(n), f"queue_{n}")
+    b.add(mixed(200), "window_stop_tile_2", window_size=128, base_id=5, next_id=5 + 128 - (tile + 6))
+    small = [pkt(100, k % 5, (U, R)[k % 7 == 0]) for k in range(200)]
+    b.add(small, "alloc_stop_tile_3", max_alloc=100 * (2 * tile + 16))
+    b.add(small[:2 * tile] + [pkt(1, channel=70)] + small, "bad_tile_3")
+    # parents set in the first tile, used two tiles later: window (packet 5) and per channel (3 and 9)
+    q = [pkt(1, 1, U) for _ in range(3 * tile + 8)]
+    q[5], q[9] = pkt(1, 3, R), pkt(1, 9, R)
+    for k in (2 * tile + 3, 2 * tile + 20, 3 * tile + 1):
+        q[k] = pkt(1, 3, U)
+    q[2 * tile + 7] = pkt(1, 9, U)
+    b.add(q, "parents_two_tiles_on", window_parent_id=0xFFFF0, channel_parents={1: 0xFFFF8, 3: 0xFFFF9}, next_id=2)
+    q = [pkt(2, 2, R) for _ in range(tile - 34)] + [pkt(3, 2, T, flush_id=1)] * 70 + [pkt(4, 2, U), pkt(4, 0, R), pkt(4, 2, U)]
+    b.add(q, "stale_run_across_tiles")
+    b.add([pkt(3, 1, T, flush_id=1)] * 199 + [pkt(6, 1, R)], "only_last_live")
+    b.add([pkt(3, 1, T, flush_id=1)] * (2 * tile), "all_stale_two_tiles")
+    b.add(mixed(3 * tile), "take_mid_tile", take=tile + 9)
+    return b
+
+
+def big_case():
+    """A MAX_PACKET_SIZE packet (65 536 items, no payload needed) between two small ones."""
+    return Senders().add([pkt(3, 1, RELIABLE, offset=0), pkt(MAX_PACKET_SIZE, 1, PERSISTENT, offset=16), pkt(9, 1, offset=3)],
+                         "max_packet", reserve_items=1)
+
+
+def random_batch(seed, n_senders=300, max_packets=150):
+    """Senders with mixed modes, channels, sizes and limits: about a third each unlimited, window-limited and
+    allocation-limited, stale and multi-fragment packets, a few bad ones."""
+    rng = random.Random(seed)
+    b = Senders()
+    for _ in range(n_senders):
+        n = rng.randrange(max_packets + 1) if rng.random() < 0.7 else rng.randrange(12)
+        flush_id = rng.randrange(3)
+        q = []
+        for _ in range(n):
+            t = rng.random()
+            size = rng.randrange(64) if t < 0.4 else rng.randrange(1500) if t < 0.8 else rng.randrange(1400, 6000)
+            mode = rng.choice((TIME_SENSITIVE, TIME_SENSITIVE, UNRELIABLE, PERSISTENT, RELIABLE))
+            ch = rng.randrange(64) if rng.random() < 0.3 else rng.randrange(3)
+            if rng.random() < 0.002:
+                ch, mode, size = rng.choice(((64, mode, size), (ch, 7, size), (ch, mode, MAX_PACKET_SIZE + 1)))
+            q.append(pkt(size, ch, mode, flush_id=flush_id if rng.random() < 0.7 else rng.randrange(3)))
+        base = rng.getrandbits(20)
+        in_flight = rng.randrange(40)
+        nxt = (base + in_flight) & ID_MASK
+        kind = rng.randrange(3)
+        window_size = 4096 if kind != 1 else 1 << rng.randrange(5, 8)
+        alloc = rng.randrange(100000)
+        max_alloc = 1 << 40 if kind != 2 else alloc + rng.randrange(1, 60000)
+        parents = {ch: (nxt - 1 - rng.randrange(in_flight)) & ID_MASK for ch in range(64) if in_flight and rng.random() < 0.1}
+        wparent = max(parents.values(), key=lambda v: sub(v, base)) if parents and rng.random() < 0.8 else None
+        if wparent is None:
+            parents = {}
+        b.add(q, flush_id=flush_id, window_size=window_size, base_id=base, next_id=nxt, alloc=alloc, max_alloc=max_alloc,
+              window_parent_id=wparent, channel_parents=parents,
+              take=0xFFFFFFFF if rng.random() < 0.8 else rng.randrange(n + 2),
+              reserve_items=0 if rng.random() < 0.7 else rng.randrange(1, 6))
+    return b
+
+
+def filled_items(n):
+    a = np.zeros(n, dtype=ITEM_DTYPE)
+    a.view(np.uint8)[:] = FILL
+    return a

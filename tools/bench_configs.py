@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -19,6 +19,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            records regrouped into many short and into a few thousand long flushes; the pack, ufc_pack_host
            with 1 and 16 threads on the same records and the build's write call over the packed frames, one
            line per grouping.  Run with --only pack.
+  emit     queued packets into datagram items on the device (ufc_emit_packets_varlen): synthetic send queues as
+           many short and as a few thousand long ones; the emit, ufc_emit_packets_host with 1 and 16 threads
+           on the same records and ufc_pack_varlen over the items produced, one line per grouping.  Run with
+           --only emit.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -458,6 +462,104 @@ def pack(eng, dev, reps, n=1_000_000):
     return out
 
 
+def emit(eng, dev, reps):
+    """The step before the pack: synthetic send queues turned into datagram items (ufc_emit_packets_varlen).
+    Two groupings of 8.4M packets of U[0, 3000] bytes, modes and 8 channels at random, half of the time-sensitive
+    packets stale, no limit that bites: many short queues (2^20 senders of 8 packets) and a few long ones (2048
+    senders of 4096 packets, the whole transfer window).  Per grouping one JSON line: the emit's time per batch
+    (events around groups of calls, after a settle), ufc_emit_packets_host on the same records with 1 and 16
+    threads (wall clock, median of 5), every output of the GPU emit against the host's, and ufc_pack_varlen over
+    the items produced, in the same process, for scale.  Run with --only emit."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import (FLUSH_DTYPE, ITEM_DTYPE, PACKET_DTYPE, PACKET_RESULT_DTYPE, SENDER_DTYPE,
+                                 SENDER_RESULT_DTYPE)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    out = []
+    for name, ns, per in (("short", 1 << 20, 8), ("long", 2048, 4096)):
+        rng = np.random.default_rng(7)
+        npk = ns * per
+        packets = np.zeros(npk, dtype=PACKET_DTYPE)
+        packets["data_len"] = rng.integers(0, 3001, npk)
+        packets["data_offset"] = np.cumsum(packets["data_len"], dtype=np.uint64) % (1 << 31)
+        packets["mode"] = rng.integers(0, 4, npk)
+        packets["channel_id"] = rng.integers(0, 8, npk)
+        packets["flush_id"] = np.where(packets["mode"] == 0, rng.integers(0, 2, npk), 1)
+        first = np.arange(ns + 1, dtype=np.uint64) * per
+        senders = np.zeros(ns, dtype=SENDER_DTYPE)
+        senders["base_id"] = senders["next_id"] = rng.integers(0, 1 << 20, ns)
+        senders["window_size"], senders["flush_id"], senders["max_alloc"] = 4096, 1, 1 << 40
+        senders["window_parent_id"], senders["take"] = N.UFC_NO_PARENT, 0xFFFFFFFF
+        senders["channel_parent_id"] = N.UFC_NO_PARENT
+        # the host call: the item total, then timed with every output kept
+        h_ff = np.zeros(ns + 1, dtype=np.uint64)
+        h_pres = np.zeros(npk, dtype=PACKET_RESULT_DTYPE)
+        h_sres = np.zeros(ns, dtype=SENDER_RESULT_DTYPE)
+        h_sout = np.zeros(ns, dtype=SENDER_DTYPE)
+        h_used = ctypes.c_uint64(0)
+        h_call = lambda items, cap, T: lib.ufc_emit_packets_host(  # noqa: E731
+            packets.ctypes.data, npk, first.ctypes.data, senders.ctypes.data, ns, items, cap, h_ff.ctypes.data,
+            h_pres.ctypes.data, h_sres.ctypes.data, h_sout.ctypes.data, ctypes.byref(h_used), T)
+        assert h_call(None, 0, 16) == 0
+        k = int(h_used.value)
+        h_items = np.zeros(k, dtype=ITEM_DTYPE)
+        host_ms = {}
+        for T in (1, 16):
+            ts = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                assert h_call(h_items.ctypes.data, k, T) == 0
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        d_packets = torch.from_numpy(packets.view(np.uint8).reshape(-1, 16)).to(dev)
+        d_first = torch.from_numpy(first.astype(np.int64)).to(dev)
+        d_senders = torch.from_numpy(senders.view(np.uint8).reshape(-1, 304)).to(dev)
+        items = torch.zeros((k, 24), dtype=torch.uint8, device=dev)
+        ff = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+        pres = torch.zeros((npk, 16), dtype=torch.uint8, device=dev)
+        sres = torch.zeros((ns, 32), dtype=torch.uint8, device=dev)
+        sout = torch.zeros((ns, 304), dtype=torch.uint8, device=dev)
+        used = torch.zeros(1, dtype=torch.int64, device=dev)
+        f_emit = lambda: lib.ufc_emit_packets_varlen(ctx, p(d_packets), npk, p(d_first), p(d_senders), ns, p(items), k,  # noqa: E731
+                                                     p(ff), p(pres), p(sres), p(sout), p(used), st)
+        assert f_emit() == 0
+        torch.cuda.synchronize()
+        assert int(used.cpu()[0]) == k
+        settle(f_emit, 500)
+        med, mean = timed(f_emit, reps)
+        extra = {}
+        if CHECK:
+            same = lambda t, h: bool(np.array_equal(t.cpu().numpy().reshape(-1), h.view(np.uint8).reshape(-1)))  # noqa: E731
+            extra["equals_host_emit"] = (same(items, h_items) and same(pres, h_pres) and same(sres, h_sres) and
+                                         same(sout, h_sout) and bool(np.array_equal(ff.cpu().numpy(), h_ff.astype(np.int64))))
+        # the pack over these items
+        flushes = np.zeros(ns, dtype=FLUSH_DTYPE)
+        flushes["kind"], flushes["flush_alloc"], flushes["window_room"] = 10, 1 << 50, 0xFFFFFFFF
+        d_flushes = torch.from_numpy(flushes.view(np.uint8).reshape(-1, 24)).to(dev)
+        infos = torch.zeros((k, 32), dtype=torch.uint8, device=dev)
+        fres = torch.zeros((ns, 24), dtype=torch.uint8, device=dev)
+        fused = torch.zeros(1, dtype=torch.int64, device=dev)
+        f_pack = lambda: lib.ufc_pack_varlen(ctx, p(items), k, p(ff), p(d_flushes), ns, None, p(infos), k, p(fres),  # noqa: E731
+                                             p(fused), st)
+        assert f_pack() == 0
+        settle(f_pack, 500)
+        w, _ = timed(f_pack, reps)
+        algo = 16 * npk + 24 * k + 16 * npk + ns * (2 * 304 + 32 + 8 + 8)
+        out.append({"config": f"f6: device packet emit, {name} queues ({ns} senders of {per} packets, U[0, 3000] B)",
+                    "packets": npk, "senders": ns, "items": k, "packets_dropped": int(h_sres["packets_dropped"].sum()),
+                    "frames": int(fused.cpu()[0]), "emit_ms": round(med, 4), "emit_mean_ms": round(mean, 4),
+                    "ns_per_packet": round(med * 1e6 / npk, 4), "algorithmic_bytes": algo,
+                    "algo_GB_s": round(algo / med / 1e-3 / 1e9, 1), "host_emit_1t_ms": round(host_ms[1], 2),
+                    "host_emit_16t_ms": round(host_ms[16], 2), "host_1t_over_gpu": round(host_ms[1] / med, 1),
+                    "host_16t_over_gpu": round(host_ms[16] / med, 1), "pack_ms": round(w, 4),
+                    "emit_over_pack": round(med / w, 3), **extra})
+        del d_packets, d_senders, items, ff, pres, sres, sout, infos, fres
+        torch.cuda.empty_cache()
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -507,8 +609,8 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what == "pack":
-            for r in pack(eng, dev, a.reps):
+        elif what in ("pack", "emit"):
+            for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:
             print(json.dumps(globals()[what](eng, dev, a.reps)), flush=True)

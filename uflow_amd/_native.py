@@ -36,6 +36,11 @@ UFC_OPT_SEAL_KERNEL, UFC_SEAL_INLINE, UFC_SEAL_TWO_PASS = 3, 0, 1
 UFC_BUILD_OK, UFC_BUILD_SKIPPED, UFC_BUILD_BAD_FIELD, UFC_BUILD_BAD_SRC = 0, 1, 2, 3
 # why a flush of the batched packs stopped (include/uflow_frame_codec.h)
 UFC_PACK_DONE, UFC_PACK_SIZE_LIMITED, UFC_PACK_WINDOW_LIMITED, UFC_PACK_BAD_RANGE = 0, 1, 2, 3
+# the batched packet emits (include/uflow_frame_codec.h): SendMode, why a sender stopped, a packet's status
+UFC_SEND_TIME_SENSITIVE, UFC_SEND_UNRELIABLE, UFC_SEND_PERSISTENT, UFC_SEND_RELIABLE = 0, 1, 2, 3
+UFC_NO_PARENT = 0xFFFFFFFF
+UFC_EMIT_DONE, UFC_EMIT_WINDOW_LIMITED, UFC_EMIT_ALLOC_LIMITED, UFC_EMIT_BAD_PACKET, UFC_EMIT_BAD_RANGE = 0, 1, 2, 3, 4
+UFC_PACKET_NOT_REACHED, UFC_PACKET_EMITTED, UFC_PACKET_DROPPED = 0, 1, 2
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -136,6 +141,14 @@ _SIGNATURES = {
     "ufc_pack_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ufc_emit_packets_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "ufc_emit_packets_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -161,6 +174,29 @@ class Flush(ctypes.Structure):
 class FlushResult(ctypes.Structure):
     _fields_ = [("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32), ("items_packed", ctypes.c_uint32),
                 ("stop", ctypes.c_uint32), ("alloc_left", ctypes.c_int64)]
+
+
+class Packet(ctypes.Structure):
+    _fields_ = [("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32), ("flush_id", ctypes.c_uint32),
+                ("channel_id", ctypes.c_uint8), ("mode", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
+
+
+class Sender(ctypes.Structure):
+    _fields_ = [("base_id", ctypes.c_uint32), ("next_id", ctypes.c_uint32), ("window_size", ctypes.c_uint32),
+                ("flush_id", ctypes.c_uint32), ("alloc", ctypes.c_uint64), ("max_alloc", ctypes.c_uint64),
+                ("window_parent_id", ctypes.c_uint32), ("take", ctypes.c_uint32), ("reserve_items", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("channel_parent_id", ctypes.c_uint32 * 64)]
+
+
+class PacketResult(ctypes.Structure):
+    _fields_ = [("sequence_id", ctypes.c_uint32), ("item_first", ctypes.c_uint32), ("item_count", ctypes.c_uint32),
+                ("status", ctypes.c_uint8), ("resend", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
+
+
+class SenderResult(ctypes.Structure):
+    _fields_ = [("item_first", ctypes.c_uint32), ("item_count", ctypes.c_uint32), ("packets_consumed", ctypes.c_uint32),
+                ("packets_emitted", ctypes.c_uint32), ("packets_dropped", ctypes.c_uint32), ("stop", ctypes.c_uint32),
+                ("bytes_dropped", ctypes.c_uint64)]
 
 
 class Builder(ctypes.Structure):

@@ -19,6 +19,8 @@ from ._native import lib, check
 
 # Items of a flush whose frame chain one wave of the pack resolves in LDS at a time (kPackTile, csrc/frame_pack.hpp).
 PACK_TILE = 256
+# Packets of a sender that one wave of the packet emit resolves at a time (kEmitTile, csrc/packet_emit.hpp).
+EMIT_TILE = 64
 
 
 def _ptr(t):
@@ -268,6 +270,47 @@ class FrameCrcEngine:
                                     _ptr(infos) if frames_cap else None, frames_cap, _ptr(results) if n else None,
                                     _ptr(used), self._stream(stream)), "ufc_pack_varlen")
         return infos, results, used
+
+    # ---- PacketSender::emit_packet and fragmentation of many senders, on the device (uflow_frame_codec.h) ----
+    def emit_packets(self, packets, packet_first, senders, items_cap, items=None, senders_out=None,
+                     want_packet_results=True, stream=None):
+        """ufc_emit_packets_varlen: turn every sender's queued packets into datagram items as
+        PacketSender::emit_packet and PendingPacket do (src/half_connection/packet_sender.rs:149-238,
+        pending_packet.rs:23-42, 84-103).  packets uint8[n_packets, 16] (ufc_packet records,
+        uflow_amd.frame.PACKET_DTYPE), packet_first int64[n_senders + 1] (CSR over the packets), senders
+        uint8[n_senders, 304] (ufc_sender records, SENDER_DTYPE).  Returns (items uint8[items_cap, 24], flush_first
+        int64[n_senders + 1], packet_results uint8[n_packets, 16] or None, sender_results uint8[n_senders, 32],
+        senders_out uint8[n_senders, 304], items_used int64[1]) device tensors: items and flush_first are what
+        pack_flushes takes (items[:items_used] when items_cap is larger).  Items at an index >= items_cap are not
+        written (compare items_used); each sender's reserve_items slots stay as they were (zero in a tensor
+        allocated here).  `items`: a tensor to write into; senders_out: where the state after the consumed
+        packets goes (may be `senders`)."""
+        n_packets = packets.shape[0]
+        n = senders.shape[0]
+        items_cap = int(items_cap)
+        self._check("packets", packets, (torch.uint8,), 16 * n_packets)
+        self._check("packet_first", packet_first, (torch.int64,), n + 1)
+        self._check("senders", senders, (torch.uint8,), 304 * n)
+        self._check("items", items, (torch.uint8,), 24 * items_cap)
+        self._check("senders_out", senders_out, (torch.uint8,), 304 * n)
+        # (the outputs are zeroed on the stream the emit is queued on)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if items is None:
+                items = torch.zeros((items_cap, 24), dtype=torch.uint8, device=self.device)
+            flush_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            packet_results = torch.zeros((n_packets, 16), dtype=torch.uint8, device=self.device) \
+                if want_packet_results else None
+            sender_results = torch.zeros((n, 32), dtype=torch.uint8, device=self.device)
+            if senders_out is None:
+                senders_out = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
+            used = torch.zeros(1, dtype=torch.int64, device=self.device)
+        check(lib().ufc_emit_packets_varlen(self._ctx, _ptr(packets) if n_packets else None, n_packets,
+                                            _ptr(packet_first), _ptr(senders) if n else None, n,
+                                            _ptr(items) if items_cap else None, items_cap, _ptr(flush_first),
+                                            _ptr(packet_results) if want_packet_results and n_packets else None,
+                                            _ptr(sender_results) if n else None, _ptr(senders_out) if n else None,
+                                            _ptr(used), self._stream(stream)), "ufc_emit_packets_varlen")
+        return items, flush_first, packet_results, sender_results, senders_out, used
 
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):

@@ -450,4 +450,120 @@ int ufc_pack_host(const ufc_item* items, size_t n_items, const uint64_t* flush_f
   return UFC_OK;
 }
 
+// ---- batched host emit ----
+namespace {
+// One sender, packet by packet (packet_sender.rs:149-238 through the core's functions).  Returns its item count,
+// reserved slots included.  out false: the count only; else every output of the sender, its items at
+// items[item_base + reserve_items ..), those below items_cap.  `sd` is a copy: senders_out may be the input.
+uint64_t emit_sender(const ufc_packet* packets, uint64_t n_packets, uint64_t first, uint64_t end, const ufc_sender sd,
+                     bool out, uint64_t item_base, ufc_item* items, uint64_t items_cap, ufc_packet_result* packet_results,
+                     ufc_sender_result* result, ufc_sender* sender_out) {
+  ufc_sender st = sd;
+  ufc_sender_result r{};
+  r.item_first = (uint32_t)item_base;
+  if (first > end || end > n_packets) {
+    if (out) {
+      r.stop = UFC_EMIT_BAD_RANGE;
+      *result = r;
+      if (sender_out) *sender_out = st;
+    }
+    return 0;
+  }
+  const uint64_t n = std::min<uint64_t>(end - first, sd.take);
+  const uint64_t max_alloc = ufc_codec::emit_max_alloc(sd.max_alloc);
+  uint64_t made = sd.reserve_items;  // the sender's items so far
+  uint64_t i = 0;
+  r.stop = UFC_EMIT_DONE;
+  for (; i < n; i++) {
+    const ufc_packet& p = packets[first + i];
+    const uint32_t cls = ufc_codec::emit_packet_class(p, sd.flush_id);
+    if (cls == ufc_codec::kEmitBad) {
+      r.stop = UFC_EMIT_BAD_PACKET;
+      break;
+    }
+    if (cls == ufc_codec::kEmitStale) {
+      r.packets_dropped++;
+      r.bytes_dropped += p.data_len;
+      if (out && packet_results) {
+        ufc_packet_result pr{};
+        pr.status = UFC_PACKET_DROPPED;
+        packet_results[first + i] = pr;
+      }
+      continue;
+    }
+    if (((st.next_id - st.base_id) & ufc_codec::kPacketIdMask) >= st.window_size) {
+      r.stop = UFC_EMIT_WINDOW_LIMITED;
+      break;
+    }
+    const uint64_t a = ufc_codec::emit_alloc_size(p.data_len);
+    if (ufc_codec::emit_alloc_fails(st.alloc, 0, a, max_alloc)) {
+      r.stop = UFC_EMIT_ALLOC_LIMITED;
+      break;
+    }
+    const uint32_t seq = st.next_id;
+    const uint16_t wl = ufc_codec::emit_lead(seq, st.window_parent_id);
+    const uint16_t cl = ufc_codec::emit_lead(seq, st.channel_parent_id[p.channel_id]);
+    st.next_id = (st.next_id + 1) & ufc_codec::kPacketIdMask;
+    st.alloc += a;
+    if (p.mode == UFC_SEND_RELIABLE) st.window_parent_id = st.channel_parent_id[p.channel_id] = seq;
+    const uint32_t count = ufc_codec::emit_fragment_count(p.data_len);
+    if (out) {
+      if (packet_results) {
+        ufc_packet_result pr{};
+        pr.sequence_id = seq;
+        pr.item_first = (uint32_t)(item_base + made);
+        pr.item_count = count;
+        pr.status = UFC_PACKET_EMITTED;
+        pr.resend = p.mode >= UFC_SEND_PERSISTENT ? 1 : 0;
+        packet_results[first + i] = pr;
+      }
+      for (uint32_t f = 0; f < count && item_base + made + f < items_cap; f++)
+        items[item_base + made + f] = ufc_codec::emit_item(p, seq, wl, cl, f, count - 1);
+    }
+    made += count;
+    r.packets_emitted++;
+  }
+  if (out) {
+    if (packet_results)
+      for (uint64_t k = first + i; k < end; k++) packet_results[k] = ufc_packet_result{};  // not reached
+    r.packets_consumed = (uint32_t)i;
+    r.item_count = (uint32_t)made;
+    *result = r;
+    if (sender_out) *sender_out = st;
+  }
+  return made;
+}
+}  // namespace
+
+int ufc_emit_packets_host(const ufc_packet* packets, size_t n_packets, const uint64_t* packet_first,
+                          const ufc_sender* senders, size_t n_senders, ufc_item* items, size_t items_cap,
+                          uint64_t* flush_first, ufc_packet_result* packet_results, ufc_sender_result* sender_results,
+                          ufc_sender* senders_out, uint64_t* items_used, int nthreads) {
+  if (n_senders == 0) return UFC_OK;
+  if (!packet_first || !senders || !flush_first || !sender_results || !items_used || (!packets && n_packets) ||
+      (!items && items_cap) || n_senders >= ((size_t)1 << 31) - 1 || n_packets >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  // Pass 1: every sender's item count, into flush_first; then their exclusive sum; pass 2: the outputs.
+  for_ranges(n_senders, nthreads, [&](size_t a, size_t b) {
+    for (size_t s = a; s < b; s++)
+      flush_first[s + 1] = emit_sender(packets, n_packets, packet_first[s], packet_first[s + 1], senders[s], false, 0,
+                                       nullptr, 0, nullptr, nullptr, nullptr);
+  });
+  uint64_t total = 0;
+  for (size_t s = 0; s < n_senders; s++) {
+    const uint64_t c = flush_first[s + 1];
+    flush_first[s] = total;
+    total += c;
+  }
+  flush_first[n_senders] = total;
+  *items_used = total;
+  if (total >= ((uint64_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
+  for_ranges(n_senders, nthreads, [&](size_t a, size_t b) {
+    for (size_t s = a; s < b; s++)
+      emit_sender(packets, n_packets, packet_first[s], packet_first[s + 1], senders[s], true, flush_first[s], items,
+                  items_cap, packet_results, &sender_results[s], senders_out ? &senders_out[s] : nullptr);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

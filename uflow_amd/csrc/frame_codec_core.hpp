@@ -1,7 +1,7 @@
 // frame_codec_core.hpp -- the payload parse of Frame::read (everything after the CRC gate), written
 // once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip); further down the
-// encode for the batched builds (frame_build.hip) and the emitters' arithmetic for the batched packs
-// (frame_pack.hip).
+// encode for the batched builds (frame_build.hip), the emitters' arithmetic for the batched packs
+// (frame_pack.hip) and the packet sender's for the batched packet emits (packet_emit.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -473,6 +473,74 @@ UFC_HD ufc_frame_info pack_frame_info(const ufc_flush& fl, bool ack, uint32_t k,
   info.item_count = item_count;
   info.item_first = (uint32_t)item_first;
   return info;
+}
+
+// ---- emit: PacketSender::emit_packet (src/half_connection/packet_sender.rs:149-238) and PendingPacket::new /
+// datagram (pending_packet.rs:23-42, 84-103), for the batched packet emits (host and GPU) ----
+//
+// Along one sender's queue, over its live packets (neither bad nor stale): the sequence id is next_id + rank
+// (rank = live packets before it) and the allocation in front of it alloc + A (A = their alloc sizes summed).
+// The window check fails from rank = room on and the allocation check from the first packet with
+// A + a > max_alloc - alloc on; both never pass again further on, so the stop is the first packet that is bad
+// or fails either.
+enum EmitClass : uint32_t { kEmitBad = 0, kEmitStale = 1, kEmitLive = 2 };
+
+// alloc_size (:16-22).
+UFC_HD uint64_t emit_alloc_size(uint32_t len) {
+  const uint64_t F = UFC_MAX_FRAGMENT_SIZE;
+  return len > F ? (len + F - 1) / F * F : (uint64_t)len;
+}
+// num_fragments of PendingPacket::new (pending_packet.rs:25): an empty packet is one empty fragment.
+UFC_HD uint32_t emit_fragment_count(uint32_t len) {
+  return len ? (uint32_t)(((uint64_t)len + UFC_MAX_FRAGMENT_SIZE - 1) / UFC_MAX_FRAGMENT_SIZE) : 1u;
+}
+// A parent lead (:180-196): packet_id::sub, then `as u16`; 0 without a parent.
+UFC_HD uint16_t emit_lead(uint32_t seq, uint32_t parent) {
+  return parent == UFC_NO_PARENT ? (uint16_t)0 : (uint16_t)((seq - parent) & kPacketIdMask);
+}
+// Bad (what enqueue_packet debug-asserts, :139-141) before stale (:150-162).
+UFC_HD uint32_t emit_packet_class(const ufc_packet& p, uint32_t flush_id) {
+  if (p.channel_id >= UFC_MAX_CHANNELS || p.mode > UFC_SEND_RELIABLE || p.data_len > UFC_MAX_PACKET_SIZE) return kEmitBad;
+  if (p.mode == UFC_SEND_TIME_SENSITIVE && p.flush_id != flush_id) return kEmitStale;
+  return kEmitLive;
+}
+// max_alloc_ceil of PacketSender::new (:100), saturating.
+UFC_HD uint64_t emit_max_alloc(uint64_t max_alloc) {
+  const uint64_t r = max_alloc % UFC_MAX_FRAGMENT_SIZE;
+  if (r == 0) return max_alloc;
+  const uint64_t up = UFC_MAX_FRAGMENT_SIZE - r;
+  return max_alloc > ~(uint64_t)0 - up ? ~(uint64_t)0 : max_alloc + up;
+}
+// Live packets the window still takes (:165-167): the check of the packet of rank r,
+// ((next_id + r - base_id) & mask) >= window_size, fails exactly from r = room on (r < 2^31).  A window_size
+// above the id mask never limits.
+UFC_HD uint32_t emit_window_room(uint32_t base_id, uint32_t next_id, uint32_t window_size) {
+  if (window_size > kPacketIdMask) return 0xFFFFFFFFu;
+  const uint32_t d = (next_id - base_id) & kPacketIdMask;
+  return d >= window_size ? 0u : window_size - d;
+}
+// alloc + A + a > max_alloc (:171), max_alloc already rounded, without overflow.
+UFC_HD bool emit_alloc_fails(uint64_t alloc, uint64_t A, uint64_t a, uint64_t max_alloc) {
+  if (alloc > max_alloc) return true;
+  const uint64_t left = max_alloc - alloc;
+  return A > left || a > left - A;
+}
+// Fragment f (<= last = emit_fragment_count(data_len) - 1) of an emitted packet (pending_packet.rs:84-103).
+UFC_HD ufc_item emit_item(const ufc_packet& p, uint32_t seq, uint16_t window_parent_lead, uint16_t channel_parent_lead,
+                          uint32_t f, uint32_t last) {
+  ufc_item it{};
+  it.id = seq;
+  it.channel_id = p.channel_id;
+  it.window_parent_lead = window_parent_lead;
+  it.channel_parent_lead = channel_parent_lead;
+  it.fragment_id = (uint16_t)f;
+  it.fragment_id_last = (uint16_t)last;
+  it.data_offset = p.data_offset + UFC_MAX_FRAGMENT_SIZE * f;
+  it.data_len = f == last ? p.data_len - UFC_MAX_FRAGMENT_SIZE * f : (uint32_t)UFC_MAX_FRAGMENT_SIZE;
+  const uint32_t hs = datagram_header_size(it);
+  it.form = (uint8_t)(hs == 6 ? 0 : (hs == 9 ? 1 : 2));
+  it.flags = datagram_is_valid(it) ? UFC_ITEM_VALID : 0;
+  return it;
 }
 
 }  // namespace ufc_codec

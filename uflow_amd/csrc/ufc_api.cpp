@@ -20,6 +20,7 @@
 #include "frame_crc_kernels.hpp"
 #include "frame_pack.hpp"
 #include "frame_parse.hpp"
+#include "packet_emit.hpp"
 #include "ufc_internal.hpp"
 
 struct ufc_ctx {
@@ -73,7 +74,8 @@ enum ScratchKind {
   kScratchDeferList = 4,
   kScratchDeferCounts = 5,
   kScratchBuild = 6,
-  kScratchPack = 7
+  kScratchPack = 7,
+  kScratchEmit = 8
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -963,6 +965,32 @@ int ufc_pack_varlen(ufc_ctx* ctx, const ufc_item* d_items, size_t n_items, const
   ufc_dev::PackArgs a{d_items, (uint64_t)n_items, d_flush_first, d_flushes, (uint64_t)n_flushes, d_nonce_bits,
                       d_infos, (uint64_t)frames_cap, d_results, d_frames_used};
   if ((e = ufc_dev::pack_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+
+// ---- batched packet emit (packet_emit.hip) ----
+int ufc_emit_packets_varlen(ufc_ctx* ctx, const ufc_packet* d_packets, size_t n_packets,
+                            const uint64_t* d_packet_first, const ufc_sender* d_senders, size_t n_senders,
+                            ufc_item* d_items, size_t items_cap, uint64_t* d_flush_first,
+                            ufc_packet_result* d_packet_results, ufc_sender_result* d_sender_results,
+                            ufc_sender* d_senders_out, uint64_t* d_items_used, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n_senders == 0) return UFC_OK;
+  // (n_senders + 1 item counts are scanned with a 32-bit count)
+  if (!d_packet_first || !d_senders || !d_flush_first || !d_sender_results || !d_items_used ||
+      (!d_packets && n_packets) || (!d_items && items_cap) || n_senders >= ((size_t)1 << 31) - 1 ||
+      n_packets >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::emit_scratch_bytes(n_senders, n_packets);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchEmit, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
+  ufc_dev::EmitArgs a{d_packets, (uint64_t)n_packets, d_packet_first, d_senders, (uint64_t)n_senders, d_items,
+                      (uint64_t)items_cap, d_flush_first, d_packet_results, d_sender_results, d_senders_out,
+                      d_items_used};
+  if ((e = ufc_dev::emit_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

@@ -9,6 +9,9 @@ and the batched receive-side parse that follows the batched CRC gate:
     parse_batch_host(bytes, offsets, valid)    <- Frame::read of every received datagram
     pack_host(items, flush_first, flushes)     <- DataFrameEmitter / AckFrameEmitter push + finalize,
                                                   src/half_connection/emit.rs:47-125, 170-211
+    emit_packets_host(packets, packet_first, senders)
+                                               <- PacketSender::emit_packet and fragmentation,
+                                                  src/half_connection/packet_sender.rs:149-238
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -21,7 +24,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, check, lib, UFC_ERR_NOMEM
+from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, Packet, PacketResult, Sender,
+                      SenderResult, check, lib, UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -44,6 +48,25 @@ FLUSH_RESULT_DTYPE = np.dtype([("frame_first", "<u4"), ("frame_count", "<u4"), (
 assert FLUSH_DTYPE.itemsize == ctypes.sizeof(Flush) == 24
 assert FLUSH_RESULT_DTYPE.itemsize == ctypes.sizeof(FlushResult) == 24
 PACK_DONE, PACK_SIZE_LIMITED, PACK_WINDOW_LIMITED, PACK_BAD_RANGE = 0, 1, 2, 3
+# ufc_packet / ufc_sender / ufc_packet_result / ufc_sender_result (batched packet emits)
+PACKET_DTYPE = np.dtype([("data_offset", "<u4"), ("data_len", "<u4"), ("flush_id", "<u4"), ("channel_id", "u1"),
+                         ("mode", "u1"), ("reserved", "<u2")])
+SENDER_DTYPE = np.dtype([("base_id", "<u4"), ("next_id", "<u4"), ("window_size", "<u4"), ("flush_id", "<u4"),
+                         ("alloc", "<u8"), ("max_alloc", "<u8"), ("window_parent_id", "<u4"), ("take", "<u4"),
+                         ("reserve_items", "<u4"), ("reserved", "<u4"), ("channel_parent_id", "<u4", (64,))])
+PACKET_RESULT_DTYPE = np.dtype([("sequence_id", "<u4"), ("item_first", "<u4"), ("item_count", "<u4"), ("status", "u1"),
+                                ("resend", "u1"), ("reserved", "<u2")])
+SENDER_RESULT_DTYPE = np.dtype([("item_first", "<u4"), ("item_count", "<u4"), ("packets_consumed", "<u4"),
+                                ("packets_emitted", "<u4"), ("packets_dropped", "<u4"), ("stop", "<u4"),
+                                ("bytes_dropped", "<u8")])
+assert PACKET_DTYPE.itemsize == ctypes.sizeof(Packet) == 16
+assert SENDER_DTYPE.itemsize == ctypes.sizeof(Sender) == 304
+assert PACKET_RESULT_DTYPE.itemsize == ctypes.sizeof(PacketResult) == 16
+assert SENDER_RESULT_DTYPE.itemsize == ctypes.sizeof(SenderResult) == 32
+SEND_TIME_SENSITIVE, SEND_UNRELIABLE, SEND_PERSISTENT, SEND_RELIABLE = 0, 1, 2, 3
+NO_PARENT = 0xFFFFFFFF
+EMIT_DONE, EMIT_WINDOW_LIMITED, EMIT_ALLOC_LIMITED, EMIT_BAD_PACKET, EMIT_BAD_RANGE = 0, 1, 2, 3, 4
+PACKET_NOT_REACHED, PACKET_EMITTED, PACKET_DROPPED = 0, 1, 2
 
 
 @dataclass
@@ -379,3 +402,56 @@ def pack_host(items: np.ndarray, flush_first: np.ndarray, flushes: np.ndarray, f
                               frames_cap, results.ctypes.data if n else None, ctypes.byref(used), nthreads),
           "ufc_pack_host")
     return infos, results, used.value
+
+
+def emit_packets_host(packets: np.ndarray, packet_first: np.ndarray, senders: np.ndarray, items_cap: Optional[int] = None,
+                      nthreads: int = 1, items: Optional[np.ndarray] = None, senders_out: Optional[np.ndarray] = None,
+                      want_packet_results: bool = True):
+    """PacketSender::emit_packet and fragmentation for many senders in host memory (ufc_emit_packets_host): sender
+    s (SENDER_DTYPE: its PacketSender state, take and reserve_items) owns packets[packet_first[s] :
+    packet_first[s + 1]] (PACKET_DTYPE records in queue order, packet_first uint64[n + 1]).  Returns (items,
+    flush_first, packet_results, sender_results, senders_out, items_used): the fragments' ITEM_DTYPE records with
+    the uint64 CSR over them that pack_host takes as its flush_first (each sender's reserve_items slots in front
+    of its new items are left as they were), one PACKET_RESULT_DTYPE record per packet (None without
+    want_packet_results), one SENDER_RESULT_DTYPE record per sender, and the senders' state after the packets they
+    consumed.  items_cap bounds the items written (default: what the call needs, found by a first call with
+    none); items: an array to write into; senders_out: where the state goes (may be `senders` itself)."""
+    packets = np.ascontiguousarray(packets, dtype=PACKET_DTYPE)
+    packet_first = np.ascontiguousarray(packet_first, dtype=np.uint64)
+    if senders.dtype != SENDER_DTYPE or not senders.flags.c_contiguous:
+        senders = np.ascontiguousarray(senders, dtype=SENDER_DTYPE)
+    n = senders.size
+    if packet_first.size < n + 1:
+        raise ValueError("packet_first must hold one more entry than there are senders")
+    if senders_out is None:
+        senders_out = np.zeros(n, dtype=SENDER_DTYPE)
+    elif senders_out.dtype != SENDER_DTYPE or not senders_out.flags.c_contiguous or senders_out.size < n:
+        raise ValueError("senders_out must be a contiguous SENDER_DTYPE array of one record per sender")
+    flush_first = np.zeros(n + 1, dtype=np.uint64)
+    packet_results = np.zeros(packets.size, dtype=PACKET_RESULT_DTYPE) if want_packet_results else None
+    sender_results = np.zeros(n, dtype=SENDER_RESULT_DTYPE)
+    used = ctypes.c_uint64(0)
+
+    def call(items_p, cap):
+        check(lib().ufc_emit_packets_host(packets.ctypes.data if packets.size else None, packets.size,
+                                          packet_first.ctypes.data, senders.ctypes.data if n else None, n, items_p, cap,
+                                          flush_first.ctypes.data, packet_results.ctypes.data
+                                          if want_packet_results and packets.size else None,
+                                          sender_results.ctypes.data if n else None,
+                                          senders_out.ctypes.data if n else None, ctypes.byref(used), nthreads),
+              "ufc_emit_packets_host")
+
+    if items_cap is None:
+        if items is not None:
+            items_cap = items.size
+        elif senders_out is senders or np.shares_memory(senders_out, senders):
+            raise ValueError("give items_cap (or items) when the state is updated in place")
+        else:
+            call(None, 0)
+            items_cap = used.value
+    if items is None:
+        items = np.zeros(items_cap, dtype=ITEM_DTYPE)
+    elif items.dtype != ITEM_DTYPE or not items.flags.c_contiguous or items.size < items_cap:
+        raise ValueError("items must be a contiguous ITEM_DTYPE array of at least items_cap records")
+    call(items.ctypes.data if items_cap else None, items_cap)
+    return items, flush_first, packet_results, sender_results, senders_out, used.value
