@@ -29,6 +29,12 @@
  *                                 new-packet loop of emit_data_frames (half_connection/mod.rs:385-427): queued
  *                                 packets into the datagram items the packs take, many senders per call, on
  *                                 the host and on the GPU
+ *   ufc_receive_packets_host, ufc_receive_packets_varlen
+ *                              <- PacketReceiver::handle_datagram, receive and resynchronize
+ *                                 (src/half_connection/packet_receiver/mod.rs:142-218, 286-402, 408-435) over
+ *                                 AssemblyWindow and FragmentBuffer (assembly_window/mod.rs:69-199,
+ *                                 fragment_buffer.rs:12-57): the parses' datagram items into delivered packets,
+ *                                 many receivers per call, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -404,6 +410,180 @@ int ufc_emit_packets_varlen(ufc_ctx* ctx, const ufc_packet* d_packets, size_t n_
                             ufc_item* d_items, size_t items_cap, uint64_t* d_flush_first,
                             ufc_packet_result* d_packet_results, ufc_sender_result* d_sender_results,
                             ufc_sender* d_senders_out, uint64_t* d_items_used, void* stream);
+
+/* ---- batched packet receive: datagram items into delivered packets, many receivers per call ----
+ * The step behind the parse, and the mirror of the emit: PacketReceiver::handle_datagram, receive and
+ * resynchronize (src/half_connection/packet_receiver/mod.rs:142-218, 286-402, 408-435), AssemblyWindow::try_add
+ * and clear (assembly_window/mod.rs:69-199) and FragmentBuffer (fragment_buffer.rs:12-57).  A receiver is one
+ * connection's PacketReceiver state; one call runs one *step* for every receiver:
+ *   1. if resync_id != UFC_NO_PARENT: resynchronize(resync_id & 0xFFFFF);
+ *   2. handle_datagram for every datagram of the receiver's frames, in frame order and then item order.
+ *      Receiver r owns frames [frame_first[r], frame_first[r + 1]) (CSR; the caller groups frames by
+ *      connection).  A frame counts when infos[i].ok, kind == UFC_FRAME_DATA and (frame_accept == NULL or
+ *      frame_accept[i] != 0): frame_accept is where the frame window's verdict (FrameAckQueue) plugs in.  The
+ *      items of a frame with ok != 0 that does not count get UFC_RX_NOT_HANDLED.  Per datagram, in this order:
+ *        - datagram_is_valid recomputed from the fields (flags is not trusted), and id < 2^20: else
+ *          DROPPED_INVALID;
+ *        - its payload is payload[src_base[i] + data_offset ..+ data_len) (src_base NULL: zero, as in the build,
+ *          so a parsed batch's offsets and bytes are passed as they are): a range that leaves [0, payload_len)
+ *          is DROPPED_BAD_SRC;
+ *        - (id - base_id) & 0xFFFFF >= window_size: DROPPED_WINDOW (:162); behind its channel's base:
+ *          DROPPED_CHANNEL (:167);
+ *        - try_add on slot id & (window_size - 1): an OPEN slot is opened by this datagram (refused by the
+ *          allocation limit: DUD, the slot CLOSED with no allocation; one fragment: COMPLETED; else STORED, the
+ *          slot ACTIVE); a CLOSED slot: DROPPED_CLOSED; an ACTIVE slot: DROPPED_MISMATCH if channel, either lead
+ *          or fragment_id_last differ from the opener's, DROPPED_DUPLICATE if the fragment was already received
+ *          (the first arrival's bytes win), else STORED, or COMPLETED when it was the last one missing.
+ *      A COMPLETED or DUD datagram enters its packet into the receive window (:177-216).
+ *   3. if deliver != 0: receive(): packets go out in sequence order, gated per channel, then the window advances.
+ * The item ranges of a batch's frames must not overlap (a parse's never do): where they do, the status of the
+ * shared items and what follows from them are unspecified, within every bound.
+ * resync_id and deliver let a caller split a batch at a sync frame: a step with deliver = 0 for the datagrams in
+ * front of it, then a step with resync_id set for the rest.
+ *
+ * The release build is the specification: debug asserts are not enforced, and every input has one answer,
+ * hostile senders included (a window that passes an undelivered packet leaves a stale receive-window entry
+ * behind, exactly as the reference does).  One deliberate difference: a packet refused by the allocation limit
+ * (assembly_window/mod.rs:95-105) makes the reference panic when it is delivered (mod.rs:337, unwrap of None);
+ * here it is delivered as a record with UFC_RX_PACKET_DUD and length 0, everything else as if sink.send had
+ * happened.  channel_base_markers are not stored: a channel base is the id after a delivered packet, its lead
+ * over base_id in 1..=window_size, so try_unset_channel_base_id over (base, new_base] unsets exactly the
+ * channels whose base lead is in 1..=advance, and that is the rule here whatever the state. */
+typedef struct ufc_receiver {        /* 560 bytes; in and out */
+  uint32_t base_id, end_id, window_size;
+  uint8_t window_ready;              /* window_ready_flag */
+  uint8_t deliver;                   /* in: run receive() in this step */
+  uint16_t reserved;
+  uint32_t resync_id;                /* in: UFC_NO_PARENT = no resynchronize in this step */
+  uint32_t reserved2;
+  uint64_t alloc, max_alloc;         /* AssemblyWindow's; max_alloc is rounded up to a multiple of 1448 at use
+                                        (assembly_window/mod.rs:73), saturating, as the emit does */
+  uint64_t channel_ready_flags;
+  uint32_t channel_base_id[UFC_MAX_CHANNELS];      /* UFC_NO_PARENT = None */
+  uint32_t channel_packet_count[UFC_MAX_CHANNELS];
+} ufc_receiver;
+
+/* One window slot (32 bytes): the assembly window's entry and, apart from it, the receive window's (stale
+ * receive-window entries outlive a cleared assembly entry in the reference).  All zero = empty.
+ * Its bytes live in the carry arena at data_offset: first the held packet's data_len bytes when DATA is set
+ * without DUD (a complete packet not yet delivered), then, 8-byte aligned, an ACTIVE slot's FragmentBuffer:
+ * n * 1448 data bytes, fragment f at f * 1448, and ceil(n / 64) uint64 received-bits words (bit f % 64 of word
+ * f / 64), n = asm_last_fragment_id + 1. */
+#define UFC_RX_ASM_OPEN 0
+#define UFC_RX_ASM_CLOSED 1
+#define UFC_RX_ASM_ACTIVE 2
+#define UFC_RX_SLOT_ENTRY 1 /* entry_flags bit */
+#define UFC_RX_SLOT_DATA 2  /* data_flags bit */
+#define UFC_RX_SLOT_DUD 4   /* with DATA: the packet has no bytes (data = None) */
+typedef struct ufc_rx_slot {
+  uint64_t data_offset;              /* the slot's region in the carry arena (8-byte aligned) */
+  uint32_t data_len;                 /* the held packet's bytes (0 without DATA, or with DUD) */
+  uint32_t asm_size;                 /* CLOSED: Closed(alloc_size); ACTIVE: the FragmentBuffer's total_size (its
+                                        alloc_size is n * 1448) */
+  uint16_t asm_window_parent_lead, asm_channel_parent_lead, asm_last_fragment_id;  /* ACTIVE: the opener's */
+  uint16_t asm_received;             /* ACTIVE: fragments received (at most n - 1) */
+  uint16_t rx_window_parent_lead, rx_channel_parent_lead; /* window_entries / channel_entries */
+  uint8_t asm_state;                 /* UFC_RX_ASM_* */
+  uint8_t asm_channel_id;            /* ACTIVE: the opener's */
+  uint8_t rx_channel_id;             /* channel_entries */
+  uint8_t rx_flags;                  /* UFC_RX_SLOT_ENTRY | _DATA | _DUD */
+} ufc_rx_slot;
+
+#define UFC_RX_PACKET_DUD 1
+typedef struct ufc_rx_packet {       /* 24 bytes: one delivered packet */
+  uint64_t out_offset;               /* its bytes: out_bytes[out_offset ..+ len) */
+  uint32_t sequence_id, len;
+  uint8_t channel_id;
+  uint8_t flags;                     /* UFC_RX_PACKET_DUD: refused by the allocation limit, len 0 */
+  uint16_t reserved;
+  uint32_t reserved2;
+} ufc_rx_packet;
+
+/* item_status values, one byte per datagram. */
+#define UFC_RX_NOT_HANDLED 0
+#define UFC_RX_STORED 1
+#define UFC_RX_COMPLETED 2
+#define UFC_RX_DUD 3
+#define UFC_RX_DROPPED_INVALID 4
+#define UFC_RX_DROPPED_WINDOW 5
+#define UFC_RX_DROPPED_CHANNEL 6
+#define UFC_RX_DROPPED_CLOSED 7
+#define UFC_RX_DROPPED_MISMATCH 8
+#define UFC_RX_DROPPED_DUPLICATE 9
+#define UFC_RX_DROPPED_BAD_SRC 10
+#define UFC_RX_STATUS_COUNT 11
+
+#define UFC_RX_DONE 0
+#define UFC_RX_BAD_STATE 1 /* window_size not a power of two in 1..4096; base_id or end_id >= 2^20; the frame range,
+                              a counted or ok frame's item range, the slot range (fewer than window_size slots) or a
+                              slot's carry region reversed or out of bounds; a slot's channel id >= 64 or asm_state
+                              > 2: nothing is done, state and slots stay as they are, no item status is written */
+typedef struct ufc_receiver_result { /* 80 bytes */
+  uint32_t packet_first, packet_count;            /* its records: packets[packet_first ..+ packet_count) */
+  uint32_t status_count[UFC_RX_STATUS_COUNT];     /* datagrams per item_status value */
+  uint32_t packets_completed, packets_dud;        /* packets that entered the receive window in this step */
+  uint32_t advanced;                              /* ids the window moved, the resynchronize included */
+  uint32_t stop;                                  /* UFC_RX_DONE or UFC_RX_BAD_STATE */
+  uint32_t reserved;
+  uint64_t bytes_delivered;
+} ufc_receiver_result;
+
+/* State: receivers[n_receivers] in, receivers_out[n_receivers] out (required; may be `receivers` itself);
+ * slot j of receiver r is slots[slot_first[r] + j], j < window_size (slot_first: CSR, n_receivers + 1 entries,
+ * inside [0, n_slots)), updated in place.  All-zero slots and a header with base_id = end_id, window_size,
+ * max_alloc, resync_id = UFC_NO_PARENT, channel_base_id all UFC_NO_PARENT and the rest zero is
+ * PacketReceiver::new.
+ * Carry: carry_in[carry_in_len) is const and, like carry_out, 8-byte aligned; carry_out[carry_cap) must not overlap it; the caller swaps them
+ * between steps.  carry_out holds every slot's region (above) laid down in receiver order, then slot-index
+ * order over all window_size slots, each region 8-byte aligned: carry_first[n_receivers + 1] (CSR) and
+ * *carry_used are outputs, the slots' data_offset point into carry_out afterwards.  Bytes of fragments not yet
+ * received, and padding, are unspecified.  The layout is part of the ABI: a carry written by the host form is
+ * read by the GPU form and the reverse.  Held bytes are copied once per step.
+ * Outputs: packets[packets_cap], delivered packets in receiver order, then delivery order; their bytes packed
+ * without gaps in out_bytes[out_cap); packet_first[n_receivers + 1] (CSR), *packets_used, *out_used;
+ * item_status[n_items] (nullable); results[n_receivers].  Records at an index >= packets_cap and bytes at an
+ * offset >= out_cap or carry_cap are not written; the used counts are exact and the state advances all the
+ * same (compare the used counts with the caps, as with the parse and the emit): a step whose carry_used exceeds
+ * carry_cap has lost held bytes.  Always enough: out_cap = carry_in_len + payload_len; packets_cap = n_items +
+ * n_slots; carry_cap = carry_in_len + payload_len + 8 * n_slots + B, where B covers the fragment buffers opened
+ * in this step: an ACTIVE slot's region is its whole FragmentBuffer, n * 1448 + 8 * ceil(n / 64) bytes with n =
+ * fragment_id_last + 1, however few fragments have arrived, so one first fragment of a 64-fragment packet needs
+ * 92 680 bytes.  B = that size summed over the step's datagrams with fragment_id_last != 0, one per (receiver,
+ * sequence id); per receiver it is also at most (max_alloc rounded up - alloc) * (1 + 1 / 11584) + 8 *
+ * window_size.  A caller that cannot bound B runs the step once on a copy of the state with caps of zero: the used
+ * counts are exact whatever the caps (the Python wrappers do this when no caps are given).
+ * n_frames, n_items, n_receivers and n_slots < 2^31 - 1; n_receivers == 0 returns UFC_OK whatever the pointers;
+ * a NULL infos with n_frames != 0, items with n_items != 0, payload with payload_len != 0, slots with n_slots
+ * != 0, carry_in with carry_in_len != 0, carry_out with carry_cap != 0, packets with packets_cap != 0, out_bytes
+ * with out_cap != 0, or a NULL frame_first, receivers, receivers_out, slot_first, carry_first, carry_used,
+ * packet_first, packets_used, out_used or results is UFC_ERR_INVALID_ARG.  frame_accept, src_base and
+ * item_status are nullable. */
+int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const uint8_t* frame_accept,
+                             const ufc_item* items, size_t n_items, const uint64_t* src_base, const uint8_t* payload,
+                             size_t payload_len, const uint64_t* frame_first, const ufc_receiver* receivers,
+                             size_t n_receivers, ufc_rx_slot* slots, const uint64_t* slot_first, size_t n_slots,
+                             const uint8_t* carry_in, size_t carry_in_len, uint8_t* carry_out, size_t carry_cap,
+                             uint64_t* carry_first, uint64_t* carry_used, ufc_rx_packet* packets, size_t packets_cap,
+                             uint64_t* packet_first, uint64_t* packets_used, uint8_t* out_bytes, size_t out_cap,
+                             uint64_t* out_used, uint8_t* item_status, ufc_receiver_result* results,
+                             ufc_receiver* receivers_out, int nthreads);
+/* The same on the GPU (gfx950 kernels, packet_receive.hip): every pointer device memory, any alignment of
+ * d_payload and d_out_bytes (d_carry_in and d_carry_out 8-byte aligned), asynchronous on `stream`, nothing
+ * allocated per call.  The context's per-stream scratch holds, in bytes: 48 n_slots (a plan record per slot) +
+ * 24 (n_items + 2 n_slots) (a copy segment per datagram and two per slot) + 8 (2 n_slots + 1) (a chunk count and
+ * its prefix per slot segment) + 2 n_items (a status and a verdict byte) + 8 * the power of two at or above 2 n_items, at least 64
+ * (the duplicate table) + 48 (n_receivers + 1) (six counts per receiver) + the scan temporaries, each part
+ * rounded up to 256.  n_slots < 2^30 - 1 here. */
+int ufc_receive_packets_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames,
+                               const uint8_t* d_frame_accept, const ufc_item* d_items, size_t n_items,
+                               const uint64_t* d_src_base, const uint8_t* d_payload, size_t payload_len,
+                               const uint64_t* d_frame_first, const ufc_receiver* d_receivers, size_t n_receivers,
+                               ufc_rx_slot* d_slots, const uint64_t* d_slot_first, size_t n_slots,
+                               const uint8_t* d_carry_in, size_t carry_in_len, uint8_t* d_carry_out, size_t carry_cap,
+                               uint64_t* d_carry_first, uint64_t* d_carry_used, ufc_rx_packet* d_packets,
+                               size_t packets_cap, uint64_t* d_packet_first, uint64_t* d_packets_used,
+                               uint8_t* d_out_bytes, size_t out_cap, uint64_t* d_out_used, uint8_t* d_item_status,
+                               ufc_receiver_result* d_results, ufc_receiver* d_receivers_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -23,6 +23,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            many short and as a few thousand long ones; the emit, ufc_emit_packets_host with 1 and 16 threads
            on the same records and ufc_pack_varlen over the items produced, one line per grouping.  Run with
            --only emit.
+  receive  datagram items into delivered packets on the device (ufc_receive_packets_varlen): the parse_mtu
+           batch's datagrams as many small receivers and as 2048 receivers; the receive, ufc_receive_packets_host
+           with 1 thread on the same records and a device-to-device copy of the delivered bytes, one line per
+           grouping.  Run with --only receive.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -560,6 +564,123 @@ def emit(eng, dev, reps):
     return out
 
 
+def receive(eng, dev, reps, n=1_000_000):
+    """The step behind the parse: the parse_mtu batch gated and parsed, its data frames' datagrams given sequence
+    ids a receiver takes (consecutive per receiver from a random base, one fragment each, no parents: every packet
+    is delivered and the window moves past it) and run through ufc_receive_packets_varlen.  Two groupings: many
+    small receivers (4 frames each, window 64) and 2048 receivers (window 4096).  Per grouping one JSON line: the
+    receive's time per batch (events around groups of calls, after a settle; a step leaves the slots empty
+    again, so every call does the same work), ufc_receive_packets_host on the same records with 1 thread (the baseline) and 16 (wall
+    clock, median of 3); a plain device-to-device copy of the delivered bytes: the ceiling of the copy
+    kernel; every output of the GPU call against the host's.  Run with --only receive."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import (FRAME_INFO_DTYPE, ITEM_DTYPE, RECEIVER_RESULT_DTYPE, RX_PACKET_DTYPE, RX_SLOT_DTYPE,
+                                 new_receivers)
+    data, offsets, lens = parse_batch(n, True)
+    d = torch.from_numpy(data).to(dev)
+    o = torch.from_numpy(offsets).to(dev)
+    _, valid = eng.crc_varlen(d, o)
+    infos0, items0, used0 = eng.parse_varlen(d, o, valid)
+    torch.cuda.synchronize()
+    k = int(used0.cpu()[0])
+    h_infos = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1).copy()
+    h_items0 = items0[:k].cpu().numpy().view(ITEM_DTYPE).reshape(-1).copy()
+    h_valid = valid.cpu().numpy().copy()
+    del infos0, items0
+    counted = (h_infos["ok"] != 0) & (h_infos["kind"] == 10) & (h_valid != 0)
+    cnt = np.where(counted, h_infos["item_count"], 0).astype(np.int64)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    src_base = offsets[:n].astype(np.uint64)
+    out = []
+    for name, nr, W in (("small", n // 4, 64), ("2048", 2048, 4096)):
+        rng = np.random.default_rng(9)
+        ff = (np.arange(nr + 1, dtype=np.uint64) * n) // nr
+        recv = new_receivers(nr, W, rng.integers(0, 1 << 20, nr))
+        # sequence ids: consecutive over each receiver's handled datagrams
+        items = h_items0.copy()
+        cc = cnt[counted]
+        fi = np.repeat(np.flatnonzero(counted), cc)                      # the frame of every handled datagram
+        pos = np.arange(fi.size)
+        idx = np.repeat(h_infos["item_first"][counted].astype(np.int64), cc) + pos - np.repeat(np.cumsum(cc) - cc, cc)
+        owner = np.searchsorted(ff, fi, side="right") - 1                # its receiver (ascending)
+        within = pos - np.searchsorted(owner, np.arange(nr), side="left")[owner]
+        items["id"][idx] = (recv["base_id"][owner] + within) & 0xFFFFF
+        items["window_parent_lead"] = items["channel_parent_lead"] = 0
+        items["fragment_id"] = items["fragment_id_last"] = 0
+        slot_first = np.arange(nr + 1, dtype=np.uint64) * W
+        ns = nr * W
+        pay = int(d.numel())
+        caps = {"carry": 8 * ns + 64, "out": pay, "packets": k}
+        # host, one thread
+        h_slots = np.zeros(ns, dtype=RX_SLOT_DTYPE)
+        h = {"carry_out": np.zeros(caps["carry"], np.uint8), "out": np.zeros(pay, np.uint8),
+             "packets": np.zeros(k, dtype=RX_PACKET_DTYPE), "cf": np.zeros(nr + 1, np.uint64), "pf": np.zeros(nr + 1, np.uint64),
+             "status": np.zeros(k, np.uint8), "res": np.zeros(nr, dtype=RECEIVER_RESULT_DTYPE), "rout": recv.copy()}
+        hu = [ctypes.c_uint64(0) for _ in range(3)]
+        c = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        h_call = lambda T: lib.ufc_receive_packets_host(  # noqa: E731
+            c(h_infos), n, c(h_valid), c(items), k, c(src_base), c(data), pay, c(ff), c(recv), nr, c(h_slots), c(slot_first), ns,
+            None, 0, c(h["carry_out"]), caps["carry"], c(h["cf"]), ctypes.addressof(hu[0]), c(h["packets"]), k, c(h["pf"]),
+            ctypes.addressof(hu[1]), c(h["out"]), pay, ctypes.addressof(hu[2]), c(h["status"]), c(h["res"]), c(h["rout"]), T)
+        host_ms = {}
+        for T in (1, 16):
+            ts = []
+            for _ in range(3):
+                h_slots[:] = 0
+                t0 = time.perf_counter()
+                assert h_call(T) == 0
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        delivered, out_used = int(hu[1].value), int(hu[2].value)
+        # device
+        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
+        g = {"infos": t(h_infos, 32), "accept": t(h_valid), "items": t(items, 24), "src": t(src_base.astype(np.int64)),
+             "ff": t(ff.astype(np.int64)), "recv": t(recv, 560), "slots": torch.zeros((ns, 32), dtype=torch.uint8, device=dev),
+             "sf": t(slot_first.astype(np.int64)), "carry_out": torch.zeros(caps["carry"], dtype=torch.uint8, device=dev),
+             "cf": torch.zeros(nr + 1, dtype=torch.int64, device=dev), "used": torch.zeros(3, dtype=torch.int64, device=dev),
+             "packets": torch.zeros((k, 24), dtype=torch.uint8, device=dev),
+             "pf": torch.zeros(nr + 1, dtype=torch.int64, device=dev), "out": torch.zeros(pay, dtype=torch.uint8, device=dev),
+             "status": torch.zeros(k, dtype=torch.uint8, device=dev), "res": torch.zeros((nr, 80), dtype=torch.uint8, device=dev),
+             "rout": torch.zeros((nr, 560), dtype=torch.uint8, device=dev)}
+        u = g["used"].data_ptr()
+        f_rx = lambda: lib.ufc_receive_packets_varlen(  # noqa: E731
+            ctx, p(g["infos"]), n, p(g["accept"]), p(g["items"]), k, p(g["src"]), p(d), pay, p(g["ff"]), p(g["recv"]), nr,
+            p(g["slots"]), p(g["sf"]), ns, None, 0, p(g["carry_out"]), caps["carry"], p(g["cf"]), ctypes.c_void_p(u),
+            p(g["packets"]), k, p(g["pf"]), ctypes.c_void_p(u + 8), p(g["out"]), pay, ctypes.c_void_p(u + 16),
+            p(g["status"]), p(g["res"]), p(g["rout"]), st)
+        assert f_rx() == 0
+        torch.cuda.synchronize()
+        extra = {}
+        if CHECK:
+            same = lambda a, b: bool(np.array_equal(a.cpu().numpy().reshape(-1), b.view(np.uint8).reshape(-1)))  # noqa: E731
+            extra["equals_host_receive"] = (same(g["packets"], h["packets"]) and same(g["status"], h["status"]) and
+                                            same(g["res"], h["res"]) and same(g["rout"], h["rout"]) and
+                                            same(g["slots"], h_slots) and
+                                            bool(np.array_equal(g["out"][:out_used].cpu().numpy(), h["out"][:out_used])) and
+                                            g["used"].cpu().tolist() == [hu[0].value, hu[1].value, hu[2].value])
+        settle(f_rx, 500)
+        med, mean = timed(f_rx, reps)
+        src_t, dst_t = d[:out_used], torch.empty(out_used, dtype=torch.uint8, device=dev)
+        f_copy = lambda: dst_t.copy_(src_t)  # noqa: E731
+        settle(f_copy, 300)
+        cp, _ = timed(f_copy, reps)
+        out.append({"config": f"f7: device packet receive of the parse_mtu batch's datagrams, {name} receivers "
+                              f"({nr} receivers, window {W})",
+                    "frames": n, "items": k, "receivers": nr, "slots": ns, "delivered": delivered, "bytes_delivered": out_used,
+                    "status_counts": h["res"]["status_count"].sum(axis=0).tolist(), "receive_ms": round(med, 4),
+                    "receive_mean_ms": round(mean, 4), "ns_per_item": round(med * 1e6 / max(k, 1), 4),
+                    "host_receive_1t_ms": round(host_ms[1], 2), "host_receive_16t_ms": round(host_ms[16], 2),
+                    "host_1t_over_gpu": round(host_ms[1] / med, 1), "host_16t_over_gpu": round(host_ms[16] / med, 1),
+                    "d2d_copy_ms": round(cp, 4), "d2d_copy_GB_s": round(2 * out_used / cp / 1e-3 / 1e9, 1),
+                    "receive_over_d2d_copy": round(med / cp, 2), **extra})
+        del g, dst_t
+        torch.cuda.empty_cache()
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -609,7 +730,7 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what in ("pack", "emit"):
+        elif what in ("pack", "emit", "receive"):
             for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:

@@ -41,9 +41,22 @@ UFC_SEND_TIME_SENSITIVE, UFC_SEND_UNRELIABLE, UFC_SEND_PERSISTENT, UFC_SEND_RELI
 UFC_NO_PARENT = 0xFFFFFFFF
 UFC_EMIT_DONE, UFC_EMIT_WINDOW_LIMITED, UFC_EMIT_ALLOC_LIMITED, UFC_EMIT_BAD_PACKET, UFC_EMIT_BAD_RANGE = 0, 1, 2, 3, 4
 UFC_PACKET_NOT_REACHED, UFC_PACKET_EMITTED, UFC_PACKET_DROPPED = 0, 1, 2
+# the batched packet receives (include/uflow_frame_codec.h): a slot's assembly state and flags, a datagram's
+# status, why a receiver stopped
+UFC_RX_ASM_OPEN, UFC_RX_ASM_CLOSED, UFC_RX_ASM_ACTIVE = 0, 1, 2
+UFC_RX_SLOT_ENTRY, UFC_RX_SLOT_DATA, UFC_RX_SLOT_DUD = 1, 2, 4
+UFC_RX_PACKET_DUD = 1
+(UFC_RX_NOT_HANDLED, UFC_RX_STORED, UFC_RX_COMPLETED, UFC_RX_DUD, UFC_RX_DROPPED_INVALID, UFC_RX_DROPPED_WINDOW,
+ UFC_RX_DROPPED_CHANNEL, UFC_RX_DROPPED_CLOSED, UFC_RX_DROPPED_MISMATCH, UFC_RX_DROPPED_DUPLICATE,
+ UFC_RX_DROPPED_BAD_SRC) = range(11)
+UFC_RX_STATUS_COUNT = 11
+UFC_RX_DONE, UFC_RX_BAD_STATE = 0, 1
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
+_V, _Z = ctypes.c_void_p, ctypes.c_size_t
+_RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, _Z, _V, _V, _V, _Z, _V,
+            _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -149,6 +162,12 @@ _SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p]),
+    # infos, n_frames, frame_accept, items, n_items, src_base, payload, payload_len, frame_first, receivers,
+    # n_receivers, slots, slot_first, n_slots, carry_in, carry_in_len, carry_out, carry_cap, carry_first, carry_used,
+    # packets, packets_cap, packet_first, packets_used, out_bytes, out_cap, out_used, item_status, results,
+    # receivers_out, then nthreads (host) / ctx first and stream last (device)
+    "ufc_receive_packets_host": (ctypes.c_int, _RX_ARGS + [ctypes.c_int]),
+    "ufc_receive_packets_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RX_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -197,6 +216,36 @@ class SenderResult(ctypes.Structure):
     _fields_ = [("item_first", ctypes.c_uint32), ("item_count", ctypes.c_uint32), ("packets_consumed", ctypes.c_uint32),
                 ("packets_emitted", ctypes.c_uint32), ("packets_dropped", ctypes.c_uint32), ("stop", ctypes.c_uint32),
                 ("bytes_dropped", ctypes.c_uint64)]
+
+
+class Receiver(ctypes.Structure):
+    _fields_ = [("base_id", ctypes.c_uint32), ("end_id", ctypes.c_uint32), ("window_size", ctypes.c_uint32),
+                ("window_ready", ctypes.c_uint8), ("deliver", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+                ("resync_id", ctypes.c_uint32), ("reserved2", ctypes.c_uint32), ("alloc", ctypes.c_uint64),
+                ("max_alloc", ctypes.c_uint64), ("channel_ready_flags", ctypes.c_uint64),
+                ("channel_base_id", ctypes.c_uint32 * 64), ("channel_packet_count", ctypes.c_uint32 * 64)]
+
+
+class RxSlot(ctypes.Structure):
+    _fields_ = [("data_offset", ctypes.c_uint64), ("data_len", ctypes.c_uint32), ("asm_size", ctypes.c_uint32),
+                ("asm_window_parent_lead", ctypes.c_uint16), ("asm_channel_parent_lead", ctypes.c_uint16),
+                ("asm_last_fragment_id", ctypes.c_uint16), ("asm_received", ctypes.c_uint16),
+                ("rx_window_parent_lead", ctypes.c_uint16), ("rx_channel_parent_lead", ctypes.c_uint16),
+                ("asm_state", ctypes.c_uint8), ("asm_channel_id", ctypes.c_uint8), ("rx_channel_id", ctypes.c_uint8),
+                ("rx_flags", ctypes.c_uint8)]
+
+
+class RxPacket(ctypes.Structure):
+    _fields_ = [("out_offset", ctypes.c_uint64), ("sequence_id", ctypes.c_uint32), ("len", ctypes.c_uint32),
+                ("channel_id", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+                ("reserved2", ctypes.c_uint32)]
+
+
+class ReceiverResult(ctypes.Structure):
+    _fields_ = [("packet_first", ctypes.c_uint32), ("packet_count", ctypes.c_uint32),
+                ("status_count", ctypes.c_uint32 * 11), ("packets_completed", ctypes.c_uint32),
+                ("packets_dud", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("bytes_delivered", ctypes.c_uint64)]
 
 
 class Builder(ctypes.Structure):

@@ -312,6 +312,85 @@ class FrameCrcEngine:
                                             _ptr(used), self._stream(stream)), "ufc_emit_packets_varlen")
         return items, flush_first, packet_results, sender_results, senders_out, used
 
+    # ---- PacketReceiver's step for many receivers, on the device (uflow_frame_codec.h) ----
+    def receive_packets(self, infos, items, payload, frame_first, receivers, slots, slot_first, carry_in,
+                        src_base=None, frame_accept=None, carry_cap=None, out_cap=None, packets_cap=None,
+                        carry_out=None, out_bytes=None, packets=None, receivers_out=None, want_item_status=True,
+                        stream=None):
+        """ufc_receive_packets_varlen: one step of PacketReceiver (handle_datagram, receive, resynchronize;
+        src/half_connection/packet_receiver/mod.rs:142-435) for every receiver.  infos uint8[n_frames, 32] and
+        items uint8[n_items, 24] (what parse_varlen returns), payload uint8 (the frames' bytes) with src_base
+        int64[n_frames] (the parse's offsets; None: zero), frame_first int64[n_receivers + 1] (CSR over the frames),
+        receivers uint8[n_receivers, 560] (ufc_receiver records, uflow_amd.frame.RECEIVER_DTYPE), slots
+        uint8[n_slots, 32] (ufc_rx_slot, updated in place), slot_first int64[n_receivers + 1], carry_in uint8 (the
+        carry arena the slots point into), frame_accept uint8[n_frames] or None.  Returns a dict of device tensors:
+        packets uint8[packets_cap, 24], packet_first int64[n + 1], packets_used, out_bytes, out_used, carry_out,
+        carry_first int64[n + 1], carry_used, item_status uint8[n_items] or None, results uint8[n, 80],
+        receivers_out uint8[n, 560] (may be given as `receivers`).  Caps that are not given are what the step needs,
+        found by a first pass on a copy of the state with caps of zero, whose counts are read back (this waits for
+        the stream; give the caps or the tensors to stay asynchronous: an ACTIVE slot holds its whole fragment
+        buffer, so the carry has no small bound from the batch's sizes alone, see the header); tensors given for
+        carry_out, out_bytes and packets are written into.
+        Pass carry_out[:carry_used] as the next step's carry_in (carry_out must not overlap carry_in)."""
+        n_frames, n_items, n, n_slots = infos.shape[0], items.shape[0], receivers.shape[0], slots.shape[0]
+        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._check("payload", payload, (torch.uint8,), 0)
+        self._check("frame_first", frame_first, (torch.int64,), n + 1)
+        self._check("receivers", receivers, (torch.uint8,), 560 * n)
+        self._check("slots", slots, (torch.uint8,), 32 * n_slots)
+        self._check("slot_first", slot_first, (torch.int64,), n + 1)
+        self._check("carry_in", carry_in, (torch.uint8,), 0)
+        self._check("src_base", src_base, (torch.int64,), n_frames)
+        self._check("frame_accept", frame_accept, (torch.uint8,), n_frames)
+        self._check("receivers_out", receivers_out, (torch.uint8,), 560 * n)
+        for name, t in (("carry_out", carry_out), ("out_bytes", out_bytes), ("packets", packets)):
+            self._check(name, t, (torch.uint8,), 0)
+        def p(t):
+            return _ptr(t) if t is not None and t.numel() else None
+
+        def size(t, width=1):
+            return 0 if t is None else t.numel() // width
+
+        def call(slots_, carry_out_, out_bytes_, packets_, status_, receivers_out_):
+            check(lib().ufc_receive_packets_varlen(
+                self._ctx, p(infos), n_frames, p(frame_accept), p(items), n_items, p(src_base), p(payload),
+                payload.numel(), _ptr(frame_first), p(receivers), n, p(slots_), _ptr(slot_first), n_slots, p(carry_in),
+                carry_in.numel(), p(carry_out_), size(carry_out_), _ptr(carry_first),
+                ctypes.c_void_p(used.data_ptr() + 16), p(packets_), size(packets_, 24), _ptr(packet_first),
+                ctypes.c_void_p(used.data_ptr()), p(out_bytes_), size(out_bytes_), ctypes.c_void_p(used.data_ptr() + 8),
+                p(status_), p(results), p(receivers_out_), self._stream(stream)), "ufc_receive_packets_varlen")
+
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            def zeros(*shape, dtype=torch.uint8):
+                return torch.zeros(shape, dtype=dtype, device=self.device)
+            carry_first = zeros(n + 1, dtype=torch.int64)
+            packet_first = zeros(n + 1, dtype=torch.int64)
+            used = zeros(3, dtype=torch.int64)
+            results = zeros(n, 80)
+            need = [(carry_out, carry_cap), (out_bytes, out_cap), (packets, packets_cap)]
+            if n and any(t is None and cap is None for t, cap in need):
+                # The used counts are exact whatever the caps: a first pass on a copy of the state, with none.
+                # Reading them back waits for the stream: give the caps (or the tensors) to stay asynchronous.
+                call(slots.clone(), None, None, None, None, zeros(n, 560))
+                u = used.cpu().tolist()
+                packets_cap = u[0] if packets_cap is None else packets_cap
+                out_cap = u[1] if out_cap is None else out_cap
+                carry_cap = u[2] if carry_cap is None else carry_cap
+            if carry_out is None:
+                carry_out = zeros(int(carry_cap or 0))
+            if out_bytes is None:
+                out_bytes = zeros(int(out_cap or 0))
+            if packets is None:
+                packets = zeros(int(packets_cap or 0), 24)
+            if receivers_out is None:
+                receivers_out = zeros(n, 560)
+            item_status = zeros(n_items) if want_item_status else None
+        call(slots, carry_out, out_bytes, packets, item_status, receivers_out)
+        return {"packets": packets, "packet_first": packet_first, "packets_used": used[0:1], "out_bytes": out_bytes,
+                "out_used": used[1:2], "carry_out": carry_out, "carry_first": carry_first, "carry_used": used[2:3],
+                "item_status": item_status, "results": results, "receivers_out": receivers_out}
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

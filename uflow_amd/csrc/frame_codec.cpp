@@ -567,3 +567,99 @@ int ufc_emit_packets_host(const ufc_packet* packets, size_t n_packets, const uin
 }
 
 }  // extern "C"
+
+// ---- batched host receive ----
+namespace {
+// body(a, b) over contiguous receiver ranges, up to nthreads of them (a receiver's walk is work enough).
+template <class F>
+void for_receivers(size_t n, int nthreads, const F& body) {
+  size_t T = nthreads > 0 ? (size_t)nthreads : 1;
+  T = std::max<size_t>(1, std::min(T, n));
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < T; t++) th.emplace_back([&, t] { body(n * t / T, n * (t + 1) / T); });
+  body(0, n / T);
+  for (auto& x : th) x.join();
+}
+// One copy segment, clipped at its destination's cap.
+void rx_copy(const ufc_codec::RxArgs& a, const ufc_codec::RxSegment& sg) {
+  if (!sg.len) return;
+  const bool to_carry = (sg.kinds & ufc_codec::kRxDstCarry) != 0;
+  const uint64_t cap = to_carry ? a.carry_cap : a.out_cap;
+  if (sg.dst >= cap) return;
+  const uint64_t len = std::min<uint64_t>(sg.len, cap - sg.dst);
+  const uint8_t* src = ((sg.kinds & ufc_codec::kRxSrcCarry) ? a.carry_in : a.payload) + sg.src;
+  std::memcpy((to_carry ? a.carry_out : a.out_bytes) + sg.dst, src, len);
+}
+}  // namespace
+
+extern "C" {
+
+int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const uint8_t* frame_accept,
+                             const ufc_item* items, size_t n_items, const uint64_t* src_base, const uint8_t* payload,
+                             size_t payload_len, const uint64_t* frame_first, const ufc_receiver* receivers,
+                             size_t n_receivers, ufc_rx_slot* slots, const uint64_t* slot_first, size_t n_slots,
+                             const uint8_t* carry_in, size_t carry_in_len, uint8_t* carry_out, size_t carry_cap,
+                             uint64_t* carry_first, uint64_t* carry_used, ufc_rx_packet* packets, size_t packets_cap,
+                             uint64_t* packet_first, uint64_t* packets_used, uint8_t* out_bytes, size_t out_cap,
+                             uint64_t* out_used, uint8_t* item_status, ufc_receiver_result* results,
+                             ufc_receiver* receivers_out, int nthreads) {
+  if (n_receivers == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!frame_first || !receivers || !receivers_out || !slot_first || !carry_first || !carry_used || !packet_first ||
+      !packets_used || !out_used || !results || (!infos && n_frames) || (!items && n_items) ||
+      (!payload && payload_len) || (!slots && n_slots) || (!carry_in && carry_in_len) || (!carry_out && carry_cap) ||
+      (!packets && packets_cap) || (!out_bytes && out_cap) || n_frames >= lim || n_items >= lim || n_receivers >= lim ||
+      n_slots >= lim || ((uintptr_t)carry_in & 7) || ((uintptr_t)carry_out & 7))  // (the bit words are read as uint64)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RxArgs a{infos, n_frames, frame_accept, items, n_items, src_base, payload, payload_len, frame_first,
+                            receivers, n_receivers, slots, slot_first, n_slots, carry_in, carry_in_len, carry_out,
+                            carry_cap, carry_first, carry_used, packets, packets_cap, packet_first, packets_used,
+                            out_bytes, out_cap, out_used, item_status, results, receivers_out};
+  std::vector<ufc_codec::RxPlan> plans(n_slots);
+  std::vector<uint8_t> own_status(item_status ? 0 : n_items);
+  uint8_t* status = item_status ? item_status : own_status.data();
+  std::vector<unsigned long long> table(ufc_codec::rx_dup_entries(n_items), 0ull);
+  const ufc_codec::RxDupSet dups{table.data(), table.size() - 1};
+  std::vector<uint64_t> out_first(n_receivers + 1);
+  // Pass 1: every receiver's step; its counts into the three CSR arrays, then their exclusive sums.
+  for_receivers(n_receivers, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) {
+      if (receivers_out != receivers) receivers_out[r] = receivers[r];
+      uint64_t c[3];
+      ufc_codec::rx_walk(a, r, plans.data(), status, dups, c);
+      packet_first[r + 1] = c[0];
+      out_first[r + 1] = c[1];
+      carry_first[r + 1] = c[2];
+    }
+  });
+  uint64_t np = 0, nb = 0, nc = 0;
+  for (size_t r = 0; r < n_receivers; r++) {
+    const uint64_t c0 = packet_first[r + 1], c1 = out_first[r + 1], c2 = carry_first[r + 1];
+    packet_first[r] = np;
+    out_first[r] = nb;
+    carry_first[r] = nc;
+    np += c0;
+    nb += c1;
+    nc += c2;
+  }
+  packet_first[n_receivers] = np;
+  out_first[n_receivers] = nb;
+  carry_first[n_receivers] = nc;
+  *packets_used = np;
+  *out_used = nb;
+  *carry_used = nc;
+  // Pass 2: records, layout, bits and segments; then the copies, the slots' before the datagrams'.
+  std::vector<ufc_codec::RxSegment> segs(2 * n_slots + n_items);
+  for_receivers(n_receivers, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) ufc_codec::rx_finish(a, r, plans.data(), status, out_first[r], segs.data(), nullptr);
+  });
+  for_ranges(2 * n_slots, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; k++) rx_copy(a, segs[k]);
+  });
+  for_ranges(n_items, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; k++) rx_copy(a, segs[2 * n_slots + k]);
+  });
+  return UFC_OK;
+}
+
+}  // extern "C"

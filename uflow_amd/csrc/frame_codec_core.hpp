@@ -1,7 +1,8 @@
 // frame_codec_core.hpp -- the payload parse of Frame::read (everything after the CRC gate), written
 // once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip); further down the
 // encode for the batched builds (frame_build.hip), the emitters' arithmetic for the batched packs
-// (frame_pack.hip) and the packet sender's for the batched packet emits (packet_emit.hip).
+// (frame_pack.hip), the packet sender's for the batched packet emits (packet_emit.hip) and the packet receiver's
+// step for the batched packet receives (packet_receive.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -541,6 +542,786 @@ UFC_HD ufc_item emit_item(const ufc_packet& p, uint32_t seq, uint16_t window_par
   it.form = (uint8_t)(hs == 6 ? 0 : (hs == 9 ? 1 : 2));
   it.flags = datagram_is_valid(it) ? UFC_ITEM_VALID : 0;
   return it;
+}
+
+// ---- receive: PacketReceiver (src/half_connection/packet_receiver/mod.rs:142-435), AssemblyWindow
+// (assembly_window/mod.rs:69-199) and FragmentBuffer (fragment_buffer.rs:12-57), for the batched packet receives
+// (host: frame_codec.cpp; GPU: packet_receive.hip) ----
+//
+// Both forms run the same three passes over caller-owned state:
+//   walk    per receiver, serial: the step (resynchronize, handle_datagram per item, receive) on the header and
+//           the slots in place; a plan record per slot remembers what the copy needs (where the slot's bytes
+//           were on entry, whether its packet was assembled in this step, its place in the delivery order); three
+//           counts per receiver: delivered packets, delivered bytes, carry bytes;
+//   (exclusive sums of the counts over the receivers: packet_first, the out offsets, carry_first)
+//   finish  per receiver: the records, the slots' new data_offset, the received-bits words, and one copy segment
+//           per stored datagram and two per slot (held packet, fragment buffer) with absolute offsets;
+//   copy    the slots' segments, then the datagrams' (a new fragment overwrites the unspecified bytes a carried
+//           fragment buffer has in its place).
+
+// packet_id::sub / add (src/packet_id.rs).
+UFC_HD uint32_t packet_id_sub(uint32_t a, uint32_t b) { return (a - b) & kPacketIdMask; }
+UFC_HD uint32_t packet_id_add(uint32_t a, uint32_t b) { return (a + b) & kPacketIdMask; }
+// packet_alloc_size (assembly_window/mod.rs:53-60).
+UFC_HD uint64_t packet_alloc_size(uint32_t fragment_id_last, uint32_t data_len) {
+  return fragment_id_last ? ((uint64_t)fragment_id_last + 1) * UFC_MAX_FRAGMENT_SIZE : (uint64_t)data_len;
+}
+// "The parent is not in the way": lead == 0 || lead > delta (mod.rs:206, 214, 336, 385).
+UFC_HD bool lead_clears(uint32_t lead, uint32_t delta) { return lead == 0 || lead > delta; }
+// alloc + a > max_alloc (assembly_window/mod.rs:95), max_alloc already rounded, without overflow.
+UFC_HD bool rx_alloc_fails(uint64_t alloc, uint64_t a, uint64_t max_alloc) {
+  return alloc > max_alloc || a > max_alloc - alloc;
+}
+UFC_HD uint64_t align8(uint64_t v) { return (v + 7) & ~(uint64_t)7; }
+// A FragmentBuffer of n fragments in the carry: n * 1448 data bytes, then ceil(n / 64) words.
+UFC_HD uint64_t rx_frag_data_bytes(uint32_t n) { return (uint64_t)n * UFC_MAX_FRAGMENT_SIZE; }
+UFC_HD uint64_t rx_frag_bytes(uint32_t n) { return rx_frag_data_bytes(n) + 8ull * ((n + 63) / 64); }
+UFC_HD uint32_t rx_slot_held(const ufc_rx_slot& s) {
+  return (s.rx_flags & (UFC_RX_SLOT_DATA | UFC_RX_SLOT_DUD)) == UFC_RX_SLOT_DATA ? s.data_len : 0u;
+}
+UFC_HD uint32_t rx_slot_nfrag(const ufc_rx_slot& s) {
+  return s.asm_state == UFC_RX_ASM_ACTIVE ? (uint32_t)s.asm_last_fragment_id + 1 : 0u;
+}
+// A slot's region in the carry.
+UFC_HD uint64_t rx_slot_region(const ufc_rx_slot& s) {
+  const uint32_t n = rx_slot_nfrag(s);
+  return align8(rx_slot_held(s)) + (n ? rx_frag_bytes(n) : 0);
+}
+
+struct RxArgs {
+  const ufc_frame_info* infos;
+  uint64_t n_frames;
+  const uint8_t* frame_accept;  // nullable
+  const ufc_item* items;
+  uint64_t n_items;
+  const uint64_t* src_base;  // nullable
+  const uint8_t* payload;
+  uint64_t payload_len;
+  const uint64_t* frame_first;
+  const ufc_receiver* receivers;
+  uint64_t n_receivers;
+  ufc_rx_slot* slots;
+  const uint64_t* slot_first;
+  uint64_t n_slots;
+  const uint8_t* carry_in;
+  uint64_t carry_in_len;
+  uint8_t* carry_out;
+  uint64_t carry_cap;
+  uint64_t* carry_first;
+  uint64_t* carry_used;
+  ufc_rx_packet* packets;
+  uint64_t packets_cap;
+  uint64_t* packet_first;
+  uint64_t* packets_used;
+  uint8_t* out_bytes;
+  uint64_t out_cap;
+  uint64_t* out_used;
+  uint8_t* item_status;  // nullable
+  ufc_receiver_result* results;
+  ufc_receiver* receivers_out;
+};
+
+// What the copy needs to know of a slot (48 bytes).
+enum RxPlanFlags : uint32_t {
+  kRxHeldIn = 1,        // the receive-window packet's bytes are the ones held in carry_in
+  kRxAsmCarry = 2,      // the fragment buffer in carry_in feeds this step's assembly
+  kRxCompletedNow = 4,  // the receive-window packet was assembled in this step
+  kRxPktOut = 8,        // finish: the packet's bytes go to out_bytes at pkt_dst ...
+  kRxPktCarry = 16,     // ... or to carry_out
+  kRxFrag = 32          // finish: ACTIVE afterwards, its buffer at frag_dst in carry_out
+};
+constexpr uint32_t kRxNotDelivered = 0xFFFFFFFFu;
+struct RxPlan {
+  uint64_t in_offset;   // the slot's region in carry_in on entry
+  uint64_t pkt_dst;     // walk: a delivered packet's bytes relative to the receiver's first; finish: absolute
+  uint64_t frag_dst;
+  uint32_t in_held_len, in_nfrag;
+  uint32_t deliver_idx;  // place in the receiver's delivery order, or kRxNotDelivered
+  uint32_t seq, len;     // the delivered packet
+  uint8_t flags, channel, pkt_flags, pad;
+};
+static_assert(sizeof(RxPlan) == 48, "plan record");
+
+// One copy: len bytes from payload (kRxSrcCarry clear) or carry_in to out_bytes (kRxDstCarry clear) or
+// carry_out, clipped at the destination's cap by the copy.
+constexpr uint32_t kRxSrcCarry = 1, kRxDstCarry = 2;
+struct RxSegment {
+  uint64_t src, dst;
+  uint32_t len, kinds;
+};
+static_assert(sizeof(RxSegment) == 24, "segment record");
+// Segment indices: two per slot first (they are copied first), then one per datagram.
+UFC_HD uint64_t rx_slot_segment(uint64_t slot, uint32_t which) { return 2 * slot + which; }
+UFC_HD uint64_t rx_item_segment(uint64_t n_slots, uint64_t g) { return 2 * n_slots + g; }
+
+// First arrivals per (receiver, slot, fragment) within a step: an open-addressed table of at least twice as
+// many entries as there are datagrams (a power of two), zeroed before the walk.  Receivers insert concurrently.
+struct RxDupSet {
+  unsigned long long* table;
+  uint64_t mask;
+  // true: the key was new.
+  UFC_HD bool insert(uint64_t r, uint32_t slot, uint32_t fragment) const {
+    const unsigned long long key = ((unsigned long long)r << 28 | (unsigned long long)slot << 16 | fragment) + 1;
+    uint64_t h = key * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 29;
+    for (uint64_t i = h & mask;; i = (i + 1) & mask) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const unsigned long long old = atomicCAS(&table[i], 0ull, key);
+#else
+      unsigned long long old = 0;
+      __atomic_compare_exchange_n(&table[i], &old, key, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+#endif
+      if (old == 0) return true;
+      if (old == key) return false;
+    }
+  }
+};
+UFC_HD uint64_t rx_dup_entries(uint64_t n_items) {
+  uint64_t c = 64;
+  while (c < 2 * n_items) c <<= 1;
+  return c;
+}
+
+// Whether frame i of the batch counts (its datagrams are handled).
+UFC_HD bool rx_frame_counts(const RxArgs& a, uint64_t i) {
+  const ufc_frame_info& f = a.infos[i];
+  return f.ok && f.kind == UFC_FRAME_DATA && (!a.frame_accept || a.frame_accept[i] != 0);
+}
+
+// AssemblyWindow::clear (assembly_window/mod.rs:185-198) of one slot.
+UFC_HD void rx_clear_slot(ufc_rx_slot& s, RxPlan& p, uint64_t& alloc) {
+  if (s.asm_state == UFC_RX_ASM_CLOSED) {
+    alloc -= s.asm_size;
+  } else if (s.asm_state == UFC_RX_ASM_ACTIVE) {
+    alloc -= rx_frag_data_bytes((uint32_t)s.asm_last_fragment_id + 1);
+    p.flags &= (uint8_t)~kRxAsmCarry;  // the buffer goes with it
+  }
+  s.asm_state = UFC_RX_ASM_OPEN;
+  s.asm_size = 0;
+  s.asm_window_parent_lead = s.asm_channel_parent_lead = s.asm_last_fragment_id = s.asm_received = 0;
+  s.asm_channel_id = 0;
+}
+
+// advance_window (mod.rs:244-282) on the receiver's working header R (in receivers_out).
+inline __host__ __device__ void rx_advance_window(ufc_receiver& R, ufc_rx_slot* slots, RxPlan* plan, uint32_t new_base,
+                                                  uint32_t& advanced) {
+  const uint32_t mask = R.window_size - 1;
+  const uint32_t delta = packet_id_sub(new_base, R.base_id);
+  if (packet_id_sub(R.end_id, R.base_id) < delta) R.end_id = new_base;
+  uint64_t alloc = R.alloc;
+  for (uint32_t id = R.base_id; id != new_base; id = packet_id_add(id, 1)) {
+    ufc_rx_slot& s = slots[id & mask];
+    s.rx_flags &= (uint8_t)~UFC_RX_SLOT_ENTRY;
+    rx_clear_slot(s, plan[id & mask], alloc);
+  }
+  R.alloc = alloc;
+  // try_unset_channel_base_id over (base, new_base]: the channels whose base lead is in 1..=delta.
+  for (uint32_t c = 0; c < UFC_MAX_CHANNELS; c++) {
+    const uint32_t cb = R.channel_base_id[c];
+    if (cb == UFC_NO_PARENT) continue;
+    const uint32_t lead = packet_id_sub(cb, R.base_id);
+    if (lead >= 1 && lead <= delta) R.channel_base_id[c] = UFC_NO_PARENT;
+  }
+  advanced += delta;
+  R.base_id = new_base;
+}
+
+// The step of receiver r in four parts, run one after the other by rx_walk (the host form, and the fallback of the
+// device form) and by separate launches on the device: begin (the state check, the plan records, resynchronize),
+// items (handle_datagram per item), receive (delivery and the window advance; serial here, in tiles of 64 ids in
+// rx_receive_tiles below) and end (the carry size, the counts).  R = a.receivers_out[r] already holds a copy of
+// the input header.  status: one byte per item (a.item_status or scratch of the same size).  begin returns false
+// for BAD_STATE (nothing done but the result, and the other parts do nothing).
+inline __host__ __device__ bool rx_walk_begin(const RxArgs& a, uint64_t r, RxPlan* plans) {
+  ufc_receiver& R = a.receivers_out[r];
+  ufc_receiver_result& res = a.results[r];  // (counted in place: no indexed array of the thread's own)
+  res = ufc_receiver_result{};
+  const uint32_t W = R.window_size;
+  const uint64_t ff0 = a.frame_first[r], ff1 = a.frame_first[r + 1];
+  const uint64_t s0 = a.slot_first[r], s1 = a.slot_first[r + 1];
+  bool bad = W == 0 || W > 4096 || (W & (W - 1)) != 0 || R.base_id > kPacketIdMask || R.end_id > kPacketIdMask ||
+             ff0 > ff1 || ff1 > a.n_frames || s0 > s1 || s1 > a.n_slots || s1 - s0 < W;
+  for (uint64_t i = ff0; !bad && i < ff1; i++) {
+    const ufc_frame_info& f = a.infos[i];
+    if (f.ok && (uint64_t)f.item_first + f.item_count > a.n_items) bad = true;
+  }
+  ufc_rx_slot* slots = a.slots + s0;
+  RxPlan* plan = plans + s0;
+  for (uint32_t j = 0; !bad && j < W; j++) {
+    const ufc_rx_slot& s = slots[j];
+    const uint64_t region = rx_slot_region(s);
+    if (s.asm_state > UFC_RX_ASM_ACTIVE || s.asm_channel_id >= UFC_MAX_CHANNELS || s.rx_channel_id >= UFC_MAX_CHANNELS ||
+        (region && ((s.data_offset & 7) || s.data_offset > a.carry_in_len || region > a.carry_in_len - s.data_offset)))
+      bad = true;
+  }
+  if (bad) {
+    res.stop = UFC_RX_BAD_STATE;
+    return false;
+  }
+  const uint32_t mask = W - 1;
+  for (uint32_t j = 0; j < W; j++) {
+    const ufc_rx_slot& s = slots[j];
+    RxPlan p{};
+    p.in_offset = s.data_offset;
+    p.in_held_len = rx_slot_held(s);
+    p.in_nfrag = rx_slot_nfrag(s);
+    p.flags = (uint8_t)((p.in_held_len ? kRxHeldIn : 0) | (p.in_nfrag ? kRxAsmCarry : 0));
+    p.deliver_idx = kRxNotDelivered;
+    plan[j] = p;
+  }
+
+  // 1. resynchronize (mod.rs:408-435).
+  if (R.resync_id != UFC_NO_PARENT) {
+    const uint32_t next = R.resync_id & kPacketIdMask;
+    if (packet_id_sub(next, R.base_id) <= W) {
+      uint32_t id = R.base_id;
+      while (id != next && !(slots[id & mask].rx_flags & UFC_RX_SLOT_ENTRY)) id = packet_id_add(id, 1);
+      rx_advance_window(R, slots, plan, id, res.advanced);
+    }
+  }
+  res.stop = UFC_RX_DONE;
+  return true;
+}
+
+// The verdicts of handle_datagram that do not depend on the order of arrival: base_id and the channel bases are
+// constant while a step's datagrams are handled (they change in receive() only), so validity, the payload
+// range, the window test (mod.rs:162) and the channel test (:167) are a function of the item alone.  Returns the
+// item's status, or kRxToAssembly for a datagram that goes on to try_add.
+constexpr uint8_t kRxToAssembly = 0xFF;
+UFC_HD uint8_t rx_item_verdict(const RxArgs& a, const ufc_receiver& R, const ufc_item& it, uint64_t sb) {
+  if (!datagram_is_valid(it) || it.id > kPacketIdMask) return UFC_RX_DROPPED_INVALID;
+  if (sb > a.payload_len || it.data_offset > a.payload_len - sb || it.data_len > a.payload_len - sb - it.data_offset)
+    return UFC_RX_DROPPED_BAD_SRC;
+  const uint32_t base = R.base_id, cb = R.channel_base_id[it.channel_id];
+  const uint32_t cbid = cb != UFC_NO_PARENT ? cb : base;
+  const uint32_t packet_lead = packet_id_sub(it.id, base);
+  if (packet_lead >= R.window_size) return UFC_RX_DROPPED_WINDOW;
+  if (packet_lead < packet_id_sub(cbid, base)) return UFC_RX_DROPPED_CHANNEL;
+  return kRxToAssembly;
+}
+// The verdicts of frame i of receiver r, into status (the item-parallel pass of the device form: any lane may
+// take any frame of a receiver whose begin passed).
+UFC_HD void rx_frame_verdicts(const RxArgs& a, uint64_t r, uint64_t i, uint8_t* verdicts) {
+  const ufc_frame_info& f = a.infos[i];
+  if (!f.ok) return;
+  const bool counts_ = rx_frame_counts(a, i);
+  const uint64_t sb = a.src_base ? a.src_base[i] : 0;
+  for (uint64_t g = f.item_first, ge = (uint64_t)f.item_first + f.item_count; g < ge; g++)
+    verdicts[g] = counts_ ? rx_item_verdict(a, a.receivers_out[r], a.items[g], sb) : (uint8_t)UFC_RX_NOT_HANDLED;
+}
+
+// 2. handle_datagram (mod.rs:142-218) over try_add (assembly_window/mod.rs:83-183).  pre (nullable): one byte per
+// item, rx_frame_verdicts' result for every item of the receiver's frames (its own array, not status: frames of
+// one receiver that share items, which no parse produces, then still get the serial walk's answer).
+inline __host__ __device__ void rx_walk_items(const RxArgs& a, uint64_t r, RxPlan* plans, uint8_t* status,
+                                              const RxDupSet& dups, const uint8_t* pre) {
+  ufc_receiver& R = a.receivers_out[r];
+  ufc_receiver_result& res = a.results[r];
+  if (res.stop != UFC_RX_DONE) return;
+  const uint32_t W = R.window_size, mask = W - 1;
+  const uint64_t ff0 = a.frame_first[r], ff1 = a.frame_first[r + 1];
+  ufc_rx_slot* slots = a.slots + a.slot_first[r];
+  RxPlan* plan = plans + a.slot_first[r];
+  const uint64_t max_alloc = emit_max_alloc(R.max_alloc);
+  const uint32_t base = R.base_id;
+  for (uint64_t i = ff0; i < ff1; i++) {
+    const ufc_frame_info& f = a.infos[i];
+    if (!f.ok) continue;
+    const bool counts_ = rx_frame_counts(a, i);
+    const uint64_t sb = a.src_base ? a.src_base[i] : 0;
+    for (uint64_t g = f.item_first, ge = (uint64_t)f.item_first + f.item_count; g < ge; g++) {
+      if (!counts_) {
+        status[g] = UFC_RX_NOT_HANDLED;
+        res.status_count[UFC_RX_NOT_HANDLED]++;
+        continue;
+      }
+      uint8_t st = pre ? pre[g] : kRxToAssembly;
+      if (pre && st != kRxToAssembly) {  // dropped by the verdict pass: the item itself is not read again
+        if (st >= UFC_RX_STATUS_COUNT) st = UFC_RX_NOT_HANDLED;  // (only where receivers share frames: unspecified)
+        status[g] = st;
+        res.status_count[st]++;
+        continue;
+      }
+      const ufc_item it = a.items[g];
+      if (!pre) st = rx_item_verdict(a, R, it, sb);
+      bool packet = false, dud = false;
+      uint32_t packet_len = 0;
+      const uint32_t ch = it.channel_id;
+      if (st == kRxToAssembly) {
+        const uint32_t cbid = R.channel_base_id[ch] != UFC_NO_PARENT ? R.channel_base_id[ch] : base;
+        const uint32_t packet_lead = packet_id_sub(it.id, base);
+        {
+          const uint32_t idx = it.id & mask;
+          ufc_rx_slot& s = slots[idx];
+          RxPlan& p = plan[idx];
+          if (s.asm_state == UFC_RX_ASM_OPEN) {
+            const uint64_t a_sz = packet_alloc_size(it.fragment_id_last, it.data_len);
+            if (rx_alloc_fails(R.alloc, a_sz, max_alloc)) {
+              s.asm_state = UFC_RX_ASM_CLOSED;
+              s.asm_size = 0;
+              st = UFC_RX_DUD;
+              packet = dud = true;
+            } else {
+              R.alloc += a_sz;
+              if (it.fragment_id_last == 0) {
+                s.asm_state = UFC_RX_ASM_CLOSED;
+                s.asm_size = (uint32_t)a_sz;
+                st = UFC_RX_COMPLETED;
+                packet = true;
+                packet_len = it.data_len;
+              } else {
+                s.asm_state = UFC_RX_ASM_ACTIVE;
+                s.asm_channel_id = it.channel_id;
+                s.asm_window_parent_lead = it.window_parent_lead;
+                s.asm_channel_parent_lead = it.channel_parent_lead;
+                s.asm_last_fragment_id = it.fragment_id_last;
+                s.asm_received = 1;
+                s.asm_size = it.data_len;
+                (void)dups.insert(r, idx, it.fragment_id);
+                st = UFC_RX_STORED;
+              }
+            }
+          } else if (s.asm_state == UFC_RX_ASM_CLOSED) {
+            st = UFC_RX_DROPPED_CLOSED;
+          } else if (it.channel_id != s.asm_channel_id || it.window_parent_lead != s.asm_window_parent_lead ||
+                     it.channel_parent_lead != s.asm_channel_parent_lead ||
+                     it.fragment_id_last != s.asm_last_fragment_id) {
+            st = UFC_RX_DROPPED_MISMATCH;
+          } else {
+            const uint32_t n = (uint32_t)s.asm_last_fragment_id + 1;
+            bool seen = false;
+            if (p.flags & kRxAsmCarry) {  // the bits received before this step
+              const uint64_t words = p.in_offset + align8(p.in_held_len) + rx_frag_data_bytes(n);
+              const uint64_t w = *(const uint64_t*)(a.carry_in + words + 8ull * (it.fragment_id >> 6));
+              seen = (w >> (it.fragment_id & 63u)) & 1u;
+            }
+            if (seen || !dups.insert(r, idx, it.fragment_id)) {
+              st = UFC_RX_DROPPED_DUPLICATE;
+            } else {
+              const uint32_t received = (uint32_t)s.asm_received + 1;
+              s.asm_size += it.data_len;
+              if (received == n) {
+                packet = true;
+                packet_len = s.asm_size;
+                s.asm_state = UFC_RX_ASM_CLOSED;  // Closed(alloc_size): the opener's fields go with the entry
+                s.asm_size = (uint32_t)rx_frag_data_bytes(n);
+                s.asm_window_parent_lead = s.asm_channel_parent_lead = s.asm_last_fragment_id = s.asm_received = 0;
+                s.asm_channel_id = 0;
+                st = UFC_RX_COMPLETED;
+              } else {
+                s.asm_received = (uint16_t)received;
+                st = UFC_RX_STORED;
+              }
+            }
+          }
+          if (packet) {  // mod.rs:177-216
+            s.rx_channel_id = it.channel_id;
+            s.rx_channel_parent_lead = it.channel_parent_lead;
+            s.rx_window_parent_lead = it.window_parent_lead;
+            s.rx_flags = (uint8_t)(UFC_RX_SLOT_ENTRY | UFC_RX_SLOT_DATA | (dud ? UFC_RX_SLOT_DUD : 0));
+            s.data_len = packet_len;
+            p.flags = (uint8_t)((p.flags & ~(kRxHeldIn | kRxCompletedNow)) | (dud ? 0 : kRxCompletedNow));
+            if (packet_id_sub(it.id, R.end_id) < W) R.end_id = packet_id_add(it.id, 1);
+            R.channel_packet_count[ch]++;
+            if (lead_clears(it.channel_parent_lead, packet_id_sub(it.id, cbid))) R.channel_ready_flags |= 1ull << ch;
+            if (lead_clears(it.window_parent_lead, packet_lead)) R.window_ready = 1;
+            if (dud) res.packets_dud++; else res.packets_completed++;
+          }
+        }
+      }
+      status[g] = st;
+      res.status_count[st]++;
+    }
+  }
+
+}
+
+// 3. receive (mod.rs:286-402), id by id.  delivered and out_bytes: the packets and bytes it delivers.
+inline __host__ __device__ void rx_receive_serial(const RxArgs& a, uint64_t r, RxPlan* plans, uint32_t& delivered,
+                                                  uint64_t& out_bytes) {
+  ufc_receiver& R = a.receivers_out[r];
+  ufc_receiver_result& res = a.results[r];
+  delivered = 0;
+  out_bytes = 0;
+  if (res.stop != UFC_RX_DONE) return;
+  const uint32_t mask = R.window_size - 1, base = R.base_id;
+  ufc_rx_slot* slots = a.slots + a.slot_first[r];
+  RxPlan* plan = plans + a.slot_first[r];
+  if (R.deliver) {
+    const uint32_t end = R.end_id;
+    for (uint32_t seq = base; seq != end && R.channel_ready_flags != 0; seq = packet_id_add(seq, 1)) {
+      ufc_rx_slot& s = slots[seq & mask];
+      if (!(s.rx_flags & UFC_RX_SLOT_DATA)) continue;
+      const uint32_t ch = s.rx_channel_id;
+      const uint64_t bit = 1ull << ch;
+      if (!(R.channel_ready_flags & bit)) continue;
+      const uint32_t cbid = R.channel_base_id[ch] != UFC_NO_PARENT ? R.channel_base_id[ch] : base;
+      if (lead_clears(s.rx_channel_parent_lead, packet_id_sub(seq, cbid))) {
+        RxPlan& p = plan[seq & mask];
+        const bool dud = (s.rx_flags & UFC_RX_SLOT_DUD) != 0;
+        p.deliver_idx = delivered++;
+        p.seq = seq;
+        p.len = dud ? 0u : s.data_len;
+        p.channel = (uint8_t)ch;
+        p.pkt_flags = dud ? UFC_RX_PACKET_DUD : 0;
+        p.pkt_dst = out_bytes;
+        out_bytes += p.len;
+        s.rx_flags &= (uint8_t)~(UFC_RX_SLOT_DATA | UFC_RX_SLOT_DUD);
+        s.data_len = 0;
+        if (--R.channel_packet_count[ch] == 0) R.channel_ready_flags &= ~bit;
+        R.channel_base_id[ch] = packet_id_add(seq, 1);  // set_channel_base_id
+      } else {
+        R.channel_ready_flags &= ~bit;
+      }
+    }
+    if (R.window_ready) {
+      R.window_ready = 0;
+      uint32_t new_base = base;
+      for (uint32_t seq = base; seq != end; seq = packet_id_add(seq, 1)) {
+        const ufc_rx_slot& s = slots[seq & mask];
+        if (s.rx_flags & UFC_RX_SLOT_ENTRY) {
+          if (!lead_clears(s.rx_window_parent_lead, packet_id_sub(seq, new_base))) break;
+          new_base = packet_id_add(seq, 1);
+        }
+      }
+      rx_advance_window(R, slots, plan, new_base, res.advanced);
+    }
+  }
+}
+
+// 3. receive (mod.rs:286-402) in tiles of 64 consecutive ids, one lane per id: the form the device runs, one wave
+// per receiver.  Written once against a wave policy Wv so that the same text runs as host code (a loop over the
+// lanes per phase: tests/c/receive_host_check.hip, against rx_receive_serial) and on the device (every lane runs
+// each phase, a wave barrier in between):
+//   Wv::lanes(f)       f(lane) for the 64 lanes; what the lanes wrote to `sh` before is visible to all after
+//   Wv::or64 / add64   atomic on the device (vector atomics on LDS), plain on the host
+// Delivery: per channel the delivered packets are a prefix of its DATA slots in id order.  A lane evaluates its
+// slot's test with the channel base taken as (the previous DATA lane of its channel) + 1, or the carried base
+// for the first; the lanes of a channel meet in a 64-bit lane mask per channel (all DATA lanes, and the failing
+// ones); a lane is delivered when its channel was ready, no lane of the channel at or below it fails, and the
+// packet count has not run out before it (the k-th delivery clears the ready flag when it takes the count to
+// zero).  Lane c then settles channel c: count, base, ready flag.  The delivery order is the id order: a rank
+// among the delivered lanes, the bytes' offsets a sum over the lanes below.  The window advance is the same shape
+// over the ENTRY slots with new_base in the place of the channel base, and stops at the first failing lane;
+// advance_window then clears its slots lane by lane.  More ids than window_size between base and end (state
+// no consistent run produces) go to rx_receive_serial, as does nothing else.
+struct RxWaveShared {
+  unsigned long long chan_mask[UFC_MAX_CHANNELS], chan_fail[UFC_MAX_CHANNELS];
+  uint32_t chan_base[UFC_MAX_CHANNELS], chan_count[UFC_MAX_CHANNELS];
+  uint32_t chan_ready[UFC_MAX_CHANNELS];
+  uint32_t lane_len[64];
+  unsigned long long deliv_mask, entry_mask, entry_fail, ready_bits, alloc_sub, out_bytes;
+  uint32_t delivered, new_base, stop;
+};
+UFC_HD uint32_t rx_high_bit(unsigned long long m) {
+  uint32_t b = 0;
+  while (m >>= 1) b++;
+  return b;
+}
+UFC_HD uint32_t rx_low_bit(unsigned long long m) {
+  uint32_t b = 0;
+  while (!(m & 1)) m >>= 1, b++;
+  return b;
+}
+UFC_HD uint32_t rx_popc(unsigned long long m) {
+  uint32_t n = 0;
+  for (; m; m &= m - 1) n++;
+  return n;
+}
+template <class Wv>
+inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh, const RxArgs& a, uint64_t r, RxPlan* plans,
+                                                 uint32_t& delivered, uint64_t& out_bytes) {
+  ufc_receiver& R = a.receivers_out[r];
+  ufc_receiver_result& res = a.results[r];
+  delivered = 0;
+  out_bytes = 0;
+  if (res.stop != UFC_RX_DONE || !R.deliver) return;
+  const uint32_t W = R.window_size, mask = W - 1, base = R.base_id, end = R.end_id;
+  const uint32_t n = packet_id_sub(end, base);
+  if (n > W) {  // (every lane takes this branch or none)
+    wv.lanes([&](uint32_t lane) {
+      if (lane == 0) {
+        uint32_t d;
+        uint64_t o;
+        rx_receive_serial(a, r, plans, d, o);
+        sh.delivered = d;
+        sh.out_bytes = o;
+      }
+    });
+    delivered = sh.delivered;
+    out_bytes = sh.out_bytes;
+    return;
+  }
+  ufc_rx_slot* slots = a.slots + a.slot_first[r];
+  RxPlan* plan = plans + a.slot_first[r];
+  const uint64_t ready_in = R.channel_ready_flags;
+  const bool window_ready = R.window_ready != 0;
+  wv.lanes([&](uint32_t c) {
+    sh.chan_base[c] = R.channel_base_id[c];
+    sh.chan_count[c] = R.channel_packet_count[c];
+    sh.chan_ready[c] = (uint32_t)((ready_in >> c) & 1u);
+    sh.chan_mask[c] = sh.chan_fail[c] = 0;
+    if (c == 0) sh.deliv_mask = sh.ready_bits = sh.alloc_sub = sh.out_bytes = 0, sh.delivered = 0;
+  });
+  auto below = [](uint32_t lane) { return (1ull << lane) - 1; };
+  for (uint32_t t0 = 0; t0 < n; t0 += 64) {
+    const uint32_t nv = n - t0 < 64 ? n - t0 : 64;
+    auto seq_of = [&](uint32_t lane) { return packet_id_add(base, t0 + lane); };
+    wv.lanes([&](uint32_t lane) {
+      sh.lane_len[lane] = 0;
+      if (lane >= nv) return;
+      const ufc_rx_slot& s = slots[seq_of(lane) & mask];
+      if (s.rx_flags & UFC_RX_SLOT_DATA) Wv::or64(&sh.chan_mask[s.rx_channel_id], 1ull << lane);
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (lane >= nv) return;
+      const ufc_rx_slot& s = slots[seq_of(lane) & mask];
+      if (!(s.rx_flags & UFC_RX_SLOT_DATA)) return;
+      const uint32_t c = s.rx_channel_id;
+      const unsigned long long m = sh.chan_mask[c] & below(lane);
+      const uint32_t cb = m ? packet_id_add(seq_of(rx_high_bit(m)), 1) : (sh.chan_base[c] != UFC_NO_PARENT ? sh.chan_base[c] : base);
+      if (!lead_clears(s.rx_channel_parent_lead, packet_id_sub(seq_of(lane), cb))) Wv::or64(&sh.chan_fail[c], 1ull << lane);
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (lane >= nv) return;
+      const ufc_rx_slot& s = slots[seq_of(lane) & mask];
+      if (!(s.rx_flags & UFC_RX_SLOT_DATA)) return;
+      const uint32_t c = s.rx_channel_id, count = sh.chan_count[c];
+      const uint32_t rank = rx_popc(sh.chan_mask[c] & below(lane));
+      if (sh.chan_ready[c] && !(sh.chan_fail[c] & (below(lane) | 1ull << lane)) && (count == 0 || rank < count)) {
+        Wv::or64(&sh.deliv_mask, 1ull << lane);
+        sh.lane_len[lane] = (s.rx_flags & UFC_RX_SLOT_DUD) ? 0u : s.data_len;
+      }
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (!((sh.deliv_mask >> lane) & 1u)) return;
+      ufc_rx_slot& s = slots[seq_of(lane) & mask];
+      RxPlan& p = plan[seq_of(lane) & mask];
+      const bool dud = (s.rx_flags & UFC_RX_SLOT_DUD) != 0;
+      uint64_t at = sh.out_bytes;
+      for (uint32_t l = 0; l < lane; l++) at += sh.lane_len[l];
+      p.deliver_idx = sh.delivered + rx_popc(sh.deliv_mask & below(lane));
+      p.seq = seq_of(lane);
+      p.len = sh.lane_len[lane];
+      p.channel = s.rx_channel_id;
+      p.pkt_flags = dud ? UFC_RX_PACKET_DUD : 0;
+      p.pkt_dst = at;
+      s.rx_flags &= (uint8_t)~(UFC_RX_SLOT_DATA | UFC_RX_SLOT_DUD);
+      s.data_len = 0;
+    });
+    wv.lanes([&](uint32_t c) {  // lane c settles channel c
+      const unsigned long long M = sh.chan_mask[c], F = sh.chan_fail[c];
+      if (sh.chan_ready[c] && M) {
+        const uint32_t count = sh.chan_count[c];
+        const uint32_t clear = F ? rx_popc(M & below(rx_low_bit(F))) : rx_popc(M);  // DATA lanes before the first failing one
+        const uint32_t nd = (count != 0 && clear > count) ? count : clear;
+        if ((count != 0 && nd == count) || (F && (count == 0 || clear < count))) sh.chan_ready[c] = 0;
+        sh.chan_count[c] = count - nd;
+        if (nd) {
+          unsigned long long m = M;
+          for (uint32_t k = 1; k < nd; k++) m &= m - 1;  // drop the nd - 1 lowest: the nd-th DATA lane is the lowest left
+          sh.chan_base[c] = packet_id_add(seq_of(rx_low_bit(m)), 1);
+        }
+      }
+      sh.chan_mask[c] = sh.chan_fail[c] = 0;
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (lane != 0) return;
+      sh.delivered += rx_popc(sh.deliv_mask);
+      for (uint32_t l = 0; l < 64; l++) sh.out_bytes += sh.lane_len[l];
+      sh.deliv_mask = 0;
+    });
+  }
+  wv.lanes([&](uint32_t c) {
+    R.channel_base_id[c] = sh.chan_base[c];
+    R.channel_packet_count[c] = sh.chan_count[c];
+    if (sh.chan_ready[c]) Wv::or64(&sh.ready_bits, 1ull << c);
+  });
+  delivered = sh.delivered;
+  out_bytes = sh.out_bytes;
+  if (!window_ready) {
+    wv.lanes([&](uint32_t lane) {
+      if (lane == 0) R.channel_ready_flags = sh.ready_bits;
+    });
+    return;
+  }
+  // the window advance: the ENTRY slots' prefix, then advance_window (mod.rs:244-282) lane by lane
+  wv.lanes([&](uint32_t lane) {
+    if (lane == 0) sh.new_base = base, sh.stop = 0, sh.entry_mask = sh.entry_fail = 0;
+  });
+  for (uint32_t t0 = 0; t0 < n; t0 += 64) {
+    const uint32_t nv = n - t0 < 64 ? n - t0 : 64;
+    auto seq_of = [&](uint32_t lane) { return packet_id_add(base, t0 + lane); };
+    wv.lanes([&](uint32_t lane) {
+      if (lane < nv && (slots[seq_of(lane) & mask].rx_flags & UFC_RX_SLOT_ENTRY)) Wv::or64(&sh.entry_mask, 1ull << lane);
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (!((sh.entry_mask >> lane) & 1u)) return;
+      const unsigned long long m = sh.entry_mask & below(lane);
+      const uint32_t nb = m ? packet_id_add(seq_of(rx_high_bit(m)), 1) : sh.new_base;
+      if (!lead_clears(slots[seq_of(lane) & mask].rx_window_parent_lead, packet_id_sub(seq_of(lane), nb)))
+        Wv::or64(&sh.entry_fail, 1ull << lane);
+    });
+    wv.lanes([&](uint32_t lane) {
+      if (lane != 0) return;
+      unsigned long long E = sh.entry_mask;
+      if (sh.entry_fail) {
+        E &= below(rx_low_bit(sh.entry_fail));
+        sh.stop = 1;
+      }
+      if (E) sh.new_base = packet_id_add(seq_of(rx_high_bit(E)), 1);
+      sh.entry_mask = sh.entry_fail = 0;
+    });
+    if (sh.stop) break;  // (read by every lane after the phase: uniform)
+  }
+  const uint32_t new_base = sh.new_base, delta = packet_id_sub(new_base, base);  // delta <= n <= W: every slot once
+  for (uint32_t k0 = 0; k0 < delta; k0 += 64)
+    wv.lanes([&](uint32_t lane) {
+      if (k0 + lane >= delta) return;
+      const uint32_t idx = packet_id_add(base, k0 + lane) & mask;
+      ufc_rx_slot& s = slots[idx];
+      s.rx_flags &= (uint8_t)~UFC_RX_SLOT_ENTRY;
+      uint64_t alloc = 0;
+      rx_clear_slot(s, plan[idx], alloc);  // (alloc counts down from zero: what the slot gives back, negated)
+      if (alloc) Wv::add64(&sh.alloc_sub, 0 - alloc);
+    });
+  wv.lanes([&](uint32_t c) {  // try_unset_channel_base_id over (base, new_base]
+    const uint32_t cb = sh.chan_base[c];
+    if (cb != UFC_NO_PARENT) {
+      const uint32_t lead = packet_id_sub(cb, base);
+      if (lead >= 1 && lead <= delta) R.channel_base_id[c] = UFC_NO_PARENT;
+    }
+  });
+  wv.lanes([&](uint32_t lane) {
+    if (lane != 0) return;
+    R.channel_ready_flags = sh.ready_bits;
+    R.window_ready = 0;
+    if (n < delta) R.end_id = new_base;
+    R.alloc -= sh.alloc_sub;
+    res.advanced += delta;
+    R.base_id = new_base;
+  });
+}
+
+// The end of the step: the result's delivery fields and the three counts ([0] delivered packets, [1] delivered
+// bytes, [2] carry bytes; all zero after BAD_STATE).
+inline __host__ __device__ void rx_walk_end(const RxArgs& a, uint64_t r, uint32_t delivered, uint64_t out_bytes,
+                                            uint64_t counts[3]) {
+  ufc_receiver_result& res = a.results[r];
+  counts[0] = counts[1] = counts[2] = 0;
+  if (res.stop != UFC_RX_DONE) return;
+  const ufc_rx_slot* slots = a.slots + a.slot_first[r];
+  uint64_t carry = 0;
+  for (uint32_t j = 0; j < a.receivers_out[r].window_size; j++) carry += rx_slot_region(slots[j]);
+  res.packet_count = delivered;
+  res.bytes_delivered = out_bytes;
+  counts[0] = delivered;
+  counts[1] = out_bytes;
+  counts[2] = carry;
+}
+
+// The whole step, serially.  Returns false for BAD_STATE.
+inline __host__ __device__ bool rx_walk(const RxArgs& a, uint64_t r, RxPlan* plans, uint8_t* status,
+                                        const RxDupSet& dups, uint64_t counts[3]) {
+  const bool ok = rx_walk_begin(a, r, plans);
+  rx_walk_items(a, r, plans, status, dups, nullptr);
+  uint32_t delivered;
+  uint64_t out_bytes;
+  rx_receive_serial(a, r, plans, delivered, out_bytes);
+  rx_walk_end(a, r, delivered, out_bytes, counts);
+  return ok;
+}
+
+// After the sums: receiver r's records, carry layout, received-bits words and copy segments (zeroed before).
+// packet_first[r], out_first and carry_first[r] are its firsts.
+inline __host__ __device__ void rx_finish(const RxArgs& a, uint64_t r, RxPlan* plans, const uint8_t* status,
+                                          uint64_t out_first, RxSegment* segs, uint32_t* seg_len_out) {
+  const uint64_t pf = a.packet_first[r];
+  a.results[r].packet_first = (uint32_t)pf;
+  if (a.results[r].stop != UFC_RX_DONE) return;
+  const ufc_receiver& R = a.receivers_out[r];
+  const uint32_t W = R.window_size, mask = W - 1;
+  const uint64_t s0 = a.slot_first[r];
+  ufc_rx_slot* slots = a.slots + s0;
+  RxPlan* plan = plans + s0;
+  auto put = [&](uint64_t k, uint64_t src, uint64_t dst, uint32_t len, uint32_t kinds) {
+    RxSegment sg;
+    sg.src = src;
+    sg.dst = dst;
+    sg.len = len;
+    sg.kinds = kinds;
+    segs[k] = sg;
+    if (seg_len_out) seg_len_out[k] = len;
+  };
+  uint64_t cursor = a.carry_first[r];
+  for (uint32_t j = 0; j < W; j++) {
+    ufc_rx_slot& s = slots[j];
+    RxPlan& p = plan[j];
+    const uint32_t held = rx_slot_held(s), n = rx_slot_nfrag(s);
+    uint32_t pkt_len = 0;
+    if (p.deliver_idx != kRxNotDelivered) {
+      p.pkt_dst += out_first;
+      p.flags |= kRxPktOut;
+      pkt_len = p.len;
+      if (pf + p.deliver_idx < a.packets_cap) {
+        ufc_rx_packet rec{};
+        rec.out_offset = p.pkt_dst;
+        rec.sequence_id = p.seq;
+        rec.len = p.len;
+        rec.channel_id = p.channel;
+        rec.flags = p.pkt_flags;
+        a.packets[pf + p.deliver_idx] = rec;
+      }
+    } else if (held) {
+      p.pkt_dst = cursor;
+      p.flags |= kRxPktCarry;
+      pkt_len = held;
+    }
+    const uint32_t dst_kind = (p.flags & kRxPktCarry) ? kRxDstCarry : 0u;
+    const uint64_t in_frag = p.in_offset + align8(p.in_held_len);
+    if (pkt_len && (p.flags & kRxHeldIn)) {
+      put(rx_slot_segment(s0 + j, 0), p.in_offset, p.pkt_dst, pkt_len, kRxSrcCarry | dst_kind);
+    } else if (pkt_len && (p.flags & kRxCompletedNow) && (p.flags & kRxAsmCarry)) {
+      // the fragments received in earlier steps (what lies in between is overwritten by this step's)
+      const uint64_t have = rx_frag_data_bytes(p.in_nfrag);
+      put(rx_slot_segment(s0 + j, 1), in_frag, p.pkt_dst, have < pkt_len ? (uint32_t)have : pkt_len,
+          kRxSrcCarry | dst_kind);
+    }
+    if (n) {
+      p.frag_dst = cursor + align8(held);
+      p.flags |= kRxFrag;
+      const uint64_t data = rx_frag_data_bytes(n), words = p.frag_dst + data;
+      const bool carried = (p.flags & kRxAsmCarry) != 0;
+      if (carried) put(rx_slot_segment(s0 + j, 1), in_frag, p.frag_dst, (uint32_t)data, kRxSrcCarry | kRxDstCarry);
+      for (uint32_t w = 0; w < (n + 63) / 64; w++)
+        if (words + 8ull * w + 8 <= a.carry_cap)
+          *(uint64_t*)(a.carry_out + words + 8ull * w) = carried ? *(const uint64_t*)(a.carry_in + in_frag + data + 8ull * w) : 0ull;
+    }
+    s.data_offset = cursor;
+    cursor += rx_slot_region(s);
+  }
+  // This step's fragments: into the slot's buffer, or into the packet they completed.
+  const uint64_t ff0 = a.frame_first[r], ff1 = a.frame_first[r + 1];
+  for (uint64_t i = ff0; i < ff1; i++) {
+    if (!rx_frame_counts(a, i)) continue;
+    const ufc_frame_info& f = a.infos[i];
+    const uint64_t sb = a.src_base ? a.src_base[i] : 0;
+    for (uint64_t g = f.item_first, ge = (uint64_t)f.item_first + f.item_count; g < ge; g++) {
+      if (status[g] != UFC_RX_STORED && status[g] != UFC_RX_COMPLETED) continue;
+      const ufc_item it = a.items[g];
+      const RxPlan& p = plan[it.id & mask];
+      const uint64_t at = (uint64_t)it.fragment_id * UFC_MAX_FRAGMENT_SIZE;
+      if (p.flags & kRxFrag) {
+        // (a stored fragment's fragment_id_last is the slot's)
+        const uint64_t word = p.frag_dst + rx_frag_data_bytes((uint32_t)it.fragment_id_last + 1) + 8ull * (it.fragment_id >> 6);
+        if (word + 8 <= a.carry_cap) *(uint64_t*)(a.carry_out + word) |= 1ull << (it.fragment_id & 63u);
+        if (it.data_len) put(rx_item_segment(a.n_slots, g), sb + it.data_offset, p.frag_dst + at, it.data_len, kRxDstCarry);
+      } else if ((p.flags & kRxCompletedNow) && (p.flags & (kRxPktOut | kRxPktCarry)) && it.data_len) {
+        put(rx_item_segment(a.n_slots, g), sb + it.data_offset, p.pkt_dst + at, it.data_len,
+            (p.flags & kRxPktCarry) ? kRxDstCarry : 0u);
+      }
+    }
+  }
 }
 
 }  // namespace ufc_codec

@@ -21,6 +21,7 @@
 #include "frame_pack.hpp"
 #include "frame_parse.hpp"
 #include "packet_emit.hpp"
+#include "packet_receive.hpp"
 #include "ufc_internal.hpp"
 
 struct ufc_ctx {
@@ -75,7 +76,8 @@ enum ScratchKind {
   kScratchDeferCounts = 5,
   kScratchBuild = 6,
   kScratchPack = 7,
-  kScratchEmit = 8
+  kScratchEmit = 8,
+  kScratchReceive = 9
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -991,6 +993,43 @@ int ufc_emit_packets_varlen(ufc_ctx* ctx, const ufc_packet* d_packets, size_t n_
                       (uint64_t)items_cap, d_flush_first, d_packet_results, d_sender_results, d_senders_out,
                       d_items_used};
   if ((e = ufc_dev::emit_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched packet receive (packet_receive.hip) ----
+int ufc_receive_packets_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames,
+                               const uint8_t* d_frame_accept, const ufc_item* d_items, size_t n_items,
+                               const uint64_t* d_src_base, const uint8_t* d_payload, size_t payload_len,
+                               const uint64_t* d_frame_first, const ufc_receiver* d_receivers, size_t n_receivers,
+                               ufc_rx_slot* d_slots, const uint64_t* d_slot_first, size_t n_slots,
+                               const uint8_t* d_carry_in, size_t carry_in_len, uint8_t* d_carry_out, size_t carry_cap,
+                               uint64_t* d_carry_first, uint64_t* d_carry_used, ufc_rx_packet* d_packets,
+                               size_t packets_cap, uint64_t* d_packet_first, uint64_t* d_packets_used,
+                               uint8_t* d_out_bytes, size_t out_cap, uint64_t* d_out_used, uint8_t* d_item_status,
+                               ufc_receiver_result* d_results, ufc_receiver* d_receivers_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n_receivers == 0) return UFC_OK;
+  // (the counts and the chunk counts are scanned with 32-bit counts)
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!d_frame_first || !d_receivers || !d_receivers_out || !d_slot_first || !d_carry_first || !d_carry_used ||
+      !d_packet_first || !d_packets_used || !d_out_used || !d_results || (!d_infos && n_frames) ||
+      (!d_items && n_items) || (!d_payload && payload_len) || (!d_slots && n_slots) || (!d_carry_in && carry_in_len) ||
+      (!d_carry_out && carry_cap) || (!d_packets && packets_cap) || (!d_out_bytes && out_cap) || n_frames >= lim ||
+      n_items >= lim || n_receivers >= lim || n_slots >= lim / 2 || ((uintptr_t)d_carry_in & 7) ||
+      ((uintptr_t)d_carry_out & 7))
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::receive_scratch_bytes(n_receivers, n_items, n_slots);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchReceive, (hipStream_t)stream, need, &scratch)) != hipSuccess)
+    return hip_fail(ctx, e);
+  const ufc_codec::RxArgs a{d_infos, n_frames, d_frame_accept, d_items, n_items, d_src_base, d_payload, payload_len,
+                            d_frame_first, d_receivers, n_receivers, d_slots, d_slot_first, n_slots, d_carry_in,
+                            carry_in_len, d_carry_out, carry_cap, d_carry_first, d_carry_used, d_packets, packets_cap,
+                            d_packet_first, d_packets_used, d_out_bytes, out_cap, d_out_used, d_item_status, d_results,
+                            d_receivers_out};
+  if ((e = ufc_dev::receive_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

@@ -12,6 +12,9 @@ and the batched receive-side parse that follows the batched CRC gate:
     emit_packets_host(packets, packet_first, senders)
                                                <- PacketSender::emit_packet and fragmentation,
                                                   src/half_connection/packet_sender.rs:149-238
+    receive_packets_host(infos, items, payload, frame_first, receivers, slots, slot_first, carry_in)
+                                               <- PacketReceiver::handle_datagram / receive / resynchronize,
+                                                  src/half_connection/packet_receiver/mod.rs:142-435
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -24,8 +27,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, Packet, PacketResult, Sender,
-                      SenderResult, check, lib, UFC_ERR_NOMEM)
+from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, Packet, PacketResult, Receiver,
+                      ReceiverResult, RxPacket, RxSlot, Sender, SenderResult, check, lib, UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -67,6 +70,44 @@ SEND_TIME_SENSITIVE, SEND_UNRELIABLE, SEND_PERSISTENT, SEND_RELIABLE = 0, 1, 2, 
 NO_PARENT = 0xFFFFFFFF
 EMIT_DONE, EMIT_WINDOW_LIMITED, EMIT_ALLOC_LIMITED, EMIT_BAD_PACKET, EMIT_BAD_RANGE = 0, 1, 2, 3, 4
 PACKET_NOT_REACHED, PACKET_EMITTED, PACKET_DROPPED = 0, 1, 2
+# ufc_receiver / ufc_rx_slot / ufc_rx_packet / ufc_receiver_result (batched packet receives)
+RECEIVER_DTYPE = np.dtype([("base_id", "<u4"), ("end_id", "<u4"), ("window_size", "<u4"), ("window_ready", "u1"),
+                           ("deliver", "u1"), ("reserved", "<u2"), ("resync_id", "<u4"), ("reserved2", "<u4"),
+                           ("alloc", "<u8"), ("max_alloc", "<u8"), ("channel_ready_flags", "<u8"),
+                           ("channel_base_id", "<u4", (64,)), ("channel_packet_count", "<u4", (64,))])
+RX_SLOT_DTYPE = np.dtype([("data_offset", "<u8"), ("data_len", "<u4"), ("asm_size", "<u4"),
+                          ("asm_window_parent_lead", "<u2"), ("asm_channel_parent_lead", "<u2"),
+                          ("asm_last_fragment_id", "<u2"), ("asm_received", "<u2"), ("rx_window_parent_lead", "<u2"),
+                          ("rx_channel_parent_lead", "<u2"), ("asm_state", "u1"), ("asm_channel_id", "u1"),
+                          ("rx_channel_id", "u1"), ("rx_flags", "u1")])
+RX_PACKET_DTYPE = np.dtype([("out_offset", "<u8"), ("sequence_id", "<u4"), ("len", "<u4"), ("channel_id", "u1"),
+                            ("flags", "u1"), ("reserved", "<u2"), ("reserved2", "<u4")])
+RECEIVER_RESULT_DTYPE = np.dtype([("packet_first", "<u4"), ("packet_count", "<u4"), ("status_count", "<u4", (11,)),
+                                  ("packets_completed", "<u4"), ("packets_dud", "<u4"), ("advanced", "<u4"),
+                                  ("stop", "<u4"), ("reserved", "<u4"), ("bytes_delivered", "<u8")])
+assert RECEIVER_DTYPE.itemsize == ctypes.sizeof(Receiver) == 560
+assert RX_SLOT_DTYPE.itemsize == ctypes.sizeof(RxSlot) == 32
+assert RX_PACKET_DTYPE.itemsize == ctypes.sizeof(RxPacket) == 24
+assert RECEIVER_RESULT_DTYPE.itemsize == ctypes.sizeof(ReceiverResult) == 80
+RX_ASM_OPEN, RX_ASM_CLOSED, RX_ASM_ACTIVE = 0, 1, 2
+RX_SLOT_ENTRY, RX_SLOT_DATA, RX_SLOT_DUD = 1, 2, 4
+RX_PACKET_DUD = 1
+(RX_NOT_HANDLED, RX_STORED, RX_COMPLETED, RX_DUD, RX_DROPPED_INVALID, RX_DROPPED_WINDOW, RX_DROPPED_CHANNEL,
+ RX_DROPPED_CLOSED, RX_DROPPED_MISMATCH, RX_DROPPED_DUPLICATE, RX_DROPPED_BAD_SRC) = range(11)
+RX_DONE, RX_BAD_STATE = 0, 1
+
+
+def new_receivers(n: int, window_size, base_id=0, max_alloc=1 << 40) -> np.ndarray:
+    """n ufc_receiver headers equal to PacketReceiver::new(window_size, base_id, max_alloc) (mod.rs:94-136), to
+    go with all-zero slots: deliver = 1, no resynchronize."""
+    r = np.zeros(n, dtype=RECEIVER_DTYPE)
+    r["base_id"] = r["end_id"] = base_id
+    r["window_size"] = window_size
+    r["max_alloc"] = max_alloc
+    r["deliver"] = 1
+    r["resync_id"] = NO_PARENT
+    r["channel_base_id"] = NO_PARENT
+    return r
 
 
 @dataclass
@@ -455,3 +496,90 @@ def emit_packets_host(packets: np.ndarray, packet_first: np.ndarray, senders: np
         raise ValueError("items must be a contiguous ITEM_DTYPE array of at least items_cap records")
     call(items.ctypes.data if items_cap else None, items_cap)
     return items, flush_first, packet_results, sender_results, senders_out, used.value
+
+
+def receive_packets_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarray, frame_first: np.ndarray,
+                         receivers: np.ndarray, slots: np.ndarray, slot_first: np.ndarray, carry_in: np.ndarray,
+                         src_base: Optional[np.ndarray] = None, frame_accept: Optional[np.ndarray] = None,
+                         carry_cap: Optional[int] = None, out_cap: Optional[int] = None,
+                         packets_cap: Optional[int] = None, nthreads: int = 1, receivers_out: Optional[np.ndarray] = None,
+                         want_item_status: bool = True, carry_out: Optional[np.ndarray] = None,
+                         out_bytes: Optional[np.ndarray] = None, packets: Optional[np.ndarray] = None):
+    """One step of PacketReceiver for many receivers in host memory (ufc_receive_packets_host): receiver r
+    (RECEIVER_DTYPE: its state, resync_id and deliver) owns frames frame_first[r] : frame_first[r + 1] of infos
+    (FRAME_INFO_DTYPE, with their ITEM_DTYPE items; src_base uint64[n_frames] and payload as in build_host) and the
+    slots slot_first[r] : slot_first[r] + window_size (RX_SLOT_DTYPE, updated in place).  carry_in uint8: the carry
+    arena the slots point into.  Returns a dict: packets (RX_PACKET_DTYPE), packet_first, packets_used, out_bytes,
+    out_used, carry_out, carry_first, carry_used, item_status (uint8 per item, or None), results
+    (RECEIVER_RESULT_DTYPE), receivers_out.  Caps that are not given are what the step needs, found by a first
+    pass on a copy of the state with caps of zero (an ACTIVE slot holds its whole fragment buffer, so the carry
+    has no small bound from the batch's sizes alone); arrays given for carry_out, out_bytes and packets are written
+    into (their sizes are then the caps).  Pass carry_out as the next step's carry_in."""
+    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
+    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    carry_in = np.ascontiguousarray(carry_in, dtype=np.uint8)
+    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
+    slot_first = np.ascontiguousarray(slot_first, dtype=np.uint64)
+    if receivers.dtype != RECEIVER_DTYPE or not receivers.flags.c_contiguous:
+        receivers = np.ascontiguousarray(receivers, dtype=RECEIVER_DTYPE)
+    if slots.dtype != RX_SLOT_DTYPE or not slots.flags.c_contiguous or not slots.flags.writeable:
+        raise ValueError("slots must be a writable contiguous RX_SLOT_DTYPE array (it is updated in place)")
+    n = receivers.size
+    if frame_first.size < n + 1 or slot_first.size < n + 1:
+        raise ValueError("frame_first and slot_first must hold one more entry than there are receivers")
+    if src_base is not None:
+        src_base = np.ascontiguousarray(src_base, dtype=np.uint64)
+        if src_base.size < infos.size:
+            raise ValueError("src_base must hold one entry per frame")
+    if frame_accept is not None:
+        frame_accept = np.ascontiguousarray(frame_accept, dtype=np.uint8)
+        if frame_accept.size < infos.size:
+            raise ValueError("frame_accept must hold one entry per frame")
+    if receivers_out is None:
+        receivers_out = np.zeros(n, dtype=RECEIVER_DTYPE)
+    elif receivers_out.dtype != RECEIVER_DTYPE or not receivers_out.flags.c_contiguous or receivers_out.size < n:
+        raise ValueError("receivers_out must be a contiguous RECEIVER_DTYPE array of one record per receiver")
+    carry_first = np.zeros(n + 1, dtype=np.uint64)
+    packet_first = np.zeros(n + 1, dtype=np.uint64)
+    results = np.zeros(n, dtype=RECEIVER_RESULT_DTYPE)
+    carry_used, packets_used, out_used = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def p(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    def call(slots_, carry_out_, out_bytes_, packets_, status_, receivers_out_):
+        size = lambda a: 0 if a is None else a.size  # noqa: E731
+        check(lib().ufc_receive_packets_host(
+            p(infos), infos.size, p(frame_accept), p(items), items.size, p(src_base), p(payload), payload.size,
+            frame_first.ctypes.data, p(receivers), n, p(slots_), slot_first.ctypes.data, slots_.size, p(carry_in),
+            carry_in.size, p(carry_out_), size(carry_out_), carry_first.ctypes.data, ctypes.addressof(carry_used),
+            p(packets_), size(packets_), packet_first.ctypes.data, ctypes.addressof(packets_used), p(out_bytes_),
+            size(out_bytes_), ctypes.addressof(out_used), p(status_), p(results), p(receivers_out_), nthreads),
+            "ufc_receive_packets_host")
+
+    need = [(carry_out, carry_cap), (out_bytes, out_cap), (packets, packets_cap)]
+    if any(arr is None and cap is None for arr, cap in need):
+        # the used counts are exact whatever the caps: a first pass on a copy of the state, with none
+        call(slots.copy(), None, None, None, None, np.zeros(n, dtype=RECEIVER_DTYPE))
+        carry_cap = carry_used.value if carry_cap is None else carry_cap
+        out_cap = out_used.value if out_cap is None else out_cap
+        packets_cap = packets_used.value if packets_cap is None else packets_cap
+    if carry_out is None:
+        carry_out = np.zeros(int(carry_cap), dtype=np.uint8)
+    if out_bytes is None:
+        out_bytes = np.zeros(int(out_cap), dtype=np.uint8)
+    if packets is None:
+        packets = np.zeros(int(packets_cap), dtype=RX_PACKET_DTYPE)
+    for name, arr, dt in (("carry_out", carry_out, np.uint8), ("out_bytes", out_bytes, np.uint8),
+                          ("packets", packets, RX_PACKET_DTYPE)):
+        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable:
+            raise ValueError(f"{name} must be a writable contiguous {dt} array")
+    if np.shares_memory(carry_out, carry_in):
+        raise ValueError("carry_out must not overlap carry_in")
+    item_status = np.zeros(items.size, dtype=np.uint8) if want_item_status else None
+    call(slots, carry_out, out_bytes, packets, item_status, receivers_out)
+    return {"packets": packets, "packet_first": packet_first, "packets_used": packets_used.value,
+            "out_bytes": out_bytes, "out_used": out_used.value, "carry_out": carry_out, "carry_first": carry_first,
+            "carry_used": carry_used.value, "item_status": item_status, "results": results,
+            "receivers_out": receivers_out}
