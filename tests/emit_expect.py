@@ -411,3 +411,48 @@ def filled_items(n):
     a = np.zeros(n, dtype=ITEM_DTYPE)
     a.view(np.uint8)[:] = FILL
     return a
+
+
+def many_max_packets(n_big=66, every=20):
+    """n_big senders with one reliable MAX_PACKET_SIZE packet each (65 536 items a sender, no payload needed: the
+    offsets are made up), ids and parents in flight so that both leads are non-zero, small senders before, after
+    every `every` of them and behind.  Returns (Senders, the big senders' indices)."""
+    rng = random.Random(41)
+    small = [pkt(3, 1, RELIABLE, offset=0), pkt(MAX_FRAGMENT_SIZE + 1, 2, UNRELIABLE, offset=8), pkt(9, 1, offset=3)]
+    b, big = Senders(), []
+    for k in range(n_big):
+        if k % every == 0:
+            b.add(small, f"small_{k}", reserve_items=k % 3, base_id=rng.getrandbits(20))
+        base = (ID_MASK - 2 if k == 0 else rng.getrandbits(20))   # (the first one's id is past the wrap)
+        ch = (7 * k) % CHANNEL_COUNT
+        big.append(len(b.senders))
+        b.add([pkt(MAX_PACKET_SIZE, ch, RELIABLE, offset=1000 * k + 16)], f"big_{k}", base_id=base, next_id=(base + 5) & ID_MASK,
+              window_parent_id=(base + 3) & ID_MASK, channel_parents={ch: (base + 1 + k % 2) & ID_MASK})
+    b.add(small, "small_last")
+    return b, big
+
+
+def check_max_packets(items, flush_first, packets, packet_first, senders, big):
+    """The items of senders that own one MAX_PACKET_SIZE packet, in closed form: fragment f of 65 536 at data_offset
+    + f * 1448, 1448 bytes each, the sequence id and the leads the restatement's: expect() runs on each sender
+    alone, its first and last three items are compared field for field, the rest by the formula."""
+    items = np.asarray(items).view(ITEM_DTYPE).reshape(-1)
+    n = MAX_PACKET_SIZE // MAX_FRAGMENT_SIZE
+    f = np.arange(n, dtype=np.int64)
+    for s in big:
+        a = int(packet_first[s])
+        pk = packets[a]
+        assert int(packet_first[s + 1]) - a == 1 and int(pk["data_len"]) == MAX_PACKET_SIZE and int(senders[s]["reserve_items"]) == 0
+        e = expect(packets[a: a + 1], np.array([0, 1], dtype=np.uint64), senders[s: s + 1])
+        got = items[int(flush_first[s]): int(flush_first[s + 1])]
+        assert got.size == n == e.items_used, (s, got.size)
+        for k in (0, 1, 2, n - 3, n - 2, n - 1):
+            assert got[k] == e.items[k], (s, k, got[k], e.items[k])
+        seq, wl, cl = (int(e.items[0][fld]) for fld in ("id", "window_parent_lead", "channel_parent_lead"))
+        assert wl != 0 and cl != 0 and seq == int(senders[s]["next_id"])
+        for fld, want in (("id", seq), ("channel_id", pk["channel_id"]), ("window_parent_lead", wl),
+                          ("channel_parent_lead", cl), ("fragment_id", f), ("fragment_id_last", n - 1),
+                          ("data_offset", (int(pk["data_offset"]) + f * MAX_FRAGMENT_SIZE) & 0xFFFFFFFF),
+                          ("data_len", MAX_FRAGMENT_SIZE)):
+            assert np.array_equal(got[fld], np.broadcast_to(want, n)), (s, fld)
+        assert (got["form"][:-1] == got["form"][0]).all() and (got["flags"][:-1] == got["flags"][0]).all(), s

@@ -6,8 +6,9 @@ by the allocation limit (a dud) is delivered as a packet without bytes where the
 
 Around it: converters between the classes and the records of ufc_receive_packets_* (header, slots, carry arena),
 the expected outputs of one batched step, batch generators, and check(), which compares every record, status,
-state field, slot field and delivered byte of a native call with the restatement.  Nothing here calls the
-library.
+state field, slot field and delivered byte of a native call with the restatement; and, for calls too large for
+that, check_receivers (check() on a sample of the receivers), check_sums and check_same (two native forms of one
+call) over batches built in numpy.  Nothing here calls the library.
 """
 import numpy as np
 
@@ -17,6 +18,17 @@ MASK = 0xFFFFF
 FRAG = 1448
 CHANNELS = 64
 NONE = 0xFFFFFFFF
+TILE = 64  # ids that the device form of receive() takes at a time (rx_receive_tiles)
+
+# The launch constants of csrc/packet_receive.hip and csrc/packet_emit.hip that the big-shape tests are sized by,
+# mirrored here: tests/test_receive_cpu.py::test_launch_constants_mirror_the_source reads them from the source.
+LAUNCH_CONSTANTS = {"kRxFew": 32768, "kRxThreads": 64, "kRxThreadsFew": 8, "kCopyThreads": 256, "kCopyBlocksMax": 16384,
+                    "kItemLanes": 16, "kRxChunk": 2048, "kEmitThreads": 256, "kItemBlocksMax": 16384}
+RX_FEW, RX_CHUNK = LAUNCH_CONSTANTS["kRxFew"], LAUNCH_CONSTANTS["kRxChunk"]
+COPY_WAVES_MAX = LAUNCH_CONSTANTS["kCopyBlocksMax"] * LAUNCH_CONSTANTS["kCopyThreads"] // 64              # 65 536 chunks
+COPY_ITEMS_MAX = LAUNCH_CONSTANTS["kCopyBlocksMax"] * LAUNCH_CONSTANTS["kCopyThreads"] // LAUNCH_CONSTANTS["kItemLanes"]
+VERDICT_GROUPS_MAX = 1 << 20   # (a literal in receive_batch's verdict launch)
+EMIT_SLOTS_MAX = LAUNCH_CONSTANTS["kItemBlocksMax"] * LAUNCH_CONSTANTS["kEmitThreads"]                     # 4 194 304
 
 
 def sub(a, b):
@@ -178,6 +190,7 @@ class PacketReceiver:
         self.window_ready_flag = False
         self.advanced = 0   # ids the window moved (a step's driver resets it)
         self.tags = set()   # branches taken, for the generators' coverage condition
+        self.receives = self.receives_over_one_tile = 0   # receive() calls, and those over more than TILE ids
 
     def handle_datagram(self, dg):
         base_id = self.base_id
@@ -259,6 +272,15 @@ class PacketReceiver:
     def receive(self, sink):
         """sink(sequence_id, channel_id, data or None) per delivered packet."""
         base_id, end_id = self.base_id, self.end_id
+        # (the tags on tiles: where the ids lie in runs of TILE from base_id, the device form's unit of work)
+        n_ids = sub(end_id, base_id)
+        self.receives += 1
+        if n_ids > TILE:
+            self.receives_over_one_tile += 1
+            self.tags.add("ids_over_one_tile")
+        if n_ids > 2 * TILE:
+            self.tags.add("ids_over_two_tiles")
+        served = set()
         seq = base_id
         while seq != end_id:
             if self.channel_ready_flags == 0:
@@ -271,6 +293,9 @@ class PacketReceiver:
                     channel = self.channels[channel_id]
                     channel_base_id = channel.base_id if channel.base_id is not None else base_id
                     if channel_parent_lead == 0 or channel_parent_lead > sub(seq, channel_base_id):
+                        if channel_id not in served and sub(seq, base_id) >= TILE:
+                            self.tags.add("first_delivery_in_later_tile")
+                        served.add(channel_id)
                         sink(seq, channel_id, self.data_entries[idx])  # (a dud: None, where the reference panics)
                         self.data_entries[idx] = None
                         self.dud_entries[idx] = False
@@ -282,6 +307,12 @@ class PacketReceiver:
                     else:
                         self.channel_ready_flags &= ~bit
                         self.tags.add("channel_stalled")
+                        later = (sub(seq, base_id) // TILE + 1) * TILE   # the first lead of the next tile
+                        for k in range(later, n_ids):
+                            j = add(base_id, k) & self.receive_window_mask
+                            if self.data_flags[j] and self.channel_entries[j][0] == channel_id:
+                                self.tags.add("stalled_with_data_in_later_tile")
+                                break
                 else:
                     self.tags.add("channel_not_ready")
             seq = add(seq, 1)
@@ -298,8 +329,12 @@ class PacketReceiver:
                         new_base_id = next_id
                     else:
                         self.tags.add("window_stalled")
+                        if sub(seq, base_id) >= TILE:
+                            self.tags.add("advance_stopped_in_later_tile")
                         break
                 seq = next_id
+            if sub(new_base_id, base_id) > TILE:
+                self.tags.add("advance_past_a_tile_edge")
             self.advance_window(new_base_id)
 
     def resynchronize(self, sender_next_id):
@@ -503,6 +538,8 @@ def expected_step(rxs, batch, bad=None):
                 counts[st] += 1
         if batch.deliver[r]:
             rx.receive(lambda seq, ch, data: delivered.append((seq, ch, data)))
+        if rx.advanced > TILE:
+            rx.tags.add("advanced_over_one_tile")
         out["delivered"].append(delivered)
         out["counts"].append(counts)
         out["completed"].append(done[0])
@@ -596,7 +633,8 @@ def check(o, exp, rxs, batch, receivers_in, slots_in, slot_first, bad=None, what
                int(res["bytes_delivered"]))
         assert got == want, (what, r, got, want)
         assert o["receivers_out"][r: r + 1].tobytes() == heads[r].tobytes(), (what, r, o["receivers_out"][r], heads[r][0])
-    for j in range(slots_exp.size):
+    assert o["slots"].size == slots_exp.size, what
+    for j in np.flatnonzero((o["slots"].view(np.uint8).reshape(-1, 32) != slots_exp.view(np.uint8).reshape(-1, 32)).any(axis=1)):
         assert o["slots"][j] == slots_exp[j], (what, j, o["slots"][j], slots_exp[j])
     # the carry: held packets and received fragments only (the rest is unspecified), and the bit words
     for r, rx in enumerate(rxs):
@@ -623,6 +661,120 @@ def check(o, exp, rxs, batch, receivers_in, slots_in, slot_first, bad=None, what
                 if lo < hi:
                     assert np.array_equal(o["carry_out"][lo:hi], c[lo - base: hi - base]), (what, r, j, lo, ln)
     assert np.all(o["carry_out"][min(cf[-1], carry_cap):] == FILL), what
+
+
+# ---- calls too large for the restatement: a sample of receivers, sums in numpy, another native form ----
+def exclusive_sum(counts):
+    return np.concatenate([[0], np.cumsum(counts, dtype=np.uint64)]).astype(np.uint64)
+
+
+def sub_batch(batch, sample):
+    """The Batch of the receivers `sample` alone: their frames, over the same items and payload."""
+    ff = batch.frame_first.astype(np.int64)
+    idx = np.concatenate([np.arange(ff[r], ff[r + 1]) for r in sample] + [np.zeros(0, np.int64)]).astype(np.int64)
+    first = exclusive_sum([ff[r + 1] - ff[r] for r in sample])
+    return Batch(batch.infos[idx], batch.items, batch.payload, first,
+                 None if batch.src_base is None else batch.src_base[idx],
+                 None if batch.frame_accept is None else batch.frame_accept[idx],
+                 [batch.resync[r] for r in sample], [batch.deliver[r] for r in sample])
+
+
+def check_receivers(o, exp, rxs, batch, sample, receivers_in, slots_in, slot_first, what=""):
+    """check() on the receivers `sample` of a call over many more: receiver r's part is cut out of the outputs `o`
+    (run_native's, no cap below its need) and laid out as the outputs of a call over the sample alone: its records
+    with out_offset relative to the sample's first byte, its delivered bytes (found from bytes_delivered, the
+    exclusive sum over all receivers), its carry and slots with data_offset moved likewise.  `exp`, `rxs`: the
+    restatement's expected_step over sub_batch(batch, sample) and the sample's PacketReceivers after it."""
+    res = o["results"]
+    pf, cf = o["packet_first"].astype(np.int64), o["carry_first"].astype(np.int64)
+    of = exclusive_sum(res["bytes_delivered"]).astype(np.int64)
+    assert o["packets_used"] <= o["packets"].size and o["out_used"] <= o["out_bytes"].size
+    assert o["carry_used"] <= o["carry_out"].size and int(of[-1]) == o["out_used"], what
+    sf = slot_first.astype(np.int64)
+    packets, outs, carries, slots, slots_before, results = [], [], [], [], [], []
+    new_pf, new_of, new_cf, new_sf = [0], [0], [0], [0]
+    for r in sample:
+        W = int(receivers_in["window_size"][r])
+        p = o["packets"][pf[r]: pf[r + 1]].copy()
+        assert p.size == int(res["packet_count"][r]), (what, r)
+        p["out_offset"] = (p["out_offset"].astype(np.int64) - of[r] + new_of[-1]).astype(np.uint64)
+        s = o["slots"][sf[r]: sf[r] + W].copy()
+        s["data_offset"] = (s["data_offset"].astype(np.int64) - cf[r] + new_cf[-1]).astype(np.uint64)
+        one = res[r: r + 1].copy()
+        one["packet_first"] = new_pf[-1]
+        packets.append(p)
+        outs.append(o["out_bytes"][of[r]: of[r + 1]])
+        carries.append(o["carry_out"][cf[r]: cf[r + 1]])
+        slots.append(s)
+        slots_before.append(slots_in[sf[r]: sf[r] + W])
+        results.append(one)
+        new_pf.append(new_pf[-1] + p.size)
+        new_of.append(new_of[-1] + int(of[r + 1] - of[r]))
+        new_cf.append(new_cf[-1] + int(cf[r + 1] - cf[r]))
+        new_sf.append(new_sf[-1] + W)
+    cut = {"packets": np.concatenate(packets), "packet_first": np.array(new_pf, np.uint64), "packets_used": new_pf[-1],
+           "out_bytes": np.concatenate(outs), "out_used": new_of[-1], "carry_out": np.concatenate(carries),
+           "carry_first": np.array(new_cf, np.uint64), "carry_used": new_cf[-1], "item_status": o["item_status"],
+           "results": np.concatenate(results), "receivers_out": o["receivers_out"][list(sample)],
+           "slots": np.concatenate(slots)}
+    check(cut, exp, rxs, batch, receivers_in[list(sample)], np.concatenate(slots_before), np.array(new_sf, np.uint64),
+          what=what)
+
+
+def slot_regions(slots):
+    """Every slot's carry region, in numpy (rx_slot_region)."""
+    held = np.where((slots["rx_flags"] & 6) == 2, slots["data_len"], 0).astype(np.uint64)
+    n = np.where(slots["asm_state"] == fr.RX_ASM_ACTIVE, slots["asm_last_fragment_id"].astype(np.uint64) + 1, 0).astype(np.uint64)
+    return ((held + 7) & ~np.uint64(7)) + n * FRAG + 8 * ((n + 63) // 64), held
+
+
+def check_sums(o, slot_first, what=""):
+    """The firsts and used counts of a call from its own per-receiver outputs: packet_first the exclusive sum of
+    the results' packet_count, carry_first that of the carry sizes recomputed from the output slots (the receivers'
+    slot ranges lie one behind the other), out_used the sum of bytes_delivered."""
+    res = o["results"]
+    assert np.array_equal(o["packet_first"], exclusive_sum(res["packet_count"])), what
+    assert np.array_equal(res["packet_first"], o["packet_first"][:-1].astype(np.uint32)), what
+    region, _ = slot_regions(o["slots"])
+    sf = slot_first.astype(np.int64)
+    per = np.add.reduceat(region, sf[:-1]) if sf.size > 1 else np.zeros(0, np.uint64)
+    per[sf[:-1] == sf[1:]] = 0
+    assert np.array_equal(o["carry_first"], exclusive_sum(per)), what
+    assert o["packets_used"] == int(o["packet_first"][-1]) and o["carry_used"] == int(o["carry_first"][-1]), what
+    assert o["out_used"] == int(res["bytes_delivered"].sum(dtype=np.uint64)), what
+
+
+def span_index(offsets, lengths):
+    """The indices of the bytes [offsets[k], offsets[k] + lengths[k]) for every k, in numpy."""
+    lengths = lengths.astype(np.int64)
+    total = int(lengths.sum())
+    starts = np.cumsum(lengths) - lengths
+    return np.repeat(offsets.astype(np.int64) - starts, lengths) + np.arange(total, dtype=np.int64)
+
+
+def check_same(o, h, what=""):
+    """Two native forms of one call over inputs that leave no ACTIVE slot behind, both from run_native (outputs
+    pre-filled with FILL): every record, count, status, state field and slot equal, the delivered bytes equal and
+    FILL behind them, the carry equal over the held packets' bytes (the padding between them is unspecified) and
+    FILL behind carry_used."""
+    for key in ("packets_used", "out_used", "carry_used"):
+        assert o[key] == h[key], (what, key, o[key], h[key])
+    for key in ("packet_first", "carry_first", "item_status", "out_bytes"):
+        assert np.array_equal(o[key], h[key]), (what, key)
+    for key in ("results", "receivers_out", "slots", "packets"):
+        assert o[key].size == h[key].size, (what, key)
+        a, b = o[key].view(np.uint8).reshape(o[key].size, -1), h[key].view(np.uint8).reshape(h[key].size, -1)
+        if not np.array_equal(a, b):
+            bad = np.flatnonzero((a != b).any(axis=1))
+            assert bad.size == 0, (what, key, bad.size, bad[:8].tolist(), o[key][bad[0]], h[key][bad[0]])
+    assert np.all(o["out_bytes"][o["out_used"]:] == FILL) and np.all(o["carry_out"][o["carry_used"]:] == FILL), what
+    assert np.all(o["packets"][o["packets_used"]:].view(np.uint8) == FILL), what
+    assert not np.any(o["slots"]["asm_state"] == fr.RX_ASM_ACTIVE), what
+    _, held = slot_regions(o["slots"])
+    k = np.flatnonzero(held)
+    idx = span_index(o["slots"]["data_offset"][k], held[k])
+    assert idx.size == 0 or int(idx.max()) < o["carry_used"], what
+    assert np.array_equal(o["carry_out"][idx], h["carry_out"][idx]), what
 
 
 # ---- generators ----
@@ -759,3 +911,63 @@ def gen_step(rng, rxs, senders, held, n_packets=10, sizes=SIZES, chaos=True, per
                 resyncs[r] = add(rx.base_id, int(rng.integers(0, rx.receive_window_size + 2)))
             delivers[r] = 0 if rng.random() < hold else 1
     return Batch(infos, items, payload, ff, frame_accept=accept, resync=resyncs, deliver=delivers)
+
+
+# ---- batches for many receivers, built in numpy ----
+def pair_batch(rng, bases, size0, size1, copies=4, lead=3):
+    """A step in which receiver r (window of two ids or more, base bases[r]) gets two whole packets of size0[r] and
+    size1[r] bytes, ids base and base + 1, channels 0 to 2, the first reliable (the second names it as its window
+    parent, and as its channel parent where the channels agree).  A packet's fragments arrive last first, every
+    datagram `copies` times in a row, the later copies with other bytes: the first arrival wins, the later ones
+    find the slot closed or, while a fragment buffer is open, their fragment's bit in the step's duplicate table.
+    One frame per datagram (its copies).  Returns a Batch that does not deliver, and the packets' channels."""
+    n = bases.size
+    size = np.stack([size0, size1], axis=1).reshape(-1).astype(np.int64)          # per packet: 2 r + k
+    nf = np.maximum(1, (size + FRAG - 1) // FRAG)
+    ch = rng.integers(0, 3, 2 * n)
+    pid = (np.repeat(bases.astype(np.int64), 2) + np.tile([0, 1], n)) & MASK
+    second = np.tile([0, 1], n)
+    cl = second * (ch == np.roll(ch, 1))
+    D = int(nf.sum())
+    p = np.repeat(np.arange(2 * n), nf)
+    f = nf[p] - 1 - (np.arange(D) - np.repeat(np.cumsum(nf) - nf, nf))
+    ln = np.where(f < nf[p] - 1, FRAG, size[p] - (nf[p] - 1) * FRAG)
+    d = np.repeat(np.arange(D), copies)
+    items = np.zeros(D * copies, dtype=fr.ITEM_DTYPE)
+    items["id"], items["channel_id"] = pid[p][d], ch[p][d]
+    items["window_parent_lead"], items["channel_parent_lead"] = second[p][d], cl[p][d]
+    items["fragment_id"], items["fragment_id_last"], items["data_len"] = f[d], (nf[p] - 1)[d], ln[d]
+    items["data_offset"] = lead + np.cumsum(ln[d]) - ln[d]
+    payload = rng.integers(0, 256, lead + int(ln[d].sum()), dtype=np.uint8)
+    infos = np.zeros(D, dtype=fr.FRAME_INFO_DTYPE)
+    infos["kind"], infos["ok"], infos["item_count"], infos["item_first"] = 10, 1, copies, np.arange(D) * copies
+    per = nf.reshape(-1, 2).sum(axis=1)
+    return Batch(infos, items, payload, exclusive_sum(per), deliver=[0] * n), ch.reshape(-1, 2)
+
+
+def sparse_batch(n, frames, rng=None, lead=3, **kw):
+    """A Batch over n receivers of which only a few have frames: frames = {receiver: [(kind, accept, [datagram
+    tuples])]}, the others' ranges empty."""
+    arena = PayloadArena(rng or np.random.default_rng(1), lead)
+    infos, items, accept, count = [], [], [], np.zeros(n, dtype=np.int64)
+    for r in sorted(frames):
+        for kind, acc, dgs in frames[r]:
+            info = np.zeros(1, dtype=fr.FRAME_INFO_DTYPE)
+            info["kind"], info["ok"], info["item_first"], info["item_count"] = kind, 1, len(items), len(dgs)
+            infos.append(info)
+            accept.append(acc)
+            items += datagram_items(arena, dgs)
+        count[r] = len(frames[r])
+    arr = np.zeros(len(items), dtype=fr.ITEM_DTYPE)
+    for k, it in enumerate(items):
+        arr[k] = it
+    infos = np.concatenate(infos) if infos else np.zeros(0, dtype=fr.FRAME_INFO_DTYPE)
+    return Batch(infos, arr, arena.array(), exclusive_sum(count), frame_accept=np.array(accept, dtype=np.uint8), **kw)
+
+
+def sample_of(rng, n, fixed, size=64):
+    """`size` receiver indices or more: the `fixed` ones that exist, the rest drawn."""
+    s = {int(r) for r in fixed if 0 <= r < n}
+    while len(s) < min(size, n):
+        s.add(int(rng.integers(0, n)))
+    return sorted(s)

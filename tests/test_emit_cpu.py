@@ -157,6 +157,26 @@ def test_max_packet():
     assert items["data_len"][2 + 65535] == EE.MAX_FRAGMENT_SIZE and items["fragment_id"][2 + 65535] == 65535
 
 
+@pytest.mark.parametrize("nthreads", [1, 4])
+def test_many_max_packets(nthreads):
+    """66 senders of one MAX_PACKET_SIZE packet each among small ones (the GPU test's batch beyond the item
+    kernel's grid): the host call, which is that test's reference, against the closed form and the restatement
+    (emit_expect.check_max_packets), and the small senders against the restatement in full."""
+    b, big = EE.many_max_packets()
+    packets, first, senders = b.arrays()
+    items, ff, pres, sres, sout, used = emit_packets_host(packets, first, senders, nthreads=nthreads)
+    assert used == len(big) * 65536 + 23 and int(ff[-1]) == used
+    EE.check_max_packets(items, ff, packets, first, senders, big)
+    for s in sorted(set(range(senders.size)) - set(big)):
+        a, z = int(first[s]), int(first[s + 1])
+        e = EE.expect(packets[a:z], np.array([0, z - a], dtype=np.uint64), senders[s: s + 1])
+        r = int(senders[s]["reserve_items"])
+        assert int(sres[s]["item_first"]) == int(ff[s]) and int(sres[s]["item_count"]) == e.items_used == int(ff[s + 1] - ff[s])
+        assert (items[int(ff[s]) + r: int(ff[s + 1])] == e.items[r:]).all(), s
+        assert sout[s: s + 1].tobytes() == e.senders_out.tobytes(), s
+    assert (sres["stop"] == EE.DONE).all() and (pres["status"] == EE.EMITTED).all()
+
+
 def test_items_cap_in_place_and_no_packet_results():
     b = EE.tile_cases()
     packets, first, senders = b.arrays()

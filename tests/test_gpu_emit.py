@@ -237,3 +237,32 @@ def test_emit_pack_build_seal_gate_parse(engine):
             parts.append(wire[a:a + int(t2["data_len"][g])])
         got = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
         assert np.array_equal(got, payload[int(pk["data_offset"]):int(pk["data_offset"]) + int(pk["data_len"])]), k
+
+
+def test_more_items_than_the_item_grid(engine):
+    """66 senders of one MAX_PACKET_SIZE packet each among small ones: 4 325 376 items and more, beyond the item
+    kernel's grid of kItemBlocksMax workgroups (its stride loop).  Every output against the host call's, field for
+    field, and the big packets' items in closed form (emit_expect.check_max_packets); the slack behind items_used
+    stays as it was."""
+    import receive_expect as E
+    from uflow_amd import frame as fr
+    b, big = EE.many_max_packets()
+    packets, first, senders = b.arrays()
+    ref = fr.emit_packets_host(packets, first, senders, nthreads=8)
+    used, slack = ref[5], 1000
+    assert used > E.EMIT_SLOTS_MAX and len(big) * 65536 > E.EMIT_SLOTS_MAX   # the threshold, from the inputs
+    items = torch.full((used + slack, 24), EE.FILL, dtype=torch.uint8, device=DEV)
+    got = _host(engine.emit_packets(*_dev(packets, first, senders), items_cap=used + slack, items=items))
+    torch.cuda.synchronize()
+    assert got[5] == used and np.array_equal(got[1].astype(np.uint64), ref[1])
+    g_items = got[0].view(ITEM_DTYPE).reshape(-1)
+    # (the reserved slots in front of a sender's items stay as they were on both sides: FILL here, zero there)
+    reserved = np.zeros(used, dtype=bool)
+    for s in np.flatnonzero(senders["reserve_items"]):
+        reserved[int(ref[1][s]): int(ref[1][s]) + int(senders["reserve_items"][s])] = True
+    same = (g_items[:used].view(np.uint8).reshape(-1, 24) == ref[0].view(np.uint8).reshape(-1, 24)).all(axis=1)
+    assert same[~reserved].all(), np.flatnonzero(~same & ~reserved)[:8]
+    assert (g_items[:used][reserved].view(np.uint8) == EE.FILL).all() and (g_items[used:].view(np.uint8) == EE.FILL).all()
+    for k, dt in ((2, EE.PACKET_RESULT_DTYPE), (3, EE.SENDER_RESULT_DTYPE), (4, SENDER_DTYPE)):
+        assert got[k].tobytes() == ref[k].tobytes(), dt.names
+    EE.check_max_packets(g_items, got[1], packets, first, senders, big)

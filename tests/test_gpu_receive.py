@@ -76,7 +76,7 @@ def test_golden_cases(engine, case):
     T.test_stalled_channel_released_two_steps_later, T.test_ready_flag_clear_on_entry,
     T.test_allocation_limit_duds_and_empty_packet, T.test_resynchronize_and_deliver_zero,
     T.test_lying_sender_leaves_a_stale_entry_behind, T.test_bad_state_and_bad_src,
-    T.test_first_fragment_alone_with_default_caps], ids=lambda f: f.__name__[5:])
+    T.test_first_fragment_alone_with_default_caps, *T.TILE_SCENARIOS, *T.COPY_SCENARIOS], ids=lambda f: f.__name__[5:])
 def test_scenarios(engine, monkeypatch, scenario):
     """The host test's scenarios with the device call in the host call's place."""
     monkeypatch.setattr(T, "host", gpu_call(engine))
@@ -179,17 +179,34 @@ def test_random_runs(engine, n_receivers):
             assert tag in tags, tag
 
 
-def test_four_steps_one_stream_no_synchronise(engine):
+@pytest.mark.parametrize("n_receivers", [12, 96])
+def test_random_tile_runs(engine, n_receivers):
+    """The random runs over several tiles of ids (tests/test_receive_cpu.py, TILE_GEN): the 12 receivers and four
+    steps of the host test, and 96 receivers over two steps.  The condition is the restatement's, as above."""
+    rxs = []
+    _, tags = T.random_run(gpu_call(engine), T.TILE_SEEDS[0] if n_receivers == 12 else 60, n_receivers,
+                           steps=4 if n_receivers == 12 else 2, windows=T.TILE_WINDOWS, gen=T.TILE_GEN, rxs_out=rxs)
+    T.assert_tile_condition(tags, rxs)
+
+
+@pytest.mark.parametrize("family", ["one_tile", "tiles"])
+def test_four_steps_one_stream_no_synchronise(engine, family):
     """Four carried steps queued back to back on one stream, state and carry staying on the device (the later
-    calls need less scratch than the first: it is reused); everything is checked afterwards."""
-    rng = np.random.default_rng(13)
-    rxs = [E.PacketReceiver((1, 8, 64)[r % 3], 0xFFFFF - 5 * r, 4000 if r % 4 == 1 else 1 << 30) for r in range(40)]
+    calls need less scratch than the first: it is reused); everything is checked afterwards.  `tiles`: windows of
+    256 ids and the generator options of the runs over several tiles."""
+    rng = np.random.default_rng(15 if family == "tiles" else 13)   # (15: the tile condition below holds)
+    if family == "tiles":
+        rxs = [E.PacketReceiver(256, 0xFFFFF - 5 * r, 4000 if r % 4 == 1 else 1 << 30) for r in range(12)]
+        gens = [T.TILE_GEN] * 4
+    else:
+        rxs = [E.PacketReceiver((1, 8, 64)[r % 3], 0xFFFFF - 5 * r, 4000 if r % 4 == 1 else 1 << 30) for r in range(40)]
+        gens = [dict(n_packets=12 if k == 0 else 4) for k in range(4)]
     txs = [E.GenSender(rx.base_id) for rx in rxs]
     held = [[] for _ in rxs]
     receivers, slots, slot_first, carry = E.new_state(rxs)
     plan = []
     for k in range(4):
-        b = E.gen_step(rng, rxs, txs, held, n_packets=12 if k == 0 else 4)
+        b = E.gen_step(rng, rxs, txs, held, **gens[k])
         exp = E.expected_step(rxs, b)
         a = _dev_args(b.infos, b.items, b.payload, b.frame_first, receivers, slots, slot_first, carry, b.src_base,
                       b.frame_accept)
@@ -221,6 +238,8 @@ def test_four_steps_one_stream_no_synchronise(engine):
         E.check(_host_out(d, slots_after), exp, rxs_k, b, recv_before.cpu().numpy().view(fr.RECEIVER_DTYPE).reshape(-1),
                 slots_before.cpu().numpy().view(fr.RX_SLOT_DTYPE).reshape(-1), slot_first, what="queued step")
     engine.release_stream(s)
+    if family == "tiles":
+        T.assert_tile_condition(set().union(*[rx.tags for rx in rxs]), rxs)
 
 
 def test_scratch_reuse_after_a_larger_call(engine):
@@ -277,3 +296,97 @@ def test_emit_to_receive_on_the_device(engine):
                     for p in packets[s * per: (s + 1) * per] if p["channel_id"] == c]
             assert got == want, (s, c)
     assert np.array_equal(h["receivers_out"]["base_id"], (senders["base_id"] + per) & 0xFFFFF)
+
+
+# ---- launch shapes beyond one grid: many receivers, the copy kernels' second pass ----
+def big_step(engine, batch, state, sample, rxs, what):
+    """One step of a call too large for the restatement, on the device: every output against the host call's
+    (which tests/test_receive_cpu.py pins to the restatement), the firsts and used counts against sums over the
+    call's own per-receiver outputs, and the receivers `sample` against the restatement (`rxs`, advanced).
+    Returns the next state."""
+    receivers, slots, slot_first, carry = state
+    dev = E.run_native(gpu_call(engine), batch, receivers, slots, slot_first, carry)
+    ref = E.run_native(fr.receive_packets_host, batch, receivers, slots, slot_first, carry, nthreads=8)
+    E.check_same(dev, ref, what)
+    E.check_sums(dev, slot_first, what)
+    sub = E.sub_batch(batch, sample)
+    E.check_receivers(dev, E.expected_step(rxs, sub), rxs, sub, sample, batch.apply(receivers.copy()), slots, slot_first,
+                      what)
+    return dev, (dev["receivers_out"], dev["slots"], slot_first, dev["carry_out"][:dev["carry_used"]].copy())
+
+
+def pair_receivers(rng, n, big=()):
+    """n receivers with a window of two ids, bases over the whole id space and at the wrap; two packets each of
+    1 to 40 bytes, every sixteenth with a second packet of two fragments; `big`: sizes of first packets that 40
+    receivers spread over the index range get instead."""
+    bases = rng.integers(0, 1 << 20, n)
+    bases[::97] = 0xFFFFF
+    size0, size1 = rng.integers(1, 41, n), rng.integers(1, 41, n)
+    size1[5::16] += FRAG
+    where = (np.arange(40) * (n - 1) // 39) if len(big) else np.zeros(0, np.int64)
+    size0[where] = np.resize(big, where.size)
+    fixed = [0, 7, 8, 63, 64, E.RX_FEW - 2, E.RX_FEW - 1, E.RX_FEW, n - 1, 5, 21, 97] + where.tolist()
+    sample = E.sample_of(rng, n, fixed, 64 + where.size)
+    rxs = [E.PacketReceiver(2, int(bases[r]), 1 << 40) for r in sample]
+    state = (fr.new_receivers(n, 2, bases), np.zeros(2 * n, dtype=fr.RX_SLOT_DTYPE), np.arange(n + 1, dtype=np.uint64) * 2,
+             np.zeros(0, U8))
+    return bases, size0, size1, sample, rxs, state
+
+
+def held_then_delivered(engine, n, big=()):
+    rng = np.random.default_rng(15)
+    bases, size0, size1, sample, rxs, state = pair_receivers(rng, n, big)
+    held, _ = E.pair_batch(rng, bases, size0, size1)
+    o, state = big_step(engine, held, state, sample, rxs, "held")
+    assert o["packets_used"] == 0 and int((o["slots"]["rx_flags"] & fr.RX_SLOT_DATA != 0).sum()) == 2 * n
+    assert fr.RX_DROPPED_DUPLICATE in o["item_status"] and fr.RX_DROPPED_CLOSED in o["item_status"]
+    extra = {r: [(10, 1, [(int(bases[r]), 0, 0, 0, 0, 0, b"again"), (E.add(int(bases[r]), 2), 0, 0, 0, 0, 0, b"beyond")])]
+             for r in sample[::2]}
+    chunks = int(((np.concatenate([size0, size1]) + E.RX_CHUNK - 1) // E.RX_CHUNK).sum())
+    o, state = big_step(engine, E.sparse_batch(n, extra), state, sample, rxs, "delivered")
+    assert o["packets_used"] == 2 * n and o["carry_used"] == 0 and o["out_used"] == int(size0.sum() + size1.sum())
+    return held, chunks
+
+
+def test_many_receivers_held_then_delivered(engine):
+    """35 000 receivers (the 64-lane form of begin, items and finish), every slot held for a step and delivered in
+    the next: 280 000 datagrams, each arriving four times (the item copy's second grid pass), then 140 000 slot
+    segments of which 70 000 hold a chunk (the slot copy's grid clipped, and more chunks than its waves)."""
+    n = 35000
+    held, chunks = held_then_delivered(engine, n)
+    assert n + 1 >= E.RX_FEW and held.items.size > E.COPY_ITEMS_MAX   # the thresholds, from the inputs
+    assert (2 * 2 * n + 3) // 4 > E.LAUNCH_CONSTANTS["kCopyBlocksMax"] and chunks > E.COPY_WAVES_MAX
+
+
+def test_multi_chunk_segments_among_many(engine):
+    """33 000 receivers as above, 40 of them over the index range holding a packet of 2047 to 4339 bytes: the
+    binary search in the chunk prefix over mixed counts, some of those chunks in the second grid pass."""
+    n = 33000
+    big = (E.RX_CHUNK - 1, E.RX_CHUNK, E.RX_CHUNK + 1, 2 * E.RX_CHUNK + 3, 3 * FRAG - 5)
+    held, chunks = held_then_delivered(engine, n, big)
+    assert n + 1 >= E.RX_FEW and chunks > E.COPY_WAVES_MAX + 2 * len(big)
+
+
+def test_more_receivers_than_verdict_workgroups(engine):
+    """2^20 + 70 receivers with a window of one id, frames for about 200 of them (valid, invalid, out-of-window
+    datagrams, frames that do not count), the others' ranges empty: the verdict kernel's stride over receivers."""
+    rng = np.random.default_rng(16)
+    top = E.VERDICT_GROUPS_MAX
+    n = top + 70
+    bases = (np.arange(n, dtype=np.int64) * 7 + 0xFFFF0) & E.MASK
+    active = sorted(set(range(top - 1, n)) | {0, 7, 8, 63, 64, E.RX_FEW - 2, E.RX_FEW - 1, E.RX_FEW}
+                    | set(rng.integers(0, top, 122).tolist()))
+    frames = {}
+    for k, r in enumerate(active):
+        b = int(bases[r])
+        good = (b, k % 3, 0, 0, 0, 0, bytes(rng.integers(0, 256, 1 + k % 40, dtype=U8)))
+        bad = [(b, 0, 0, 0, 2, 1, b"fragment 2 of 2"), (E.add(b, 1), 0, 0, 0, 0, 0, b"beyond"), (b, 64, 0, 0, 0, 0, b"channel")]
+        frames[r] = [(10, 1, [bad[k % 3], good, good]), (12, 1, [good]), (10, k % 5 != 0, [good, bad[(k + 1) % 3]])]
+    batch = E.sparse_batch(n, frames, rng)
+    sample = E.sample_of(rng, n, active, len(active) + 8)
+    rxs = [E.PacketReceiver(1, int(bases[r]), 1 << 40) for r in sample]
+    state = (fr.new_receivers(n, 1, bases), np.zeros(n, dtype=fr.RX_SLOT_DTYPE), np.arange(n + 1, dtype=np.uint64),
+             np.zeros(0, U8))
+    assert n > E.VERDICT_GROUPS_MAX and {top - 1, top, top + 1, n - 1} <= set(sample)
+    o, _ = big_step(engine, batch, state, sample, rxs, "verdict stride")
+    assert o["packets_used"] == len(active) and (o["results"]["packet_count"][active] == 1).all()

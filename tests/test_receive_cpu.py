@@ -1,6 +1,7 @@
 """ufc_receive_packets_host against the plain Python restatement of PacketReceiver / AssemblyWindow /
 FragmentBuffer (tests/receive_expect.py): every record, status, state field, slot field and delivered byte, all
 exact.  The golden cases are the reference's own unit tests (tests/golden/packet_receiver_cases.json)."""
+import copy
 import json
 import os
 
@@ -290,18 +291,26 @@ BRANCHES = ("multi_completed", "empty_packet", "channel_stalled", "channel_not_r
             "window_passed_undelivered", "stale_overwritten", "active_cleared")
 
 
-def random_run(call, seed, n_receivers, steps=4, windows=(1, 8, 64), **kw):
-    """`steps` random steps with the carry swapped each time; returns the status totals and the tags seen."""
+def random_receivers(rng, n_receivers, windows):
+    return [E.PacketReceiver(windows[r % len(windows)], int(rng.integers(0, 1 << 20)) | 3 if r % 2 else 0xFFFFF - r,
+                             4000 if r % 5 == 1 else 1 << 30) for r in range(n_receivers)]
+
+
+def random_run(call, seed, n_receivers, steps=4, windows=(1, 8, 64), gen=None, rxs_out=None, **kw):
+    """`steps` random steps with the carry swapped each time; returns the status totals and the tags seen.  gen:
+    options of receive_expect.gen_step; the other keywords go to the native call.  rxs_out: a list that receives
+    the PacketReceivers."""
     rng = np.random.default_rng(seed)
-    rxs = [E.PacketReceiver(windows[r % len(windows)], int(rng.integers(0, 1 << 20)) | 3 if r % 2 else 0xFFFFF - r,
-                            4000 if r % 5 == 1 else 1 << 30) for r in range(n_receivers)]
+    rxs = random_receivers(rng, n_receivers, windows)
     txs = [E.GenSender(rx.base_id) for rx in rxs]
     held = [[] for _ in rxs]
     h = E.Harness(rxs, call)
     total = np.zeros(11, dtype=np.int64)
     for k in range(steps):
-        _, exp = h.step(E.gen_step(rng, rxs, txs, held), what=f"seed {seed} step {k}", **kw)
+        _, exp = h.step(E.gen_step(rng, rxs, txs, held, **(gen or {})), what=f"seed {seed} step {k}", **kw)
         total += np.sum(exp["counts"], axis=0)
+    if rxs_out is not None:
+        rxs_out += rxs
     return total, set().union(*[rx.tags for rx in rxs])
 
 
@@ -317,6 +326,322 @@ def test_random_multi_step_runs(nthreads):
     for tag in BRANCHES:
         assert tag in tags, tag
     assert total[fr.RX_DUD] > 0
+
+
+# The second family of random runs: receive() over several tiles of ids (the device form takes E.TILE at a time
+# and carries the channels' base, count and ready flag, the window's new base and the running sums from tile to
+# tile in LDS).  Windows of 128 to 1024 ids, as many new packets a step as the window has room for, three
+# channels, small packets (a few of two fragments) so that the restatement stays cheap, and every kind of chaos.
+TILE_WINDOWS = (128, 256, 1024)
+TILE_GEN = dict(n_packets=300, sizes=(0, 1, 7, 8, 33, 64, 100, 200) * 5 + (FRAG + 9, 2 * FRAG))
+# What these runs must reach (receive_expect.PacketReceiver.tags): the inputs' condition, not the kernels'.
+TILE_SEEDS = (44, 45)   # (each reaches every one of TILE_BRANCHES on its own)
+TILE_BRANCHES = ("ids_over_one_tile", "ids_over_two_tiles", "stalled_with_data_in_later_tile",
+                 "first_delivery_in_later_tile", "advance_stopped_in_later_tile", "advance_past_a_tile_edge",
+                 "advanced_over_one_tile")
+
+
+def assert_tile_condition(tags, rxs):
+    for tag in TILE_BRANCHES:
+        assert tag in tags, tag
+    receives = sum(rx.receives for rx in rxs)
+    over = sum(rx.receives_over_one_tile for rx in rxs)
+    assert 2 * over > receives, (over, receives)   # most receive() calls see more than a tile of ids
+
+
+@pytest.mark.parametrize("nthreads", [1, 4])
+def test_random_multi_tile_runs(nthreads):
+    tags, rxs = set(), []
+    for seed in TILE_SEEDS:
+        _, g = random_run(host, seed, 12, windows=TILE_WINDOWS, gen=TILE_GEN, rxs_out=rxs, nthreads=nthreads)
+        tags |= g
+    assert_tile_condition(tags, rxs)
+
+
+def test_launch_constants_mirror_the_source():
+    """receive_expect.LAUNCH_CONSTANTS, by which the big-shape GPU tests are sized, are the source's."""
+    import re
+    csrc = os.path.join(HERE, "..", "uflow_amd", "csrc")
+    text = ""
+    for name in ("packet_receive.hip", "packet_receive.hpp", "packet_emit.hip", "packet_emit.hpp", "frame_codec_core.hpp"):
+        with open(os.path.join(csrc, name)) as f:
+            text += f.read()
+    for name, value in E.LAUNCH_CONSTANTS.items():
+        m = re.search(r"constexpr\s+uint(?:32|64)_t\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert m and int(m.group(1)) == value, name
+    assert re.search(r"std::min<uint64_t>\(a\.n_receivers,\s*1u << 20\)", text) and E.VERDICT_GROUPS_MAX == 1 << 20
+    assert "n1 < kRxFew ? kRxThreadsFew : kRxThreads" in text
+    assert E.TILE == 64 and "for (uint32_t t0 = 0; t0 < n; t0 += 64)" in text   # rx_receive_tiles
+
+
+# ---- receive() over more than one tile of ids: directed scenarios (run on the device by tests/test_gpu_receive.py) ----
+def chain(first, n, ch=0, size=lambda k: (7 * k) % 23):
+    """n packets of consecutive ids on one channel, each the reliable parent of the next (leads of one), the
+    first without a parent: every lead clears once the packet before is delivered."""
+    return [(E.add(first, k), ch, 1 if k else 0, 1 if k else 0, 0, 0, iota(k, size(k))) for k in range(n)]
+
+
+def delivered_ids(o):
+    return o["packets"][:o["packets_used"]]["sequence_id"].tolist()
+
+
+@pytest.mark.parametrize("base", [5, 0xFFFFF - 70, 256 - 20], ids=["plain", "ids_wrap_in_tile_1", "ring_wraps_in_tile_0"])
+def test_tile_edge_counts(base):
+    """63 to 129 ids between base and end and a full window of 128, one channel, every lead clearing: all
+    delivered in id order, out_offset a running sum over the tile edge.  From 0xFFFFF - 70 the ids wrap at lead 71
+    (tile 1), and so does the ring index (both are multiples of the window size apart from the base, so they wrap
+    together); from 236 the ring of 256 slots wraps at lead 20, inside tile 0."""
+    counts = (63, 64, 65, 127, 128, 129, 128)
+    windows = (128, 128, 128, 128, 128, 256, 128)   # (the last: n == W)
+    rxs = [E.PacketReceiver(W, base, 1 << 30) for W in windows]
+    h = E.Harness(rxs, host)
+    o, exp = h.step(E.simple_batch([chain(base, n) for n in counts], per_frame=50), what=f"edge counts from {base}")
+    for r, n in enumerate(counts):
+        recs = o["packets"][int(o["packet_first"][r]): int(o["packet_first"][r + 1])]
+        assert recs["sequence_id"].tolist() == [E.add(base, k) for k in range(n)], (r, n)
+        assert recs["len"].tolist() == [(7 * k) % 23 for k in range(n)]
+        assert np.array_equal(np.diff(recs["out_offset"].astype(np.int64)), recs["len"][:-1]), (r, n)
+        assert rxs[r].base_id == E.add(base, n) and int(o["results"][r]["advanced"]) == n
+    assert o["carry_used"] == 0 and "advance_past_a_tile_edge" in rxs[2].tags
+
+
+def test_stall_in_tile_0_holds_the_later_tiles():
+    """Channel 1 (the even leads) stalls at lead 10: its reliable parent, lead 8, is withheld.  Everything it has in
+    tiles 1 and 2 would clear on its own leads (the first of each tile names no parent, the others the packet
+    before) and none of it may go; channel 2 (the odd leads) is delivered throughout.  A step later the parent
+    arrives and the rest goes in order."""
+    base, n = 0xFFFFF - 100, 192
+    rx = E.PacketReceiver(256, base, 1 << 30)
+    h = E.Harness([rx], host)
+    dgs = []
+    for k in range(n):
+        seq, data = E.add(base, k), iota(k, k % 19)
+        if k % 2:       # channel 2, unreliable; from lead 9 on the packet before it is the window's parent
+            dgs.append((seq, 2, 1 if k > 8 else 0, 0, 0, 0, data))
+        elif k < 8:
+            dgs.append((seq, 1, 0, 0, 0, 0, data))
+        elif k == 8:    # channel 1 is reliable from here on: each names the one before as both parents
+            parent = (seq, 1, 0, 0, 0, 0, data)
+        else:
+            dgs.append((seq, 1, 2, 0 if k % 64 < 2 else 2, 0, 0, data))
+    o, exp = h.step(E.simple_batch([dgs], per_frame=64), what="stalled")
+    got = exp["delivered"][0]
+    assert [d[0] for d in got if d[1] == 1] == [E.add(base, k) for k in (0, 2, 4, 6)]
+    assert [d[0] for d in got if d[1] == 2] == [E.add(base, k) for k in range(1, n, 2)]
+    assert "stalled_with_data_in_later_tile" in rx.tags and rx.base_id == E.add(base, 8)
+    o, exp = h.step(E.simple_batch([[parent]]), what="released")
+    assert delivered_ids(o) == [E.add(base, k) for k in range(8, n, 2)]
+    assert o["carry_used"] == 0 and rx.base_id == E.add(base, n)
+
+
+@pytest.mark.parametrize("variant", ["all", "part", "count_runs_out"])
+def test_channel_count_across_the_tile_edge(variant):
+    """70 packets of one channel held over a step without delivery, across the tile edge: receive() starts with
+    channel_packet_count = 70 and the ready flag set, and the count that is left and the ready flag are the
+    restatement's.  `part`: lead 65 is withheld and lead 66 names it, so 65 packets go and 5 stay.
+    `count_runs_out`: the header says 66 where 70 wait (state no run produces; the restatement delivers 66 and
+    clears the ready flag with the last of them, in tile 1)."""
+    base = 0xFFFFF - 30
+    rx = E.PacketReceiver(128, base, 1 << 30)
+    h = E.Harness([rx], host)
+    if variant == "part":
+        dgs = [(E.add(base, k), 4, int(k == 66), int(k == 66), 0, 0, iota(k, 1 + k % 9)) for k in range(71) if k != 65]
+    else:
+        dgs = [(E.add(base, k), 4, 0, 0, 0, 0, iota(k, 1 + k % 9)) for k in range(70)]
+    o, _ = h.step(E.simple_batch([dgs], per_frame=32, deliver=[0]), what="held")
+    assert o["packets_used"] == 0 and rx.channels[4].packet_count == 70 and rx.channel_ready_flags == 1 << 4
+    if variant == "count_runs_out":
+        rx.channels[4].packet_count = 66
+        h.receivers["channel_packet_count"][0, 4] = 66
+    o, _ = h.step(E.simple_batch([[]]), what=variant)
+    want, left = {"all": (70, 0), "part": (65, 5), "count_runs_out": (66, 0)}[variant]
+    assert delivered_ids(o) == [E.add(base, k) for k in range(want)]
+    assert int(o["receivers_out"][0]["channel_packet_count"][4]) == left == rx.channels[4].packet_count
+    assert int(o["receivers_out"][0]["channel_ready_flags"]) == 0 and "ids_over_one_tile" in rx.tags
+
+
+@pytest.mark.parametrize("stop", [False, True], ids=["runs_through", "stops_at_the_edge"])
+def test_window_advance_over_the_tile_edge(stop):
+    """ENTRY slots at leads 62, 63 (tile 0) and 64, 65 (tile 1), each naming the packet before as its window
+    parent: the advance runs through, on the new base carried over the edge.  With lead 64 withheld, lead 65
+    fails (an entry next to a cleared one cannot: its lead is measured from the new base) and the advance stops
+    at base + 64, whatever clears in tile 2: channel bases are unset only in (base, base + 64], the allocation is
+    given back by the cleared slots only (a CLOSED entry at 62 and 63, an ACTIVE buffer at lead 10; the ACTIVE
+    buffer at lead 70 and the entries beyond stay)."""
+    rng = np.random.default_rng(21)
+    base = 0xFFFFF - 63   # the ids wrap at the tile edge
+    rx = E.PacketReceiver(256, base, 1 << 30)
+    h = E.Harness([rx], host)
+    at = lambda k: E.add(base, k)  # noqa: E731
+    dgs = [frags(at(10), 3, 0, 0, rnd(rng, FRAG + 40))[1], frags(at(70), 3, 0, 0, rnd(rng, 2 * FRAG))[0]]
+    dgs += [(at(62), 0, 0, 0, 0, 0, b"sixty-two"), (at(63), 0, 1, 0, 0, 0, b"sixty-three")]
+    if not stop:
+        dgs.append((at(64), 0, 1, 0, 0, 0, b"sixty-four"))
+    dgs += [(at(65), 1, 1, 0, 0, 0, b"sixty-five"), (at(130), 5, 0, 0, 0, 0, b"tile two"), (at(131), 5, 0, 0, 0, 0, b"too")]
+    o, _ = h.step(E.simple_batch([dgs]), what="advance")
+    out = o["receivers_out"][0]
+    if stop:
+        assert rx.base_id == at(64) and "window_stalled" in rx.tags and "advance_stopped_in_later_tile" in rx.tags
+        assert int(out["channel_base_id"][0]) == E.NONE and int(out["channel_base_id"][1]) == at(66)
+        assert int(out["alloc"]) == 2 * FRAG + len(b"sixty-five") + len(b"tile two") + len(b"too")
+    else:
+        assert rx.base_id == at(132) and "advance_past_a_tile_edge" in rx.tags
+        assert int(out["channel_base_id"][5]) == E.NONE and int(out["alloc"]) == 0
+    assert int(out["base_id"]) == rx.base_id and "active_cleared" in rx.tags
+    assert delivered_ids(o) == [at(k) for k in (62, 63, 64, 65, 130, 131) if not (stop and k == 64)]
+
+
+def test_window_not_ready_with_deliveries_in_tile_2():
+    """window_ready is 0 (no arrival's window lead cleared) while channels deliver in tile 2: the channels' state
+    and the ready flags are written, the window does not move, end_id stays."""
+    base = 0xFFFFF - 140
+    rx = E.PacketReceiver(256, base, 1 << 30)
+    h = E.Harness([rx], host)
+    at = lambda k: E.add(base, k)  # noqa: E731
+    dgs = [(at(130 + k), 0, 5, 0, 0, 0, b"zero %d" % k) for k in range(4)]
+    dgs += [(at(135), 1, 5, 0, 0, 0, b"one"), (at(145), 1, 5, 6, 0, 0, b"waits for 139"), (at(150), 2, 9, 0, 0, 0, b"two")]
+    o, _ = h.step(E.simple_batch([dgs]), what="window not ready")
+    out = o["receivers_out"][0]
+    assert delivered_ids(o) == [at(k) for k in (130, 131, 132, 133, 135, 150)]
+    assert (int(out["base_id"]), int(out["end_id"]), int(out["window_ready"])) == (base, at(151), 0)
+    assert int(out["channel_ready_flags"]) == 0 and int(out["channel_packet_count"][1]) == 1
+    assert int(o["results"][0]["advanced"]) == 0 and "first_delivery_in_later_tile" in rx.tags
+
+
+TILE_SCENARIOS = [test_stall_in_tile_0_holds_the_later_tiles, test_window_not_ready_with_deliveries_in_tile_2]
+TILE_SCENARIOS += [pytest.param(lambda b=b: test_tile_edge_counts(b), id=f"tile_edge_counts_{b}") for b in (5, 0xFFFFF - 70, 236)]
+TILE_SCENARIOS += [pytest.param(lambda v=v: test_channel_count_across_the_tile_edge(v), id=f"channel_count_{v}")
+                   for v in ("all", "part", "count_runs_out")]
+TILE_SCENARIOS += [pytest.param(lambda s=s: test_window_advance_over_the_tile_edge(s), id=f"window_advance_stop_{s}")
+                   for s in (False, True)]
+
+
+# ---- the copies: the cap inside a chunk, and every alignment ----
+def held_state(call):
+    """One receiver after two steps without delivery: a 3-byte packet (so that the next one's delivered bytes
+    start at an odd offset), a 5000-byte packet of four fragments, and an ACTIVE buffer with two of its three
+    fragments.  Returns (harness, the three steps' batches): the harness has run the first `steps`."""
+    rng = np.random.default_rng(22)
+    rx = E.PacketReceiver(8, 0xFFFF8, 1 << 30)   # (the carry is laid out in slot order: these are slots 0, 1, 2)
+    big, part = frags(0xFFFF9, 0, 0, 0, rnd(rng, 5000)), frags(0xFFFFA, 1, 0, 0, rnd(rng, 2 * FRAG + 77))
+    first = E.simple_batch([[(0xFFFF8, 0, 0, 0, 0, 0, b"odd")] + big[::-1] + [part[2], part[0]]], deliver=[0])
+    return E.Harness([rx], call), [first, E.simple_batch([[]], deliver=[0]), E.simple_batch([[]])]
+
+
+# The cap in turn inside the head bytes of a copy (delivered bytes only: a carry destination is 8-byte aligned),
+# inside the word body, inside the tail of chunk 0, at the chunk's edge, inside chunk 1 and inside the next segment.
+CARRY_CAPS = (8 + 1001, 8 + E.RX_CHUNK - 1, 8 + E.RX_CHUNK, 8 + 3000, 5008 + 100, 5008 + FRAG + 5)
+OUT_CAPS = (2, 5, 3 + 5 + 994, 3 + E.RX_CHUNK - 2, 3 + E.RX_CHUNK, 3 + 3000)
+
+
+@pytest.mark.parametrize("step", [0, 1, 2], ids=["datagrams_to_carry", "carry_to_carry", "carry_to_out"])
+def test_cap_inside_a_chunk(step):
+    """carry_cap (the datagrams' copy into the carry, then the slot copy from carry to carry) and out_cap (the
+    slot copy of the delivering step) below the need, falling inside a copy: the bytes below the cap are right,
+    nothing at or beyond it is written (check() compares the whole pre-filled arrays), the used counts exact."""
+    for cap in (OUT_CAPS if step == 2 else CARRY_CAPS):
+        h, batches = held_state(host)
+        for k in range(step):
+            h.step(batches[k], what=f"before, step {k}")
+        o, _ = h.step(batches[step], caps={"out" if step == 2 else "carry": cap}, what=f"step {step} cap {cap}")
+        assert o["carry_used"] == 8 + 5000 + 3 * FRAG + 8 - (5008 if step == 2 else 0)
+        assert o["out_used"] == (5003 if step == 2 else 0)
+
+
+ALIGN_LENGTHS = tuple(range(18)) + (23, 24, 25)
+
+
+def aligned_packets(lengths_and_alignments, base=0xFFFFF - 9):
+    """One receiver's batch of single-fragment packets of consecutive ids on one channel without parents, given as
+    (length, delivered offset mod 8, payload offset mod 8): a filler packet in front of each moves the running sum
+    of the delivered lengths, padding in the payload arena the source.  Returns (Batch, [(length, dst & 7, src & 7)]
+    as the inputs have them: the delivered offset from the lengths in id order, the source from the items)."""
+    rng = np.random.default_rng(23)
+    arena = E.PayloadArena(rng)
+    items, got, seq = [], [], base
+    for ln, d, s in lengths_and_alignments:
+        for size, src in (((d - sum(int(it["data_len"]) for it in items)) % 8, None), (ln, s)):
+            if src is not None:
+                arena.put(bytes((src - len(arena.buf)) % 8))
+            data = rnd(rng, size)
+            last = max((size + FRAG - 1) // FRAG, 1) - 1
+            first = len(items)
+            items += [E.make_item(seq, 0, 0, 0, f, last, arena.put(data[f * FRAG: (f + 1) * FRAG]),
+                                  len(data[f * FRAG: (f + 1) * FRAG])) for f in range(last + 1)]
+            if src is not None:
+                before = sum(int(it["data_len"]) for it in items[:first])
+                got.append((sum(int(it["data_len"]) for it in items[first:]), before & 7, int(items[first]["data_offset"]) & 7))
+            seq = E.add(seq, 1)
+    infos, arr, ff = E.frames_of([items], per_frame=100)
+    return E.Batch(infos, arr, arena.array(), ff), got
+
+
+def test_item_copy_alignments():
+    """The copy of a datagram's bytes (16 lanes, head / 8-byte words / tail): lengths 0..17 and 23..25, delivered
+    in the step they arrive in; destination and source together take all 64 (dst & 7, src & 7) pairs in each length
+    class (below 8, 8 to 15, 16 and more)."""
+    classes = ([n for n in ALIGN_LENGTHS if 0 < n < 8], [n for n in ALIGN_LENGTHS if 8 <= n < 16],
+               [n for n in ALIGN_LENGTHS if n >= 16])
+    want = [(c[(p + p // 8) % len(c)], p & 7, p >> 3) for c in classes for p in range(64)] + [(0, d, 7 - d) for d in range(8)]
+    batch, got = aligned_packets(want)
+    assert got == want
+    assert {(min(ln // 8, 2), d, s) for ln, d, s in got if ln} == {(c, d, s) for c in range(3) for d in range(8) for s in range(8)}
+    assert {ln for ln, _, _ in got} == set(ALIGN_LENGTHS)
+    rx = E.PacketReceiver(1024, 0xFFFFF - 9, 1 << 30)
+    o, _ = E.Harness([rx], host).step(batch, what="item copy alignments")
+    assert o["packets_used"] == 2 * len(want) and o["carry_used"] == 0
+
+
+def test_slot_copy_alignments():
+    """The copy of a held packet (a wave per 2048-byte chunk): the same lengths and 2047, 2048, 2049, held for a
+    step and delivered in the next at every destination alignment; in the carry the neighbours' sizes put them at
+    every multiple of 8."""
+    want = [(ln, d, (ln + d) % 8) for ln in ALIGN_LENGTHS + (E.RX_CHUNK - 1, E.RX_CHUNK, E.RX_CHUNK + 1) for d in range(8)]
+    batch, got = aligned_packets(want)
+    assert got == want
+    batch.deliver = [0]
+    rx = E.PacketReceiver(1024, 0xFFFFF - 9, 1 << 30)
+    h = E.Harness([rx], host)
+    o, _ = h.step(batch, what="held")
+    assert o["packets_used"] == 0 and o["carry_used"] > 8 * 3 * E.RX_CHUNK
+    o, _ = h.step(E.simple_batch([[]]), what="slot copy alignments")
+    assert o["packets_used"] == 2 * len(want) and o["carry_used"] == 0
+    assert [(int(p["len"]), int(p["out_offset"]) & 7) for p in o["packets"][1:2 * len(want):2]] == [w[:2] for w in want]
+
+
+COPY_SCENARIOS = [pytest.param(lambda k=k: test_cap_inside_a_chunk(k), id=f"cap_inside_a_chunk_{k}") for k in range(3)]
+COPY_SCENARIOS += [test_item_copy_alignments, test_slot_copy_alignments]
+
+
+def test_many_receivers_helpers_on_the_host():
+    """The big-shape GPU tests' batch builders and checks at a size the restatement affords, on the host call alone:
+    pair_batch and sparse_batch against the restatement over every receiver (Harness), then check_receivers on a
+    sample, check_sums and check_same (one thread against four) on the same outputs."""
+    rng = np.random.default_rng(24)
+    n = 150
+    bases = rng.integers(0, 1 << 20, n)
+    bases[::7] = 0xFFFFF
+    size0, size1 = rng.integers(1, 41, n), rng.integers(1, 41, n)
+    size1[5::16] += FRAG
+    size0[3::50] = (2047, 2048, 4096 + 3)
+    rxs = [E.PacketReceiver(2, int(b), 1 << 40) for b in bases]
+    h = E.Harness(rxs, host)
+    sample = E.sample_of(rng, n, (0, 7, 8, 63, 64, n - 1, 5, 21, 3, 53), 20)
+    held, _ = E.pair_batch(rng, bases, size0, size1)
+    extra = {r: [(10, 1, [(int(bases[r]), 0, 0, 0, 0, 0, b"again"), (E.add(int(bases[r]), 2), 0, 0, 0, 0, 0, b"beyond")])]
+             for r in sample[::2]}
+    for k, batch in enumerate((held, E.sparse_batch(n, extra))):
+        before = (h.receivers.copy(), h.slots.copy(), h.carry.copy(), [copy.deepcopy(rxs[r]) for r in sample])
+        o, exp = h.step(batch, what=f"pairs step {k}")
+        if k == 0:   # the later copies: the duplicate table while a buffer is open, a closed slot otherwise
+            assert fr.RX_DROPPED_DUPLICATE in exp["status"] and fr.RX_DROPPED_CLOSED in exp["status"]
+        assert (o["packets_used"], int((h.slots["rx_flags"] & 2 != 0).sum())) == ((0, 2 * n) if k == 0 else (2 * n, 0))
+        o4 = E.run_native(host, batch, before[0], before[1], h.slot_first, before[2], nthreads=4)
+        E.check_same(o4, o, what=f"threads step {k}")
+        E.check_sums(o4, h.slot_first, what=f"sums step {k}")
+        sub = E.sub_batch(batch, sample)
+        E.check_receivers(o4, E.expected_step(before[3], sub), before[3], sub, sample, batch.apply(before[0].copy()),
+                          before[1], h.slot_first, what=f"sample step {k}")
 
 
 def test_first_fragment_alone_with_default_caps():
