@@ -35,6 +35,12 @@
  *                                 AssemblyWindow and FragmentBuffer (assembly_window/mod.rs:69-199,
  *                                 fragment_buffer.rs:12-57): the parses' datagram items into delivered packets,
  *                                 many receivers per call, on the host and on the GPU
+ *   ufc_frame_window_host, ufc_frame_window_varlen
+ *                              <- FrameAckQueue::window_contains, mark_seen, resynchronize and base_id
+ *                                 (src/half_connection/frame_ack_queue.rs) as handle_data_frame and
+ *                                 handle_sync_frame call them (src/half_connection/mod.rs:132-152): the parses'
+ *                                 frames into the receive's frame_accept verdicts and the packs' ack groups,
+ *                                 many connections per call, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -584,6 +590,83 @@ int ufc_receive_packets_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size
                                size_t packets_cap, uint64_t* d_packet_first, uint64_t* d_packets_used,
                                uint8_t* d_out_bytes, size_t out_cap, uint64_t* d_out_used, uint8_t* d_item_status,
                                ufc_receiver_result* d_results, ufc_receiver* d_receivers_out, void* stream);
+
+/* ---- batched frame window: accept verdicts and ack groups, many connections per call ----
+ * The step between the parse and the receive, and the source of the ack flushes the pack takes: FrameAckQueue
+ * (src/half_connection/frame_ack_queue.rs, whole file) as handle_data_frame and handle_sync_frame drive it
+ * (src/half_connection/mod.rs:132-152).  The release build is the specification, wrapping u32 arithmetic
+ * included.  A window is one connection's state: the ReceiveWindow (base_id, size), the last entry of the
+ * deque of pending ack groups (the only entry mark_seen ever reads or changes) and sync_reply.  One call runs
+ * every connection's frames, in arrival order:
+ *   data frame (ok, kind == UFC_FRAME_DATA; id = f[0], nonce = aux & 1):
+ *     if (id - base_id) < size (wrapping) it is accepted and base_id = id + 1; then, with a tail and
+ *     bit = id - tail_base_id < 32: if that bit of tail_bitfield is clear it is set and tail_nonce ^= nonce (a set
+ *     bit changes nothing: the rule is kept literal although consistent states never meet it); otherwise the
+ *     tail is closed and (id, 1, nonce) is the new tail.  A frame that is not accepted changes nothing;
+ *   sync frame (ok, kind == UFC_FRAME_SYNC): if aux bit 0 (next_frame_id = f[0] present), d = f[0] - base_id
+ *     (wrapping), and 0 < d <= size: base_id = f[0].  next_packet_id (aux bit 1) belongs to the packet receiver:
+ *     ufc_receive_packets_* takes it as resync_id.  sync_reply is set whatever aux holds;
+ *   every other kind, and every frame with ok == 0: no effect. */
+typedef struct ufc_frame_window {      /* 24 bytes; in and out */
+  uint32_t base_id, size;              /* ReceiveWindow */
+  uint32_t tail_base_id, tail_bitfield;/* the last pending ack group, if has_tail */
+  uint8_t  tail_nonce, has_tail, sync_reply, reserved;
+  uint32_t reserved2;
+} ufc_frame_window;
+
+#define UFC_FW_DONE 0
+#define UFC_FW_BAD_STATE 1  /* size > 2^31, or the frame range reversed or outside [0, n_frames): nothing done,
+                               state copied through, its frames' frame_accept written 0 only where the range is usable */
+typedef struct ufc_frame_window_result { /* 40 bytes */
+  uint32_t group_first, group_count;   /* its groups: groups[group_first ..+ group_count) */
+  uint32_t accepted, refused;          /* ok data frames inside / outside the window */
+  uint32_t syncs, packet_syncs;        /* ok sync frames; those with next_packet_id present */
+  uint32_t first_packet_sync;          /* frame index of the first of those, UFC_NO_PARENT if none: where the caller
+                                          splits the receive step (resync_id / deliver) */
+  uint32_t advanced;                   /* ids base_id moved in this step (wrapping sum) */
+  uint32_t stop, reserved;
+} ufc_frame_window_result;
+
+/* Connection r owns frames [frame_first[r], frame_first[r + 1]) (CSR, n_windows + 1 entries) in arrival order: the
+ * CSR the receive takes, so one grouping serves both calls.  Outputs:
+ *   frame_accept[n_frames]  written for every frame of every usable range: 1 exactly for accepted data frames, 0 for
+ *                      everything else, so that it is passed to ufc_receive_packets_* unchanged.  Frames outside
+ *                      every range are not touched.
+ *   groups, groups_cap ufc_item records in the ack-group form of the parse and the pack: form = 3, id = base_id,
+ *                      channel_id = nonce (0/1), data_offset = bitfield, everything else 0.  For connection r the
+ *                      carried tail comes first if has_tail != 0, as updated, and is written even when unchanged;
+ *                      the groups opened in this step follow in order.  Groups at an index >= groups_cap are not
+ *                      written; *groups_used is exact and the state advances all the same (compare, as with the
+ *                      parse).  groups_cap = n_windows + n_frames is always enough.
+ *   group_first        [n_windows + 1], the exclusive sum of the connections' group counts: directly the
+ *                      flush_first of ufc_pack_* (an ack flush per connection: kind = UFC_FRAME_ACK, id0 = the new
+ *                      base_id, id1 = the packet receiver's base_id).  *groups_used = group_first[n_windows].
+ *   results            [n_windows].  A BAD_STATE connection has no groups, zero counts and first_packet_sync =
+ *                      UFC_NO_PARENT.
+ *   windows_out        [n_windows], required, may be `windows` itself: the new base_id; the tail = the connection's
+ *                      last output group, with has_tail = 1 if any group came out (else has_tail = 0 and the tail
+ *                      fields as they came); sync_reply = the input OR'd with 1 if the range holds an ok sync frame;
+ *                      size and the reserved fields copied.  tail_nonce is read as tail_nonce & 1.
+ * A caller that flushed every group clears has_tail: the reference's empty deque then opens a new group even
+ * within 32 ids of the old one.  After a SIZE_LIMITED ack flush the caller keeps the unpacked groups and leaves the
+ * tail as it is.  Any 24 bytes are a state, and every input has one answer (size <= 2^31 is what makes the ids of one
+ * group strictly increasing, so that the answer does not depend on the order in which a tile's lanes meet).  Ranges
+ * of different connections must not overlap; where they do, the frame_accept of the shared frames is unspecified.
+ * n_frames and n_windows < 2^31 - 1; n_windows == 0 returns UFC_OK whatever the pointers; a NULL infos with
+ * n_frames != 0, groups with groups_cap != 0, or a NULL frame_first, windows, windows_out, frame_accept, group_first,
+ * groups_used or results is UFC_ERR_INVALID_ARG. */
+int ufc_frame_window_host(const ufc_frame_info* infos, size_t n_frames, const uint64_t* frame_first,
+                          const ufc_frame_window* windows, size_t n_windows, uint8_t* frame_accept,
+                          ufc_item* groups, size_t groups_cap, uint64_t* group_first, uint64_t* groups_used,
+                          ufc_frame_window_result* results, ufc_frame_window* windows_out, int nthreads);
+/* The same on the GPU (gfx950 kernels, frame_window.hip): every pointer device memory, asynchronous on `stream`,
+ * nothing allocated per call.  One wave walks a connection in tiles of 64 frames, twice: once for the group
+ * counts, and after their exclusive sum once more to write.  The context's per-stream scratch holds, in bytes:
+ * 8 (n_windows + 1) (a group count per connection) + the scan's temporaries, each part rounded up to 256. */
+int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const uint64_t* d_frame_first,
+                            const ufc_frame_window* d_windows, size_t n_windows, uint8_t* d_frame_accept,
+                            ufc_item* d_groups, size_t groups_cap, uint64_t* d_group_first, uint64_t* d_groups_used,
+                            ufc_frame_window_result* d_results, ufc_frame_window* d_windows_out, void* stream);
 
 #ifdef __cplusplus
 }

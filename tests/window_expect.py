@@ -1,0 +1,307 @@
+"""The frame window as the reference has it, restated in Python class for class, the step around it, and a traffic
+generator: what ufc_frame_window_host / _varlen are tested against (tests/test_window_cpu.py,
+tests/test_gpu_window.py).
+
+    ReceiveWindow, FrameAckQueue   <- src/half_connection/frame_ack_queue.rs (whole file), u32 arithmetic wrapping
+                                      as the release build's does
+    Connection                     <- handle_data_frame / handle_sync_frame, src/half_connection/mod.rs:132-152
+    expect_batch                   <- the C ABI's record formats around them (include/uflow_frame_codec.h)
+    make_batch                     <- seeded traffic
+
+Nothing here calls the library.
+"""
+import numpy as np
+
+from uflow_amd.frame import (DATA, SYNC, ACK, FRAME_INFO_DTYPE, FRAME_WINDOW_DTYPE, FRAME_WINDOW_RESULT_DTYPE, ITEM_DTYPE,
+                             NO_PARENT)
+
+M32 = 0xFFFFFFFF
+FW_MAX_SIZE = 1 << 31
+
+
+class ReceiveWindow:
+    def __init__(self, base_id, size):
+        self.base_id, self.size = base_id, size
+
+    def contains(self, frame_id):
+        return ((frame_id - self.base_id) & M32) < self.size
+
+    def advance(self, new_base_id):
+        delta = (new_base_id - self.base_id) & M32
+        if delta > 0 and delta <= self.size:
+            self.base_id = new_base_id
+            return True
+        return False
+
+
+class AckGroup:
+    def __init__(self, base_id, bitfield, nonce):
+        self.base_id, self.bitfield, self.nonce = base_id, bitfield, nonce
+
+
+class FrameAckQueue:
+    def __init__(self, size, base_id):
+        self.entries = []
+        self.receive_window = ReceiveWindow(base_id, size)
+
+    def base_id(self):
+        return self.receive_window.base_id
+
+    def resynchronize(self, sender_next_id):
+        return self.receive_window.advance(sender_next_id)
+
+    def window_contains(self, frame_id):
+        return self.receive_window.contains(frame_id)
+
+    def mark_seen(self, frame_id, nonce):
+        if self.receive_window.contains(frame_id):
+            self.receive_window.advance((frame_id + 1) & M32)
+            if self.entries:
+                last = self.entries[-1]
+                bit = (frame_id - last.base_id) & M32
+                if bit < 32:
+                    if last.bitfield & (1 << bit) == 0:
+                        last.bitfield |= 1 << bit
+                        last.nonce ^= nonce
+                else:
+                    self.entries.append(AckGroup(frame_id, 1, nonce))
+            else:
+                self.entries.append(AckGroup(frame_id, 1, nonce))
+
+
+class Connection:
+    """The window's part of HalfConnection: the queue and sync_reply."""
+
+    def __init__(self, size, base_id):
+        self.frame_ack_queue = FrameAckQueue(size, base_id)
+        self.sync_reply = False
+
+    def handle_data_frame(self, sequence_id, nonce):
+        """True when the frame's datagrams go on to the packet receiver."""
+        if self.frame_ack_queue.window_contains(sequence_id):
+            self.frame_ack_queue.mark_seen(sequence_id, nonce)
+            return True
+        return False
+
+    def handle_sync_frame(self, next_frame_id, next_packet_id):
+        """True when the window moved (next_packet_id is the packet receiver's)."""
+        moved = False
+        if next_frame_id is not None:
+            moved = self.frame_ack_queue.resynchronize(next_frame_id)
+        self.sync_reply = True
+        return moved
+
+
+def expect_connection(window, infos, first):
+    """One connection's step.  window: a FRAME_WINDOW_DTYPE record; infos: its frames; first: the index of its first
+    frame in the batch.  Returns (verdicts uint8, groups [(base_id, bitfield, nonce)], window_out record, result
+    dict, facts dict).  facts says what the traffic exercised (for the generator's conditions)."""
+    out = window.copy()
+    n = len(infos)
+    verdicts = np.zeros(n, dtype=np.uint8)
+    res = dict(group_count=0, accepted=0, refused=0, syncs=0, packet_syncs=0, first_packet_sync=NO_PARENT, advanced=0,
+               stop=0)
+    facts = dict(refused=0, sync_moved=0, sync_stayed=0, tail_fold=0, tiles_with_rounds=0, max_rounds=1)
+    if int(window["size"]) > FW_MAX_SIZE:
+        res["stop"] = 1
+        return verdicts, [], out, res, facts
+    c = Connection(int(window["size"]), int(window["base_id"]))
+    c.sync_reply = bool(window["sync_reply"])
+    carried = bool(window["has_tail"])
+    if carried:
+        c.frame_ack_queue.entries.append(AckGroup(int(window["tail_base_id"]), int(window["tail_bitfield"]),
+                                                  int(window["tail_nonce"]) & 1))
+    failed_in_tile = {}
+    for k in range(n):
+        f = infos[k]
+        if not f["ok"]:
+            continue
+        if f["kind"] == DATA:
+            seq, nonce = int(f["f"][0]), int(f["aux"]) & 1
+            only_tail = carried and len(c.frame_ack_queue.entries) == 1
+            tail_bits = c.frame_ack_queue.entries[0].bitfield if only_tail else 0
+            if c.handle_data_frame(seq, nonce):
+                verdicts[k] = 1
+                res["accepted"] += 1
+                if only_tail and len(c.frame_ack_queue.entries) == 1 and c.frame_ack_queue.entries[0].bitfield != tail_bits:
+                    facts["tail_fold"] += 1
+            else:
+                res["refused"] += 1
+                facts["refused"] += 1
+                failed_in_tile[k // 64] = failed_in_tile.get(k // 64, 0) + 1
+        elif f["kind"] == SYNC:
+            aux = int(f["aux"])
+            moved = c.handle_sync_frame(int(f["f"][0]) if aux & 1 else None, int(f["f"][1]) if aux & 2 else None)
+            res["syncs"] += 1
+            if aux & 2:
+                if res["packet_syncs"] == 0:
+                    res["first_packet_sync"] = first + k
+                res["packet_syncs"] += 1
+            if aux & 1:
+                facts["sync_moved" if moved else "sync_stayed"] += 1
+                if not moved:
+                    failed_in_tile[k // 64] = failed_in_tile.get(k // 64, 0) + 1
+    facts["tiles_with_rounds"] = len(failed_in_tile)
+    facts["max_rounds"] = 1 + max(failed_in_tile.values(), default=0)
+    q = c.frame_ack_queue
+    groups = [(g.base_id, g.bitfield, g.nonce) for g in q.entries]
+    res["group_count"] = len(groups)
+    res["advanced"] = (q.base_id() - int(window["base_id"])) & M32
+    out["base_id"] = q.base_id()
+    if groups:
+        out["tail_base_id"], out["tail_bitfield"], out["tail_nonce"] = groups[-1]
+    out["has_tail"] = 1 if groups else 0
+    out["sync_reply"] = int(window["sync_reply"]) | (1 if res["syncs"] else 0)
+    return verdicts, groups, out, res, facts
+
+
+def expect_batch(infos, frame_first, windows, groups_cap=None, prefill=None):
+    """What the call must leave in every output.  prefill: dict of arrays the outputs start from (frame_accept,
+    groups, group_first, results, windows_out); whatever the call does not write keeps its bytes.  Returns the
+    outputs as the wrappers' dict does, plus "facts": the connections' facts summed."""
+    n, nf = len(windows), len(infos)
+    if groups_cap is None:
+        groups_cap = n + nf
+    pre = prefill or {}
+    accept = pre["frame_accept"].copy() if "frame_accept" in pre else np.zeros(nf, dtype=np.uint8)
+    groups = pre["groups"].copy() if "groups" in pre else np.zeros(groups_cap, dtype=ITEM_DTYPE)
+    group_first = np.zeros(n + 1, dtype=np.uint64)
+    results = np.zeros(n, dtype=FRAME_WINDOW_RESULT_DTYPE)
+    windows_out = np.zeros(n, dtype=FRAME_WINDOW_DTYPE)
+    facts = {}
+    total = 0
+    for r in range(n):
+        f0, f1 = int(frame_first[r]), int(frame_first[r + 1])
+        group_first[r] = total
+        results[r]["group_first"] = total
+        if f0 > f1 or f1 > nf:
+            windows_out[r] = windows[r]
+            results[r]["first_packet_sync"] = NO_PARENT
+            results[r]["stop"] = 1
+            continue
+        v, g, w, res, fc = expect_connection(windows[r], infos[f0:f1], f0)
+        accept[f0:f1] = v
+        for k, (e, b, nn) in enumerate(g):
+            if total + k < groups_cap:
+                rec = np.zeros((), dtype=ITEM_DTYPE)
+                rec["id"], rec["channel_id"], rec["form"], rec["data_offset"] = e, nn, 3, b
+                groups[total + k] = rec
+        total += len(g)
+        windows_out[r] = w
+        for key, val in res.items():
+            results[r][key] = val
+        for key, val in fc.items():
+            facts[key] = max(facts.get(key, 0), val) if key == "max_rounds" else facts.get(key, 0) + val
+    group_first[n] = total
+    return {"frame_accept": accept, "groups": groups, "group_first": group_first, "groups_used": total,
+            "results": results, "windows_out": windows_out, "facts": facts}
+
+
+def data_info(seq, nonce=0, ok=1):
+    f = np.zeros((), dtype=FRAME_INFO_DTYPE)
+    f["kind"], f["ok"], f["aux"], f["crc_ok"] = DATA, ok, nonce, 1
+    f["f"][0] = seq & M32
+    return f
+
+
+def sync_info(next_frame_id=None, next_packet_id=None, ok=1):
+    f = np.zeros((), dtype=FRAME_INFO_DTYPE)
+    f["kind"], f["ok"], f["crc_ok"] = SYNC, ok, 1
+    f["aux"] = (1 if next_frame_id is not None else 0) | (2 if next_packet_id is not None else 0)
+    f["f"][0] = (next_frame_id or 0) & M32
+    f["f"][1] = (next_packet_id or 0) & M32
+    return f
+
+
+def make_connection(rng, n_frames, hostile=False, size=None, base=None):
+    """One connection's state and n_frames frames of seeded traffic.  Ordinary traffic: ids in order from the base
+    with gaps of 1 to 40, late and duplicated frames, frames with ok = 0 and other kinds, syncs that advance and
+    syncs that do not, packet syncs, a carried tail within reach of the first ids; the base near 2^32 for some.
+    hostile: random ids around the base and all over the id space, and 24 random bytes of state."""
+    w = np.zeros((), dtype=FRAME_WINDOW_DTYPE)
+    if hostile:
+        w = np.frombuffer(rng.integers(0, 256, size=24, dtype=np.uint8).tobytes(), dtype=FRAME_WINDOW_DTYPE)[0].copy()
+        w["size"] = size if size is not None else [1, 2, 7, 64, 4096, 1 << 31, int(rng.integers(1, 1 << 31))][int(rng.integers(0, 7))]
+        if rng.integers(0, 3) == 0:
+            w["tail_base_id"] = (int(w["base_id"]) - int(rng.integers(0, 40))) & M32
+    else:
+        w["size"] = size if size is not None else [64, 256, 4096][int(rng.integers(0, 3))]
+        w["base_id"] = base if base is not None else \
+            [int(rng.integers(0, 1 << 32)), (M32 - int(rng.integers(0, 50))) & M32, 0][int(rng.integers(0, 3))]
+        if rng.integers(0, 4) != 0:  # a tail left by the last step, its newest frame right below the base
+            back = int(rng.integers(1, 20))
+            w["tail_base_id"] = (int(w["base_id"]) - back) & M32
+            w["tail_bitfield"] = (1 | (1 << (back - 1)) | int(rng.integers(0, 1 << (back - 1)))) & M32 if back > 1 else 1
+            w["tail_nonce"] = int(rng.integers(0, 2))
+            w["has_tail"] = 1
+    size_, base_ = int(w["size"]), int(w["base_id"])
+    infos = np.zeros(n_frames, dtype=FRAME_INFO_DTYPE)
+    nxt = base_
+    sent = []
+    for k in range(n_frames):
+        u = int(rng.integers(0, 100))
+        if hostile:
+            if u < 45:
+                seq = (nxt + int(rng.integers(-3, 6))) & M32
+            elif u < 60:
+                seq = int(rng.integers(0, 1 << 32))
+            elif u < 75:
+                seq = (nxt + size_ - 1 + int(rng.integers(-1, 2))) & M32
+            else:
+                seq = None
+            if seq is not None:
+                infos[k] = data_info(seq, int(rng.integers(0, 4)) if u % 7 == 0 else int(rng.integers(0, 2)),
+                                     ok=0 if u % 11 == 0 else 1)
+                if ((seq - nxt) & M32) < size_ and u % 11:
+                    nxt = (seq + 1) & M32
+            elif u < 90:
+                nfi = (nxt + [0, 1, size_, size_ + 1, int(rng.integers(0, 1 << 32))][int(rng.integers(0, 5))]) & M32
+                infos[k] = sync_info(nfi if u % 5 else None, int(rng.integers(0, 1 << 20)) if u % 2 else None)
+                d = (nfi - nxt) & M32
+                if u % 5 and 0 < d <= size_:
+                    nxt = nfi
+            else:
+                infos[k]["kind"], infos[k]["ok"] = [ACK, 0, 4, 0xFF][int(rng.integers(0, 4))], int(rng.integers(0, 2))
+                infos[k]["f"][0] = nxt
+            continue
+        if u < 70:  # the next frame, after a gap now and then
+            gap = int(rng.integers(1, 41)) if u < 6 else 0
+            seq = (nxt + gap) & M32
+            if gap < size_:
+                infos[k] = data_info(seq, int(rng.integers(0, 2)))
+                sent.append(seq)
+                nxt = (seq + 1) & M32
+            else:
+                infos[k] = data_info(nxt, int(rng.integers(0, 2)))
+                sent.append(nxt)
+                nxt = (nxt + 1) & M32
+        elif u < 78 and sent:  # a duplicate, or a late frame from further back
+            infos[k] = data_info(sent[-1] if u < 74 else sent[int(rng.integers(0, len(sent)))], int(rng.integers(0, 2)))
+        elif u < 82:
+            infos[k] = data_info(nxt, 1, ok=0)
+        elif u < 86:
+            infos[k]["kind"], infos[k]["ok"] = [ACK, 4, 5][int(rng.integers(0, 3))], 1
+            infos[k]["f"][0] = nxt
+        elif u < 91:  # a sync that advances
+            nxt = (nxt + int(rng.integers(1, min(size_, 50) + 1))) & M32
+            infos[k] = sync_info(nxt, int(rng.integers(0, 1 << 20)) if u % 2 else None)
+        elif u < 96:  # a sync that does not: the base itself, or behind it
+            infos[k] = sync_info((nxt - int(rng.integers(0, 9))) & M32, None)
+        else:
+            infos[k] = sync_info(None, int(rng.integers(0, 1 << 20)))
+    return w, infos
+
+
+def make_batch(rng, counts, hostile_every=0, **kw):
+    """A batch: one connection per entry of `counts` (its frame count).  hostile_every = k: every k-th connection
+    is hostile.  Returns (infos, frame_first uint64, windows)."""
+    ws, fs = [], []
+    for r, c in enumerate(counts):
+        w, f = make_connection(rng, c, hostile=bool(hostile_every) and r % hostile_every == hostile_every - 1, **kw)
+        ws.append(w)
+        fs.append(f)
+    windows = np.array(ws, dtype=FRAME_WINDOW_DTYPE) if ws else np.zeros(0, dtype=FRAME_WINDOW_DTYPE)
+    infos = np.concatenate(fs) if fs else np.zeros(0, dtype=FRAME_INFO_DTYPE)
+    frame_first = np.zeros(len(counts) + 1, dtype=np.uint64)
+    frame_first[1:] = np.cumsum(np.asarray(counts, dtype=np.uint64))
+    return infos, frame_first, windows

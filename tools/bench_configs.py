@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -27,6 +27,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            batch's datagrams as many small receivers and as 2048 receivers; the receive, ufc_receive_packets_host
            with 1 thread on the same records and a device-to-device copy of the delivered bytes, one line per
            grouping.  Run with --only receive.
+  window   parsed frames into accept verdicts and ack groups on the device (ufc_frame_window_varlen): the parse_mtu
+           batch's frames as 250,000 connections and as 2,048; the call, ufc_frame_window_host with 1 and 16
+           threads on the same records and a plain device read of the records as the floor, one line per
+           grouping, also written to profiles/window_configs.jsonl.  Run with --only window.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -681,6 +685,105 @@ def receive(eng, dev, reps, n=1_000_000):
     return out
 
 
+WINDOW_OUT = os.path.join(REPO, "profiles", "window_configs.jsonl")
+
+
+def window(eng, dev, reps, n=1_000_000):
+    """The step between the parse and the receive: the parse_mtu batch gated and parsed, its data frames given
+    consecutive sequence ids per connection from a random base, about 0.5 % of them repeating the id before
+    (duplicates) and 0.5 % skipping one (a frame lost), and run through ufc_frame_window_varlen.  Two groupings:
+    250,000 connections of 4 frames and 2,048 connections of about 488 (window 4096 in both).  Per grouping one JSON
+    line, also written to profiles/window_configs.jsonl: the call's time per batch (events around groups of calls,
+    after a settle; the state is not written back, so every call does the same work), ufc_frame_window_host on the
+    same records with 1 and 16 threads (wall clock, median of 3), a plain device read of the same 32 MB of
+    records as the floor, and every output of the GPU call against the host's.  Run with --only window."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import FRAME_INFO_DTYPE, FRAME_WINDOW_DTYPE, FRAME_WINDOW_RESULT_DTYPE, ITEM_DTYPE, new_frame_windows
+    data, offsets, lens = parse_batch(n, True)
+    d = torch.from_numpy(data).to(dev)
+    o = torch.from_numpy(offsets).to(dev)
+    _, valid = eng.crc_varlen(d, o)
+    infos0, _, _ = eng.parse_varlen(d, o, valid)
+    torch.cuda.synchronize()
+    h_infos0 = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1).copy()
+    del infos0, d, o
+    torch.cuda.empty_cache()
+    is_data = (h_infos0["ok"] != 0) & (h_infos0["kind"] == 10)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    c = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    out = []
+    for name, nw in (("250,000", 250_000), ("2,048", 2048)):
+        rng = np.random.default_rng(10)
+        ff = (np.arange(nw + 1, dtype=np.uint64) * n) // nw
+        win = new_frame_windows(nw, 4096, rng.integers(0, 1 << 32, nw, dtype=np.uint64).astype(np.uint32))
+        infos = h_infos0.copy()
+        di = np.flatnonzero(is_data)
+        owner = np.searchsorted(ff, di, side="right") - 1
+        u = rng.random(di.size)
+        inc = np.where(u < 0.005, 0, np.where(u < 0.010, 2, 1)).astype(np.int64)
+        first = np.searchsorted(owner, np.arange(nw), side="left")     # each connection's first data frame
+        first = first[first < di.size]
+        inc[first] = 1
+        run = np.cumsum(inc)
+        start = run[first] - 1                                           # the running sum in front of each connection
+        seq = run - 1 - start[np.searchsorted(first, np.arange(di.size), side="right") - 1]
+        infos["f"][di, 0] = (win["base_id"][owner].astype(np.int64) + seq) & 0xFFFFFFFF
+        cap = nw + n
+        h = {"accept": np.zeros(n, np.uint8), "groups": np.zeros(cap, dtype=ITEM_DTYPE), "gf": np.zeros(nw + 1, np.uint64),
+             "res": np.zeros(nw, dtype=FRAME_WINDOW_RESULT_DTYPE), "wout": np.zeros(nw, dtype=FRAME_WINDOW_DTYPE)}
+        hu = ctypes.c_uint64(0)
+        h_call = lambda T: lib.ufc_frame_window_host(  # noqa: E731
+            c(infos), n, c(ff), c(win), nw, c(h["accept"]), c(h["groups"]), cap, c(h["gf"]), ctypes.addressof(hu),
+            c(h["res"]), c(h["wout"]), T)
+        host_ms = {}
+        for T in (1, 16):
+            ts = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                assert h_call(T) == 0
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
+        g = {"infos": t(infos, 32), "ff": t(ff.astype(np.int64)), "win": t(win, 24),
+             "accept": torch.zeros(n, dtype=torch.uint8, device=dev), "groups": torch.zeros((cap, 24), dtype=torch.uint8, device=dev),
+             "gf": torch.zeros(nw + 1, dtype=torch.int64, device=dev), "used": torch.zeros(1, dtype=torch.int64, device=dev),
+             "res": torch.zeros((nw, 40), dtype=torch.uint8, device=dev), "wout": torch.zeros((nw, 24), dtype=torch.uint8, device=dev)}
+        f_fw = lambda: lib.ufc_frame_window_varlen(  # noqa: E731
+            ctx, p(g["infos"]), n, p(g["ff"]), p(g["win"]), nw, p(g["accept"]), p(g["groups"]), cap, p(g["gf"]), p(g["used"]),
+            p(g["res"]), p(g["wout"]), st)
+        assert f_fw() == 0
+        torch.cuda.synchronize()
+        extra = {}
+        if CHECK:
+            same = lambda a, b: bool(np.array_equal(a.cpu().numpy().reshape(-1), b.view(np.uint8).reshape(-1)))  # noqa: E731
+            extra["equals_host"] = (same(g["accept"], h["accept"]) and same(g["groups"], h["groups"]) and
+                                    same(g["res"], h["res"]) and same(g["wout"], h["wout"]) and
+                                    bool(np.array_equal(g["gf"].cpu().numpy().astype(np.uint64), h["gf"])) and
+                                    int(g["used"].cpu()[0]) == hu.value)
+        settle(f_fw, 500)
+        med, mean = timed(f_fw, reps)
+        read_gbs = ceiling(eng, g["infos"].reshape(-1), reps)
+        read_ms = 32 * n / read_gbs / 1e9 * 1e3
+        res = h["res"]
+        out.append({"config": f"f8: device frame window of the parse_mtu batch's frames, {name} connections (window 4096)",
+                    "frames": n, "connections": nw, "data_frames": int(is_data.sum()), "accepted": int(res["accepted"].sum()),
+                    "refused": int(res["refused"].sum()), "syncs": int(res["syncs"].sum()), "groups": int(hu.value),
+                    "window_ms": round(med, 4), "window_mean_ms": round(mean, 4), "ns_per_frame": round(med * 1e6 / n, 4),
+                    "host_1t_ms": round(host_ms[1], 2), "host_16t_ms": round(host_ms[16], 2),
+                    "host_1t_over_gpu": round(host_ms[1] / med, 1), "host_16t_over_gpu": round(host_ms[16] / med, 1),
+                    "infos_read_GBs": read_gbs, "infos_read_ms": round(read_ms, 4), "window_over_read": round(med / read_ms, 1),
+                    **extra})
+        del g
+        torch.cuda.empty_cache()
+    with open(WINDOW_OUT, "w") as f:
+        for r in out:
+            f.write(json.dumps(r) + "\n")
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -730,7 +833,7 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what in ("pack", "emit", "receive"):
+        elif what in ("pack", "emit", "receive", "window"):
             for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:

@@ -51,12 +51,15 @@ UFC_RX_PACKET_DUD = 1
  UFC_RX_DROPPED_BAD_SRC) = range(11)
 UFC_RX_STATUS_COUNT = 11
 UFC_RX_DONE, UFC_RX_BAD_STATE = 0, 1
+# the batched frame windows (include/uflow_frame_codec.h): why a connection stopped
+UFC_FW_DONE, UFC_FW_BAD_STATE = 0, 1
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _V, _Z = ctypes.c_void_p, ctypes.c_size_t
 _RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, _Z, _V, _V, _V, _Z, _V,
             _V, _V, _V]
+_FW_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -168,6 +171,10 @@ _SIGNATURES = {
     # receivers_out, then nthreads (host) / ctx first and stream last (device)
     "ufc_receive_packets_host": (ctypes.c_int, _RX_ARGS + [ctypes.c_int]),
     "ufc_receive_packets_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RX_ARGS + [ctypes.c_void_p]),
+    # infos, n_frames, frame_first, windows, n_windows, frame_accept, groups, groups_cap, group_first, groups_used,
+    # results, windows_out, then nthreads (host) / ctx first and stream last (device)
+    "ufc_frame_window_host": (ctypes.c_int, _FW_ARGS + [ctypes.c_int]),
+    "ufc_frame_window_varlen": (ctypes.c_int, [ctypes.c_void_p] + _FW_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -246,6 +253,19 @@ class ReceiverResult(ctypes.Structure):
                 ("status_count", ctypes.c_uint32 * 11), ("packets_completed", ctypes.c_uint32),
                 ("packets_dud", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32), ("bytes_delivered", ctypes.c_uint64)]
+
+
+class FrameWindow(ctypes.Structure):
+    _fields_ = [("base_id", ctypes.c_uint32), ("size", ctypes.c_uint32), ("tail_base_id", ctypes.c_uint32),
+                ("tail_bitfield", ctypes.c_uint32), ("tail_nonce", ctypes.c_uint8), ("has_tail", ctypes.c_uint8),
+                ("sync_reply", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("reserved2", ctypes.c_uint32)]
+
+
+class FrameWindowResult(ctypes.Structure):
+    _fields_ = [("group_first", ctypes.c_uint32), ("group_count", ctypes.c_uint32), ("accepted", ctypes.c_uint32),
+                ("refused", ctypes.c_uint32), ("syncs", ctypes.c_uint32), ("packet_syncs", ctypes.c_uint32),
+                ("first_packet_sync", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class Builder(ctypes.Structure):

@@ -391,6 +391,52 @@ class FrameCrcEngine:
                 "out_used": used[1:2], "carry_out": carry_out, "carry_first": carry_first, "carry_used": used[2:3],
                 "item_status": item_status, "results": results, "receivers_out": receivers_out}
 
+    # ---- FrameAckQueue's step for many connections, on the device (uflow_frame_codec.h) ----
+    def frame_window(self, infos, frame_first, windows, groups_cap=None, frame_accept=None, groups=None,
+                     windows_out=None, stream=None):
+        """ufc_frame_window_varlen: one step of FrameAckQueue (window_contains, mark_seen, resynchronize;
+        src/half_connection/frame_ack_queue.rs as half_connection/mod.rs:132-152 drives it) for every connection.
+        infos uint8[n_frames, 32] (what parse_varlen returns), frame_first int64[n + 1] (CSR over the frames, the one
+        receive_packets takes), windows uint8[n, 24] (ufc_frame_window records, uflow_amd.frame.FRAME_WINDOW_DTYPE).
+        Returns a dict of device tensors: frame_accept uint8[n_frames] (1 for the data frames inside the window:
+        pass it to receive_packets), groups uint8[groups_cap, 24] (ack groups as ufc_item records, each
+        connection's carried tail first), group_first int64[n + 1] (CSR over the groups: pack_flushes' flush_first),
+        groups_used int64[1], results uint8[n, 40], windows_out uint8[n, 24] (may be given as `windows`).  groups_cap
+        defaults to n + n_frames, which is always enough; groups at an index >= groups_cap are not written (compare
+        groups_used).  Tensors given for frame_accept, groups and windows_out are written into."""
+        n_frames, n = infos.shape[0], windows.shape[0]
+        if groups_cap is None:
+            groups_cap = groups.shape[0] if groups is not None else n + n_frames
+        groups_cap = int(groups_cap)
+        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._check("frame_first", frame_first, (torch.int64,), n + 1)
+        self._check("windows", windows, (torch.uint8,), 24 * n)
+        self._check("frame_accept", frame_accept, (torch.uint8,), n_frames)
+        self._check("groups", groups, (torch.uint8,), 24 * groups_cap)
+        self._check("windows_out", windows_out, (torch.uint8,), 24 * n)
+        # (the outputs are zeroed on the stream the call is queued on)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if frame_accept is None:
+                frame_accept = torch.zeros(n_frames, dtype=torch.uint8, device=self.device)
+            # (the pointer is required even when there are no frames, and an empty tensor has none)
+            accept_arg = frame_accept if n_frames else torch.zeros(1, dtype=torch.uint8, device=self.device)
+            if groups is None:
+                groups = torch.zeros((groups_cap, 24), dtype=torch.uint8, device=self.device)
+            if windows_out is None:
+                windows_out = torch.zeros((n, 24), dtype=torch.uint8, device=self.device)
+            group_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            results = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
+            used = torch.zeros(1, dtype=torch.int64, device=self.device)
+        check(lib().ufc_frame_window_varlen(self._ctx, _ptr(infos) if n_frames else None, n_frames, _ptr(frame_first),
+                                            _ptr(windows) if n else None, n,
+                                            _ptr(accept_arg) if n else None,
+                                            _ptr(groups) if groups_cap else None, groups_cap, _ptr(group_first),
+                                            _ptr(used), _ptr(results) if n else None,
+                                            _ptr(windows_out) if n else None, self._stream(stream)),
+              "ufc_frame_window_varlen")
+        return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used,
+                "results": results, "windows_out": windows_out}
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

@@ -662,4 +662,34 @@ int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const
   return UFC_OK;
 }
 
+// ---- batched host frame window ----
+int ufc_frame_window_host(const ufc_frame_info* infos, size_t n_frames, const uint64_t* frame_first,
+                          const ufc_frame_window* windows, size_t n_windows, uint8_t* frame_accept,
+                          ufc_item* groups, size_t groups_cap, uint64_t* group_first, uint64_t* groups_used,
+                          ufc_frame_window_result* results, ufc_frame_window* windows_out, int nthreads) {
+  if (n_windows == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!frame_first || !windows || !windows_out || !frame_accept || !group_first || !groups_used || !results ||
+      (!infos && n_frames) || (!groups && groups_cap) || n_frames >= lim || n_windows >= lim)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::FwArgs a{infos, n_frames, frame_first, windows, n_windows, frame_accept, groups, groups_cap,
+                            group_first, groups_used, results, windows_out};
+  // Pass 1: every connection's group count, into group_first; then their exclusive sum; pass 2: the outputs.
+  for_receivers(n_windows, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) group_first[r + 1] = ufc_codec::fw_walk_serial(a, r, false, 0);
+  });
+  uint64_t total = 0;
+  for (size_t r = 0; r < n_windows; r++) {
+    const uint64_t c = group_first[r + 1];
+    group_first[r] = total;
+    total += c;
+  }
+  group_first[n_windows] = total;
+  *groups_used = total;
+  for_receivers(n_windows, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) ufc_codec::fw_walk_serial(a, r, true, group_first[r]);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

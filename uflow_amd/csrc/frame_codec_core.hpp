@@ -1,8 +1,9 @@
 // frame_codec_core.hpp -- the payload parse of Frame::read (everything after the CRC gate), written
 // once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip); further down the
 // encode for the batched builds (frame_build.hip), the emitters' arithmetic for the batched packs
-// (frame_pack.hip), the packet sender's for the batched packet emits (packet_emit.hip) and the packet receiver's
-// step for the batched packet receives (packet_receive.hip).
+// (frame_pack.hip), the packet sender's for the batched packet emits (packet_emit.hip), the packet receiver's
+// step for the batched packet receives (packet_receive.hip) and the frame window's for the batched frame windows
+// (frame_window.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -1322,6 +1323,317 @@ inline __host__ __device__ void rx_finish(const RxArgs& a, uint64_t r, RxPlan* p
       }
     }
   }
+}
+
+// ---- the frame window: FrameAckQueue as handle_data_frame and handle_sync_frame drive it ----
+// Restates src/half_connection/frame_ack_queue.rs (ReceiveWindow::contains / advance :14-26, mark_seen :58-84) and
+// half_connection/mod.rs:132-152, for the batched frame windows (frame_window.hip, ufc_frame_window_host).  A
+// connection's step is walked twice with the same code: once for its group count (write = false: nothing is
+// stored), and after the exclusive sum of the counts once more with its first group index (write = true).
+struct FwArgs {
+  const ufc_frame_info* infos;
+  uint64_t n_frames;
+  const uint64_t* frame_first;
+  const ufc_frame_window* windows;
+  uint64_t n_windows;
+  uint8_t* frame_accept;
+  ufc_item* groups;
+  uint64_t groups_cap;
+  uint64_t* group_first;
+  uint64_t* groups_used;
+  ufc_frame_window_result* results;
+  ufc_frame_window* windows_out;
+};
+
+constexpr uint32_t kFwMaxSize = 0x80000000u;
+// What a frame is to the window.
+constexpr uint32_t kFwData = 1, kFwFrameSync = 2, kFwSync = 4, kFwPacketSync = 8, kFwNonce = 16;
+
+// The class of a frame and its target: the base it leaves behind when it passes (id + 1, or next_frame_id).
+UFC_HD uint32_t fw_classify(const ufc_frame_info& f, uint32_t& target) {
+  target = 0;
+  if (!f.ok) return 0;
+  if (f.kind == UFC_FRAME_DATA) {
+    target = f.f[0] + 1;
+    return kFwData | ((f.aux & 1u) ? kFwNonce : 0u);
+  }
+  if (f.kind == UFC_FRAME_SYNC) {
+    target = f.f[0];
+    return kFwSync | ((f.aux & 1u) ? kFwFrameSync : 0u) | ((f.aux & 2u) ? kFwPacketSync : 0u);
+  }
+  return 0;
+}
+// A candidate (a data frame, or a sync frame with a frame id) against base b: contains(id), or advance's
+// 0 < delta <= size.
+UFC_HD bool fw_passes(uint32_t cls, uint32_t target, uint32_t b, uint32_t size) {
+  if (cls & kFwData) return (uint32_t)(target - 1 - b) < size;
+  const uint32_t d = target - b;
+  return d > 0 && d <= size;
+}
+
+// A connection's running state: the base, the open group (the deque's last entry) and the result's counts.
+struct FwRun {
+  uint32_t base, ge, gb, gn;
+  bool has;
+  uint32_t groups;  // groups closed so far (the open one comes after them)
+  uint32_t accepted, refused, syncs, psyncs, first_psync, reply;
+};
+UFC_HD FwRun fw_run_begin(const ufc_frame_window& W) {
+  FwRun s{};
+  s.base = W.base_id;
+  s.ge = W.tail_base_id;
+  s.gb = W.tail_bitfield;
+  s.gn = W.tail_nonce & 1u;
+  s.has = W.has_tail != 0;
+  s.first_psync = UFC_NO_PARENT;
+  return s;
+}
+UFC_HD bool fw_range_ok(const FwArgs& a, uint64_t ff0, uint64_t ff1) { return ff0 <= ff1 && ff1 <= a.n_frames; }
+UFC_HD void fw_put_group(const FwArgs& a, uint64_t at, uint32_t e, uint32_t b, uint32_t n) {
+  if (at >= a.groups_cap) return;
+  ufc_item g{};
+  g.id = e;
+  g.channel_id = (uint8_t)n;
+  g.form = 3;
+  g.data_offset = b;
+  a.groups[at] = g;
+}
+// mark_seen's second half for an accepted frame.
+UFC_HD void fw_mark(const FwArgs& a, FwRun& s, bool write, uint64_t gfirst, uint32_t id, uint32_t nonce) {
+  const uint32_t off = id - s.ge;
+  if (s.has && off < 32) {
+    if (!(s.gb & (1u << off))) {
+      s.gb |= 1u << off;
+      s.gn ^= nonce;
+    }
+    return;
+  }
+  if (s.has) {
+    if (write) fw_put_group(a, gfirst + s.groups, s.ge, s.gb, s.gn);
+    s.groups++;
+  }
+  s.ge = id;
+  s.gb = 1;
+  s.gn = nonce;
+  s.has = true;
+}
+// BAD_STATE: the state copied through, an empty result.
+UFC_HD void fw_bad(const FwArgs& a, uint64_t r, const ufc_frame_window& W, uint64_t gfirst) {
+  ufc_frame_window_result res{};
+  res.group_first = (uint32_t)gfirst;
+  res.first_packet_sync = UFC_NO_PARENT;
+  res.stop = UFC_FW_BAD_STATE;
+  a.results[r] = res;
+  a.windows_out[r] = W;
+}
+// The end of a step: the open group as the connection's last, the result, the state.  Returns the group count.
+UFC_HD uint64_t fw_end(const FwArgs& a, uint64_t r, const ufc_frame_window& W, const FwRun& s, bool write, uint64_t gfirst) {
+  const uint32_t count = s.groups + (s.has ? 1u : 0u);
+  if (!write) return count;
+  if (s.has) fw_put_group(a, gfirst + s.groups, s.ge, s.gb, s.gn);
+  ufc_frame_window_result res{};
+  res.group_first = (uint32_t)gfirst;
+  res.group_count = count;
+  res.accepted = s.accepted;
+  res.refused = s.refused;
+  res.syncs = s.syncs;
+  res.packet_syncs = s.psyncs;
+  res.first_packet_sync = s.first_psync;
+  res.advanced = s.base - W.base_id;  // (the wrapping sum of the moves)
+  res.stop = UFC_FW_DONE;
+  a.results[r] = res;
+  ufc_frame_window O = W;
+  O.base_id = s.base;
+  if (s.has) {
+    O.tail_base_id = s.ge;
+    O.tail_bitfield = s.gb;
+    O.tail_nonce = (uint8_t)s.gn;
+  }
+  O.has_tail = s.has ? 1 : 0;
+  O.sync_reply = (uint8_t)(W.sync_reply | s.reply);
+  a.windows_out[r] = O;
+  return count;
+}
+
+// The step frame by frame, as the reference runs it.
+inline __host__ __device__ uint64_t fw_walk_serial(const FwArgs& a, uint64_t r, bool write, uint64_t gfirst) {
+  const ufc_frame_window W = a.windows[r];
+  const uint64_t ff0 = a.frame_first[r], ff1 = a.frame_first[r + 1];
+  const bool usable = fw_range_ok(a, ff0, ff1);
+  if (!usable || W.size > kFwMaxSize) {
+    if (write) {
+      if (usable)
+        for (uint64_t i = ff0; i < ff1; i++) a.frame_accept[i] = 0;
+      fw_bad(a, r, W, gfirst);
+    }
+    return 0;
+  }
+  FwRun s = fw_run_begin(W);
+  for (uint64_t i = ff0; i < ff1; i++) {
+    uint32_t target;
+    const uint32_t cls = fw_classify(a.infos[i], target);
+    bool accepted = false;
+    if (cls & kFwData) {
+      accepted = fw_passes(cls, target, s.base, W.size);
+      if (accepted) {
+        s.base = target;
+        s.accepted++;
+        fw_mark(a, s, write, gfirst, target - 1, (cls & kFwNonce) ? 1u : 0u);
+      } else {
+        s.refused++;
+      }
+    } else if (cls & kFwSync) {
+      if ((cls & kFwFrameSync) && fw_passes(cls, target, s.base, W.size)) s.base = target;
+      if (cls & kFwPacketSync) {
+        if (!s.psyncs) s.first_psync = (uint32_t)i;
+        s.psyncs++;
+      }
+      s.syncs++;
+      s.reply = 1;
+    }
+    if (write) a.frame_accept[i] = accepted ? 1 : 0;
+  }
+  return fw_end(a, r, W, s, write, gfirst);
+}
+
+// The same step in tiles of 64 consecutive frames, one lane per frame: the form the device runs, one wave per
+// connection (frame_window.hip), written against a wave policy as rx_receive_tiles is, so that the same text runs
+// as host code (tests/c/window_host_check.hip, against fw_walk_serial):
+//   Wv::lanes(f)   f(lane) for the 64 lanes; what the lanes wrote to `sh` before is visible to all after
+//   Wv::one(f)     f() once
+//   Wv::or64       atomic on the device (vector atomics on LDS), plain on the host
+// What is written outside a phase is the same for every lane (the running state, the masks read back from `sh`).
+// The window: a candidate lane (a data frame, or a sync frame with a frame id) tests itself against the target of
+// the candidate lane before it, the tile's base for the first.  If no lane fails, every verdict is final.
+// Otherwise the first failing lane does fail (all before it passed, so its base was the true one): it drops out
+// as a candidate, and the lanes after it test again.  Rounds per tile = 1 + the refused candidates.
+// The groups, over the accepted lanes in order: the lanes whose id lies within 32 of the open group's base fold into
+// it (an OR of their bits; the parity of the nonces of those whose bit was clear) up to the first lane that does
+// not, which closes the group and opens the next.  A fold also stops in front of a lane whose bit is not above
+// the bit of the lane before it (after a sync frame the ids may come back): that lane folds in the next round,
+// against the bits as they are then, so the bits of one fold are distinct and "only if the bit was clear" stays
+// literal.  A word of `sh` per round, zeroed once per tile: at most 65 window rounds and 64 group rounds.
+struct FwWaveShared {
+  unsigned long long fail[65], stop[65], bits[65], par[65];
+  unsigned long long data_mask, cand_mask, sync_mask, psync_mask;
+  uint32_t target[64];
+  uint8_t cls[64];
+};
+UFC_HD uint32_t fw_high_bit(unsigned long long m) { return 63u - (uint32_t)__builtin_clzll(m); }
+UFC_HD uint32_t fw_low_bit(unsigned long long m) { return (uint32_t)__builtin_ctzll(m); }
+UFC_HD uint32_t fw_popc(unsigned long long m) { return (uint32_t)__builtin_popcountll(m); }
+
+template <class Wv>
+inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh, const FwArgs& a, uint64_t r, bool write,
+                                                  uint64_t gfirst) {
+  const ufc_frame_window W = a.windows[r];
+  const uint64_t ff0 = a.frame_first[r], ff1 = a.frame_first[r + 1];
+  const bool usable = fw_range_ok(a, ff0, ff1);
+  if (!usable || W.size > kFwMaxSize) {  // (every lane takes this branch or none)
+    if (write) {
+      if (usable)
+        for (uint64_t t0 = ff0; t0 < ff1; t0 += 64)
+          wv.lanes([&](uint32_t lane) {
+            if (t0 + lane < ff1) a.frame_accept[t0 + lane] = 0;
+          });
+      wv.one([&]() { fw_bad(a, r, W, gfirst); });
+    }
+    return 0;
+  }
+  FwRun s = fw_run_begin(W);
+  const uint32_t size = W.size;
+  auto below = [](uint32_t lane) { return (1ull << lane) - 1; };
+  for (uint64_t t0 = ff0; t0 < ff1; t0 += 64) {
+    const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
+    wv.lanes([&](uint32_t lane) {
+      sh.fail[lane] = sh.stop[lane] = sh.bits[lane] = sh.par[lane] = 0;
+      if (lane == 0) {
+        sh.fail[64] = sh.stop[64] = sh.bits[64] = sh.par[64] = 0;
+        sh.data_mask = sh.cand_mask = sh.sync_mask = sh.psync_mask = 0;
+      }
+    });
+    wv.lanes([&](uint32_t lane) {
+      uint32_t target = 0, cls = 0;
+      if (lane < nv) cls = fw_classify(a.infos[t0 + lane], target);
+      sh.target[lane] = target;
+      sh.cls[lane] = (uint8_t)cls;
+      const unsigned long long bit = 1ull << lane;
+      if (cls & kFwData) Wv::or64(&sh.data_mask, bit);
+      if (cls & (kFwData | kFwFrameSync)) Wv::or64(&sh.cand_mask, bit);
+      if (cls & kFwSync) Wv::or64(&sh.sync_mask, bit);
+      if (cls & kFwPacketSync) Wv::or64(&sh.psync_mask, bit);
+    });
+    const unsigned long long cand = sh.cand_mask, data = sh.data_mask, syncs = sh.sync_mask, psyncs = sh.psync_mask;
+    // the window
+    unsigned long long failed = 0;
+    uint32_t from = 0;  // the lanes below are final
+    for (uint32_t k = 0;; k++) {
+      const unsigned long long live = cand & ~failed;
+      wv.lanes([&](uint32_t lane) {
+        if (lane < from || !((live >> lane) & 1u)) return;
+        const unsigned long long m = live & below(lane);
+        const uint32_t b = m ? sh.target[fw_high_bit(m)] : s.base;
+        if (!fw_passes(sh.cls[lane], sh.target[lane], b, size)) Wv::or64(&sh.fail[k], 1ull << lane);
+      });
+      const unsigned long long F = sh.fail[k];
+      if (!F) break;
+      const uint32_t f = fw_low_bit(F);
+      failed |= 1ull << f;
+      from = f + 1;
+    }
+    const unsigned long long passing = cand & ~failed, acc = data & passing;
+    if (passing) s.base = sh.target[fw_high_bit(passing)];
+    s.accepted += fw_popc(acc);
+    s.refused += fw_popc(data & ~acc);
+    s.syncs += fw_popc(syncs);
+    if (psyncs && !s.psyncs) s.first_psync = (uint32_t)(t0 + fw_low_bit(psyncs));
+    s.psyncs += fw_popc(psyncs);
+    if (syncs) s.reply = 1;
+    if (write)
+      wv.lanes([&](uint32_t lane) {
+        if (lane < nv) a.frame_accept[t0 + lane] = (uint8_t)((acc >> lane) & 1u);
+      });
+    // the groups
+    unsigned long long rem = acc;
+    for (uint32_t k = 0; rem; k++) {
+      if (!s.has) {  // the first lane left opens a group
+        const uint32_t o = fw_low_bit(rem);
+        s.ge = sh.target[o] - 1;
+        s.gb = 1;
+        s.gn = (sh.cls[o] & kFwNonce) ? 1u : 0u;
+        s.has = true;
+        rem &= rem - 1;
+        if (!rem) break;
+      }
+      wv.lanes([&](uint32_t lane) {
+        if (!((rem >> lane) & 1u)) return;
+        const uint32_t off = sh.target[lane] - 1 - s.ge;
+        const unsigned long long m = rem & below(lane);
+        if (off >= 32 || (m && sh.target[fw_high_bit(m)] - 1 - s.ge >= off)) Wv::or64(&sh.stop[k], 1ull << lane);
+      });
+      const unsigned long long S = sh.stop[k];
+      const unsigned long long fold = S ? rem & below(fw_low_bit(S)) : rem;
+      if (fold) {
+        wv.lanes([&](uint32_t lane) {
+          if (!((fold >> lane) & 1u)) return;
+          const uint32_t bit = 1u << (sh.target[lane] - 1 - s.ge);
+          Wv::or64(&sh.bits[k], bit);
+          if (!(s.gb & bit) && (sh.cls[lane] & kFwNonce)) Wv::or64(&sh.par[k], 1ull << lane);
+        });
+        s.gb |= (uint32_t)sh.bits[k];
+        s.gn ^= fw_popc(sh.par[k]) & 1u;
+        rem &= ~fold;
+      }
+      if (rem && sh.target[fw_low_bit(rem)] - 1 - s.ge >= 32) {  // the next lane closes the group
+        const uint64_t at = gfirst + s.groups;
+        if (write) wv.one([&]() { fw_put_group(a, at, s.ge, s.gb, s.gn); });
+        s.groups++;
+        s.has = false;
+      }
+    }
+  }
+  if (write) wv.one([&]() { fw_end(a, r, W, s, true, gfirst); });
+  return s.groups + (s.has ? 1u : 0u);
 }
 
 }  // namespace ufc_codec

@@ -20,6 +20,7 @@
 #include "frame_crc_kernels.hpp"
 #include "frame_pack.hpp"
 #include "frame_parse.hpp"
+#include "frame_window.hpp"
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
 #include "ufc_internal.hpp"
@@ -77,7 +78,8 @@ enum ScratchKind {
   kScratchBuild = 6,
   kScratchPack = 7,
   kScratchEmit = 8,
-  kScratchReceive = 9
+  kScratchReceive = 9,
+  kScratchWindow = 10
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -1030,6 +1032,30 @@ int ufc_receive_packets_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size
                             d_packet_first, d_packets_used, d_out_bytes, out_cap, d_out_used, d_item_status, d_results,
                             d_receivers_out};
   if ((e = ufc_dev::receive_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched frame window (frame_window.hip) ----
+int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const uint64_t* d_frame_first,
+                            const ufc_frame_window* d_windows, size_t n_windows, uint8_t* d_frame_accept,
+                            ufc_item* d_groups, size_t groups_cap, uint64_t* d_group_first, uint64_t* d_groups_used,
+                            ufc_frame_window_result* d_results, ufc_frame_window* d_windows_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n_windows == 0) return UFC_OK;
+  // (the n_windows + 1 group counts are scanned with a 32-bit count)
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!d_frame_first || !d_windows || !d_windows_out || !d_frame_accept || !d_group_first || !d_groups_used ||
+      !d_results || (!d_infos && n_frames) || (!d_groups && groups_cap) || n_frames >= lim || n_windows >= lim)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const size_t need = ufc_dev::window_scratch_bytes(n_windows);
+  void* scratch = nullptr;
+  if ((e = stream_scratch(ctx, kScratchWindow, (hipStream_t)stream, need, &scratch)) != hipSuccess)
+    return hip_fail(ctx, e);
+  const ufc_codec::FwArgs a{d_infos, n_frames, d_frame_first, d_windows, n_windows, d_frame_accept, d_groups,
+                            groups_cap, d_group_first, d_groups_used, d_results, d_windows_out};
+  if ((e = ufc_dev::window_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

@@ -15,6 +15,10 @@ and the batched receive-side parse that follows the batched CRC gate:
     receive_packets_host(infos, items, payload, frame_first, receivers, slots, slot_first, carry_in)
                                                <- PacketReceiver::handle_datagram / receive / resynchronize,
                                                   src/half_connection/packet_receiver/mod.rs:142-435
+    frame_window_host(infos, frame_first, windows)
+                                               <- FrameAckQueue::window_contains / mark_seen / resynchronize,
+                                                  src/half_connection/frame_ack_queue.rs, as handle_data_frame and
+                                                  handle_sync_frame call them (half_connection/mod.rs:132-152)
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -27,8 +31,9 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, Item, Packet, PacketResult, Receiver,
-                      ReceiverResult, RxPacket, RxSlot, Sender, SenderResult, check, lib, UFC_ERR_NOMEM)
+from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameWindow, FrameWindowResult, Item, Packet,
+                      PacketResult, Receiver, ReceiverResult, RxPacket, RxSlot, Sender, SenderResult, check, lib,
+                      UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -95,6 +100,26 @@ RX_PACKET_DUD = 1
 (RX_NOT_HANDLED, RX_STORED, RX_COMPLETED, RX_DUD, RX_DROPPED_INVALID, RX_DROPPED_WINDOW, RX_DROPPED_CHANNEL,
  RX_DROPPED_CLOSED, RX_DROPPED_MISMATCH, RX_DROPPED_DUPLICATE, RX_DROPPED_BAD_SRC) = range(11)
 RX_DONE, RX_BAD_STATE = 0, 1
+# ufc_frame_window / ufc_frame_window_result (batched frame windows)
+FRAME_WINDOW_DTYPE = np.dtype([("base_id", "<u4"), ("size", "<u4"), ("tail_base_id", "<u4"), ("tail_bitfield", "<u4"),
+                               ("tail_nonce", "u1"), ("has_tail", "u1"), ("sync_reply", "u1"), ("reserved", "u1"),
+                               ("reserved2", "<u4")])
+FRAME_WINDOW_RESULT_DTYPE = np.dtype([("group_first", "<u4"), ("group_count", "<u4"), ("accepted", "<u4"),
+                                      ("refused", "<u4"), ("syncs", "<u4"), ("packet_syncs", "<u4"),
+                                      ("first_packet_sync", "<u4"), ("advanced", "<u4"), ("stop", "<u4"),
+                                      ("reserved", "<u4")])
+assert FRAME_WINDOW_DTYPE.itemsize == ctypes.sizeof(FrameWindow) == 24
+assert FRAME_WINDOW_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameWindowResult) == 40
+FW_DONE, FW_BAD_STATE = 0, 1
+
+
+def new_frame_windows(n: int, size, base_id=0) -> np.ndarray:
+    """n ufc_frame_window records equal to FrameAckQueue::new(size, base_id) (frame_ack_queue.rs:39-44): no pending
+    ack group, no sync reply owed."""
+    w = np.zeros(n, dtype=FRAME_WINDOW_DTYPE)
+    w["base_id"] = base_id
+    w["size"] = size
+    return w
 
 
 def new_receivers(n: int, window_size, base_id=0, max_alloc=1 << 40) -> np.ndarray:
@@ -583,3 +608,50 @@ def receive_packets_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarr
             "out_bytes": out_bytes, "out_used": out_used.value, "carry_out": carry_out, "carry_first": carry_first,
             "carry_used": carry_used.value, "item_status": item_status, "results": results,
             "receivers_out": receivers_out}
+
+
+def frame_window_host(infos: np.ndarray, frame_first: np.ndarray, windows: np.ndarray, groups_cap: Optional[int] = None,
+                      nthreads: int = 1, frame_accept: Optional[np.ndarray] = None, groups: Optional[np.ndarray] = None,
+                      group_first: Optional[np.ndarray] = None, results: Optional[np.ndarray] = None,
+                      windows_out: Optional[np.ndarray] = None):
+    """One step of FrameAckQueue for many connections in host memory (ufc_frame_window_host): connection r
+    (FRAME_WINDOW_DTYPE: its ReceiveWindow, the last pending ack group and sync_reply) owns frames frame_first[r] :
+    frame_first[r + 1] of infos (FRAME_INFO_DTYPE, what the parse returns) in arrival order.  Returns a dict:
+    frame_accept (uint8 per frame: 1 for the data frames inside the window, what receive_packets_host takes as
+    its frame_accept), groups (ITEM_DTYPE ack groups, the carried tail first), group_first (uint64 CSR over them:
+    pack_host's flush_first), groups_used, results (FRAME_WINDOW_RESULT_DTYPE), windows_out.  groups_cap bounds
+    the groups written (default n_windows + n_frames, always enough); arrays given for frame_accept, groups,
+    group_first, results and windows_out (which may be `windows`) are written into."""
+    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
+    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
+    if windows.dtype != FRAME_WINDOW_DTYPE or not windows.flags.c_contiguous:
+        windows = np.ascontiguousarray(windows, dtype=FRAME_WINDOW_DTYPE)
+    n = windows.size
+    if frame_first.size < n + 1:
+        raise ValueError("frame_first must hold one more entry than there are windows")
+    if groups_cap is None:
+        groups_cap = groups.size if groups is not None else n + infos.size
+    groups_cap = int(groups_cap)
+
+    def out(name, arr, size, dt):
+        if arr is None:
+            return np.zeros(size, dtype=dt)
+        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
+            raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
+        return arr
+
+    frame_accept = out("frame_accept", frame_accept, infos.size, np.dtype(np.uint8))
+    groups = out("groups", groups, groups_cap, ITEM_DTYPE)
+    group_first = out("group_first", group_first, n + 1, np.dtype(np.uint64))
+    results = out("results", results, n, FRAME_WINDOW_RESULT_DTYPE)
+    windows_out = out("windows_out", windows_out, n, FRAME_WINDOW_DTYPE)
+    used = ctypes.c_uint64(0)
+    one = np.zeros(1, dtype=np.uint8)  # (frame_accept is required even when there are no frames)
+    check(lib().ufc_frame_window_host(infos.ctypes.data if infos.size else None, infos.size, frame_first.ctypes.data,
+                                      windows.ctypes.data if n else None, n,
+                                      frame_accept.ctypes.data if frame_accept.size else one.ctypes.data,
+                                      groups.ctypes.data if groups_cap else None, groups_cap, group_first.ctypes.data,
+                                      ctypes.addressof(used), results.ctypes.data if n else None,
+                                      windows_out.ctypes.data if n else None, nthreads), "ufc_frame_window_host")
+    return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used.value,
+            "results": results, "windows_out": windows_out}
