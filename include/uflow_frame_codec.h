@@ -668,6 +668,153 @@ int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
                             ufc_item* d_groups, size_t groups_cap, uint64_t* d_group_first, uint64_t* d_groups_used,
                             ufc_frame_window_result* d_results, ufc_frame_window* d_windows_out, void* stream);
 
+/* ---- batched sender frame queue: received acks into acked fragments, the transfer window and feedback ----
+ * The step behind the parse on the sender's side: FrameQueue (src/half_connection/frame_queue.rs:209-388) with its
+ * FrameLog (:24-84) and FeedbackGen (:96-195), ReorderBuffer (reorder_buffer.rs:2-179, whole file) and
+ * LossIntervalQueue (loss_rate.rs:19-110, whole file), as HalfConnection::handle_ack_frame, step and the emitters
+ * drive it.  The release build is the specification, wrapping u32 and u64 arithmetic included (send_time_ms +
+ * rtt_ms, now_ms - last_send_time_ms and total_ack_size all wrap).  SendRateComp (send_rate.rs, recv_rate_set.rs),
+ * PacketSender::acknowledge (it needs the per-packet window table that ufc_sender does not hold) and the resend
+ * and pending queues stay with the caller.
+ *
+ * A log slot is one frame_queue::Entry (:14-21).  fragment_refs is the range [ref_first, ref_first + ref_count) of a
+ * fragment table the caller owns: in the device pipeline the frame's item_first / item_count from the pack. */
+#define UFC_SENT_NONCE 1         /* Entry.nonce */
+#define UFC_SENT_RATE_LIMITED 2  /* Entry.rate_limited; ignored on input to a push */
+#define UFC_SENT_ACKED 4         /* Entry.acked; ignored on input to a push */
+#define UFC_SENT_MARK 8          /* input to a push only: mark_rate_limited() (:240) was called since the push before */
+typedef struct ufc_sent_frame {        /* 24 bytes */
+  uint64_t send_time_ms;
+  uint32_t size;
+  uint32_t ref_first, ref_count;
+  uint8_t flags;                       /* UFC_SENT_* */
+  uint8_t reserved[3];                 /* stored as 0 */
+} ufc_sent_frame;
+
+/* One connection's FrameQueue, in and out.  Frame `id` of the log lives at log[log_first + (id & (log_cap - 1))],
+ * a ring in the caller's log arena; the rings of different connections must not overlap. */
+typedef struct ufc_frame_queue {       /* 192 bytes */
+  uint32_t log_base_id, log_next_id;   /* FrameLog (:24-28); its length is log_next_id - log_base_id */
+  uint32_t window_base_id, window_size, tail_size;  /* TransferWindow (:197-201) */
+  uint32_t rb_base_id, rb_max_span, rb_frames[2], rb_count;  /* ReorderBuffer (reorder_buffer.rs:2-7) */
+  uint8_t rate_limited;                /* FrameQueue.rate_limited (:214): the pending mark */
+  uint8_t has_ack_data;                /* FeedbackGen.ack_data is Some (:101) */
+  uint8_t ack_rate_limited;            /* AckData.rate_limited */
+  uint8_t has_last_feedback;           /* FeedbackGen.last_feedback_ms is Some (:98) */
+  uint32_t li_count;                   /* LossIntervalQueue.entries.len(), 0..9 */
+  uint64_t ack_last_send_time_ms, ack_total_size;  /* AckData (:90-94); 0 when has_ack_data is 0 on output */
+  uint64_t last_feedback_ms;
+  uint64_t li_end_time_ms[9];          /* front (the latest interval) first; entries at li_count and beyond are
+                                          ignored on input and written 0 */
+  uint32_t li_length[9];
+  uint32_t log_cap;                    /* a power of two, >= window_size + tail_size */
+  uint64_t log_first;
+} ufc_frame_queue;
+
+#define UFC_FQ_HAS_RTT 1            /* rtt_ms is Some; otherwise FeedbackGen::INITIAL_RTT_MS = 100 is used (:111, :170) */
+#define UFC_FQ_RESET_LOSS 2         /* reset_loss_rate(reset_loss_rate) first */
+#define UFC_FQ_MARK_RATE_LIMITED 4  /* mark_rate_limited() behind the pushes */
+#define UFC_FQ_FORGET 8             /* forget_frames(thresh_ms, rtt) behind the ack frames */
+#define UFC_FQ_FEEDBACK 16          /* get_feedback(now_ms) last */
+typedef struct ufc_frame_queue_step {  /* 40 bytes: what to do for one connection in this call */
+  uint32_t flags, reserved;
+  uint64_t rtt_ms;                     /* the Option<u64> handle_ack_frame and forget_frames pass, constant through the
+                                          call as it is between two step()s of the reference */
+  uint64_t thresh_ms, now_ms;
+  double reset_loss_rate;
+} ufc_frame_queue_step;
+
+#define UFC_FQ_DONE 0
+#define UFC_FQ_BAD_STATE 1
+typedef struct ufc_frame_queue_result { /* 80 bytes */
+  uint32_t stop;
+  uint32_t pushes_taken, pushes_refused;
+  uint32_t ack_frames, groups;         /* ok ack frames; their groups */
+  uint32_t groups_dud, groups_unknown, groups_bad_nonce;  /* acknowledge_group's three silent returns */
+  uint32_t frames_acked;               /* log entries newly acked */
+  uint32_t li_acks, li_nacks;          /* push_ack / push_nack calls */
+  uint32_t window_advanced, log_culled;/* ids the transfer window's and the log's base moved (wrapping sums) */
+  uint32_t window_room;                /* window_size - (log_next_id - window_base_id) if positive, else 0: the pack's
+                                          ufc_flush.window_room, with id0 = log_next_id */
+  uint8_t has_feedback, rate_limited;  /* get_feedback returned Some; FeedbackData.rate_limited */
+  uint16_t reserved;
+  uint32_t receive_rate;
+  uint64_t rtt_ms;
+  double loss_rate;
+} ufc_frame_queue_result;
+
+/* One call runs one step for every connection c, in this order:
+ *   1. UFC_FQ_RESET_LOSS: LossIntervalQueue::reset (loss_rate.rs:33-54): the queue is truncated to its front entry,
+ *      whose length becomes (1.0 / p).clamp(0, u32::MAX).round() as u32 (half away from zero, NaN gives 0).
+ *   2. FrameQueue::push (:244-259) for sent[sent_first[c] .. sent_first[c + 1]) in order: while (log_next_id -
+ *      window_base_id) < window_size (can_push, :228) the record is stored with ACKED clear, NONCE as given,
+ *      RATE_LIMITED = the pending mark OR the record's MARK, reserved 0; the pending mark is cleared and log_next_id
+ *      += 1.  The window does not move during pushes, so the refused records are a suffix; they are only counted.
+ *      Then UFC_FQ_MARK_RATE_LIMITED sets the pending mark.
+ *   3. The frames infos[frame_first[c] .. frame_first[c + 1]) in arrival order (the CSR the frame window and the
+ *      receive take).  A frame with ok and kind == UFC_FRAME_ACK: each of its groups items[item_first ..+ item_count)
+ *      goes through acknowledge_group (:279-355) with base_id = id, bitfield = data_offset, nonce = channel_id & 1;
+ *      then advance_transfer_window(f[0], rtt) (:357-380, cull_log_entries :382-387, notify_advancement :179-194).
+ *      Every other frame has no effect.  acknowledge_group is literal: a bitfield of 0 is a dud (:294); a group
+ *      with an id outside the log returns (:307); a nonce that is not the XOR of the claimed frames' returns (:313);
+ *      rate_limited is OR-ed over every frame of the span, acked or not (:323); a frame newly acked gets ACKED, its
+ *      size and send time enter the AckData, notify_ack (:159-177) runs, and ref_acked[ref_first ..+ ref_count) is
+ *      set to 1 where the index is below refs_cap (the batched acknowledge_fragment; ref_acked is nullable and is
+ *      never written 0); put_ack_data (:149-157) runs even when no frame was newly acked.  notify_ack's old-frame
+ *      branch does nothing (:173-176).
+ *   4. UFC_FQ_FORGET: forget_frames(thresh_ms, rtt) (:261-269, find_expiration_cutoff :67-77).
+ *   5. UFC_FQ_FEEDBACK: get_feedback(now_ms) (:126-147).  receive_rate = (total_ack_size as f64 / ((now_ms -
+ *      last_feedback_ms) as f64 / 1000.0)).clamp(0, u32::MAX) as u32 with Rust's casts: a difference of 0 gives
+ *      u32::MAX, 0 / 0 gives NaN and so 0, and 0 without an earlier feedback.  loss_rate = compute_loss_rate
+ *      (loss_rate.rs:86-109), the sums in the reference's order and never fused, so host and device agree in
+ *      every bit.
+ * queues_out[c] (required, may be `queues` itself) gets the new state; the log rings are updated in place.
+ *
+ * The reference unwrap()s and indexes without checks, so a state is checked first.  A connection stops
+ * UFC_FQ_BAD_STATE, its state copied through, its result zero but for `stop`, its ring and ref_acked untouched, when:
+ *   - log_cap is not a power of two, log_cap < window_size + tail_size, or the ring [log_first, log_first + log_cap)
+ *     leaves [0, n_log);
+ *   - log_next_id - log_base_id > log_cap;
+ *   - log_next_id - window_base_id > window_size, or log_next_id - log_base_id > (log_next_id - window_base_id) +
+ *     tail_size (all wrapping): the log then starts more than tail_size behind the window.  push and
+ *     advance_transfer_window keep both true from FrameQueue::new on; without them a push would outgrow the ring;
+ *   - rb_max_span < window_size + tail_size or rb_max_span > 2^31 (FrameQueue::new sets it to the sum, :221);
+ *   - rb_base_id - log_base_id > log_next_id - log_base_id;
+ *   - rb_count > 2; a reorder-buffer frame not strictly after rb_base_id, or not inside the log: with d = frame -
+ *     rb_base_id, d == 0 or (rb_base_id - log_base_id) + d >= the log's length; two frames out of order (d0 >= d1);
+ *   - li_count > 9; UFC_FQ_RESET_LOSS with li_count == 0 (the reference indexes entries[0], loss_rate.rs:53);
+ *   - the frame or the sent range reversed or outside its array; an ok ack frame's item range outside [0, n_items).
+ * A state that passes never reaches a failing unwrap or index of the reference, and the state that comes out
+ * passes again unless a reorder-buffer frame was acked a second time.  The reasoning: with L = the log's length,
+ * the rules give L <= window_size + tail_size <= rb_max_span <= 2^31 and keep it so (a push needs log_next_id -
+ * window_base_id < window_size; an advance culls to window_base_id - tail_size whenever that lies ahead).
+ * acknowledge_group unwraps only ids its first loop found (:302, :321).  notify_ack puts only ids inside the log:
+ * one at or ahead of rb_base_id passes can_put since its distance is below L, one behind it is at a wrapped
+ * distance of at least 2^32 - 2^31 and does not.  put and advance call back for rb_base_id up to the nearest of
+ * the new id and the held frames, or up to the new log base, and then for held frames: all at or ahead of
+ * rb_base_id and inside the log (:165, :185).  A cull's new base lies within L of log_base_id, so it is either at or
+ * behind rb_base_id (can_advance fails at distance 0 or >= 2^31 + 1, and rb_base_id stays inside the log) or ahead of
+ * it by at most L <= rb_max_span (can_advance holds, and rb_base_id ends at or ahead of it); drain (:79-83) gets
+ * at most L.  A frame held twice (acked again from a state that held it unacked) stays behind as a stale entry at
+ * a wrapped distance no put or advance ever selects.
+ * Counts: n_frames, n_items, n_sent, n_queues < 2^31 - 1; n_queues == 0 returns UFC_OK whatever the pointers; a NULL
+ * infos with n_frames != 0, items with n_items != 0, sent with n_sent != 0, log with n_log != 0, or a NULL
+ * frame_first, sent_first, queues, steps, results or queues_out is UFC_ERR_INVALID_ARG.  ref_acked is nullable. */
+int ufc_frame_queue_host(const ufc_frame_info* infos, size_t n_frames, const ufc_item* items, size_t n_items,
+                         const uint64_t* frame_first, const ufc_sent_frame* sent, size_t n_sent,
+                         const uint64_t* sent_first, const ufc_frame_queue* queues, const ufc_frame_queue_step* steps,
+                         size_t n_queues, ufc_sent_frame* log, size_t n_log, uint8_t* ref_acked, size_t refs_cap,
+                         ufc_frame_queue_result* results, ufc_frame_queue* queues_out, int nthreads);
+/* The same on the GPU (gfx950 kernel, frame_queue.hip): every pointer device memory, asynchronous on `stream`,
+ * nothing allocated per call.  One wave per connection and one launch: no output needs a scan.  Per-stream
+ * scratch: none (0 bytes); the wave's working set is about 2 KiB of LDS. */
+int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const ufc_item* d_items,
+                           size_t n_items, const uint64_t* d_frame_first, const ufc_sent_frame* d_sent, size_t n_sent,
+                           const uint64_t* d_sent_first, const ufc_frame_queue* d_queues,
+                           const ufc_frame_queue_step* d_steps, size_t n_queues, ufc_sent_frame* d_log, size_t n_log,
+                           uint8_t* d_ref_acked, size_t refs_cap, ufc_frame_queue_result* d_results,
+                           ufc_frame_queue* d_queues_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

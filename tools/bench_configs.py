@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,queue,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -31,6 +31,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            batch's frames as 250,000 connections and as 2,048; the call, ufc_frame_window_host with 1 and 16
            threads on the same records and a plain device read of the records as the floor, one line per
            grouping, also written to profiles/window_configs.jsonl.  Run with --only window.
+  queue    parsed ack frames into acked fragments, the transfer window and feedback on the device
+           (ufc_frame_queue_varlen): 1M synthesized ack frames over filled logs, as 250,000 connections and as 2,048;
+           the call and ufc_frame_queue_host with 1 and 16 threads; one line per grouping, also written to
+           profiles/queue_configs.jsonl.  Run with --only queue.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -784,6 +788,129 @@ def window(eng, dev, reps, n=1_000_000):
     return out
 
 
+QUEUE_OUT = os.path.join(REPO, "profiles", "queue_configs.jsonl")
+
+
+def queue(eng, dev, reps, n=1_000_000):
+    """The sender's step behind the parse: 1M synthesized ack frames over filled logs, run through
+    ufc_frame_queue_varlen.  Two groupings: 250,000 connections of 4 frames (window 64, tail 64: each frame
+    acknowledges 16 of the 64 logged frames) and 2,048 connections of about 488 (window 4096, tail 4096: each frame
+    acknowledges 8 of the 4096).  Every frame carries one group; 2 % of its bits are clear (frames lost, nacked once
+    three later ones are acked), its frame window base is the id behind its group, and every step asks for
+    feedback.  The call marks the log in place, so the log and ref_acked are restored from a pristine copy before
+    every call, outside the timed span: an event pair around each call on the device, wall clock around each call on
+    the host (1 and 16 threads, median of 3).  Per grouping one JSON line, also written to
+    profiles/queue_configs.jsonl, with every output of the GPU call against the host's.  Run with --only queue."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import (FRAME_INFO_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_RESULT_DTYPE, FRAME_QUEUE_STEP_DTYPE,
+                                 ITEM_DTYPE, SENT_FRAME_DTYPE, new_frame_queues)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    c = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    out = []
+    for name, nq, W, S in (("250,000", 250_000, 64, 16), ("2,048", 2048, 4096, 8)):
+        rng = np.random.default_rng(12)
+        ff = (np.arange(nq + 1, dtype=np.uint64) * n) // nq
+        base = rng.integers(0, 1 << 32, nq, dtype=np.uint64).astype(np.uint32)
+        queues, log = new_frame_queues(nq, W, W, base)
+        cap = int(queues["log_cap"][0])
+        queues["log_next_id"] = base + np.uint32(W)                      # the window is full: W frames logged
+        nonce = rng.integers(0, 2, (nq, W), dtype=np.uint8)
+        rel = np.arange(W, dtype=np.int64)
+        slot = (queues["log_first"].astype(np.int64)[:, None] + ((base.astype(np.int64)[:, None] + rel) & (cap - 1))).reshape(-1)
+        log["send_time_ms"][slot] = np.tile(10 * rel, nq)
+        log["size"][slot] = 1000
+        log["ref_first"][slot] = np.arange(nq * W)
+        log["ref_count"][slot] = 1
+        log["flags"][slot] = nonce.reshape(-1)
+        own = (np.searchsorted(ff, np.arange(n), side="right") - 1).astype(np.int64)
+        j = np.arange(n, dtype=np.int64) - ff[own].astype(np.int64)       # the frame's index in its connection
+        bits = (rng.random((n, S)) >= 0.02)
+        bits[:, 0] = True
+        claimed = nonce[own[:, None], j[:, None] * S + np.arange(S)] & bits
+        items = np.zeros(n, dtype=ITEM_DTYPE)
+        items["form"] = 3
+        items["id"] = (base[own].astype(np.int64) + j * S) & 0xFFFFFFFF
+        items["data_offset"] = (bits * (1 << np.arange(S))).sum(axis=1)
+        items["channel_id"] = claimed.sum(axis=1) & 1
+        infos = np.zeros(n, dtype=FRAME_INFO_DTYPE)
+        infos["kind"], infos["ok"], infos["crc_ok"], infos["item_count"], infos["item_first"] = 12, 1, 1, 1, np.arange(n)
+        infos["f"][:, 0] = (base[own].astype(np.int64) + j * S + S) & 0xFFFFFFFF
+        steps = np.zeros(nq, dtype=FRAME_QUEUE_STEP_DTYPE)
+        steps["flags"], steps["rtt_ms"], steps["now_ms"] = N.UFC_FQ_HAS_RTT | N.UFC_FQ_FEEDBACK, 50, 10 * W + 100
+        none = np.zeros(nq + 1, dtype=np.uint64)
+        sent = np.zeros(0, dtype=SENT_FRAME_DTYPE)
+        refs0 = np.zeros(nq * W, dtype=np.uint8)
+        h = {"log": log.copy(), "refs": refs0.copy(), "res": np.zeros(nq, dtype=FRAME_QUEUE_RESULT_DTYPE),
+             "qout": np.zeros(nq, dtype=FRAME_QUEUE_DTYPE)}
+        h_call = lambda T: lib.ufc_frame_queue_host(  # noqa: E731
+            c(infos), n, c(items), n, c(ff), c(sent), 0, c(none), c(queues), c(steps), nq, c(h["log"]), h["log"].size,
+            c(h["refs"]), h["refs"].size, c(h["res"]), c(h["qout"]), T)
+        host_ms = {}
+        for T in (1, 16):
+            ts = []
+            for _ in range(3):
+                np.copyto(h["log"], log)
+                h["refs"][:] = 0
+                t0 = time.perf_counter()
+                assert h_call(T) == 0
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
+        g = {"infos": t(infos, 32), "items": t(items, 24), "ff": t(ff.astype(np.int64)), "none": t(none.astype(np.int64)),
+             "queues": t(queues, 192), "steps": t(steps, 40), "log0": t(log, 24), "log": t(log, 24),
+             "refs": torch.zeros(nq * W, dtype=torch.uint8, device=dev),
+             "res": torch.zeros((nq, 80), dtype=torch.uint8, device=dev), "qout": torch.zeros((nq, 192), dtype=torch.uint8, device=dev)}
+
+        def restore():
+            g["log"].copy_(g["log0"])
+            g["refs"].zero_()
+
+        f_fq = lambda: lib.ufc_frame_queue_varlen(  # noqa: E731
+            ctx, p(g["infos"]), n, p(g["items"]), n, p(g["ff"]), None, 0, p(g["none"]), p(g["queues"]), p(g["steps"]), nq,
+            p(g["log"]), g["log"].shape[0], p(g["refs"]), g["refs"].numel(), p(g["res"]), p(g["qout"]), st)
+        restore()
+        assert f_fq() == 0
+        torch.cuda.synchronize()
+        extra = {}
+        if CHECK:
+            same = lambda a, b: bool(np.array_equal(a.cpu().numpy().reshape(-1), b.view(np.uint8).reshape(-1)))  # noqa: E731
+            extra["equals_host"] = (same(g["res"], h["res"]) and same(g["qout"], h["qout"]) and same(g["log"], h["log"]) and
+                                    same(g["refs"], h["refs"]))
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.5:                             # (out of idle clocks)
+            restore()
+            f_fq()
+            torch.cuda.synchronize()
+        s = torch.cuda.current_stream()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        for e0, e1 in evs:
+            restore()
+            e0.record(s)
+            f_fq()
+            e1.record(s)
+        torch.cuda.synchronize()
+        ms = [a.elapsed_time(b) for a, b in evs]
+        med, mean = float(np.median(ms)), float(np.mean(ms))
+        res = h["res"]
+        out.append({"config": f"f9: device frame queue of 1M synthesized ack frames, {name} connections (window {W}, tail {W})",
+                    "frames": n, "connections": nq, "groups": int(res["groups"].sum()), "frames_acked": int(res["frames_acked"].sum()),
+                    "li_acks": int(res["li_acks"].sum()), "li_nacks": int(res["li_nacks"].sum()),
+                    "feedbacks": int(res["has_feedback"].sum()), "bad_state": int((res["stop"] != 0).sum()),
+                    "queue_ms": round(med, 4), "queue_mean_ms": round(mean, 4), "ns_per_frame": round(med * 1e6 / n, 4),
+                    "host_1t_ms": round(host_ms[1], 2), "host_16t_ms": round(host_ms[16], 2),
+                    "host_1t_over_gpu": round(host_ms[1] / med, 1), "host_16t_over_gpu": round(host_ms[16] / med, 1),
+                    "timing": "an event pair around each call, the log restored in front of it", **extra})
+        del g
+        torch.cuda.empty_cache()
+    with open(QUEUE_OUT, "w") as f:
+        for r in out:
+            f.write(json.dumps(r) + "\n")
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -833,7 +960,7 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what in ("pack", "emit", "receive", "window"):
+        elif what in ("pack", "emit", "receive", "window", "queue"):
             for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:

@@ -53,6 +53,10 @@ UFC_RX_STATUS_COUNT = 11
 UFC_RX_DONE, UFC_RX_BAD_STATE = 0, 1
 # the batched frame windows (include/uflow_frame_codec.h): why a connection stopped
 UFC_FW_DONE, UFC_FW_BAD_STATE = 0, 1
+# the batched frame queues (include/uflow_frame_codec.h): a log slot's flags, a step's flags, why a connection stopped
+UFC_SENT_NONCE, UFC_SENT_RATE_LIMITED, UFC_SENT_ACKED, UFC_SENT_MARK = 1, 2, 4, 8
+UFC_FQ_HAS_RTT, UFC_FQ_RESET_LOSS, UFC_FQ_MARK_RATE_LIMITED, UFC_FQ_FORGET, UFC_FQ_FEEDBACK = 1, 2, 4, 8, 16
+UFC_FQ_DONE, UFC_FQ_BAD_STATE = 0, 1
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -60,6 +64,7 @@ _V, _Z = ctypes.c_void_p, ctypes.c_size_t
 _RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, _Z, _V, _V, _V, _Z, _V,
             _V, _V, _V]
 _FW_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V]
+_FQ_ARGS = [_V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -175,6 +180,10 @@ _SIGNATURES = {
     # results, windows_out, then nthreads (host) / ctx first and stream last (device)
     "ufc_frame_window_host": (ctypes.c_int, _FW_ARGS + [ctypes.c_int]),
     "ufc_frame_window_varlen": (ctypes.c_int, [ctypes.c_void_p] + _FW_ARGS + [ctypes.c_void_p]),
+    # infos, n_frames, items, n_items, frame_first, sent, n_sent, sent_first, queues, steps, n_queues, log, n_log,
+    # ref_acked, refs_cap, results, queues_out, then nthreads (host) / ctx first and stream last (device)
+    "ufc_frame_queue_host": (ctypes.c_int, _FQ_ARGS + [ctypes.c_int]),
+    "ufc_frame_queue_varlen": (ctypes.c_int, [ctypes.c_void_p] + _FQ_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -266,6 +275,37 @@ class FrameWindowResult(ctypes.Structure):
                 ("refused", ctypes.c_uint32), ("syncs", ctypes.c_uint32), ("packet_syncs", ctypes.c_uint32),
                 ("first_packet_sync", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class SentFrame(ctypes.Structure):
+    _fields_ = [("send_time_ms", ctypes.c_uint64), ("size", ctypes.c_uint32), ("ref_first", ctypes.c_uint32),
+                ("ref_count", ctypes.c_uint32), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+class FrameQueue(ctypes.Structure):
+    _fields_ = [("log_base_id", ctypes.c_uint32), ("log_next_id", ctypes.c_uint32), ("window_base_id", ctypes.c_uint32),
+                ("window_size", ctypes.c_uint32), ("tail_size", ctypes.c_uint32), ("rb_base_id", ctypes.c_uint32),
+                ("rb_max_span", ctypes.c_uint32), ("rb_frames", ctypes.c_uint32 * 2), ("rb_count", ctypes.c_uint32),
+                ("rate_limited", ctypes.c_uint8), ("has_ack_data", ctypes.c_uint8), ("ack_rate_limited", ctypes.c_uint8),
+                ("has_last_feedback", ctypes.c_uint8), ("li_count", ctypes.c_uint32),
+                ("ack_last_send_time_ms", ctypes.c_uint64), ("ack_total_size", ctypes.c_uint64),
+                ("last_feedback_ms", ctypes.c_uint64), ("li_end_time_ms", ctypes.c_uint64 * 9),
+                ("li_length", ctypes.c_uint32 * 9), ("log_cap", ctypes.c_uint32), ("log_first", ctypes.c_uint64)]
+
+
+class FrameQueueStep(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("rtt_ms", ctypes.c_uint64),
+                ("thresh_ms", ctypes.c_uint64), ("now_ms", ctypes.c_uint64), ("reset_loss_rate", ctypes.c_double)]
+
+
+class FrameQueueResult(ctypes.Structure):
+    _fields_ = [("stop", ctypes.c_uint32), ("pushes_taken", ctypes.c_uint32), ("pushes_refused", ctypes.c_uint32),
+                ("ack_frames", ctypes.c_uint32), ("groups", ctypes.c_uint32), ("groups_dud", ctypes.c_uint32),
+                ("groups_unknown", ctypes.c_uint32), ("groups_bad_nonce", ctypes.c_uint32),
+                ("frames_acked", ctypes.c_uint32), ("li_acks", ctypes.c_uint32), ("li_nacks", ctypes.c_uint32),
+                ("window_advanced", ctypes.c_uint32), ("log_culled", ctypes.c_uint32), ("window_room", ctypes.c_uint32),
+                ("has_feedback", ctypes.c_uint8), ("rate_limited", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+                ("receive_rate", ctypes.c_uint32), ("rtt_ms", ctypes.c_uint64), ("loss_rate", ctypes.c_double)]
 
 
 class Builder(ctypes.Structure):

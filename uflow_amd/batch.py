@@ -437,6 +437,45 @@ class FrameCrcEngine:
         return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used,
                 "results": results, "windows_out": windows_out}
 
+    # ---- the sender's FrameQueue step for many connections, on the device (uflow_frame_codec.h) ----
+    def frame_queue(self, infos, items, frame_first, sent, sent_first, queues, steps, log, ref_acked=None,
+                    queues_out=None, stream=None):
+        """ufc_frame_queue_varlen: one step of the sender's FrameQueue (push, acknowledge_group,
+        advance_transfer_window, forget_frames, get_feedback; src/half_connection/frame_queue.rs with
+        reorder_buffer.rs and loss_rate.rs) for every connection.  infos uint8[n_frames, 32] and items uint8[n_items,
+        24] (what parse_varlen returns), frame_first int64[n + 1] (CSR over the frames), sent uint8[n_sent, 24]
+        (ufc_sent_frame records to push) with sent_first int64[n + 1], queues uint8[n, 192], steps uint8[n, 40], log
+        uint8[n_log, 24] (the log arena, updated in place), ref_acked uint8[refs_cap] or None (set to 1 for the
+        fragments of newly acked frames, in place).  Returns a dict of device tensors: results uint8[n, 80],
+        queues_out uint8[n, 192] (may be given as `queues`), log, ref_acked.  The record layouts are
+        uflow_amd.frame's FRAME_QUEUE_DTYPE, FRAME_QUEUE_STEP_DTYPE, SENT_FRAME_DTYPE and FRAME_QUEUE_RESULT_DTYPE."""
+        n_frames, n_items, n_sent, n, n_log = infos.shape[0], items.shape[0], sent.shape[0], queues.shape[0], log.shape[0]
+        refs_cap = ref_acked.shape[0] if ref_acked is not None else 0
+        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._check("frame_first", frame_first, (torch.int64,), n + 1)
+        self._check("sent", sent, (torch.uint8,), 24 * n_sent)
+        self._check("sent_first", sent_first, (torch.int64,), n + 1)
+        self._check("queues", queues, (torch.uint8,), 192 * n)
+        self._check("steps", steps, (torch.uint8,), 40 * n)
+        self._check("log", log, (torch.uint8,), 24 * n_log)
+        self._check("ref_acked", ref_acked, (torch.uint8,), refs_cap)
+        self._check("queues_out", queues_out, (torch.uint8,), 192 * n)
+        # (the outputs are zeroed on the stream the call is queued on)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if queues_out is None:
+                queues_out = torch.zeros((n, 192), dtype=torch.uint8, device=self.device)
+            results = torch.zeros((n, 80), dtype=torch.uint8, device=self.device)
+        check(lib().ufc_frame_queue_varlen(self._ctx, _ptr(infos) if n_frames else None, n_frames,
+                                           _ptr(items) if n_items else None, n_items, _ptr(frame_first),
+                                           _ptr(sent) if n_sent else None, n_sent, _ptr(sent_first),
+                                           _ptr(queues) if n else None, _ptr(steps) if n else None, n,
+                                           _ptr(log) if n_log else None, n_log,
+                                           _ptr(ref_acked) if refs_cap else None, refs_cap,
+                                           _ptr(results) if n else None, _ptr(queues_out) if n else None,
+                                           self._stream(stream)), "ufc_frame_queue_varlen")
+        return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

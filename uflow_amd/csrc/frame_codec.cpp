@@ -692,4 +692,27 @@ int ufc_frame_window_host(const ufc_frame_info* infos, size_t n_frames, const ui
   return UFC_OK;
 }
 
+// ---- batched host frame queue ----
+int ufc_frame_queue_host(const ufc_frame_info* infos, size_t n_frames, const ufc_item* items, size_t n_items,
+                         const uint64_t* frame_first, const ufc_sent_frame* sent, size_t n_sent,
+                         const uint64_t* sent_first, const ufc_frame_queue* queues, const ufc_frame_queue_step* steps,
+                         size_t n_queues, ufc_sent_frame* log, size_t n_log, uint8_t* ref_acked, size_t refs_cap,
+                         ufc_frame_queue_result* results, ufc_frame_queue* queues_out, int nthreads) {
+  if (n_queues == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!frame_first || !sent_first || !queues || !steps || !results || !queues_out || (!infos && n_frames) ||
+      (!items && n_items) || (!sent && n_sent) || (!log && n_log) || n_frames >= lim || n_items >= lim ||
+      n_sent >= lim || n_queues >= lim)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::FqArgs a{infos, n_frames, items, n_items, frame_first, sent, n_sent, sent_first, queues, steps,
+                            n_queues, log, n_log, ref_acked, refs_cap, results, queues_out};
+  // The step the device runs, the lanes of a phase one after the other; a connection touches its own ring, its
+  // own records and (with ranges that do not overlap) its own fragment marks, so the connections run in parallel.
+  for_receivers(n_queues, nthreads, [&](size_t lo, size_t hi) {
+    ufc_codec::FqWaveShared sh;
+    for (size_t c = lo; c < hi; c++) ufc_codec::fq_step(ufc_codec::FqHostWave{}, sh, a, c);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

@@ -2,8 +2,8 @@
 // once for the host codec (frame_codec.cpp) and the GPU batch parse (frame_parse.hip); further down the
 // encode for the batched builds (frame_build.hip), the emitters' arithmetic for the batched packs
 // (frame_pack.hip), the packet sender's for the batched packet emits (packet_emit.hip), the packet receiver's
-// step for the batched packet receives (packet_receive.hip) and the frame window's for the batched frame windows
-// (frame_window.hip).
+// step for the batched packet receives (packet_receive.hip), the frame window's for the batched frame windows
+// (frame_window.hip) and the sender's frame queue's for the batched frame queues (frame_queue.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -1635,5 +1635,547 @@ inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh
   if (write) wv.one([&]() { fw_end(a, r, W, s, true, gfirst); });
   return s.groups + (s.has ? 1u : 0u);
 }
+
+// ---- the sender's frame queue: FrameQueue as handle_ack_frame, step and the emitters drive it ----
+// Restates src/half_connection/frame_queue.rs (FrameLog :24-84, FeedbackGen :96-195, FrameQueue :209-388),
+// reorder_buffer.rs:2-179 and loss_rate.rs:19-110 for the batched frame queues (frame_queue.hip,
+// ufc_frame_queue_host; the rules are in include/uflow_frame_codec.h).  Written once, against the wave policy of
+// fw_walk_tiles with one addition:
+//   Wv::ballot(f)  the 64-bit mask of the lanes for which f(lane) is true; what f wrote to `sh` is visible to all
+//                  after (the device's wave ballot; a loop on the host)
+// One wave runs a connection's step.  What is written outside a phase is the same for every lane: the running
+// state FqRun (the log's and the window's ids, the reorder buffer, the pending AckData, the front interval's end
+// time and the interval count).  The loss intervals themselves live in `sh` and are touched by Wv::one alone (lane 0
+// on the device, in its program order).  Everything that touches a run of log entries takes a lane per entry:
+//   group span     the <= 32 entries of a group: outside-the-log test, nonce parity, rate_limited OR and the newly
+//                  acked lanes are ballots; ACKED and ref_acked are stored by the entries' lanes; the send times
+//                  and sizes of the newly acked go through `sh` into the serial put()s;
+//   nack runs      put's and advance's `while base_id != ...` loops, in tiles of 64 ids.  A ballot finds the first
+//                  entry at or after the front interval's end; the lanes in front of it add to the front's length
+//                  in one step, that entry opens the next interval, and the lanes behind it vote again against the
+//                  new end.  That is push_nack entry by entry for any log, monotone or not; a monotone log with a
+//                  positive rtt opens few intervals, so a tile takes one or two votes;
+//   expiry cutoff  a ballot per tile of 64 entries for the first one at or after the threshold;
+//   pushes         a copy of 64 records per phase;
+//   frames         a ballot per tile of 64 frames finds the ok ack frames; only they are visited.
+struct FqArgs {
+  const ufc_frame_info* infos;
+  uint64_t n_frames;
+  const ufc_item* items;
+  uint64_t n_items;
+  const uint64_t* frame_first;
+  const ufc_sent_frame* sent;
+  uint64_t n_sent;
+  const uint64_t* sent_first;
+  const ufc_frame_queue* queues;
+  const ufc_frame_queue_step* steps;
+  uint64_t n_queues;
+  ufc_sent_frame* log;
+  uint64_t n_log;
+  uint8_t* ref_acked;
+  uint64_t refs_cap;
+  ufc_frame_queue_result* results;
+  ufc_frame_queue* queues_out;
+};
+
+constexpr uint64_t kFqInitialRttMs = 100;         // FeedbackGen::INITIAL_RTT_MS, frame_queue.rs:111
+constexpr uint32_t kFqMaxIntervals = 9;           // loss_rate.rs:72
+constexpr uint32_t kFqMaxSpan = 0x80000000u;
+constexpr uint32_t kFqOwnRefs = 16;               // a lane marks up to this many fragments itself
+
+struct FqWaveShared {
+  uint64_t tile_time[64];                          // a nack or expiry tile's send times
+  uint64_t group_time[32];                         // a group's entries
+  uint32_t group_size[32], group_ref_first[32], group_ref_count[32];
+  uint8_t group_flags[32];
+  // Wv::one only from here on: the loss intervals, the pending AckData, the result's counters
+  uint64_t li_end[kFqMaxIntervals];
+  uint32_t li_len[kFqMaxIntervals];
+  uint32_t has_ack, ack_rl;
+  uint64_t ack_last, ack_total;
+  ufc_frame_queue_result res;
+};
+
+struct FqRun {
+  uint32_t log_base, log_next, window_base, rb_base, rb_f0, rb_f1, rb_count;
+  uint32_t rb_max_span, window_size, tail_size, mask;
+  uint64_t ring, rtt;
+  bool pending;
+  uint32_t li_count;
+  uint64_t li_end;                                 // the front interval's end time, if li_count
+};
+
+UFC_HD uint32_t fq_sat_add(uint32_t v, uint32_t k) {  // k saturating_add(1)s
+  const uint64_t s = (uint64_t)v + k;
+  return s > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s;
+}
+// (1.0 / p).clamp(0.0, u32::MAX as f64).round() as u32, loss_rate.rs:53.
+UFC_HD uint32_t fq_reset_length(double p) {
+#pragma clang fp contract(off)
+  double v = 1.0 / p;
+  if (v != v) return 0;  // (clamp keeps a NaN, `as u32` makes it 0)
+  if (v < 0.0) v = 0.0;
+  if (v > 4294967295.0) v = 4294967295.0;
+  uint64_t t = (uint64_t)v;
+  if (v - (double)t >= 0.5) t++;  // round(): half away from zero; v - t is exact
+  return (uint32_t)t;
+}
+// (total as f64 / ms_to_s(delta)).clamp(0.0, u32::MAX as f64) as u32, frame_queue.rs:131-132.
+UFC_HD uint32_t fq_receive_rate(uint64_t total, uint64_t delta_ms) {
+#pragma clang fp contract(off)
+  const double s = (double)delta_ms / 1000.0;
+  const double v = (double)total / s;
+  if (v != v) return 0;
+  if (v < 0.0) return 0;
+  if (v > 4294967295.0) return 0xFFFFFFFFu;
+  return (uint32_t)v;
+}
+// compute_loss_rate, loss_rate.rs:86-109, sum by sum.
+UFC_HD double fq_loss_rate(const uint32_t* len, uint32_t n) {
+#pragma clang fp contract(off)
+  const double W[8] = {1.0, 1.0, 1.0, 1.0, 0.8, 0.6, 0.4, 0.2};
+  if (n == 0) return 0.0;
+  if (n == 1) return W[0] / ((double)len[0] * W[0]);
+  double i0 = 0.0, i1 = 0.0, w = 0.0;
+  for (uint32_t i = 0; i + 1 < n; i++) {
+    const double term = (double)len[i] * W[i];
+    i0 = i0 + term;
+    w = w + W[i];
+  }
+  for (uint32_t i = 1; i < n; i++) {
+    const double term = (double)len[i] * W[i - 1];
+    i1 = i1 + term;
+  }
+  return w / (i0 > i1 ? i0 : i1);
+}
+
+// The checks of the header comment, in its order; the frames' item ranges are checked by the caller's tiles.
+UFC_HD bool fq_state_ok(const FqArgs& a, const ufc_frame_queue& Q, const ufc_frame_queue_step& S, uint64_t ff0, uint64_t ff1,
+                        uint64_t sf0, uint64_t sf1) {
+  const uint64_t span = (uint64_t)Q.window_size + Q.tail_size;
+  if (Q.log_cap == 0 || (Q.log_cap & (Q.log_cap - 1)) || Q.log_cap < span) return false;
+  if (Q.log_first > a.n_log || a.n_log - Q.log_first < Q.log_cap) return false;
+  const uint32_t len = Q.log_next_id - Q.log_base_id, ahead = Q.log_next_id - Q.window_base_id;
+  if (len > Q.log_cap || ahead > Q.window_size || (uint64_t)len > (uint64_t)ahead + Q.tail_size) return false;
+  if (Q.rb_max_span < span || Q.rb_max_span > kFqMaxSpan) return false;
+  const uint32_t rb = Q.rb_base_id - Q.log_base_id;
+  if (rb > len || Q.rb_count > 2) return false;
+  const uint32_t d0 = Q.rb_frames[0] - Q.rb_base_id, d1 = Q.rb_frames[1] - Q.rb_base_id;
+  if (Q.rb_count >= 1 && (d0 == 0 || (uint64_t)rb + d0 >= len)) return false;
+  if (Q.rb_count == 2 && (d1 == 0 || (uint64_t)rb + d1 >= len || d0 >= d1)) return false;
+  if (Q.li_count > kFqMaxIntervals || ((S.flags & UFC_FQ_RESET_LOSS) && Q.li_count == 0)) return false;
+  return ff0 <= ff1 && ff1 <= a.n_frames && sf0 <= sf1 && sf1 <= a.n_sent;
+}
+UFC_HD bool fq_is_ack(const ufc_frame_info& f) { return f.ok && f.kind == UFC_FRAME_ACK; }
+UFC_HD uint64_t fq_slot(const FqRun& s, uint32_t id) { return s.ring + (id & s.mask); }
+
+// push_ack k times (loss_rate.rs:56-61).
+template <class Wv>
+UFC_HD void fq_acks(const Wv& wv, FqWaveShared& sh, FqRun& s, uint32_t k) {
+  wv.one([&]() { sh.res.li_acks += k; });
+  if (s.li_count) wv.one([&]() { sh.li_len[0] = fq_sat_add(sh.li_len[0], k); });
+}
+// push_nack (loss_rate.rs:63-84) for the ids from, from + 1, ... (count of them), with their send times.
+template <class Wv>
+inline __host__ __device__ void fq_nacks(const Wv& wv, FqWaveShared& sh, const FqArgs& a, FqRun& s, uint32_t from,
+                                         uint32_t count) {
+  wv.one([&]() { sh.res.li_nacks += count; });
+  for (uint32_t t = 0; t < count; t += 64) {
+    const uint32_t nv = count - t < 64 ? count - t : 64u;
+    wv.lanes([&](uint32_t lane) {
+      if (lane < nv) sh.tile_time[lane] = a.log[fq_slot(s, from + t + lane)].send_time_ms;
+    });
+    uint32_t pos = 0;
+    while (pos < nv) {
+      uint32_t f = pos;  // with no interval the entry opens one whatever its time (:77-83)
+      if (s.li_count) {
+        const uint64_t end = s.li_end;
+        const unsigned long long M =
+            wv.ballot([&](uint32_t lane) { return lane >= pos && lane < nv && sh.tile_time[lane] >= end; });
+        f = M ? fw_low_bit(M) : nv;
+        const uint32_t adds = f - pos;  // they fall under the front interval (:75)
+        if (adds) wv.one([&]() { sh.li_len[0] = fq_sat_add(sh.li_len[0], adds); });
+        if (f >= nv) break;
+      }
+      const uint64_t end = sh.tile_time[f] + s.rtt;
+      const uint32_t held = s.li_count < kFqMaxIntervals ? s.li_count : kFqMaxIntervals - 1;
+      wv.one([&]() {  // push_front, truncate(9)
+        for (uint32_t k = held; k > 0; k--) {
+          sh.li_end[k] = sh.li_end[k - 1];
+          sh.li_len[k] = sh.li_len[k - 1];
+        }
+        sh.li_end[0] = end;
+        sh.li_len[0] = 1;
+      });
+      s.li_count = held + 1;
+      s.li_end = end;
+      pos = f + 1;
+    }
+  }
+}
+
+// ReorderBuffer::put (reorder_buffer.rs:28-115) with FeedbackGen's callback (frame_queue.rs:164-172).
+template <class Wv>
+inline __host__ __device__ void fq_rb_put(const Wv& wv, FqWaveShared& sh, const FqArgs& a, FqRun& s, uint32_t id) {
+  if (s.rb_count == 0) {
+    if (id == s.rb_base) {
+      fq_acks(wv, sh, s, 1);
+      s.rb_base++;
+    } else {
+      s.rb_f0 = id;
+      s.rb_count = 1;
+    }
+  } else if (s.rb_count == 1) {
+    if (id == s.rb_base) {
+      fq_acks(wv, sh, s, 1);
+      s.rb_base++;
+      if (s.rb_f0 == s.rb_base) {
+        fq_acks(wv, sh, s, 1);
+        s.rb_base++;
+        s.rb_count = 0;
+      }
+    } else {
+      if (id - s.rb_base < s.rb_f0 - s.rb_base) {
+        s.rb_f1 = s.rb_f0;
+        s.rb_f0 = id;
+      } else {
+        s.rb_f1 = id;
+      }
+      s.rb_count = 2;
+    }
+  } else if (s.rb_count == 2) {
+    uint32_t min_id = id, delta_min = id - s.rb_base;
+    const uint32_t delta_1 = s.rb_f1 - s.rb_base;
+    if (delta_1 < delta_min) {
+      const uint32_t t = s.rb_f1;
+      s.rb_f1 = min_id;
+      min_id = t;
+      delta_min = delta_1;
+    }
+    if (s.rb_f0 - s.rb_base < delta_min) {
+      const uint32_t t = s.rb_f0;
+      s.rb_f0 = min_id;
+      min_id = t;
+    }
+    fq_nacks(wv, sh, a, s, s.rb_base, min_id - s.rb_base);
+    fq_acks(wv, sh, s, 1);
+    s.rb_base = min_id + 1;
+    if (s.rb_f0 == s.rb_base) {
+      fq_acks(wv, sh, s, 1);
+      s.rb_base++;
+      s.rb_count--;
+      if (s.rb_f1 == s.rb_base) {
+        fq_acks(wv, sh, s, 1);
+        s.rb_base++;
+        s.rb_count--;
+      } else {
+        s.rb_f0 = s.rb_f1;
+      }
+    }
+  }
+}
+// ReorderBuffer::advance (:122-178) with the same callback (frame_queue.rs:184-192).
+template <class Wv>
+inline __host__ __device__ void fq_rb_advance(const Wv& wv, FqWaveShared& sh, const FqArgs& a, FqRun& s, uint32_t new_base) {
+  while (s.rb_count > 0 && s.rb_f0 - s.rb_base < new_base - s.rb_base) {
+    fq_nacks(wv, sh, a, s, s.rb_base, s.rb_f0 - s.rb_base);
+    fq_acks(wv, sh, s, 1);
+    s.rb_base = s.rb_f0 + 1;
+    if (s.rb_count == 2) s.rb_f0 = s.rb_f1;
+    s.rb_count--;
+  }
+  fq_nacks(wv, sh, a, s, s.rb_base, new_base - s.rb_base);
+  s.rb_base = new_base;
+  if (s.rb_count == 1) {
+    if (s.rb_f0 == s.rb_base) {
+      fq_acks(wv, sh, s, 1);
+      s.rb_base++;
+      s.rb_count = 0;
+    }
+  } else if (s.rb_count == 2) {
+    if (s.rb_f0 == s.rb_base) {
+      fq_acks(wv, sh, s, 1);
+      s.rb_base++;
+      s.rb_count--;
+      if (s.rb_f1 == s.rb_base) {
+        fq_acks(wv, sh, s, 1);
+        s.rb_base++;
+        s.rb_count--;
+      } else {
+        s.rb_f0 = s.rb_f1;
+      }
+    }
+  }
+}
+// cull_log_entries (frame_queue.rs:382-387): notify_advancement (:179-194), then FrameLog::drain (:79-83).
+template <class Wv>
+inline __host__ __device__ void fq_cull(const Wv& wv, FqWaveShared& sh, const FqArgs& a, FqRun& s, uint32_t new_base) {
+  const uint32_t delta = new_base - s.rb_base;
+  if (delta >= 1 && delta <= s.rb_max_span) fq_rb_advance(wv, sh, a, s, new_base);
+  wv.one([&]() { sh.res.log_culled += new_base - s.log_base; });
+  s.log_base = new_base;
+}
+
+// acknowledge_group (frame_queue.rs:279-355).
+template <class Wv>
+inline __host__ __device__ void fq_group(const Wv& wv, FqWaveShared& sh, const FqArgs& a, FqRun& s, const ufc_item& g) {
+  const uint32_t base = g.id, bits = g.data_offset, nonce = g.channel_id & 1u;
+  wv.one([&]() { sh.res.groups++; });
+  if (bits == 0) {  // a dud (:294)
+    wv.one([&]() { sh.res.groups_dud++; });
+    return;
+  }
+  const uint32_t n = 32u - (uint32_t)__builtin_clz(bits), len = s.log_next - s.log_base;
+  const unsigned long long outside = wv.ballot([&](uint32_t lane) {
+    if (lane >= n) return false;
+    const uint32_t id = base + lane;
+    if (id - s.log_base >= len) return true;
+    const ufc_sent_frame e = a.log[fq_slot(s, id)];
+    sh.group_time[lane] = e.send_time_ms;
+    sh.group_size[lane] = e.size;
+    sh.group_ref_first[lane] = e.ref_first;
+    sh.group_ref_count[lane] = e.ref_count;
+    sh.group_flags[lane] = e.flags;
+    return false;
+  });
+  if (outside) {  // forgotten, or beyond the log (:307)
+    wv.one([&]() { sh.res.groups_unknown++; });
+    return;
+  }
+  const unsigned long long claimed = bits;
+  const unsigned long long odd =
+      wv.ballot([&](uint32_t lane) { return lane < n && ((claimed >> lane) & 1u) && (sh.group_flags[lane] & UFC_SENT_NONCE); });
+  if ((fw_popc(odd) & 1u) != nonce) {  // (:313)
+    wv.one([&]() { sh.res.groups_bad_nonce++; });
+    return;
+  }
+  const unsigned long long limited = wv.ballot([&](uint32_t lane) { return lane < n && (sh.group_flags[lane] & UFC_SENT_RATE_LIMITED); });
+  const unsigned long long fresh =
+      wv.ballot([&](uint32_t lane) { return lane < n && ((claimed >> lane) & 1u) && !(sh.group_flags[lane] & UFC_SENT_ACKED); });
+  // acked = true, and the fragments of the frame (:328-339)
+  auto ref_end = [&](uint32_t lane) {
+    const uint64_t e = (uint64_t)sh.group_ref_first[lane] + sh.group_ref_count[lane];
+    return a.ref_acked ? (e < a.refs_cap ? e : a.refs_cap) : 0;
+  };
+  const unsigned long long wide = wv.ballot([&](uint32_t lane) {
+    if (lane >= n || !((fresh >> lane) & 1u)) return false;
+    a.log[fq_slot(s, base + lane)].flags = (uint8_t)(sh.group_flags[lane] | UFC_SENT_ACKED);
+    const uint64_t first = sh.group_ref_first[lane], end = ref_end(lane);
+    if (end > first && end - first > kFqOwnRefs) return true;
+    for (uint64_t j = first; j < end; j++) a.ref_acked[j] = 1;
+    return false;
+  });
+  for (unsigned long long w = wide; w; w &= w - 1) {  // a frame with many fragments: all lanes mark them
+    const uint32_t o = fw_low_bit(w);
+    const uint64_t first = sh.group_ref_first[o], end = ref_end(o);
+    wv.lanes([&](uint32_t lane) {
+      for (uint64_t j = first + lane; j < end; j += 64) a.ref_acked[j] = 1;
+    });
+  }
+  uint64_t last = 0, total = 0;
+  for (unsigned long long w = fresh; w; w &= w - 1) {
+    const uint32_t o = fw_low_bit(w), id = base + o;
+    const uint64_t t = sh.group_time[o];
+    last = last > t ? last : t;
+    total += sh.group_size[o];
+    wv.one([&]() { sh.res.frames_acked++; });
+    if (id - s.rb_base < s.rb_max_span) fq_rb_put(wv, sh, a, s, id);  // notify_ack (:159-177)
+  }
+  // put_ack_data (:149-157)
+  wv.one([&]() {
+    if (sh.has_ack) {
+      sh.ack_last = sh.ack_last > last ? sh.ack_last : last;
+      sh.ack_total += total;
+      sh.ack_rl |= limited != 0;
+    } else {
+      sh.has_ack = 1;
+      sh.ack_last = last;
+      sh.ack_total = total;
+      sh.ack_rl = limited != 0;
+    }
+  });
+}
+
+// One connection's step.
+template <class Wv>
+inline __host__ __device__ void fq_step(const Wv& wv, FqWaveShared& sh, const FqArgs& a, uint64_t c) {
+  // (read in place: queues_out[c], which may be queues[c], is written last, behind every read)
+  const ufc_frame_queue& Q = a.queues[c];
+  const ufc_frame_queue_step& S = a.steps[c];
+  const uint64_t ff0 = a.frame_first[c], ff1 = a.frame_first[c + 1], sf0 = a.sent_first[c], sf1 = a.sent_first[c + 1];
+  bool ok = fq_state_ok(a, Q, S, ff0, ff1, sf0, sf1);
+  for (uint64_t t0 = ff0; ok && t0 < ff1; t0 += 64) {  // the ack frames' item ranges
+    const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
+    const unsigned long long bad = wv.ballot([&](uint32_t lane) {
+      if (lane >= nv) return false;
+      const ufc_frame_info f = a.infos[t0 + lane];
+      return fq_is_ack(f) && (uint64_t)f.item_first + f.item_count > a.n_items;
+    });
+    if (bad) ok = false;
+  }
+  if (!ok) {  // (every lane takes this branch or none)
+    wv.one([&]() {
+      ufc_frame_queue_result res{};
+      res.stop = UFC_FQ_BAD_STATE;
+      a.results[c] = res;
+      const ufc_frame_queue O = Q;
+      a.queues_out[c] = O;
+    });
+    return;
+  }
+  FqRun s{};
+  s.log_base = Q.log_base_id;
+  s.log_next = Q.log_next_id;
+  s.window_base = Q.window_base_id;
+  s.window_size = Q.window_size;
+  s.tail_size = Q.tail_size;
+  s.rb_base = Q.rb_base_id;
+  s.rb_max_span = Q.rb_max_span;
+  s.rb_f0 = Q.rb_frames[0];
+  s.rb_f1 = Q.rb_frames[1];
+  s.rb_count = Q.rb_count;
+  s.mask = Q.log_cap - 1;
+  s.ring = Q.log_first;
+  s.rtt = (S.flags & UFC_FQ_HAS_RTT) ? S.rtt_ms : kFqInitialRttMs;
+  s.pending = Q.rate_limited != 0;
+  s.li_count = Q.li_count;
+  s.li_end = Q.li_end_time_ms[0];
+  wv.one([&]() {
+    for (uint32_t k = 0; k < kFqMaxIntervals; k++) {
+      sh.li_end[k] = Q.li_end_time_ms[k];
+      sh.li_len[k] = Q.li_length[k];
+    }
+    sh.has_ack = Q.has_ack_data != 0;
+    sh.ack_rl = Q.ack_rate_limited != 0;
+    sh.ack_last = Q.ack_last_send_time_ms;
+    sh.ack_total = Q.ack_total_size;
+    sh.res = ufc_frame_queue_result{};
+  });
+  // 1. reset_loss_rate
+  if (S.flags & UFC_FQ_RESET_LOSS) {
+    s.li_count = 1;
+    wv.one([&]() { sh.li_len[0] = fq_reset_length(S.reset_loss_rate); });
+  }
+  // 2. push
+  {
+    const uint32_t ahead = s.log_next - s.window_base, count = (uint32_t)(sf1 - sf0);
+    const uint32_t room = s.window_size - ahead, taken = count < room ? count : room;
+    const uint32_t first_id = s.log_next;
+    const bool pending = s.pending;
+    for (uint32_t t = 0; t < taken; t += 64)
+      wv.lanes([&](uint32_t lane) {
+        const uint32_t j = t + lane;
+        if (j >= taken) return;
+        const ufc_sent_frame in = a.sent[sf0 + j];
+        ufc_sent_frame e{};
+        e.send_time_ms = in.send_time_ms;
+        e.size = in.size;
+        e.ref_first = in.ref_first;
+        e.ref_count = in.ref_count;
+        e.flags = (uint8_t)((in.flags & UFC_SENT_NONCE) |
+                            (((in.flags & UFC_SENT_MARK) || (j == 0 && pending)) ? UFC_SENT_RATE_LIMITED : 0));
+        a.log[fq_slot(s, first_id + j)] = e;
+      });
+    if (taken) s.pending = false;
+    s.log_next += taken;
+    wv.one([&]() {
+      sh.res.pushes_taken = taken;
+      sh.res.pushes_refused = count - taken;
+    });
+    if (S.flags & UFC_FQ_MARK_RATE_LIMITED) s.pending = true;
+  }
+  // 3. the ack frames
+  for (uint64_t t0 = ff0; t0 < ff1; t0 += 64) {
+    const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
+    unsigned long long acks = wv.ballot([&](uint32_t lane) { return lane < nv && fq_is_ack(a.infos[t0 + lane]); });
+    for (; acks; acks &= acks - 1) {
+      const ufc_frame_info f = a.infos[t0 + fw_low_bit(acks)];
+      wv.one([&]() { sh.res.ack_frames++; });
+      for (uint64_t g = f.item_first, ge = (uint64_t)f.item_first + f.item_count; g < ge; g++) fq_group(wv, sh, a, s, a.items[g]);
+      // advance_transfer_window (:357-380)
+      const uint32_t delta = f.f[0] - s.window_base;
+      if (delta != 0 && delta <= s.log_next - s.window_base) {
+        s.window_base = f.f[0];
+        wv.one([&]() { sh.res.window_advanced += delta; });
+        const uint32_t max_base = s.window_base - s.tail_size, cut = max_base - s.log_base;
+        if (cut != 0 && cut <= s.log_next - s.log_base) fq_cull(wv, sh, a, s, max_base);
+      }
+    }
+  }
+  // 4. forget_frames (:261-269)
+  if (S.flags & UFC_FQ_FORGET) {
+    const uint32_t len = s.log_next - s.log_base;
+    uint32_t expired = 0;
+    for (uint32_t t = 0; t < len; t += 64) {
+      const uint32_t nv = len - t < 64 ? len - t : 64u;
+      const unsigned long long kept = wv.ballot(
+          [&](uint32_t lane) { return lane < nv && a.log[fq_slot(s, s.log_base + t + lane)].send_time_ms >= S.thresh_ms; });
+      if (kept) {
+        expired += fw_low_bit(kept);
+        break;
+      }
+      expired += nv;
+    }
+    if (expired) fq_cull(wv, sh, a, s, s.log_base + expired);
+  }
+  // 5. get_feedback (:126-147), the result and the state
+  wv.one([&]() {
+    ufc_frame_queue O = Q;
+    ufc_frame_queue_result res = sh.res;
+    res.stop = UFC_FQ_DONE;
+    bool has_ack = sh.has_ack != 0;
+    if ((S.flags & UFC_FQ_FEEDBACK) && has_ack) {
+      res.has_feedback = 1;
+      res.rtt_ms = S.now_ms - sh.ack_last;
+      res.receive_rate = Q.has_last_feedback ? fq_receive_rate(sh.ack_total, S.now_ms - Q.last_feedback_ms) : 0;
+      res.loss_rate = fq_loss_rate(sh.li_len, s.li_count);
+      res.rate_limited = sh.ack_rl ? 1 : 0;
+      O.has_last_feedback = 1;
+      O.last_feedback_ms = S.now_ms;
+      has_ack = false;
+    }
+    const uint32_t ahead = s.log_next - s.window_base;
+    res.window_room = ahead < s.window_size ? s.window_size - ahead : 0;
+    O.log_base_id = s.log_base;
+    O.log_next_id = s.log_next;
+    O.window_base_id = s.window_base;
+    O.rb_base_id = s.rb_base;
+    O.rb_frames[0] = s.rb_f0;
+    O.rb_frames[1] = s.rb_f1;
+    O.rb_count = s.rb_count;
+    O.rate_limited = s.pending ? 1 : 0;
+    O.has_ack_data = has_ack ? 1 : 0;
+    O.ack_rate_limited = (has_ack && sh.ack_rl) ? 1 : 0;
+    O.ack_last_send_time_ms = has_ack ? sh.ack_last : 0;
+    O.ack_total_size = has_ack ? sh.ack_total : 0;
+    O.li_count = s.li_count;
+    for (uint32_t k = 0; k < kFqMaxIntervals; k++) {  // (the entries behind the count: zero)
+      O.li_end_time_ms[k] = k < s.li_count ? sh.li_end[k] : 0;
+      O.li_length[k] = k < s.li_count ? sh.li_len[k] : 0;
+    }
+    a.results[c] = res;
+    a.queues_out[c] = O;
+  });
+}
+
+// The wave policy as host code: a phase is a loop over the 64 lanes (ufc_frame_queue_host and
+// tests/c/queue_host_check.hip).
+struct FqHostWave {
+  template <class F>
+  void lanes(const F& f) const {
+    for (uint32_t l = 0; l < 64; l++) f(l);
+  }
+  template <class F>
+  void one(const F& f) const {
+    f();
+  }
+  template <class F>
+  unsigned long long ballot(const F& f) const {
+    unsigned long long m = 0;
+    for (uint32_t l = 0; l < 64; l++)
+      if (f(l)) m |= 1ull << l;
+    return m;
+  }
+};
 
 }  // namespace ufc_codec

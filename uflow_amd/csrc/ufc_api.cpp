@@ -20,6 +20,7 @@
 #include "frame_crc_kernels.hpp"
 #include "frame_pack.hpp"
 #include "frame_parse.hpp"
+#include "frame_queue.hpp"
 #include "frame_window.hpp"
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
@@ -1056,6 +1057,29 @@ int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
   const ufc_codec::FwArgs a{d_infos, n_frames, d_frame_first, d_windows, n_windows, d_frame_accept, d_groups,
                             groups_cap, d_group_first, d_groups_used, d_results, d_windows_out};
   if ((e = ufc_dev::window_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched frame queue (frame_queue.hip) ----
+int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const ufc_item* d_items,
+                           size_t n_items, const uint64_t* d_frame_first, const ufc_sent_frame* d_sent, size_t n_sent,
+                           const uint64_t* d_sent_first, const ufc_frame_queue* d_queues,
+                           const ufc_frame_queue_step* d_steps, size_t n_queues, ufc_sent_frame* d_log, size_t n_log,
+                           uint8_t* d_ref_acked, size_t refs_cap, ufc_frame_queue_result* d_results,
+                           ufc_frame_queue* d_queues_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n_queues == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!d_frame_first || !d_sent_first || !d_queues || !d_steps || !d_results || !d_queues_out ||
+      (!d_infos && n_frames) || (!d_items && n_items) || (!d_sent && n_sent) || (!d_log && n_log) || n_frames >= lim ||
+      n_items >= lim || n_sent >= lim || n_queues >= lim)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  // (one launch and no scan: the call needs none of the context's per-stream scratch)
+  const ufc_codec::FqArgs a{d_infos, n_frames, d_items, n_items, d_frame_first, d_sent, n_sent, d_sent_first, d_queues,
+                            d_steps, n_queues, d_log, n_log, d_ref_acked, refs_cap, d_results, d_queues_out};
+  if ((e = ufc_dev::queue_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

@@ -19,6 +19,10 @@ and the batched receive-side parse that follows the batched CRC gate:
                                                <- FrameAckQueue::window_contains / mark_seen / resynchronize,
                                                   src/half_connection/frame_ack_queue.rs, as handle_data_frame and
                                                   handle_sync_frame call them (half_connection/mod.rs:132-152)
+    frame_queue_host(infos, items, frame_first, sent, sent_first, queues, steps, log)
+                                               <- FrameQueue::push / acknowledge_group / advance_transfer_window /
+                                                  forget_frames / get_feedback, src/half_connection/frame_queue.rs
+                                                  with reorder_buffer.rs and loss_rate.rs
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -31,9 +35,9 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameWindow, FrameWindowResult, Item, Packet,
-                      PacketResult, Receiver, ReceiverResult, RxPacket, RxSlot, Sender, SenderResult, check, lib,
-                      UFC_ERR_NOMEM)
+from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameQueue, FrameQueueResult, FrameQueueStep,
+                      FrameWindow, FrameWindowResult, Item, Packet, PacketResult, Receiver, ReceiverResult, RxPacket,
+                      RxSlot, SentFrame, Sender, SenderResult, check, lib, UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -111,6 +115,55 @@ FRAME_WINDOW_RESULT_DTYPE = np.dtype([("group_first", "<u4"), ("group_count", "<
 assert FRAME_WINDOW_DTYPE.itemsize == ctypes.sizeof(FrameWindow) == 24
 assert FRAME_WINDOW_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameWindowResult) == 40
 FW_DONE, FW_BAD_STATE = 0, 1
+# ufc_sent_frame / ufc_frame_queue / ufc_frame_queue_step / ufc_frame_queue_result (batched sender frame queues)
+SENT_FRAME_DTYPE = np.dtype([("send_time_ms", "<u8"), ("size", "<u4"), ("ref_first", "<u4"), ("ref_count", "<u4"),
+                             ("flags", "u1"), ("reserved", "u1", (3,))])
+FRAME_QUEUE_DTYPE = np.dtype([("log_base_id", "<u4"), ("log_next_id", "<u4"), ("window_base_id", "<u4"),
+                              ("window_size", "<u4"), ("tail_size", "<u4"), ("rb_base_id", "<u4"), ("rb_max_span", "<u4"),
+                              ("rb_frames", "<u4", (2,)), ("rb_count", "<u4"), ("rate_limited", "u1"),
+                              ("has_ack_data", "u1"), ("ack_rate_limited", "u1"), ("has_last_feedback", "u1"),
+                              ("li_count", "<u4"), ("ack_last_send_time_ms", "<u8"), ("ack_total_size", "<u8"),
+                              ("last_feedback_ms", "<u8"), ("li_end_time_ms", "<u8", (9,)), ("li_length", "<u4", (9,)),
+                              ("log_cap", "<u4"), ("log_first", "<u8")])
+FRAME_QUEUE_STEP_DTYPE = np.dtype([("flags", "<u4"), ("reserved", "<u4"), ("rtt_ms", "<u8"), ("thresh_ms", "<u8"),
+                                   ("now_ms", "<u8"), ("reset_loss_rate", "<f8")])
+FRAME_QUEUE_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("pushes_taken", "<u4"), ("pushes_refused", "<u4"),
+                                     ("ack_frames", "<u4"), ("groups", "<u4"), ("groups_dud", "<u4"),
+                                     ("groups_unknown", "<u4"), ("groups_bad_nonce", "<u4"), ("frames_acked", "<u4"),
+                                     ("li_acks", "<u4"), ("li_nacks", "<u4"), ("window_advanced", "<u4"),
+                                     ("log_culled", "<u4"), ("window_room", "<u4"), ("has_feedback", "u1"),
+                                     ("rate_limited", "u1"), ("reserved", "<u2"), ("receive_rate", "<u4"),
+                                     ("rtt_ms", "<u8"), ("loss_rate", "<f8")])
+assert SENT_FRAME_DTYPE.itemsize == ctypes.sizeof(SentFrame) == 24
+assert FRAME_QUEUE_DTYPE.itemsize == ctypes.sizeof(FrameQueue) == 192
+assert FRAME_QUEUE_STEP_DTYPE.itemsize == ctypes.sizeof(FrameQueueStep) == 40
+assert FRAME_QUEUE_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameQueueResult) == 80
+SENT_NONCE, SENT_RATE_LIMITED, SENT_ACKED, SENT_MARK = 1, 2, 4, 8
+FQ_HAS_RTT, FQ_RESET_LOSS, FQ_MARK_RATE_LIMITED, FQ_FORGET, FQ_FEEDBACK = 1, 2, 4, 8, 16
+FQ_DONE, FQ_BAD_STATE = 0, 1
+
+
+def new_frame_queues(n: int, window_size, tail_size, base_id=0, log_cap=None):
+    """n ufc_frame_queue records equal to FrameQueue::new(window_size, tail_size, base_id) (frame_queue.rs:218-226)
+    and their log arena: returns (queues, log).  log_cap (a power of two, default the smallest one holding
+    window_size + tail_size) is every connection's ring size; the rings lie back to back, log_first = c * log_cap."""
+    span = int(window_size) + int(tail_size)
+    if log_cap is None:
+        log_cap = 1
+        while log_cap < span:
+            log_cap *= 2
+    log_cap = int(log_cap)
+    if log_cap < max(span, 1) or log_cap & (log_cap - 1) or log_cap > 1 << 31:
+        raise ValueError("log_cap must be a power of two of at least window_size + tail_size")
+    q = np.zeros(n, dtype=FRAME_QUEUE_DTYPE)
+    for k in ("log_base_id", "log_next_id", "window_base_id", "rb_base_id"):
+        q[k] = base_id
+    q["window_size"] = window_size
+    q["tail_size"] = tail_size
+    q["rb_max_span"] = span
+    q["log_cap"] = log_cap
+    q["log_first"] = np.arange(n, dtype=np.uint64) * np.uint64(log_cap)
+    return q, np.zeros(n * log_cap, dtype=SENT_FRAME_DTYPE)
 
 
 def new_frame_windows(n: int, size, base_id=0) -> np.ndarray:
@@ -655,3 +708,50 @@ def frame_window_host(infos: np.ndarray, frame_first: np.ndarray, windows: np.nd
                                       windows_out.ctypes.data if n else None, nthreads), "ufc_frame_window_host")
     return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used.value,
             "results": results, "windows_out": windows_out}
+
+
+def frame_queue_host(infos: np.ndarray, items: np.ndarray, frame_first: np.ndarray, sent: np.ndarray,
+                     sent_first: np.ndarray, queues: np.ndarray, steps: np.ndarray, log: np.ndarray,
+                     ref_acked: Optional[np.ndarray] = None, nthreads: int = 1, results: Optional[np.ndarray] = None,
+                     queues_out: Optional[np.ndarray] = None):
+    """One step of the sender's FrameQueue for many connections in host memory (ufc_frame_queue_host): connection c
+    (FRAME_QUEUE_DTYPE; what to do in FRAME_QUEUE_STEP_DTYPE) pushes sent[sent_first[c] : sent_first[c + 1]]
+    (SENT_FRAME_DTYPE), then handles the ack frames among infos[frame_first[c] : frame_first[c + 1]] (their groups
+    in items, as the parse returns them), then forgets and produces feedback as its step asks.  log (SENT_FRAME_DTYPE,
+    the arena new_frame_queues returns) and ref_acked (uint8, optional: set to 1 for every fragment of a newly
+    acked frame) are updated in place.  Returns a dict: results (FRAME_QUEUE_RESULT_DTYPE), queues_out (may be
+    given as `queues`), log, ref_acked."""
+    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
+    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+    sent = np.ascontiguousarray(sent, dtype=SENT_FRAME_DTYPE)
+    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
+    sent_first = np.ascontiguousarray(sent_first, dtype=np.uint64)
+    steps = np.ascontiguousarray(steps, dtype=FRAME_QUEUE_STEP_DTYPE)
+    if queues.dtype != FRAME_QUEUE_DTYPE or not queues.flags.c_contiguous:
+        queues = np.ascontiguousarray(queues, dtype=FRAME_QUEUE_DTYPE)
+    n = queues.size
+    if frame_first.size < n + 1 or sent_first.size < n + 1 or steps.size < n:
+        raise ValueError("frame_first and sent_first must hold one more entry than there are queues, steps one each")
+
+    def inout(name, arr, size, dt):
+        if arr is None:
+            return np.zeros(size, dtype=dt)
+        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
+            raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
+        return arr
+
+    log = inout("log", log, 0, SENT_FRAME_DTYPE)
+    if ref_acked is not None:
+        ref_acked = inout("ref_acked", ref_acked, 0, np.dtype(np.uint8))
+    results = inout("results", results, n, FRAME_QUEUE_RESULT_DTYPE)
+    queues_out = inout("queues_out", queues_out, n, FRAME_QUEUE_DTYPE)
+    refs_cap = ref_acked.size if ref_acked is not None else 0
+    check(lib().ufc_frame_queue_host(infos.ctypes.data if infos.size else None, infos.size,
+                                     items.ctypes.data if items.size else None, items.size, frame_first.ctypes.data,
+                                     sent.ctypes.data if sent.size else None, sent.size, sent_first.ctypes.data,
+                                     queues.ctypes.data if n else None, steps.ctypes.data if n else None, n,
+                                     log.ctypes.data if log.size else None, log.size,
+                                     ref_acked.ctypes.data if refs_cap else None, refs_cap,
+                                     results.ctypes.data if n else None, queues_out.ctypes.data if n else None, nthreads),
+          "ufc_frame_queue_host")
+    return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
