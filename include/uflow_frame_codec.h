@@ -673,9 +673,9 @@ int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
  * FrameLog (:24-84) and FeedbackGen (:96-195), ReorderBuffer (reorder_buffer.rs:2-179, whole file) and
  * LossIntervalQueue (loss_rate.rs:19-110, whole file), as HalfConnection::handle_ack_frame, step and the emitters
  * drive it.  The release build is the specification, wrapping u32 and u64 arithmetic included (send_time_ms +
- * rtt_ms, now_ms - last_send_time_ms and total_ack_size all wrap).  SendRateComp (send_rate.rs, recv_rate_set.rs),
- * PacketSender::acknowledge (it needs the per-packet window table that ufc_sender does not hold) and the resend
- * and pending queues stay with the caller.
+ * rtt_ms, now_ms - last_send_time_ms and total_ack_size all wrap).  SendRateComp (send_rate.rs, recv_rate_set.rs)
+ * is ufc_rate_begin_* / ufc_rate_step_* below; PacketSender::acknowledge (it needs the per-packet window table that
+ * ufc_sender does not hold) and the resend and pending queues stay with the caller.
  *
  * A log slot is one frame_queue::Entry (:14-21).  fragment_refs is the range [ref_first, ref_first + ref_count) of a
  * fragment table the caller owns: in the device pipeline the frame's item_first / item_count from the pack. */
@@ -814,6 +814,166 @@ int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n
                            const ufc_frame_queue_step* d_steps, size_t n_queues, ufc_sent_frame* d_log, size_t n_log,
                            uint8_t* d_ref_acked, size_t refs_cap, ufc_frame_queue_result* d_results,
                            ufc_frame_queue* d_queues_out, void* stream);
+
+/* ---- batched send rate control: the TFRC step and the flush allocation ----
+ * The two steps around the frame queue call that close a tick on the sender's side: SendRateComp
+ * (src/half_connection/send_rate.rs, whole file) with its RecvRateSet (recv_rate_set.rs, whole file), as
+ * HalfConnection::step (half_connection/mod.rs:165-193), fill_flush_alloc (:200-215) and the notify_frame_sent call
+ * of emit_data_frames (:342-347) drive them.  The release build is the specification: u32 and u64 arithmetic wraps
+ * (2*send_rate, 2*recover_rate, now_ms + 2000, now_ms - time_last_doubled_ms, now_ms - e.timestamp_ms, 2*rtt_ms,
+ * rtt_ms*4, now_ms + s_to_ms(rto)), saturating_mul / saturating_sub / saturating_add apply where the reference
+ * writes them, `as u32` / `as u64` / `as isize` on a float saturate with NaN giving 0, f64::round is half away from
+ * zero, f64::max returns the other operand for a NaN, and debug_assert!s do not exist.  MSS = UFC_MAX_FRAME_SIZE,
+ * MINIMUM_RATE = MSS / 64 = 23, INITIAL_TCP_WINDOW = 4380.  PacketSender::acknowledge, the resend and pending
+ * queues and the sync frame's decision stay with the caller.
+ *
+ * A tick of a device-resident sender is five queued calls with no host code between them:
+ *   ufc_rate_begin_varlen -> ufc_frame_queue_varlen -> ufc_rate_step_varlen -> (emit) -> ufc_pack_varlen,
+ * the rate step writing the coming flush's flush_alloc and reading the last flush's alloc_left. */
+typedef struct ufc_recv_rate_entry {   /* 16 bytes: one RecvEntry (recv_rate_set.rs:3-7) */
+  uint64_t timestamp_ms;
+  uint32_t value;
+  uint8_t is_initial;
+  uint8_t reserved[3];                 /* stored as 0 */
+} ufc_recv_rate_entry;
+
+#define UFC_RATE_AWAIT_SEND 0
+#define UFC_RATE_SLOW_START 1
+#define UFC_RATE_THROUGHPUT_EQN 2
+/* One connection's SendRateComp (send_rate.rs:83-108) and the HalfConnection fields that go with it, in and out.
+ * Its RecvRateSet is entries[recv_first .. recv_first + recv_count) in Vec order, inside the room
+ * [recv_first, recv_first + recv_cap) of the caller's entry arena; the rooms of different connections must not
+ * overlap.  A has_* byte is an Option's Some bit: nonzero on input means Some, it is written 0 or 1, and a value
+ * whose bit is 0 is ignored on input and written 0 (so are time_last_doubled_ms outside SLOW_START and
+ * send_rate_tcp outside THROUGHPUT_EQN). */
+typedef struct ufc_rate_state {        /* 112 bytes */
+  uint32_t mode;                       /* UFC_RATE_* */
+  uint32_t send_rate, max_send_rate;
+  uint32_t send_rate_tcp;              /* ThroughputEqnState */
+  uint8_t has_time_last_doubled;       /* SlowStartState.time_last_doubled_ms is Some */
+  uint8_t has_nofeedback_exp;
+  uint8_t nofeedback_idle;
+  uint8_t has_rtt_s, has_rtt_ms, has_rto_ms;
+  uint8_t has_last_flush;              /* HalfConnection.time_last_flushed is Some */
+  uint8_t has_reset;                   /* a reset_loss_rate(reset_loss_rate) is pending for the next frame queue call */
+  uint64_t time_last_doubled_ms;
+  double prev_loss_rate;
+  uint64_t nofeedback_exp_ms;
+  double rtt_s;
+  uint64_t rtt_ms, rto_ms;
+  uint64_t now_ms;                     /* HalfConnection.now_ms: the time the next flush stamps on its frames */
+  int64_t flush_alloc;                 /* HalfConnection.flush_alloc */
+  double reset_loss_rate;
+  uint64_t recv_first;
+  uint32_t recv_count, recv_cap;
+} ufc_rate_state;
+
+#define UFC_RATE_FRAME_SENT 1          /* the last flush emitted at least one data frame (notify_frame_sent) */
+typedef struct ufc_rate_tick {         /* 32 bytes: one connection's input to ufc_rate_step_* */
+  uint64_t now_ms;
+  double delta_time_s;                 /* (now - time_last_flushed).as_secs_f64(); ignored without has_last_flush */
+  int64_t alloc_adjust;                /* added (wrapping) to flush_alloc first: bytes spent on frames the pack did
+                                          not see, such as the sync frame, as a negative number */
+  uint32_t flags, reserved;            /* UFC_RATE_FRAME_SENT */
+} ufc_rate_tick;
+
+#define UFC_RATE_DONE 0
+#define UFC_RATE_BAD_STATE 1
+#define UFC_RATE_REF_PANIC 2           /* the reference panics here: rate_limited_update emptied the set */
+#define UFC_RATE_RECV_FULL 3           /* the set would outgrow recv_cap */
+#define UFC_RATE_FEEDBACK 1            /* result flags: handle_feedback ran */
+#define UFC_RATE_NOFEEDBACK 2          /*   nofeedback_expired ran */
+#define UFC_RATE_RESET_ISSUED 4        /*   reset_loss_rate was called: has_reset is set in states_out */
+#define UFC_RATE_ENTERED_EQN 8         /*   SLOW_START became THROUGHPUT_EQN */
+#define UFC_RATE_INV_STALLED 16        /*   the bisection stopped by the stall rule below */
+typedef struct ufc_rate_result {       /* 56 bytes */
+  uint32_t stop, mode;                 /* mode after the step */
+  uint64_t now_ms;                     /* the three values the coming flush uses (mod.rs:173-175, :197): */
+  uint64_t rtt_ms, rto_ms;             /*   rtt_ms().unwrap_or(150) and rto_ms().unwrap_or(600) before the rate step */
+  int64_t flush_alloc;                 /* after the fill */
+  uint32_t send_rate;                  /* after the step */
+  uint32_t flags;                      /* UFC_RATE_FEEDBACK .. UFC_RATE_INV_STALLED */
+  uint32_t inv_iterations;             /* eval_tcp_throughput calls of the bisection, 0 when it did not run */
+  uint32_t recv_count;
+} ufc_rate_result;
+
+/* ufc_rate_begin_*: opens a tick, in front of ufc_frame_queue_*.  For every connection c it writes steps[c]:
+ *   flags = UFC_FQ_FORGET | UFC_FQ_FEEDBACK | (has_rtt_ms ? UFC_FQ_HAS_RTT : 0) | (has_reset ? UFC_FQ_RESET_LOSS : 0)
+ *           | extra_flags[c] (nullable; the caller's UFC_FQ_MARK_RATE_LIMITED, emit.rs:67 and :85);
+ *   rtt_ms = the state's rtt_ms or 0 for None; thresh_ms = now_ms.saturating_sub(rtt_ms.unwrap_or(150) * 4), the
+ *   product wrapping (mod.rs:178); now_ms = now_ms[c]; reset_loss_rate = the pending value, or 0; reserved 0.
+ * states_out[c] (required, may be `states`) is the state with has_reset and reset_loss_rate cleared and nothing
+ * else changed, not even canonicalised.  The pending flag is equivalent to the reference's immediate callback: the
+ * reference resets the loss intervals inside step(), before any later ack, and the frame queue call applies
+ * UFC_FQ_RESET_LOSS first of all, so a reset issued in tick T and carried to tick T+1's call sees the same sequence
+ * of operations.  No state is judged here.
+ *
+ * ufc_rate_step_*: closes the tick, behind ufc_frame_queue_*.  fq[c] is that call's result for the connection
+ * (has_feedback, rtt_ms, receive_rate, loss_rate and rate_limited are read).  Per connection, in this order:
+ *   1. Accounting of the last flush.  With flush_results != NULL and i = result_index[c] < n_flush_results:
+ *      flush_alloc = flush_results[i].alloc_left, and frame_count > 0 counts as UFC_RATE_FRAME_SENT.  An index at or
+ *      beyond n_flush_results (UFC_NO_PARENT is one) means no gather.  Then flush_alloc += alloc_adjust, wrapping.
+ *      If a frame was sent, notify_frame_sent(state.now_ms) (send_rate.rs:155-168): AWAIT_SEND becomes SLOW_START
+ *      with nofeedback_exp_ms = now_ms + 2000 and the set reset to its initial entry (u32::MAX); nofeedback_idle = 0.
+ *   2. state.now_ms = tick.now_ms; the result's rtt_ms and rto_ms are taken, with their defaults.
+ *   3. fill_flush_alloc with send_rate and rtt_s as they are now: new_bytes = (send_rate as f64 *
+ *      delta_time_s).round() as isize, alloc_max = (send_rate as f64 * rtt_s.unwrap_or(0.0)).round() as isize,
+ *      flush_alloc = flush_alloc.saturating_add(new_bytes).min(alloc_max); without has_last_flush only
+ *      has_last_flush is set.
+ *   4. SendRateComp::step(now_ms, feedback, reset) (:170-185) literally: nothing in AWAIT_SEND; handle_feedback
+ *      (:187-284) if fq[c].has_feedback; else nofeedback_expired (:286-365) if the timer is set and now_ms has
+ *      reached it.  reset_loss_rate(initial_p) sets has_reset and reset_loss_rate.
+ *   5. results[c], states_out[c] (required, may be `states`), the set updated in place, and with flushes != NULL
+ *      and j = flush_index[c] < n_flushes: flushes[j].flush_alloc = the new flush_alloc, no other field touched.
+ *      Two connections must not name the same flush.
+ *
+ * Where the reference does not return, the batched call gives an answer:
+ *   - eval_tcp_throughput_inv (:30-59) spins for ever when the target lies more than delta below
+ *     eval_tcp_throughput(rtt, 1.0): the midpoint reaches 1.0 after 54 halvings and stays (rtt 0.01 s with target 5,
+ *     rtt 0.05 s with target 11; a small max_send_rate or a small receive limit in front of send_rate/2 gets
+ *     there).  The rule: when a new midpoint equals a or b bit for bit and no return condition holds, that
+ *     midpoint is returned and UFC_RATE_INV_STALLED set.  Every interval step moves a or b to a new double
+ *     strictly between them, so the loop ends after at most about 1,100 evaluations (a target no rate reaches walks
+ *     b down through the denormals).
+ *   - rate_limited_update (recv_rate_set.rs:55-65) can empty the set, and max() then unwraps None: an updated
+ *     rtt_ms of 0 (a loopback RTT below 0.5 ms) makes 2 * rtt_ms zero, and no entry is younger than that.  The
+ *     connection stops UFC_RATE_REF_PANIC.
+ *   - The reference's Vec has no bound (feedback at every tick that saw an ack keeps about 2 * rtt / tick entries).
+ *     Here the entries are retained first and the new one appended; if more than recv_cap survive, the connection
+ *     stops UFC_RATE_RECV_FULL.
+ *   - UFC_RATE_BAD_STATE for: mode > 2; recv_cap == 0; recv_count > recv_cap; the room outside [0, n_entries);
+ *     mode != AWAIT_SEND with recv_count == 0; mode == THROUGHPUT_EQN without has_rtt_s (the unwrap at :340).
+ * A stopped connection changes nothing: states_out[c] is the input state byte for byte, its entries and its flush
+ * are untouched, and its result is zero but for `stop` (the step works on a copy and commits at the end).
+ * A state that passes never reaches an unwrap or panic of the reference other than the REF_PANIC one: max()
+ * (:79-87) is called by replace_max only behind its is_empty test, by rate_limited_update (REF_PANIC), and by
+ * nofeedback_expired in THROUGHPUT_EQN on a set the rules keep non-empty; rtt_s.unwrap() (:340) has its rule; the
+ * two `_ => panic!()` arms (:276, :354) stand behind the AWAIT_SEND return of step().  Every stop copies the state
+ * through, so each leaves a passing state passing, and UFC_RATE_DONE does too: every set update ends with at least
+ * one entry and at most recv_cap, and THROUGHPUT_EQN is entered only by handle_feedback, which sets rtt_s.
+ *
+ * Floats: every operation is an IEEE double operation in the reference's order, never fused; sqrt is correctly
+ * rounded on both sides, so host and device agree in every bit.
+ * Counts: n < 2^31 - 1; n == 0 returns UFC_OK whatever the pointers; a NULL states, now_ms / ticks, fq, steps /
+ * results or states_out, a NULL entries with n_entries != 0, a NULL result_index with flush_results, or a NULL
+ * flush_index with flushes is UFC_ERR_INVALID_ARG. */
+int ufc_rate_begin_host(const ufc_rate_state* states, const uint64_t* now_ms, const uint32_t* extra_flags, size_t n,
+                        ufc_frame_queue_step* steps, ufc_rate_state* states_out, int nthreads);
+int ufc_rate_step_host(const ufc_rate_state* states, const ufc_rate_tick* ticks, const ufc_frame_queue_result* fq,
+                       size_t n, ufc_recv_rate_entry* entries, size_t n_entries, const ufc_flush_result* flush_results,
+                       size_t n_flush_results, const uint32_t* result_index, ufc_flush* flushes, size_t n_flushes,
+                       const uint32_t* flush_index, ufc_rate_result* results, ufc_rate_state* states_out, int nthreads);
+/* The same on the GPU (gfx950 kernels, send_rate.hip): every pointer device memory, asynchronous on `stream`,
+ * nothing allocated per call, no scratch.  One lane per connection; a wave moves its 64 states, ticks and frame
+ * queue results through 15 KiB of LDS with coalesced loads and stores. */
+int ufc_rate_begin_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const uint64_t* d_now_ms,
+                          const uint32_t* d_extra_flags, size_t n, ufc_frame_queue_step* d_steps,
+                          ufc_rate_state* d_states_out, void* stream);
+int ufc_rate_step_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ufc_rate_tick* d_ticks,
+                         const ufc_frame_queue_result* d_fq, size_t n, ufc_recv_rate_entry* d_entries, size_t n_entries,
+                         const ufc_flush_result* d_flush_results, size_t n_flush_results, const uint32_t* d_result_index,
+                         ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_flush_index,
+                         ufc_rate_result* d_results, ufc_rate_state* d_states_out, void* stream);
 
 #ifdef __cplusplus
 }

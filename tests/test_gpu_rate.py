@@ -1,0 +1,337 @@
+"""GPU: the batched send rate control (ufc_rate_begin_varlen, ufc_rate_step_varlen; FrameCrcEngine.rate_begin and
+rate_step) against the host calls, byte for byte on states (every double as its 64 bits), results, the entry arena,
+the frame queue steps and the gathered flushes: generated batches at the tile edges of the LDS staging and past the
+launch grid, the square root's exactness through the public call, and 200 ticks of begin -> frame_queue -> step queued
+on device tensors with nothing read back before the end.  tests/test_rate_cpu.py holds the host calls against the
+restatement of the reference."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from uflow_amd import frame as fr
+
+import queue_expect as Q
+import rate_expect as E
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+U8 = np.uint8
+
+
+def _t(a, width=None):
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint64:
+        a = a.view(np.int64)
+    elif a.dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
+
+
+def _back(t, dtype):
+    return t.cpu().numpy().view(dtype).reshape(-1)
+
+
+def same(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    if got.tobytes() != want.tobytes():
+        bad = [k for k in range(len(got)) if got[k].tobytes() != want[k].tobytes()]
+        raise AssertionError(f"{what}: {len(bad)} records differ, first at {bad[0]}: got {got[bad[0]]}, want {want[bad[0]]}")
+
+
+def device_step(engine, b, in_place=False, gather_in=True, gather_out=True):
+    """ufc_rate_step_varlen on the batch `b` (rate_expect.random_batch's dict); the outputs as host arrays."""
+    states = _t(b["states"], 112)
+    d = engine.rate_step(states, _t(b["ticks"], 32), _t(b["fq"], 80), _t(b["entries"], 16),
+                         flush_results=_t(b["flush_results"], 24) if gather_in else None,
+                         result_index=_t(b["result_index"]) if gather_in else None,
+                         flushes=_t(b["flushes"], 24) if gather_out else None,
+                         flush_index=_t(b["flush_index"]) if gather_out else None,
+                         states_out=states if in_place else None)
+    torch.cuda.synchronize()
+    if not in_place:
+        same(_back(states, fr.RATE_STATE_DTYPE), b["states"], "states (input)")
+    return {"results": _back(d["results"], fr.RATE_RESULT_DTYPE), "states_out": _back(d["states_out"], fr.RATE_STATE_DTYPE),
+            "entries": _back(d["entries"], fr.RECV_RATE_ENTRY_DTYPE),
+            "flushes": _back(d["flushes"], fr.FLUSH_DTYPE) if gather_out else None}
+
+
+def host_step(b, gather_in=True, gather_out=True):
+    return fr.rate_step_host(b["states"], b["ticks"], b["fq"], b["entries"].copy(),
+                             flush_results=b["flush_results"] if gather_in else None,
+                             result_index=b["result_index"] if gather_in else None,
+                             flushes=b["flushes"].copy() if gather_out else None,
+                             flush_index=b["flush_index"] if gather_out else None, nthreads=16)
+
+
+def compare_step(engine, b, **kw):
+    gathers = {k: kw[k] for k in ("gather_in", "gather_out") if k in kw}
+    want = host_step(b, **gathers)
+    got = device_step(engine, b, **kw)
+    for k in ("results", "states_out", "entries"):
+        same(got[k], want[k], k)
+    if want["flushes"] is not None:
+        same(got["flushes"], want["flushes"], "flushes")
+    return want
+
+
+def compare_begin(engine, states, now, extra, in_place=False):
+    want = fr.rate_begin_host(states, now, extra)
+    d_states = _t(states, 112)
+    d = engine.rate_begin(d_states, _t(now), _t(extra) if extra is not None else None,
+                          states_out=d_states if in_place else None)
+    torch.cuda.synchronize()
+    same(_back(d["steps"], fr.FRAME_QUEUE_STEP_DTYPE), want["steps"], "steps")
+    same(_back(d["states_out"], fr.RATE_STATE_DTYPE), want["states_out"], "states_out")
+
+
+# ---- parity at the tile edges ----
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 130])
+def test_equals_the_host_calls(engine, n):
+    """States over all three modes with feedback, no feedback and expired timers, BAD_STATE, REF_PANIC and RECV_FULL
+    connections among them (the whole batch of n = 1 is drawn until it holds one of each in turn), with separate and
+    aliased states_out, with and without each gather."""
+    rng = np.random.default_rng(1000 + n)
+    seen = np.zeros(4, dtype=int)
+    rounds = 0
+    while rounds < 3 or (seen == 0).any():
+        b = E.random_batch(rng, n, recv_cap=1 + rounds % 3, spoil=0.1)
+        variant = rounds % 4
+        want = compare_step(engine, b, in_place=variant in (1, 3), gather_in=variant != 2, gather_out=variant != 3)
+        seen += np.bincount(want["results"]["stop"], minlength=4)
+        extra = rng.integers(0, 8, n).astype(np.uint32) if rounds % 2 else None
+        compare_begin(engine, b["states"], b["ticks"]["now_ms"].copy(), extra, in_place=bool(rounds % 2))
+        rounds += 1
+        assert rounds < 400, seen
+
+
+def tiled_batch(rng, n, unit=2000, recv_cap=3):
+    """n connections made of a generated batch of `unit`, repeated: every copy with its own room in the arena and
+    its own flush."""
+    b = E.random_batch(rng, unit, recv_cap=recv_cap, spoil=0.0)
+    reps = -(-n // unit)
+    span = len(b["entries"])
+    states = np.tile(b["states"], reps)[:n].copy()
+    states["recv_first"] += np.arange(n, dtype=np.uint64) // np.uint64(unit) * np.uint64(span)
+    bad = np.nonzero(rng.random(n) < 0.03)[0]          # (rules that do not depend on where the room lies)
+    states["mode"][bad[0::3]] = 3
+    states["recv_cap"][bad[1::3]] = 0
+    states["recv_first"][bad[2::3]] = E.M64
+    flush_index = np.arange(n, dtype=np.uint32)
+    flush_index[rng.random(n) < 0.2] = fr.NO_INDEX
+    flushes = np.tile(b["flushes"][:1], n)
+    m = len(b["flush_results"])
+    return {"states": states, "entries": np.tile(b["entries"], reps), "ticks": np.tile(b["ticks"], reps)[:n].copy(),
+            "fq": np.tile(b["fq"], reps)[:n].copy(), "flush_results": b["flush_results"],
+            "result_index": rng.integers(0, m + 2, n).astype(np.uint32), "flushes": flushes, "flush_index": flush_index}
+
+
+@pytest.mark.parametrize("n", [70000, 270000])
+def test_many_connections_equal_the_host_calls(engine, n):
+    """70,000: past 65,536 connections, a thousand tiles in flight.  270,000: past the 262,144 lanes of the launch
+    grid (4,096 blocks of one wave), so that the blocks go round a second time."""
+    rng = np.random.default_rng(n)
+    b = tiled_batch(rng, n)
+    want = compare_step(engine, b)
+    assert (np.bincount(want["results"]["stop"], minlength=4) > 0).all()
+    compare_step(engine, b, in_place=True, gather_in=False)
+    compare_begin(engine, b["states"], b["ticks"]["now_ms"].copy(), rng.integers(0, 8, n).astype(np.uint32))
+
+
+# ---- the square root ----
+def sweep_values():
+    """4096 (rtt_ms, loss_rate) pairs: loss rates over the decades with their neighbours in the last bit, 0, 1,
+    denormals, infinity and NaN; RTTs over the decades."""
+    rng = np.random.default_rng(42)
+    decades = 10.0 ** rng.uniform(-12, 0.5, 1200)
+    near = np.concatenate([np.nextafter(decades[:400], 0.0), np.nextafter(decades[:400], 2.0)])
+    third = np.array([2.0 / 3.0, 1.5, 8.0 / 3.0, 0.375, 0.25, 1.0, 0.0, -0.0, np.inf, np.nan, -1.0, 5e-324, 1e-310,
+                      2.2250738585072014e-308, 2.225073858507201e-308, 1e-300, 4.0, 1e300])
+    edges = np.concatenate([third, np.nextafter(third, 0.0), np.nextafter(third, np.inf)])
+    squares = (rng.integers(1, 1 << 26, 600).astype(np.float64) ** 2) * 1.5 / 2.0 ** 60   # p*2/3 a perfect square
+    loss = np.concatenate([decades, near, edges, squares, np.nextafter(squares, 0.0), np.nextafter(squares, 1.0)])
+    loss = np.resize(loss, 4096)
+    rtt = np.resize(np.concatenate([[0, 1, 2, 3, 10, 50, 100, 1000, 60000, 1 << 40],
+                                    (10.0 ** rng.uniform(0, 4.5, 500)).astype(np.uint64)]), 4096).astype(np.uint64)
+    return rtt, rng.permutation(loss)
+
+
+def sweep_batch(mode):
+    rtt, loss = sweep_values()
+    n = len(rtt)
+    rng = np.random.default_rng(43)
+    states, entries = fr.new_rate_states(n, 0xFFFFFFFF, 2)
+    states["mode"] = mode
+    states["send_rate"] = (10.0 ** rng.uniform(0, 9, n)).astype(np.uint32)
+    states["recv_count"], states["now_ms"] = 1, 1000
+    states["has_time_last_doubled"] = rng.integers(0, 2, n)
+    entries["value"], entries["timestamp_ms"] = 0xFFFFFFFF, 1000
+    if mode == E.THROUGHPUT_EQN:
+        states["has_rtt_s"], states["has_rtt_ms"] = 1, 1
+        states["rtt_s"] = rtt.astype(np.float64) / 1000.0
+        states["rtt_ms"] = rtt
+        states["prev_loss_rate"] = 2.0
+    ticks = np.zeros(n, dtype=fr.RATE_TICK_DTYPE)
+    ticks["now_ms"] = 1100
+    fq = np.zeros(n, dtype=fr.FRAME_QUEUE_RESULT_DTYPE)
+    fq["has_feedback"], fq["rtt_ms"], fq["receive_rate"], fq["loss_rate"] = 1, rtt, 0xFFFFFFFF, loss
+    none = np.zeros(0, dtype=np.uint32)
+    return {"states": states, "entries": entries, "ticks": ticks, "fq": fq, "flush_results": None, "result_index": none,
+            "flushes": None, "flush_index": none}
+
+
+def test_square_root_exactness_throughput_equation(engine):
+    """4096 connections in THROUGHPUT_EQN: eval_tcp_throughput's two square roots over swept (rtt_ms, loss_rate);
+    send_rate_tcp and send_rate equal the host's."""
+    b = sweep_batch(E.THROUGHPUT_EQN)
+    want = host_step(b, gather_in=False, gather_out=False)
+    got = device_step(engine, b, gather_in=False, gather_out=False)
+    assert (want["results"]["stop"] == fr.RATE_DONE).all()
+    assert len(np.unique(want["states_out"]["send_rate_tcp"])) > 1000
+    bad = np.nonzero(got["states_out"]["send_rate_tcp"] != want["states_out"]["send_rate_tcp"])[0]
+    assert len(bad) == 0, (len(bad), b["fq"][bad[:5]], got["states_out"]["send_rate_tcp"][bad[:5]],
+                           want["states_out"]["send_rate_tcp"][bad[:5]])
+    assert (got["results"]["send_rate"] == want["results"]["send_rate"]).all()
+    same(got["states_out"], want["states_out"], "states_out")
+    same(got["results"], want["results"], "results")
+
+
+def test_square_root_exactness_first_loss(engine):
+    """4096 first-loss transitions: the bisection over eval_tcp_throughput; the pending initial_p equal as 64 bits,
+    inv_iterations equal."""
+    b = sweep_batch(E.SLOW_START)
+    b["fq"]["loss_rate"] = np.where(b["fq"]["loss_rate"] > 0.0, b["fq"]["loss_rate"], 0.5)   # every one a loss increase
+    want = host_step(b, gather_in=False, gather_out=False)
+    got = device_step(engine, b, gather_in=False, gather_out=False)
+    entered = (want["results"]["flags"] & fr.RATE_ENTERED_EQN) != 0
+    assert entered.all() and (want["results"]["flags"] & fr.RATE_INV_STALLED != 0).sum() > 10
+    assert len(np.unique(want["states_out"]["reset_loss_rate"])) > 100
+    assert (got["states_out"]["reset_loss_rate"].view(np.uint64) == want["states_out"]["reset_loss_rate"].view(np.uint64)).all()
+    assert (got["results"]["inv_iterations"] == want["results"]["inv_iterations"]).all()
+    same(got["states_out"], want["states_out"], "states_out")
+    same(got["results"], want["results"], "results")
+
+
+# ---- the closed loop ----
+def loop_traffic(n, ticks, seed):
+    """Per tick and connection, generated up front: the sent frames of the last flush, the acks that arrived, the
+    rate tick.  Returns (queues, log, states, entries, [per-tick dict])."""
+    rng = np.random.default_rng(seed)
+    window = 16
+    queues, log = fr.new_frame_queues(n, window, window, 0)
+    states, entries = fr.new_rate_states(n, 300000, 24)
+    refs = [0]
+    peers = [Q.Peer(rng, window, 0, 0, refs) for _ in range(n)]
+    now = np.zeros(n, dtype=np.uint64)
+    last = [[] for _ in range(n)]
+    out = []
+    arr = lambda xs, dt: np.array(xs, dtype=dt) if xs else np.zeros(0, dtype=dt)
+    for t in range(ticks):
+        dt = rng.integers(5, 60, n)
+        quiet = rng.random(n) < 0.02
+        dt[quiet] += rng.integers(500, 5000, int(quiet.sum()))
+        now = now + dt.astype(np.uint64)
+        infos, items, sent, ff, sf = [], [], [], [0], [0]
+        rate_ticks = np.zeros(n, dtype=fr.RATE_TICK_DTYPE)
+        for c, p in enumerate(peers):
+            for base, groups in (p.acks(loss=0.05 if t % 50 < 40 else 0.4, frames=int(rng.integers(1, 3)), hostile=0.1)
+                                 if t else []):
+                infos.append(Q.ack_info(base, len(items), len(groups)))
+                items += [Q.group_item(*g) for g in groups]
+            sent += last[c]
+            ff.append(len(infos))
+            sf.append(len(sent))
+            rate_ticks[c] = E.make_tick(int(now[c]), float(dt[c]) / 1000.0, -sum(int(s["size"]) for s in last[c]),
+                                        fr.RATE_FRAME_SENT if last[c] else 0)
+            # the coming flush, stamped with this tick's time; only what the window takes goes out
+            p.now = int(now[c])
+            before = p.next_id
+            frames = p.send(int(rng.integers(0, 4)) if rng.random() < 0.9 else 0)
+            for s in frames:
+                s["send_time_ms"] = now[c]
+            last[c] = frames[:(p.next_id - before) & Q.M32]
+        out.append({"infos": arr(infos, fr.FRAME_INFO_DTYPE), "items": arr(items, fr.ITEM_DTYPE),
+                    "frame_first": np.array(ff, dtype=np.uint64), "sent": arr(sent, fr.SENT_FRAME_DTYPE),
+                    "sent_first": np.array(sf, dtype=np.uint64), "now": now.copy(), "ticks": rate_ticks,
+                    "extra": (rng.random(n) < 0.1).astype(np.uint32) * np.uint32(fr.FQ_MARK_RATE_LIMITED)})
+    return queues, log, states, entries, out
+
+
+def test_closed_loop_on_the_device(engine):
+    """130 connections, 200 ticks of begin -> frame_queue -> step on device tensors only: the acks and the sent frames
+    are uploaded up front, every tick's results stay on the device, and nothing is read back until the end.  The
+    final states, logs, entries, flushes and every tick's results equal the host calls' run of the same ticks."""
+    n, ticks = 130, 200
+    queues, log, states, entries, traffic = loop_traffic(n, ticks, 9)
+    flush_index = np.arange(n, dtype=np.uint32)[::-1].copy()
+    flushes = np.zeros(n, dtype=fr.FLUSH_DTYPE)
+    flushes["kind"], flushes["id1"] = 1, 77
+    # the host calls
+    h_q, h_log, h_s, h_e, h_fl = queues.copy(), log.copy(), states.copy(), entries.copy(), flushes.copy()
+    h_fq, h_rate = [], []
+    for tr in traffic:
+        opened = fr.rate_begin_host(h_s, tr["now"], tr["extra"], nthreads=16)
+        fq = fr.frame_queue_host(tr["infos"], tr["items"], tr["frame_first"], tr["sent"], tr["sent_first"], h_q,
+                                 opened["steps"], h_log, nthreads=16)
+        closed = fr.rate_step_host(opened["states_out"], tr["ticks"], fq["results"], h_e, flushes=h_fl,
+                                   flush_index=flush_index, nthreads=16)
+        h_q, h_s = fq["queues_out"], closed["states_out"]
+        h_fq.append(fq["results"])
+        h_rate.append(closed["results"])
+    flags = np.bitwise_or.reduce(np.concatenate(h_rate)["flags"])
+    assert flags & 15 == 15 and (np.concatenate(h_rate)["stop"] == fr.RATE_DONE).all()
+    assert (np.concatenate(h_fq)["stop"] == fr.FQ_DONE).all()
+    # the device: everything uploaded first, then 600 calls queued, then one synchronize
+    up = [{"infos": _t(tr["infos"], 32), "items": _t(tr["items"], 24), "frame_first": _t(tr["frame_first"]),
+           "sent": _t(tr["sent"], 24), "sent_first": _t(tr["sent_first"]), "now": _t(tr["now"]),
+           "ticks": _t(tr["ticks"], 32), "extra": _t(tr["extra"])} for tr in traffic]
+    d_q, d_log, d_s, d_e = _t(queues, 192), _t(log, 24), _t(states, 112), _t(entries, 16)
+    d_fl, d_fi = _t(flushes, 24), _t(flush_index)
+    d_steps = torch.zeros((n, 40), dtype=torch.uint8, device=DEV)
+    d_fq = torch.zeros((ticks, n, 80), dtype=torch.uint8, device=DEV)
+    d_rate = torch.zeros((ticks, n, 56), dtype=torch.uint8, device=DEV)
+    torch.cuda.synchronize()
+    for t, u in enumerate(up):
+        engine.rate_begin(d_s, u["now"], u["extra"], steps=d_steps, states_out=d_s)
+        fq = engine.frame_queue(u["infos"], u["items"], u["frame_first"], u["sent"], u["sent_first"], d_q, d_steps, d_log,
+                                queues_out=d_q)
+        d_fq[t].copy_(fq["results"])
+        engine.rate_step(d_s, u["ticks"], d_fq[t], d_e, flushes=d_fl, flush_index=d_fi, results=d_rate[t], states_out=d_s)
+    torch.cuda.synchronize()
+    same(_back(d_s, fr.RATE_STATE_DTYPE), h_s, "states")
+    same(_back(d_q, fr.FRAME_QUEUE_DTYPE), h_q, "queues")
+    same(_back(d_log, fr.SENT_FRAME_DTYPE), h_log, "log")
+    same(_back(d_e, fr.RECV_RATE_ENTRY_DTYPE), h_e, "entries")
+    same(_back(d_fl, fr.FLUSH_DTYPE), h_fl, "flushes")
+    same(_back(d_fq, fr.FRAME_QUEUE_RESULT_DTYPE), np.concatenate(h_fq), "frame queue results")
+    same(_back(d_rate, fr.RATE_RESULT_DTYPE), np.concatenate(h_rate), "rate results")
+
+
+def test_argument_checks(engine):
+    states, entries = fr.new_rate_states(2, 1000, 2)
+    s, e = _t(states, 112), _t(entries, 16)
+    tk, fq = torch.zeros((2, 32), dtype=torch.uint8, device=DEV), torch.zeros((2, 80), dtype=torch.uint8, device=DEV)
+    with pytest.raises(ValueError):
+        engine.rate_step(s, tk[:1], fq, e)
+    with pytest.raises(ValueError):
+        engine.rate_step(s, tk, fq, e, flushes=torch.zeros((1, 24), dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        engine.rate_step(s, tk, fq, e, results=torch.zeros(10, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        engine.rate_begin(s, torch.zeros(1, dtype=torch.int64, device=DEV))
+    V = ctypes.c_void_p
+    st = V(torch.cuda.current_stream().cuda_stream)
+    L = fr.lib()
+    p = lambda t: V(t.data_ptr())
+    res = torch.zeros((2, 56), dtype=torch.uint8, device=DEV)
+    assert L.ufc_rate_step_varlen(None, p(s), p(tk), p(fq), 2, p(e), 4, None, 0, None, None, 0, None, p(res), p(s), st) != 0
+    assert L.ufc_rate_step_varlen(engine._ctx, None, None, None, 0, None, 0, None, 0, None, None, 0, None, None, None, st) == 0
+    assert L.ufc_rate_step_varlen(engine._ctx, p(s), p(tk), p(fq), 2, p(e), 4, None, 0, None, None, 0, None, None, p(s), st) != 0
+    assert L.ufc_rate_step_varlen(engine._ctx, p(s), p(tk), p(fq), 2, p(e), 4, p(res), 1, None, None, 0, None, p(res), p(s), st) != 0
+    assert L.ufc_rate_begin_varlen(engine._ctx, p(s), None, None, 2, p(res), p(s), st) != 0
+    assert L.ufc_rate_begin_varlen(engine._ctx, None, None, None, 0, None, None, st) == 0
+    d = engine.rate_step(s[:0], tk[:0], fq[:0], e)
+    assert d["results"].shape[0] == 0
+    torch.cuda.synchronize()

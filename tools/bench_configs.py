@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,queue,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,queue,rate,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -35,6 +35,10 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            (ufc_frame_queue_varlen): 1M synthesized ack frames over filled logs, as 250,000 connections and as 2,048;
            the call and ufc_frame_queue_host with 1 and 16 threads; one line per grouping, also written to
            profiles/queue_configs.jsonl.  Run with --only queue.
+  rate     the send rate control behind the frame queue on the device (ufc_rate_step_varlen): one tick of 250,000
+           and of 2,048 connections in a mix of modes, most with feedback; the call, ufc_rate_step_host with 1 and 16
+           threads and a device-to-device copy of the bytes the call reads and writes; one line per grouping, also
+           written to profiles/rate_configs.jsonl.  Run with --only rate.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -911,6 +915,152 @@ def queue(eng, dev, reps, n=1_000_000):
     return out
 
 
+RATE_OUT = os.path.join(REPO, "profiles", "rate_configs.jsonl")
+
+
+def rate(eng, dev, reps, n=None):
+    """The step that closes a sender's tick: ufc_rate_step_varlen for 250,000 and for 2,048 connections (the frame
+    queue's groupings).  5 % of the connections await their first send, 25 % are in slow start (half of them before
+    their first feedback), 70 % in the throughput equation; 90 % have feedback this tick (30 % of it rate limited;
+    in the throughput equation half of it with a higher loss rate, in slow start 5 % with a first loss and so a
+    bisection), a few timers have expired; the sets hold 1 to 4 entries in rooms of 8; both
+    flush gathers are used.  The call updates the entries in place, so they are restored from a pristine copy before
+    every call, outside the timed span: an event pair around each call on the device, wall clock around each call on
+    the host (1 and 16 threads, median of 3).  The floor is one device-to-device copy of (bytes read + bytes written)
+    / 2 bytes, which reads and writes as much as the call does: per connection the state in and out, the tick, the
+    frame queue result, the rate result, two indices, a flush result and a flush_alloc, and the entries read (every
+    entry of a connection that looks at its set) and written (one per feedback).  Per grouping one JSON line, also
+    written to profiles/rate_configs.jsonl, with every output of the GPU call against the host's."""
+    import ctypes
+    from uflow_amd import _native as N
+    from uflow_amd.frame import (FLUSH_DTYPE, FLUSH_RESULT_DTYPE, FRAME_QUEUE_RESULT_DTYPE, RATE_RESULT_DTYPE,
+                                 RATE_STATE_DTYPE, RATE_TICK_DTYPE, new_rate_states)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    c = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, ctx = N.lib(), eng._ctx
+    out = []
+    for name, nq in (("250,000", 250_000), ("2,048", 2048)):
+        rng = np.random.default_rng(13)
+        cap, now = 8, 100_000
+        states, entries = new_rate_states(nq, 0xFFFFFFFF, cap)
+        u = rng.random(nq)
+        mode = np.where(u < 0.05, 0, np.where(u < 0.30, 1, 2)).astype(np.uint32)
+        fresh = (mode == 1) & (rng.random(nq) < 0.5)                     # slow start before the first feedback
+        live = (mode != 0) & ~fresh
+        states["mode"] = mode
+        states["send_rate"] = np.where(mode == 0, 1472, (10.0 ** rng.uniform(3, 7, nq))).astype(np.uint32)
+        states["send_rate_tcp"] = np.where(mode == 2, states["send_rate"], 0)
+        states["has_time_last_doubled"] = live & (mode == 1)
+        states["time_last_doubled_ms"] = np.where(live & (mode == 1), now - rng.integers(0, 300, nq), 0)
+        states["has_nofeedback_exp"] = mode != 0
+        states["nofeedback_exp_ms"] = np.where(mode != 0, now + rng.integers(-100, 2000, nq), 0)
+        states["nofeedback_idle"] = live & (rng.random(nq) < 0.5)
+        rtt = rng.uniform(0.01, 0.3, nq)
+        for k in ("has_rtt_s", "has_rtt_ms", "has_rto_ms"):
+            states[k] = live
+        states["rtt_s"] = np.where(live, rtt, 0.0)
+        states["rtt_ms"] = np.where(live, np.round(rtt * 1000), 0).astype(np.uint64)
+        states["rto_ms"] = np.where(live, np.round(rtt * 4000), 0).astype(np.uint64)
+        states["prev_loss_rate"] = np.where(live, rng.uniform(0, 0.05, nq), 0.0)
+        states["now_ms"], states["has_last_flush"] = now, 1
+        states["flush_alloc"] = rng.integers(-1500, 20000, nq)
+        count = np.where(mode == 0, 0, np.where(fresh, 1, rng.integers(1, 5, nq))).astype(np.uint32)
+        states["recv_count"] = count
+        entries["timestamp_ms"] = now - rng.integers(0, 300, nq * cap)
+        entries["value"] = (10.0 ** rng.uniform(3, 7, nq * cap)).astype(np.uint32)
+        first = np.arange(nq) * cap
+        entries["value"][first[fresh]], entries["is_initial"][first[fresh]] = 0xFFFFFFFF, 1
+        ticks = np.zeros(nq, dtype=RATE_TICK_DTYPE)
+        ticks["now_ms"], ticks["delta_time_s"] = now + 20, 0.02
+        ticks["alloc_adjust"] = -rng.integers(0, 64, nq)
+        fq = np.zeros(nq, dtype=FRAME_QUEUE_RESULT_DTYPE)
+        fb = rng.random(nq) < 0.9
+        fq["has_feedback"] = fb
+        fq["rtt_ms"] = np.where(fb, rng.integers(10, 300, nq), 0)
+        fq["receive_rate"] = np.where(fb, (10.0 ** rng.uniform(3, 7, nq)), 0).astype(np.uint32)
+        fq["loss_rate"] = np.where(fb & ((mode == 2) | (rng.random(nq) < 0.05)), rng.uniform(0, 0.05, nq), 0.0)
+        fq["rate_limited"] = fb & (rng.random(nq) < 0.3)
+        fres = np.zeros(nq, dtype=FLUSH_RESULT_DTYPE)
+        fres["frame_count"] = rng.integers(0, 3, nq)
+        fres["alloc_left"] = rng.integers(-1500, 20000, nq)
+        ri = rng.permutation(nq).astype(np.uint32)
+        flushes = np.zeros(nq, dtype=FLUSH_DTYPE)
+        fi = np.arange(nq, dtype=np.uint32)
+        h = {"entries": entries.copy(), "res": np.zeros(nq, dtype=RATE_RESULT_DTYPE), "out": np.zeros(nq, dtype=RATE_STATE_DTYPE),
+             "flushes": flushes.copy()}
+        h_call = lambda T: lib.ufc_rate_step_host(  # noqa: E731
+            c(states), c(ticks), c(fq), nq, c(h["entries"]), h["entries"].size, c(fres), nq, c(ri), c(h["flushes"]), nq, c(fi),
+            c(h["res"]), c(h["out"]), T)
+        host_ms = {}
+        for T in (1, 16):
+            ts = []
+            for _ in range(3):
+                np.copyto(h["entries"], entries)
+                t0 = time.perf_counter()
+                assert h_call(T) == 0
+                ts.append(time.perf_counter() - t0)
+            host_ms[T] = float(np.median(ts)) * 1e3
+        res = h["res"]
+        fed = (res["flags"] & N.UFC_RATE_FEEDBACK) != 0
+        looked = fed | ((res["flags"] & N.UFC_RATE_NOFEEDBACK) != 0) & (mode == 2)
+        read = nq * (112 + 32 + 80 + 4 + 24 + 4) + 16 * int(count[looked].sum())
+        written = nq * (112 + 56 + 8) + 16 * int(fed.sum())
+        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a.view(np.int32)).to(dev)  # noqa: E731
+        g = {"states": t(states, 112), "ticks": t(ticks, 32), "fq": t(fq, 80), "entries0": t(entries, 16),
+             "entries": t(entries, 16), "fres": t(fres, 24), "ri": t(ri), "flushes": t(flushes, 24), "fi": t(fi),
+             "res": torch.zeros((nq, 56), dtype=torch.uint8, device=dev), "out": torch.zeros((nq, 112), dtype=torch.uint8, device=dev),
+             "src": torch.zeros((read + written) // 2, dtype=torch.uint8, device=dev),
+             "dst": torch.zeros((read + written) // 2, dtype=torch.uint8, device=dev)}
+        restore = lambda: g["entries"].copy_(g["entries0"])  # noqa: E731
+        f_rate = lambda: lib.ufc_rate_step_varlen(  # noqa: E731
+            ctx, p(g["states"]), p(g["ticks"]), p(g["fq"]), nq, p(g["entries"]), g["entries"].shape[0], p(g["fres"]), nq,
+            p(g["ri"]), p(g["flushes"]), nq, p(g["fi"]), p(g["res"]), p(g["out"]), st)
+        restore()
+        assert f_rate() == 0
+        torch.cuda.synchronize()
+        extra = {}
+        if CHECK:
+            same = lambda a, b: bool(np.array_equal(a.cpu().numpy().reshape(-1), b.view(np.uint8).reshape(-1)))  # noqa: E731
+            extra["equals_host"] = (same(g["res"], h["res"]) and same(g["out"], h["out"]) and same(g["entries"], h["entries"])
+                                    and same(g["flushes"], h["flushes"]))
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.5:                             # (out of idle clocks)
+            restore()
+            f_rate()
+            g["dst"].copy_(g["src"])
+            torch.cuda.synchronize()
+        s = torch.cuda.current_stream()
+        timed = {}
+        for what, f in (("rate", f_rate), ("copy", lambda: g["dst"].copy_(g["src"]))):
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for e0, e1 in evs:
+                restore()
+                e0.record(s)
+                f()
+                e1.record(s)
+            torch.cuda.synchronize()
+            timed[what] = [a.elapsed_time(b) for a, b in evs]
+        med, mean, copy = float(np.median(timed["rate"])), float(np.mean(timed["rate"])), float(np.median(timed["copy"]))
+        out.append({"config": f"f10: device send rate step of one tick, {name} connections (rooms of {cap} entries)",
+                    "connections": nq, "feedbacks": int(fed.sum()),
+                    "nofeedback": int(((res["flags"] & N.UFC_RATE_NOFEEDBACK) != 0).sum()),
+                    "resets": int(((res["flags"] & N.UFC_RATE_RESET_ISSUED) != 0).sum()),
+                    "inv_iterations": int(res["inv_iterations"].sum()), "stopped": int((res["stop"] != 0).sum()),
+                    "bytes_read": read, "bytes_written": written,
+                    "rate_ms": round(med, 4), "rate_mean_ms": round(mean, 4), "ns_per_connection": round(med * 1e6 / nq, 3),
+                    "copy_ms": round(copy, 4), "rate_over_copy": round(med / copy, 2),
+                    "host_1t_ms": round(host_ms[1], 3), "host_16t_ms": round(host_ms[16], 3),
+                    "host_1t_over_gpu": round(host_ms[1] / med, 1), "host_16t_over_gpu": round(host_ms[16] / med, 1),
+                    "timing": "an event pair around each call, the entries restored in front of it", **extra})
+        del g
+        torch.cuda.empty_cache()
+    with open(RATE_OUT, "w") as f:
+        for r in out:
+            f.write(json.dumps(r) + "\n")
+    return out
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -960,7 +1110,7 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what in ("pack", "emit", "receive", "window", "queue"):
+        elif what in ("pack", "emit", "receive", "window", "queue", "rate"):
             for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:

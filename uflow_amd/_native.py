@@ -57,6 +57,11 @@ UFC_FW_DONE, UFC_FW_BAD_STATE = 0, 1
 UFC_SENT_NONCE, UFC_SENT_RATE_LIMITED, UFC_SENT_ACKED, UFC_SENT_MARK = 1, 2, 4, 8
 UFC_FQ_HAS_RTT, UFC_FQ_RESET_LOSS, UFC_FQ_MARK_RATE_LIMITED, UFC_FQ_FORGET, UFC_FQ_FEEDBACK = 1, 2, 4, 8, 16
 UFC_FQ_DONE, UFC_FQ_BAD_STATE = 0, 1
+# the batched send rate control (include/uflow_frame_codec.h): modes, the tick's flag, stops, the result's flags
+UFC_RATE_AWAIT_SEND, UFC_RATE_SLOW_START, UFC_RATE_THROUGHPUT_EQN = 0, 1, 2
+UFC_RATE_FRAME_SENT = 1
+UFC_RATE_DONE, UFC_RATE_BAD_STATE, UFC_RATE_REF_PANIC, UFC_RATE_RECV_FULL = 0, 1, 2, 3
+UFC_RATE_FEEDBACK, UFC_RATE_NOFEEDBACK, UFC_RATE_RESET_ISSUED, UFC_RATE_ENTERED_EQN, UFC_RATE_INV_STALLED = 1, 2, 4, 8, 16
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -65,6 +70,8 @@ _RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, 
             _V, _V, _V]
 _FW_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V]
 _FQ_ARGS = [_V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V]
+_RATE_BEGIN_ARGS = [_V, _V, _V, _Z, _V, _V]
+_RATE_STEP_ARGS = [_V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -184,6 +191,13 @@ _SIGNATURES = {
     # ref_acked, refs_cap, results, queues_out, then nthreads (host) / ctx first and stream last (device)
     "ufc_frame_queue_host": (ctypes.c_int, _FQ_ARGS + [ctypes.c_int]),
     "ufc_frame_queue_varlen": (ctypes.c_int, [ctypes.c_void_p] + _FQ_ARGS + [ctypes.c_void_p]),
+    # states, now_ms, extra_flags, n, steps, states_out, then nthreads (host) / ctx first and stream last (device)
+    "ufc_rate_begin_host": (ctypes.c_int, _RATE_BEGIN_ARGS + [ctypes.c_int]),
+    "ufc_rate_begin_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RATE_BEGIN_ARGS + [ctypes.c_void_p]),
+    # states, ticks, fq, n, entries, n_entries, flush_results, n_flush_results, result_index, flushes, n_flushes,
+    # flush_index, results, states_out, then nthreads (host) / ctx first and stream last (device)
+    "ufc_rate_step_host": (ctypes.c_int, _RATE_STEP_ARGS + [ctypes.c_int]),
+    "ufc_rate_step_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RATE_STEP_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -306,6 +320,36 @@ class FrameQueueResult(ctypes.Structure):
                 ("window_advanced", ctypes.c_uint32), ("log_culled", ctypes.c_uint32), ("window_room", ctypes.c_uint32),
                 ("has_feedback", ctypes.c_uint8), ("rate_limited", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
                 ("receive_rate", ctypes.c_uint32), ("rtt_ms", ctypes.c_uint64), ("loss_rate", ctypes.c_double)]
+
+
+class RecvRateEntry(ctypes.Structure):
+    _fields_ = [("timestamp_ms", ctypes.c_uint64), ("value", ctypes.c_uint32), ("is_initial", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 3)]
+
+
+class RateState(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("send_rate", ctypes.c_uint32), ("max_send_rate", ctypes.c_uint32),
+                ("send_rate_tcp", ctypes.c_uint32), ("has_time_last_doubled", ctypes.c_uint8),
+                ("has_nofeedback_exp", ctypes.c_uint8), ("nofeedback_idle", ctypes.c_uint8),
+                ("has_rtt_s", ctypes.c_uint8), ("has_rtt_ms", ctypes.c_uint8), ("has_rto_ms", ctypes.c_uint8),
+                ("has_last_flush", ctypes.c_uint8), ("has_reset", ctypes.c_uint8),
+                ("time_last_doubled_ms", ctypes.c_uint64), ("prev_loss_rate", ctypes.c_double),
+                ("nofeedback_exp_ms", ctypes.c_uint64), ("rtt_s", ctypes.c_double), ("rtt_ms", ctypes.c_uint64),
+                ("rto_ms", ctypes.c_uint64), ("now_ms", ctypes.c_uint64), ("flush_alloc", ctypes.c_int64),
+                ("reset_loss_rate", ctypes.c_double), ("recv_first", ctypes.c_uint64),
+                ("recv_count", ctypes.c_uint32), ("recv_cap", ctypes.c_uint32)]
+
+
+class RateTick(ctypes.Structure):
+    _fields_ = [("now_ms", ctypes.c_uint64), ("delta_time_s", ctypes.c_double), ("alloc_adjust", ctypes.c_int64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class RateResult(ctypes.Structure):
+    _fields_ = [("stop", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("now_ms", ctypes.c_uint64),
+                ("rtt_ms", ctypes.c_uint64), ("rto_ms", ctypes.c_uint64), ("flush_alloc", ctypes.c_int64),
+                ("send_rate", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("inv_iterations", ctypes.c_uint32),
+                ("recv_count", ctypes.c_uint32)]
 
 
 class Builder(ctypes.Structure):

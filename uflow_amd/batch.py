@@ -476,6 +476,67 @@ class FrameCrcEngine:
                                            self._stream(stream)), "ufc_frame_queue_varlen")
         return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
 
+    # ---- the send rate control around the frame queue call, on the device (uflow_frame_codec.h) ----
+    def rate_begin(self, states, now_ms, extra_flags=None, steps=None, states_out=None, stream=None):
+        """ufc_rate_begin_varlen: opens a tick.  states uint8[n, 112] (RATE_STATE_DTYPE records), now_ms int64[n],
+        extra_flags int32[n] or None (OR-ed into the steps' flags: FQ_MARK_RATE_LIMITED).  Returns a dict of device
+        tensors: steps uint8[n, 40] (what frame_queue takes), states_out uint8[n, 112] (may be given as `states`)."""
+        n = states.shape[0]
+        self._check("states", states, (torch.uint8,), 112 * n)
+        self._check("now_ms", now_ms, (torch.int64, torch.uint64), n)
+        self._check("extra_flags", extra_flags, (torch.int32, torch.uint32), n)
+        self._check("steps", steps, (torch.uint8,), 40 * n)
+        self._check("states_out", states_out, (torch.uint8,), 112 * n)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if steps is None:
+                steps = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
+            if states_out is None:
+                states_out = torch.zeros((n, 112), dtype=torch.uint8, device=self.device)
+        check(lib().ufc_rate_begin_varlen(self._ctx, _ptr(states) if n else None, _ptr(now_ms) if n else None,
+                                          _ptr(extra_flags) if n else None, n, _ptr(steps) if n else None,
+                                          _ptr(states_out) if n else None, self._stream(stream)),
+              "ufc_rate_begin_varlen")
+        return {"steps": steps, "states_out": states_out}
+
+    def rate_step(self, states, ticks, fq_results, entries, flush_results=None, result_index=None, flushes=None,
+                  flush_index=None, results=None, states_out=None, stream=None):
+        """ufc_rate_step_varlen: closes a tick behind frame_queue (notify_frame_sent, fill_flush_alloc and
+        SendRateComp::step; src/half_connection/send_rate.rs, recv_rate_set.rs, mod.rs:165-215) for every connection.
+        states uint8[n, 112], ticks uint8[n, 32], fq_results uint8[n, 80] (frame_queue's results), entries
+        uint8[n_entries, 16] (the receive-rate sets, updated in place); flush_results uint8[m, 24] with result_index
+        int32[n] (the last data flush of each connection, -1 for none) and flushes uint8[k, 24] with flush_index
+        int32[n] (where the new flush_alloc goes, in place) are optional.  Returns a dict of device tensors: results
+        uint8[n, 56], states_out uint8[n, 112] (may be given as `states`), entries, flushes.  The record layouts are
+        uflow_amd.frame's RATE_STATE_DTYPE, RATE_TICK_DTYPE, RATE_RESULT_DTYPE and RECV_RATE_ENTRY_DTYPE."""
+        n, n_entries = states.shape[0], entries.shape[0]
+        n_fr = flush_results.shape[0] if flush_results is not None else 0
+        n_fl = flushes.shape[0] if flushes is not None else 0
+        if (n_fr and result_index is None) or (n_fl and flush_index is None):
+            raise ValueError("flush_results needs result_index, flushes needs flush_index")
+        self._check("states", states, (torch.uint8,), 112 * n)
+        self._check("ticks", ticks, (torch.uint8,), 32 * n)
+        self._check("fq_results", fq_results, (torch.uint8,), 80 * n)
+        self._check("entries", entries, (torch.uint8,), 16 * n_entries)
+        self._check("flush_results", flush_results, (torch.uint8,), 24 * n_fr)
+        self._check("result_index", result_index, (torch.int32, torch.uint32), n)
+        self._check("flushes", flushes, (torch.uint8,), 24 * n_fl)
+        self._check("flush_index", flush_index, (torch.int32, torch.uint32), n)
+        self._check("results", results, (torch.uint8,), 56 * n)
+        self._check("states_out", states_out, (torch.uint8,), 112 * n)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if results is None:
+                results = torch.zeros((n, 56), dtype=torch.uint8, device=self.device)
+            if states_out is None:
+                states_out = torch.zeros((n, 112), dtype=torch.uint8, device=self.device)
+        check(lib().ufc_rate_step_varlen(self._ctx, _ptr(states) if n else None, _ptr(ticks) if n else None,
+                                         _ptr(fq_results) if n else None, n, _ptr(entries) if n_entries else None,
+                                         n_entries, _ptr(flush_results) if n_fr else None, n_fr,
+                                         _ptr(result_index) if n_fr else None, _ptr(flushes) if n_fl else None, n_fl,
+                                         _ptr(flush_index) if n_fl else None, _ptr(results) if n else None,
+                                         _ptr(states_out) if n else None, self._stream(stream)),
+              "ufc_rate_step_varlen")
+        return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

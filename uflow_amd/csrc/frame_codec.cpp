@@ -715,4 +715,44 @@ int ufc_frame_queue_host(const ufc_frame_info* infos, size_t n_frames, const ufc
   return UFC_OK;
 }
 
+// ---- batched host send rate control ----
+int ufc_rate_begin_host(const ufc_rate_state* states, const uint64_t* now_ms, const uint32_t* extra_flags, size_t n,
+                        ufc_frame_queue_step* steps, ufc_rate_state* states_out, int nthreads) {
+  if (n == 0) return UFC_OK;
+  if (!states || !now_ms || !steps || !states_out || n >= ((size_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
+  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t c = lo; c < hi; c++) {
+      ufc_rate_state S = states[c];
+      ufc_frame_queue_step Q;
+      ufc_codec::rate_begin(S, now_ms[c], extra_flags ? extra_flags[c] : 0, Q);
+      steps[c] = Q;
+      states_out[c] = S;
+    }
+  });
+  return UFC_OK;
+}
+
+int ufc_rate_step_host(const ufc_rate_state* states, const ufc_rate_tick* ticks, const ufc_frame_queue_result* fq,
+                       size_t n, ufc_recv_rate_entry* entries, size_t n_entries, const ufc_flush_result* flush_results,
+                       size_t n_flush_results, const uint32_t* result_index, ufc_flush* flushes, size_t n_flushes,
+                       const uint32_t* flush_index, ufc_rate_result* results, ufc_rate_state* states_out, int nthreads) {
+  if (n == 0) return UFC_OK;
+  if (!states || !ticks || !fq || !results || !states_out || (!entries && n_entries) ||
+      (flush_results && !result_index) || (flushes && !flush_index) || n >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RateArgs a{states, ticks, fq, n, entries, n_entries, flush_results, n_flush_results, result_index,
+                              flushes, n_flushes, flush_index, results, states_out};
+  // The step the device gives a lane; a connection touches its own records, its own entries and its own flush.
+  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t c = lo; c < hi; c++) {
+      ufc_rate_state S = states[c];
+      ufc_rate_result R;
+      ufc_codec::rate_step(a, c, S, ticks[c], fq[c], R);
+      results[c] = R;
+      states_out[c] = S;
+    }
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

@@ -2178,4 +2178,438 @@ struct FqHostWave {
   }
 };
 
+// ---- batched send rate control (ufc_rate_begin_*, ufc_rate_step_*) ----
+// SendRateComp and RecvRateSet (src/half_connection/send_rate.rs, recv_rate_set.rs) with HalfConnection's
+// fill_flush_alloc, one connection per call of rate_step: the host entry loops over it, the kernel gives it a lane.
+// Every float operation is written out one per statement under fp contract(off), so host and device round alike.
+struct RateArgs {
+  const ufc_rate_state* states;
+  const ufc_rate_tick* ticks;
+  const ufc_frame_queue_result* fq;
+  size_t n;
+  ufc_recv_rate_entry* entries;
+  size_t n_entries;
+  const ufc_flush_result* flush_results;
+  size_t n_flush_results;
+  const uint32_t* result_index;
+  ufc_flush* flushes;
+  size_t n_flushes;
+  const uint32_t* flush_index;
+  ufc_rate_result* results;
+  ufc_rate_state* states_out;
+};
+struct RateBeginArgs {
+  const ufc_rate_state* states;
+  const uint64_t* now_ms;
+  const uint32_t* extra_flags;
+  size_t n;
+  ufc_frame_queue_step* steps;
+  ufc_rate_state* states_out;
+};
+
+constexpr uint32_t kRateMinimum = UFC_MAX_FRAME_SIZE / 64;  // MINIMUM_RATE
+constexpr uint32_t kRateInitialWindow = 4380;               // INITIAL_TCP_WINDOW
+
+// Rust's float casts: saturating, NaN gives 0.
+UFC_HD uint32_t rate_f64_u32(double v) {
+  if (!(v > 0.0)) return 0;
+  if (v >= 4294967296.0) return 0xFFFFFFFFu;
+  return (uint32_t)v;
+}
+UFC_HD uint64_t rate_f64_u64(double v) {
+  if (!(v > 0.0)) return 0;
+  if (v >= 18446744073709551616.0) return ~0ull;
+  return (uint64_t)v;
+}
+UFC_HD int64_t rate_f64_i64(double v) {
+  if (v != v) return 0;
+  if (v >= 9223372036854775808.0) return INT64_MAX;
+  if (v <= -9223372036854775808.0) return INT64_MIN;
+  return (int64_t)v;
+}
+// f64::round: half away from zero.  v - t is exact, so no second rounding enters.
+UFC_HD double rate_round(double v) {
+#pragma clang fp contract(off)
+  const double t = __builtin_trunc(v);
+  const double d = v - t;
+  if (d >= 0.5) return t + 1.0;
+  if (d <= -0.5) return t - 1.0;
+  return t;  // (an infinity or a NaN gives d = NaN and comes back as it is)
+}
+// f64::max: a NaN operand gives the other one.
+UFC_HD double rate_max(double x, double y) {
+  if (x != x) return y;
+  if (y != y) return x;
+  return x > y ? x : y;
+}
+UFC_HD uint32_t rate_min_u32(uint32_t x, uint32_t y) { return x < y ? x : y; }
+UFC_HD uint32_t rate_max_u32(uint32_t x, uint32_t y) { return x > y ? x : y; }
+UFC_HD uint32_t rate_sat_mul2(uint32_t v) { return v > 0x7FFFFFFFu ? 0xFFFFFFFFu : 2 * v; }
+UFC_HD uint64_t rate_s_to_ms(double v_s) {  // send_rate.rs:16-18
+#pragma clang fp contract(off)
+  const double ms = v_s * 1000.0;
+  return rate_f64_u64(rate_round(rate_max(ms, 0.0)));
+}
+UFC_HD uint32_t rate_initial_send_rate(double rtt_s) {  // :110-112
+#pragma clang fp contract(off)
+  const double v = (double)kRateInitialWindow / rtt_s;
+  return rate_f64_u32(v);
+}
+UFC_HD uint32_t rate_tcp_throughput(double rtt, double p) {  // :24-28
+#pragma clang fp contract(off)
+  const double s = (double)UFC_MAX_FRAME_SIZE;
+  const double p2 = p * 2.0;
+  const double q0 = p2 / 3.0;
+  const double r0 = __builtin_sqrt(q0);
+  const double p3 = p * 3.0;
+  const double q1 = p3 / 8.0;
+  const double r1 = __builtin_sqrt(q1);
+  const double t0 = 12.0 * r1;
+  const double t1 = t0 * p;
+  const double u0 = 32.0 * p;
+  const double u1 = u0 * p;
+  const double u2 = 1.0 + u1;
+  const double t2 = t1 * u2;
+  const double f_p = r0 + t2;
+  const double den = rtt * f_p;
+  const double v = s / den;
+  return rate_f64_u32(v);
+}
+// eval_tcp_throughput_inv (:30-59) with the stall rule of the header: a midpoint equal to an end of the interval
+// is returned where the reference would go round for ever.
+UFC_HD double rate_tcp_throughput_inv(double rtt, uint32_t target, uint32_t& iterations, bool& stalled) {
+#pragma clang fp contract(off)
+  const double d = (double)target * 0.05;
+  const uint32_t delta = rate_f64_u32(d);
+  double a = 0.0, b = 1.0;
+  iterations = 0;
+  stalled = false;
+  for (;;) {
+    const double sum = b + a;
+    const double c = sum / 2.0;
+    const uint32_t rate = rate_tcp_throughput(rtt, c);
+    iterations++;
+    if (rate > target) {
+      if (rate - target <= delta) return c;
+    } else if (rate < target) {
+      if (target - rate <= delta) return c;
+    } else {
+      return c;
+    }
+    if (c == a || c == b) {  // (a, b and c are never negative or NaN: equal values are equal bits)
+      stalled = true;
+      return c;
+    }
+    if (rate > target)
+      a = c;
+    else
+      b = c;
+  }
+}
+UFC_HD double rate_update_rto(ufc_rate_state& S, double rtt_s, uint32_t send_rate) {  // :381-386
+#pragma clang fp contract(off)
+  const double x = 4.0 * rtt_s;
+  const double y = (double)(2 * UFC_MAX_FRAME_SIZE) / (double)send_rate;
+  const double rto_s = rate_max(x, y);
+  S.has_rto_ms = 1;
+  S.rto_ms = rate_s_to_ms(rto_s);
+  return rto_s;
+}
+UFC_HD ufc_recv_rate_entry rate_entry(uint64_t t, uint32_t value, bool initial) {
+  ufc_recv_rate_entry e;
+  e.timestamp_ms = t;
+  e.value = value;
+  e.is_initial = initial ? 1 : 0;
+  e.reserved[0] = e.reserved[1] = e.reserved[2] = 0;
+  return e;
+}
+
+// The set a step works on: the connection's entries as they lie in the arena, or the single entry a reset put in
+// their place earlier in the same step.  What the step leaves behind is described, not stored, until it commits.
+// The first kRateHeld entries are loaded together when the step begins, so that the loops over the set do not wait
+// for one load after the other (a lane has nothing else to hide them behind); longer sets go on from memory.
+constexpr uint32_t kRateHeld = 4;
+struct RateSet {
+  const ufc_recv_rate_entry* base;
+  uint32_t count;
+  bool single;
+  ufc_recv_rate_entry e0;
+  uint64_t held_t[kRateHeld];
+  uint32_t held_v[kRateHeld];
+  bool held_i[kRateHeld];
+  UFC_HD void load() {
+#pragma unroll
+    for (uint32_t k = 0; k < kRateHeld; k++)
+      if (k < count) {
+        held_t[k] = base[k].timestamp_ms;
+        held_v[k] = base[k].value;
+        held_i[k] = base[k].is_initial != 0;
+      }
+  }
+  UFC_HD uint32_t size() const { return single ? 1u : count; }
+  // f(timestamp_ms, value, is_initial) for every entry in Vec order.  f may store into the arena at or before the
+  // entry it is given.
+  template <class F>
+  UFC_HD void each(const F& f) const {
+    if (single) {
+      f(e0.timestamp_ms, e0.value, e0.is_initial != 0);
+      return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kRateHeld; k++)
+      if (k < count) f(held_t[k], held_v[k], held_i[k]);
+    for (uint32_t k = kRateHeld; k < count; k++) f(base[k].timestamp_ms, base[k].value, base[k].is_initial != 0);
+  }
+  UFC_HD void reset(const ufc_recv_rate_entry& e) {
+    single = true;
+    e0 = e;
+  }
+};
+
+inline __host__ __device__ bool rate_state_ok(const ufc_rate_state& S, uint64_t n_entries) {
+  if (S.mode > UFC_RATE_THROUGHPUT_EQN || S.recv_cap == 0 || S.recv_count > S.recv_cap) return false;
+  if (S.recv_first > n_entries || n_entries - S.recv_first < S.recv_cap) return false;
+  if (S.mode != UFC_RATE_AWAIT_SEND && S.recv_count == 0) return false;
+  if (S.mode == UFC_RATE_THROUGHPUT_EQN && !S.has_rtt_s) return false;
+  return true;
+}
+
+// One connection's step.  `S` comes in as the state and goes out as states_out's record; the entries and the
+// gathered flush are written here, once nothing can stop the step any more.
+inline __host__ __device__ void rate_step(const RateArgs& a, uint64_t c, ufc_rate_state& S, const ufc_rate_tick& T,
+                                          const ufc_frame_queue_result& F, ufc_rate_result& R) {
+#pragma clang fp contract(off)
+  R = ufc_rate_result{};
+  if (!rate_state_ok(S, a.n_entries)) {
+    R.stop = UFC_RATE_BAD_STATE;
+    return;
+  }
+  const ufc_rate_state in = S;
+  ufc_recv_rate_entry* const arena = a.entries + S.recv_first;
+  RateSet set;
+  set.base = arena;
+  set.count = S.recv_count;
+  set.single = false;
+  set.load();
+  // (the Option bits as 0 / 1, the values behind a clear bit as 0)
+  S.has_time_last_doubled = S.mode == UFC_RATE_SLOW_START && S.has_time_last_doubled;
+  S.has_nofeedback_exp = S.has_nofeedback_exp != 0;
+  S.nofeedback_idle = S.nofeedback_idle != 0;
+  S.has_rtt_s = S.has_rtt_s != 0;
+  S.has_rtt_ms = S.has_rtt_ms != 0;
+  S.has_rto_ms = S.has_rto_ms != 0;
+  S.has_reset = S.has_reset != 0;
+  if (!S.has_time_last_doubled) S.time_last_doubled_ms = 0;
+  if (!S.has_nofeedback_exp) S.nofeedback_exp_ms = 0;
+  if (!S.has_rtt_s) S.rtt_s = 0.0;
+  if (!S.has_rtt_ms) S.rtt_ms = 0;
+  if (!S.has_rto_ms) S.rto_ms = 0;
+  if (!S.has_reset) S.reset_loss_rate = 0.0;
+  if (S.mode != UFC_RATE_THROUGHPUT_EQN) S.send_rate_tcp = 0;
+
+  // 1. the last flush's accounting
+  int64_t alloc = S.flush_alloc;
+  bool sent = (T.flags & UFC_RATE_FRAME_SENT) != 0;
+  if (a.flush_results) {
+    const uint32_t i = a.result_index[c];
+    if (i < a.n_flush_results) {
+      alloc = a.flush_results[i].alloc_left;
+      sent = sent || a.flush_results[i].frame_count > 0;
+    }
+  }
+  alloc = (int64_t)((uint64_t)alloc + (uint64_t)T.alloc_adjust);
+  if (sent) {  // notify_frame_sent(now_ms of that flush), :155-168
+    if (S.mode == UFC_RATE_AWAIT_SEND) {
+      S.has_nofeedback_exp = 1;
+      S.nofeedback_exp_ms = S.now_ms + 2000;
+      S.mode = UFC_RATE_SLOW_START;
+      set.reset(rate_entry(S.now_ms, 0xFFFFFFFFu, true));
+    }
+    S.nofeedback_idle = 0;
+  }
+  // 2. the values the coming flush uses
+  const uint64_t now = T.now_ms;
+  S.now_ms = now;
+  const uint64_t flush_rtt_ms = S.has_rtt_ms ? S.rtt_ms : 150, flush_rto_ms = S.has_rto_ms ? S.rto_ms : 600;
+  // 3. fill_flush_alloc, mod.rs:200-215
+  if (S.has_last_flush) {
+    const double rate = (double)S.send_rate;
+    const double nb = rate * T.delta_time_s;
+    const double am = rate * (S.has_rtt_s ? S.rtt_s : 0.0);
+    const int64_t new_bytes = rate_f64_i64(rate_round(nb)), alloc_max = rate_f64_i64(rate_round(am));
+    int64_t sum;
+    if (__builtin_add_overflow(alloc, new_bytes, &sum)) sum = new_bytes < 0 ? INT64_MIN : INT64_MAX;
+    alloc = sum < alloc_max ? sum : alloc_max;
+  }
+  S.has_last_flush = 1;
+  S.flush_alloc = alloc;
+
+  // 4. SendRateComp::step, :170-185
+  uint32_t flags = 0, iterations = 0;
+  bool append = false;       // a rate-limited update: the survivors of `set`, then `fresh`
+  uint64_t two_rtt = 0;
+  ufc_recv_rate_entry fresh = {};
+  if (S.mode != UFC_RATE_AWAIT_SEND && F.has_feedback) {  // handle_feedback, :187-284
+    flags |= UFC_RATE_FEEDBACK;
+    const double rtt_sample_s = (double)F.rtt_ms / 1000.0;
+    double rtt_s = rtt_sample_s;  // update_rtt, :367-379
+    if (S.has_rtt_s) {
+      const double keep = (1.0 - 0.1) * S.rtt_s;
+      const double take = 0.1 * rtt_sample_s;
+      rtt_s = keep + take;
+    }
+    const uint64_t rtt_ms = rate_s_to_ms(rtt_s);
+    S.has_rtt_s = S.has_rtt_ms = 1;
+    S.rtt_s = rtt_s;
+    S.rtt_ms = rtt_ms;
+    const double rto_s = rate_update_rto(S, rtt_s, S.send_rate);
+    const double loss_rate = F.loss_rate;
+    const bool loss_increase = loss_rate > S.prev_loss_rate;
+    uint32_t recv_limit;
+    if (F.rate_limited) {  // rate_limited_update, recv_rate_set.rs:55-65
+      two_rtt = 2 * rtt_ms;
+      uint32_t kept = 0, max_val = 0;
+      set.each([&](uint64_t t, uint32_t value, bool) {
+        if (now - t < two_rtt) {
+          kept++;
+          max_val = rate_max_u32(max_val, value);
+        }
+      });
+      if (two_rtt == 0) {  // (not even the new entry, of age 0, stays: max() unwraps None)
+        S = in;
+        R.stop = UFC_RATE_REF_PANIC;
+        return;
+      }
+      if (kept >= S.recv_cap) {
+        S = in;
+        R.stop = UFC_RATE_RECV_FULL;
+        return;
+      }
+      append = true;
+      fresh = rate_entry(now, F.receive_rate, false);
+      max_val = rate_max_u32(max_val, F.receive_rate);
+      recv_limit = rate_sat_mul2(max_val);
+    } else {  // loss_increase_update / data_limited_update through replace_max, :31-43, :67-77
+      uint32_t recv_rate = F.receive_rate;
+      if (loss_increase) {
+        const double scaled = (double)recv_rate * 0.85;
+        recv_rate = rate_f64_u32(scaled);
+      }
+      uint32_t max_rate = recv_rate;
+      set.each([&](uint64_t, uint32_t value, bool initial) {
+        if (!initial) max_rate = rate_max_u32(max_rate, loss_increase ? value / 2 : value);
+      });
+      set.reset(rate_entry(now, max_rate, false));
+      recv_limit = loss_increase ? max_rate : rate_sat_mul2(max_rate);
+    }
+    S.prev_loss_rate = loss_rate;
+    if (S.mode == UFC_RATE_SLOW_START) {
+      if (loss_increase) {  // section 6.3.1: into the throughput equation
+        uint32_t target;
+        if (!S.has_time_last_doubled) {
+          const double v = (double)(UFC_MAX_FRAME_SIZE / 2) / rtt_s;  // compute_initial_loss_send_rate
+          target = rate_f64_u32(v);
+        } else {
+          target = S.send_rate / 2;
+        }
+        bool stalled;
+        const double initial_p = rate_tcp_throughput_inv(rtt_s, target, iterations, stalled);
+        S.has_reset = 1;
+        S.reset_loss_rate = initial_p;
+        flags |= UFC_RATE_RESET_ISSUED | UFC_RATE_ENTERED_EQN | (stalled ? UFC_RATE_INV_STALLED : 0);
+        S.send_rate = rate_max_u32(rate_min_u32(target, recv_limit), kRateMinimum);
+        S.mode = UFC_RATE_THROUGHPUT_EQN;
+        S.send_rate_tcp = target;
+        S.has_time_last_doubled = 0;
+        S.time_last_doubled_ms = 0;
+      } else {
+        const uint32_t initial_rate = rate_initial_send_rate(rtt_s);
+        if (S.has_time_last_doubled) {
+          if (now - S.time_last_doubled_ms >= rtt_ms) {
+            S.time_last_doubled_ms = now;
+            S.send_rate = rate_max_u32(rate_min_u32(2 * S.send_rate, recv_limit), initial_rate);
+          }
+        } else {
+          S.has_time_last_doubled = 1;
+          S.time_last_doubled_ms = now;
+          S.send_rate = initial_rate;
+        }
+      }
+    } else {
+      S.send_rate_tcp = rate_tcp_throughput(rtt_s, loss_rate);
+      S.send_rate = rate_max_u32(rate_min_u32(S.send_rate_tcp, recv_limit), kRateMinimum);
+    }
+    S.send_rate = rate_min_u32(S.send_rate, S.max_send_rate);
+    S.has_nofeedback_exp = 1;
+    S.nofeedback_exp_ms = now + rate_s_to_ms(rto_s);
+    S.nofeedback_idle = 1;
+  } else if (S.mode != UFC_RATE_AWAIT_SEND && S.has_nofeedback_exp && now >= S.nofeedback_exp_ms) {
+    flags |= UFC_RATE_NOFEEDBACK;  // nofeedback_expired, :286-365
+    if (S.mode == UFC_RATE_SLOW_START) {
+      bool halve = true;
+      if (S.has_rtt_s) {
+        const uint32_t recover_rate = rate_initial_send_rate(S.rtt_s);
+        halve = !(S.nofeedback_idle && S.send_rate < 2 * recover_rate);
+      }
+      if (halve) S.send_rate = rate_max_u32(S.send_rate / 2, kRateMinimum);
+    } else {
+      const uint32_t recover_rate = rate_initial_send_rate(S.rtt_s);
+      uint32_t recv_rate = 0;  // max(), :79-87, of a set the state check found non-empty
+      set.each([&](uint64_t, uint32_t value, bool) { recv_rate = rate_max_u32(recv_rate, value); });
+      if (!(S.nofeedback_idle && recv_rate < recover_rate)) {
+        const uint32_t current_limit = rate_min_u32(S.send_rate_tcp, rate_sat_mul2(recv_rate));
+        const uint32_t new_limit = rate_max_u32(current_limit / 2, kRateMinimum);
+        set.reset(rate_entry(now, new_limit / 2, false));
+        S.send_rate = rate_min_u32(S.send_rate_tcp, new_limit);
+      }
+    }
+    const double rto_s = rate_update_rto(S, S.has_rtt_s ? S.rtt_s : 0.0, S.send_rate);
+    S.nofeedback_exp_ms = now + rate_s_to_ms(rto_s);
+    S.nofeedback_idle = 1;
+  }
+
+  // 5. commit: the set, the flush, the result
+  uint32_t count = 0;
+  if (append) {
+    set.each([&](uint64_t t, uint32_t value, bool initial) {  // (retain in place: never ahead of the entry read)
+      if (now - t < two_rtt) arena[count++] = rate_entry(t, value, initial);
+    });
+    arena[count++] = fresh;
+  } else if (set.single) {
+    arena[0] = set.e0;
+    count = 1;
+  } else {
+    count = set.count;
+  }
+  S.recv_count = count;
+  if (a.flushes) {
+    const uint32_t j = a.flush_index[c];
+    if (j < a.n_flushes) a.flushes[j].flush_alloc = alloc;
+  }
+  R.mode = S.mode;
+  R.now_ms = now;
+  R.rtt_ms = flush_rtt_ms;
+  R.rto_ms = flush_rto_ms;
+  R.flush_alloc = alloc;
+  R.send_rate = S.send_rate;
+  R.flags = flags;
+  R.inv_iterations = iterations;
+  R.recv_count = count;
+}
+
+// One connection of ufc_rate_begin_*: the frame queue's step record, and the pending reset taken.
+inline __host__ __device__ void rate_begin(ufc_rate_state& S, uint64_t now, uint32_t extra, ufc_frame_queue_step& Q) {
+  const uint64_t rtt = S.has_rtt_ms ? S.rtt_ms : 150;
+  const uint64_t back = rtt * 4;
+  Q.flags = UFC_FQ_FORGET | UFC_FQ_FEEDBACK | (S.has_rtt_ms ? UFC_FQ_HAS_RTT : 0) | (S.has_reset ? UFC_FQ_RESET_LOSS : 0) |
+            extra;
+  Q.reserved = 0;
+  Q.rtt_ms = S.has_rtt_ms ? S.rtt_ms : 0;
+  Q.thresh_ms = now > back ? now - back : 0;
+  Q.now_ms = now;
+  Q.reset_loss_rate = S.has_reset ? S.reset_loss_rate : 0.0;
+  S.has_reset = 0;
+  S.reset_loss_rate = 0.0;
+}
+
 }  // namespace ufc_codec

@@ -24,6 +24,7 @@
 #include "frame_window.hpp"
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
+#include "send_rate.hpp"
 #include "ufc_internal.hpp"
 
 struct ufc_ctx {
@@ -1080,6 +1081,39 @@ int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n
   const ufc_codec::FqArgs a{d_infos, n_frames, d_items, n_items, d_frame_first, d_sent, n_sent, d_sent_first, d_queues,
                             d_steps, n_queues, d_log, n_log, d_ref_acked, refs_cap, d_results, d_queues_out};
   if ((e = ufc_dev::queue_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched send rate control (send_rate.hip) ----
+int ufc_rate_begin_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const uint64_t* d_now_ms,
+                          const uint32_t* d_extra_flags, size_t n, ufc_frame_queue_step* d_steps,
+                          ufc_rate_state* d_states_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  if (!d_states || !d_now_ms || !d_steps || !d_states_out || n >= ((size_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const ufc_codec::RateBeginArgs a{d_states, d_now_ms, d_extra_flags, n, d_steps, d_states_out};
+  if ((e = ufc_dev::rate_begin_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+int ufc_rate_step_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ufc_rate_tick* d_ticks,
+                         const ufc_frame_queue_result* d_fq, size_t n, ufc_recv_rate_entry* d_entries, size_t n_entries,
+                         const ufc_flush_result* d_flush_results, size_t n_flush_results, const uint32_t* d_result_index,
+                         ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_flush_index,
+                         ufc_rate_result* d_results, ufc_rate_state* d_states_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  if (!d_states || !d_ticks || !d_fq || !d_results || !d_states_out || (!d_entries && n_entries) ||
+      (d_flush_results && !d_result_index) || (d_flushes && !d_flush_index) || n >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  // (one launch, no scan: the call needs none of the context's per-stream scratch)
+  const ufc_codec::RateArgs a{d_states, d_ticks, d_fq, n, d_entries, n_entries, d_flush_results, n_flush_results,
+                              d_result_index, d_flushes, n_flushes, d_flush_index, d_results, d_states_out};
+  if ((e = ufc_dev::rate_step_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

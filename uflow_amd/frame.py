@@ -23,6 +23,10 @@ and the batched receive-side parse that follows the batched CRC gate:
                                                <- FrameQueue::push / acknowledge_group / advance_transfer_window /
                                                   forget_frames / get_feedback, src/half_connection/frame_queue.rs
                                                   with reorder_buffer.rs and loss_rate.rs
+    rate_begin_host(states, now_ms) / rate_step_host(states, ticks, fq_results, entries)
+                                               <- SendRateComp::step / notify_frame_sent with RecvRateSet,
+                                                  src/half_connection/send_rate.rs and recv_rate_set.rs, and
+                                                  HalfConnection::step / fill_flush_alloc (mod.rs:165-215)
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -36,8 +40,9 @@ from typing import List, Optional
 import numpy as np
 
 from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameQueue, FrameQueueResult, FrameQueueStep,
-                      FrameWindow, FrameWindowResult, Item, Packet, PacketResult, Receiver, ReceiverResult, RxPacket,
-                      RxSlot, SentFrame, Sender, SenderResult, check, lib, UFC_ERR_NOMEM)
+                      FrameWindow, FrameWindowResult, Item, Packet, PacketResult, RateResult, RateState, RateTick,
+                      Receiver, ReceiverResult, RecvRateEntry, RxPacket, RxSlot, SentFrame, Sender, SenderResult, check,
+                      lib, UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -141,6 +146,45 @@ assert FRAME_QUEUE_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameQueueResult) == 8
 SENT_NONCE, SENT_RATE_LIMITED, SENT_ACKED, SENT_MARK = 1, 2, 4, 8
 FQ_HAS_RTT, FQ_RESET_LOSS, FQ_MARK_RATE_LIMITED, FQ_FORGET, FQ_FEEDBACK = 1, 2, 4, 8, 16
 FQ_DONE, FQ_BAD_STATE = 0, 1
+# ufc_recv_rate_entry / ufc_rate_state / ufc_rate_tick / ufc_rate_result (batched send rate control)
+RECV_RATE_ENTRY_DTYPE = np.dtype([("timestamp_ms", "<u8"), ("value", "<u4"), ("is_initial", "u1"),
+                                  ("reserved", "u1", (3,))])
+RATE_STATE_DTYPE = np.dtype([("mode", "<u4"), ("send_rate", "<u4"), ("max_send_rate", "<u4"), ("send_rate_tcp", "<u4"),
+                             ("has_time_last_doubled", "u1"), ("has_nofeedback_exp", "u1"), ("nofeedback_idle", "u1"),
+                             ("has_rtt_s", "u1"), ("has_rtt_ms", "u1"), ("has_rto_ms", "u1"), ("has_last_flush", "u1"),
+                             ("has_reset", "u1"), ("time_last_doubled_ms", "<u8"), ("prev_loss_rate", "<f8"),
+                             ("nofeedback_exp_ms", "<u8"), ("rtt_s", "<f8"), ("rtt_ms", "<u8"), ("rto_ms", "<u8"),
+                             ("now_ms", "<u8"), ("flush_alloc", "<i8"), ("reset_loss_rate", "<f8"),
+                             ("recv_first", "<u8"), ("recv_count", "<u4"), ("recv_cap", "<u4")])
+RATE_TICK_DTYPE = np.dtype([("now_ms", "<u8"), ("delta_time_s", "<f8"), ("alloc_adjust", "<i8"), ("flags", "<u4"),
+                            ("reserved", "<u4")])
+RATE_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("mode", "<u4"), ("now_ms", "<u8"), ("rtt_ms", "<u8"), ("rto_ms", "<u8"),
+                              ("flush_alloc", "<i8"), ("send_rate", "<u4"), ("flags", "<u4"), ("inv_iterations", "<u4"),
+                              ("recv_count", "<u4")])
+assert RECV_RATE_ENTRY_DTYPE.itemsize == ctypes.sizeof(RecvRateEntry) == 16
+assert RATE_STATE_DTYPE.itemsize == ctypes.sizeof(RateState) == 112
+assert RATE_TICK_DTYPE.itemsize == ctypes.sizeof(RateTick) == 32
+assert RATE_RESULT_DTYPE.itemsize == ctypes.sizeof(RateResult) == 56
+RATE_AWAIT_SEND, RATE_SLOW_START, RATE_THROUGHPUT_EQN = 0, 1, 2
+RATE_FRAME_SENT = 1
+RATE_DONE, RATE_BAD_STATE, RATE_REF_PANIC, RATE_RECV_FULL = 0, 1, 2, 3
+RATE_FEEDBACK, RATE_NOFEEDBACK, RATE_RESET_ISSUED, RATE_ENTERED_EQN, RATE_INV_STALLED = 1, 2, 4, 8, 16
+NO_INDEX = 0xFFFFFFFF  # UFC_NO_PARENT in result_index / flush_index: no gather for this connection
+
+
+def new_rate_states(n: int, max_send_rate, recv_cap: int):
+    """n ufc_rate_state records equal to SendRateComp::new(max_send_rate) (send_rate.rs:119-137) inside a new
+    HalfConnection (flush_alloc 0, now_ms 0, never flushed) and their entry arena: returns (states, entries).  Every
+    connection's RecvRateSet has room for recv_cap entries; the rooms lie back to back, recv_first = c * recv_cap."""
+    if int(recv_cap) < 1:
+        raise ValueError("recv_cap must be at least 1")
+    s = np.zeros(n, dtype=RATE_STATE_DTYPE)
+    s["mode"] = RATE_AWAIT_SEND
+    s["send_rate"] = MAX_FRAME_SIZE
+    s["max_send_rate"] = max_send_rate
+    s["recv_cap"] = recv_cap
+    s["recv_first"] = np.arange(n, dtype=np.uint64) * np.uint64(recv_cap)
+    return s, np.zeros(n * int(recv_cap), dtype=RECV_RATE_ENTRY_DTYPE)
 
 
 def new_frame_queues(n: int, window_size, tail_size, base_id=0, log_cap=None):
@@ -755,3 +799,83 @@ def frame_queue_host(infos: np.ndarray, items: np.ndarray, frame_first: np.ndarr
                                      results.ctypes.data if n else None, queues_out.ctypes.data if n else None, nthreads),
           "ufc_frame_queue_host")
     return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
+
+
+def _rate_inout(name, arr, size, dt):
+    if arr is None:
+        return np.zeros(size, dtype=dt)
+    if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
+        raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
+    return arr
+
+
+def rate_begin_host(states: np.ndarray, now_ms: np.ndarray, extra_flags: Optional[np.ndarray] = None,
+                    nthreads: int = 1, steps: Optional[np.ndarray] = None, states_out: Optional[np.ndarray] = None):
+    """Opens a tick for many connections in host memory (ufc_rate_begin_host): from every RATE_STATE_DTYPE record and
+    its now_ms, the FRAME_QUEUE_STEP_DTYPE record the frame queue call of this tick takes (forget, feedback, the rtt
+    and a pending reset_loss_rate, OR-ed with extra_flags: the caller's FQ_MARK_RATE_LIMITED).  Returns a dict:
+    steps, states_out (the pending reset taken; may be given as `states`)."""
+    if states.dtype != RATE_STATE_DTYPE or not states.flags.c_contiguous:
+        states = np.ascontiguousarray(states, dtype=RATE_STATE_DTYPE)
+    n = states.size
+    now_ms = np.ascontiguousarray(now_ms, dtype=np.uint64)
+    if extra_flags is not None:
+        extra_flags = np.ascontiguousarray(extra_flags, dtype=np.uint32)
+    if now_ms.size < n or (extra_flags is not None and extra_flags.size < n):
+        raise ValueError("now_ms and extra_flags must hold one entry per state")
+    steps = _rate_inout("steps", steps, n, FRAME_QUEUE_STEP_DTYPE)
+    states_out = _rate_inout("states_out", states_out, n, RATE_STATE_DTYPE)
+    check(lib().ufc_rate_begin_host(states.ctypes.data if n else None, now_ms.ctypes.data if n else None,
+                                    extra_flags.ctypes.data if extra_flags is not None and n else None, n,
+                                    steps.ctypes.data if n else None, states_out.ctypes.data if n else None, nthreads),
+          "ufc_rate_begin_host")
+    return {"steps": steps, "states_out": states_out}
+
+
+def rate_step_host(states: np.ndarray, ticks: np.ndarray, fq_results: np.ndarray, entries: np.ndarray,
+                   flush_results: Optional[np.ndarray] = None, result_index: Optional[np.ndarray] = None,
+                   flushes: Optional[np.ndarray] = None, flush_index: Optional[np.ndarray] = None, nthreads: int = 1,
+                   results: Optional[np.ndarray] = None, states_out: Optional[np.ndarray] = None):
+    """Closes a tick for many connections in host memory (ufc_rate_step_host): the last flush's accounting
+    (notify_frame_sent), fill_flush_alloc and SendRateComp::step on the frame queue's results (fq_results,
+    FRAME_QUEUE_RESULT_DTYPE) for every RATE_STATE_DTYPE record with its RATE_TICK_DTYPE input.  entries
+    (RECV_RATE_ENTRY_DTYPE, the arena new_rate_states returns) is updated in place.  flush_results
+    (FLUSH_RESULT_DTYPE) with result_index (uint32 per connection, NO_INDEX for none) gathers the last flush's
+    alloc_left and frame_count; flushes (FLUSH_DTYPE, updated in place) with flush_index receives the new
+    flush_alloc.  Returns a dict: results (RATE_RESULT_DTYPE), states_out (may be given as `states`), entries,
+    flushes."""
+    if states.dtype != RATE_STATE_DTYPE or not states.flags.c_contiguous:
+        states = np.ascontiguousarray(states, dtype=RATE_STATE_DTYPE)
+    n = states.size
+    ticks = np.ascontiguousarray(ticks, dtype=RATE_TICK_DTYPE)
+    fq_results = np.ascontiguousarray(fq_results, dtype=FRAME_QUEUE_RESULT_DTYPE)
+    if ticks.size < n or fq_results.size < n:
+        raise ValueError("ticks and fq_results must hold one record per state")
+    entries = _rate_inout("entries", entries, 0, RECV_RATE_ENTRY_DTYPE)
+    n_fr = n_fl = 0
+    if (flush_results is not None and result_index is None) or (flushes is not None and flush_index is None):
+        raise ValueError("flush_results needs result_index, flushes needs flush_index")
+    if flush_results is not None:
+        flush_results = np.ascontiguousarray(flush_results, dtype=FLUSH_RESULT_DTYPE)
+        result_index = np.ascontiguousarray(result_index, dtype=np.uint32)
+        n_fr = flush_results.size
+        if result_index.size < n:
+            raise ValueError("result_index must hold one entry per state")
+    if flushes is not None:
+        flushes = _rate_inout("flushes", flushes, 0, FLUSH_DTYPE)
+        flush_index = np.ascontiguousarray(flush_index, dtype=np.uint32)
+        n_fl = flushes.size
+        if flush_index.size < n:
+            raise ValueError("flush_index must hold one entry per state")
+    results = _rate_inout("results", results, n, RATE_RESULT_DTYPE)
+    states_out = _rate_inout("states_out", states_out, n, RATE_STATE_DTYPE)
+    check(lib().ufc_rate_step_host(states.ctypes.data if n else None, ticks.ctypes.data if n else None,
+                                   fq_results.ctypes.data if n else None, n,
+                                   entries.ctypes.data if entries.size else None, entries.size,
+                                   flush_results.ctypes.data if n_fr else None, n_fr,
+                                   result_index.ctypes.data if n_fr else None,
+                                   flushes.ctypes.data if n_fl else None, n_fl,
+                                   flush_index.ctypes.data if n_fl else None,
+                                   results.ctypes.data if n else None, states_out.ctypes.data if n else None, nthreads),
+          "ufc_rate_step_host")
+    return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
