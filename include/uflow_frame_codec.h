@@ -41,6 +41,13 @@
  *                                 handle_sync_frame call them (src/half_connection/mod.rs:132-152): the parses'
  *                                 frames into the receive's frame_accept verdicts and the packs' ack groups,
  *                                 many connections per call, on the host and on the GPU
+ *   ufc_frame_queue_*, ufc_rate_begin_*, ufc_rate_step_*
+ *                              <- FrameQueue, SendRateComp and HalfConnection::step (their sections below)
+ *   ufc_resend_begin_*, ufc_resend_place_*, ufc_resend_commit_*
+ *                              <- PacketSender::acknowledge (packet_sender.rs:242-275), the resend queue
+ *                                 (resend_queue.rs), the pending queue (pending_queue.rs) and emit_data_frames
+ *                                 (half_connection/mod.rs:335-432) around the emit and the pack, many connections per
+ *                                 call, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -387,8 +394,8 @@ typedef struct ufc_sender_result {   /* 32 bytes */
  *                      each packet's fragments in order; items at an index >= items_cap are not written
  *                      (compare *items_used with items_cap, as with the parse; items_cap = 0 gives the records
  *                      and the state alone).  The reserve_items slots in front of a sender's new items are
- *                      never written: the caller puts the flush's resent and leftover fragments there, as the
- *                      reference sends them first (mod.rs:351-383 before :385).
+ *                      never written: ufc_resend_place_* (below) puts the flush's resent and leftover fragments
+ *                      there, as the reference sends them first (mod.rs:351-383 before :385).
  *   flush_first        [n_senders + 1], the exclusive sum of the senders' item counts, reserved slots
  *                      included: what ufc_pack_* takes as its flush_first.  *items_used = flush_first[n_senders].
  *   packet_results     [n_packets], nullable.  Every packet of a sender's range gets a record; packets that
@@ -675,10 +682,11 @@ int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
  * drive it.  The release build is the specification, wrapping u32 and u64 arithmetic included (send_time_ms +
  * rtt_ms, now_ms - last_send_time_ms and total_ack_size all wrap).  SendRateComp (send_rate.rs, recv_rate_set.rs)
  * is ufc_rate_begin_* / ufc_rate_step_* below; PacketSender::acknowledge (it needs the per-packet window table that
- * ufc_sender does not hold) and the resend and pending queues stay with the caller.
+ * ufc_sender does not hold) and the resend and pending queues are ufc_resend_* further below.
  *
  * A log slot is one frame_queue::Entry (:14-21).  fragment_refs is the range [ref_first, ref_first + ref_count) of a
- * fragment table the caller owns: in the device pipeline the frame's item_first / item_count from the pack. */
+ * fragment table the caller owns: in the device pipeline the connection's transmission ring, which
+ * ufc_resend_commit_* fills and whose marks ufc_resend_begin_* consumes. */
 #define UFC_SENT_NONCE 1         /* Entry.nonce */
 #define UFC_SENT_RATE_LIMITED 2  /* Entry.rate_limited; ignored on input to a push */
 #define UFC_SENT_ACKED 4         /* Entry.acked; ignored on input to a push */
@@ -824,12 +832,13 @@ int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n
  * rtt_ms*4, now_ms + s_to_ms(rto)), saturating_mul / saturating_sub / saturating_add apply where the reference
  * writes them, `as u32` / `as u64` / `as isize` on a float saturate with NaN giving 0, f64::round is half away from
  * zero, f64::max returns the other operand for a NaN, and debug_assert!s do not exist.  MSS = UFC_MAX_FRAME_SIZE,
- * MINIMUM_RATE = MSS / 64 = 23, INITIAL_TCP_WINDOW = 4380.  PacketSender::acknowledge, the resend and pending
- * queues and the sync frame's decision stay with the caller.
+ * MINIMUM_RATE = MSS / 64 = 23, INITIAL_TCP_WINDOW = 4380.  PacketSender::acknowledge and the resend and pending
+ * queues are ufc_resend_* below; the sync frame's decision (and push_dud) stay with the caller.
  *
- * A tick of a device-resident sender is five queued calls with no host code between them:
+ * A tick of a device-resident sender is queued calls with no host code between them:
  *   ufc_rate_begin_varlen -> ufc_frame_queue_varlen -> ufc_rate_step_varlen -> (emit) -> ufc_pack_varlen,
- * the rate step writing the coming flush's flush_alloc and reading the last flush's alloc_left. */
+ * the rate step writing the coming flush's flush_alloc and reading the last flush's alloc_left; with resends and
+ * leftover fragments the ufc_resend_* calls go around the emit and the pack (their section has the full order). */
 typedef struct ufc_recv_rate_entry {   /* 16 bytes: one RecvEntry (recv_rate_set.rs:3-7) */
   uint64_t timestamp_ms;
   uint32_t value;
@@ -974,6 +983,262 @@ int ufc_rate_step_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ufc
                          const ufc_flush_result* d_flush_results, size_t n_flush_results, const uint32_t* d_result_index,
                          ufc_flush* d_flushes, size_t n_flushes, const uint32_t* d_flush_index,
                          ufc_rate_result* d_results, ufc_rate_state* d_states_out, void* stream);
+
+/* ---- batched resend: packet acks, the resend queue and the pending queue ----
+ * The last serial piece of HalfConnection's data path: PacketSender::acknowledge (packet_sender.rs:242-275), the ack
+ * flags of PendingPacket (pending_packet.rs:64-78), the resend queue (resend_queue.rs: std's BinaryHeap ordered on
+ * resend_time alone, reversed), the pending queue (pending_queue.rs) and emit_data_frames (half_connection/mod.rs:
+ * 335-432: the resend loop :351-383, the pending / new-packet loop :385-427), as handle_ack_frame (:154-163) and flush
+ * drive them.  The release build is the specification.  Three calls go around the emit and the pack, so that a tick of
+ * a device-resident sender is queued with no host code in it:
+ *   ufc_rate_begin -> ufc_frame_queue -> ufc_rate_step -> ufc_resend_begin -> ufc_emit_packets -> ufc_resend_place ->
+ *   ufc_pack (the data flushes alone: flush c = connection c) -> ufc_build_sizes -> ufc_resend_commit ->
+ *   ufc_emit_packets (senders = retake, items_cap = 0: the state after the packets the reference emitted) -> build.
+ *
+ * State, caller-owned like the frame queue's log arena: one ufc_resend per connection, in and out, with regions in
+ * six arenas.  The regions of different connections must not overlap.
+ *   heap      [heap_first, heap_first + heap_cap) of ufc_resend_entry: std's BinaryHeap array index for index, entry i
+ *             with children 2i+1 and 2i+2; heap_len entries are live.  push appends and sifts up; pop swaps the last
+ *             entry into the root, sifts it down to the bottom along the children chosen by `child += (d[child] <=
+ *             d[child+1])`, and sifts it up again, "a <= b" meaning a.resend_time_ms >= b.resend_time_ms.  The order of
+ *             entries with equal times is observable (all fragments of one flush share a time) and is std's: host and
+ *             device agree on the region's bytes.
+ *   packets   a ring of ufc_sent_packet, pkt_cap a power of two >= window_size, packet seq at slot seq & (pkt_cap - 1):
+ *             the WindowEntry and the PendingPacket's header.  alloc_size is recomputed from data_len.
+ *   ack flags one byte per fragment in the ring frag_acked[frag_first + (i & (frag_cap - 1))], frag_cap a power of two
+ *             >= ceil(max_alloc / 1448) + window_size (the allocation limit bounds the live fragments and packets are
+ *             freed in order, so a live byte is never overwritten).  A packet's fragment f is i = its frag_first + f,
+ *             taken from the monotone frag_next and zeroed when the packet enters the table.
+ *   tx ring   ufc_tx_ref records, tx_cap a power of two >= (window_size + tail_size + 1) * 127 of the connection's
+ *             frame queue, positions from the monotone tx_head / tx_tail: the fragment table that
+ *             ufc_sent_frame.ref_first / ref_count and ref_acked[] index (ref_first = tx_first + (position & (tx_cap -
+ *             1)), an index into the arena, so the arena holds < 2^32 records).  A frame's refs are its items in
+ *             order, contiguous, and never straddle the region's end: if they would, the head skips to its start.
+ *   stage     [stage_first, stage_first + stage_cap) of ufc_item: what ufc_resend_begin found to send first.
+ *   pending   the pending queue only ever holds fragments f..last of one packet (emit_packet is called only when it is
+ *             empty, mod.rs:386), so it is pending_seq, pending_next (the front's fragment id), pending_count and
+ *             pending_resend.
+ *   window_bytes  the sum of data_len over the window: the part of total_size that acknowledge subtracts.
+ * The ufc_sender stays the emit's record and is passed alongside (base_id, next_id, alloc and the parents).
+ * All-zero counters with the regions set is HalfConnection::new. */
+typedef struct ufc_resend_entry {      /* 16 bytes: resend_queue::Entry */
+  uint64_t resend_time_ms;
+  uint32_t sequence_id;
+  uint16_t fragment_id;
+  uint8_t send_count;
+  uint8_t reserved;                    /* stored as 0 */
+} ufc_resend_entry;
+
+typedef struct ufc_sent_packet {       /* 24 bytes: one packet of the transfer window */
+  uint32_t data_offset, data_len;      /* in the payload arena */
+  uint32_t frag_first;                 /* its first ack byte's position in the ack ring (monotone, masked at use) */
+  uint32_t sequence_id;
+  uint16_t window_parent_lead, channel_parent_lead;
+  uint8_t channel_id;
+  uint8_t resend;                      /* mode >= PERSISTENT */
+  uint16_t reserved;                   /* stored as 0 */
+} ufc_sent_packet;
+
+#define UFC_TX_RESEND 1                /* the fragment was pushed with resend = true (emit.rs:75, :104) */
+typedef struct ufc_tx_ref {            /* 8 bytes: one sent fragment */
+  uint32_t sequence_id;
+  uint16_t fragment_id;
+  uint16_t flags;                      /* UFC_TX_* */
+} ufc_tx_ref;
+
+typedef struct ufc_resend {            /* 104 bytes; in and out */
+  uint64_t heap_first;
+  uint32_t heap_cap, heap_len;
+  uint64_t pkt_first;
+  uint32_t pkt_cap, frag_next;
+  uint64_t frag_first;
+  uint32_t frag_cap, tx_cap;
+  uint64_t tx_first;
+  uint32_t tx_head, tx_tail;
+  uint64_t stage_first;
+  uint32_t stage_cap, pending_seq;
+  uint32_t pending_next, pending_count;
+  uint8_t pending_resend;
+  uint8_t reserved0;                   /* the reserved fields are copied */
+  uint16_t reserved1;
+  uint32_t reserved2;
+  uint64_t window_bytes;
+} ufc_resend;
+
+#define UFC_RS_NO_DATA_FLUSH 1         /* flags[c]: emit_ack_frames returned Err, the tick has no data flush */
+
+#define UFC_RS_DONE 0
+#define UFC_RS_SIZE_LIMITED 1          /* DataPushError::SizeLimited in the resend loop: the flush ends, mark_rate_limited */
+#define UFC_RS_WINDOW_LIMITED 2        /* DataPushError::WindowLimited in the resend loop: the flush ends */
+#define UFC_RS_REF_HANG 3              /* the reference never returns from mod.rs:405-407 / :422-424 (below) */
+#define UFC_RS_BAD_STATE 4
+#define UFC_RS_STAGE_FULL 5            /* the stage's capacity; ends the flush like WINDOW_LIMITED */
+#define UFC_RS_HEAP_FULL 6             /* commit only: the heap's capacity */
+typedef struct ufc_resend_result {     /* 48 bytes: ufc_resend_begin_* */
+  uint32_t stop;
+  uint32_t n_resent, n_pending_staged; /* the stage: resent fragments, then pending ones */
+  uint32_t heap_popped_dead, heap_popped_acked;
+  uint32_t packets_freed;              /* by acknowledge */
+  uint32_t refs_acked;                 /* ack bytes set from ref_acked */
+  uint32_t heap_len, pending_count;    /* after the call: with base_id != next_id, what the sync frame's decision
+                                          (mod.rs:257-263) and is_send_pending (:120-122) need */
+  uint32_t acks_ignored;               /* ack frames acknowledge returned from at :246 (or whose id is no packet id) */
+  uint64_t bytes_freed;
+} ufc_resend_result;
+
+typedef struct ufc_resend_commit_result { /* 40 bytes: ufc_resend_commit_* */
+  uint32_t stop;
+  uint32_t pending_packed;             /* pending fragments that left the pending queue */
+  uint32_t packets_entered;            /* new packets the reference emitted: entered into the table */
+  uint32_t heap_pushed, heap_dropped;  /* dropped: pushes that found the heap full (HEAP_FULL) */
+  uint32_t refs_written, frames;       /* tx refs and sent records written */
+  uint32_t take;                       /* retake[c].take */
+  uint32_t heap_len, pending_count;    /* after the call */
+} ufc_resend_commit_result;
+
+/* ufc_resend_begin_*: behind ufc_rate_step_*, in front of the emit.  Connection c owns the frames [frame_first[c],
+ * frame_first[c + 1]) (the CSR the frame queue takes) and reads queues[c] and its log ring as ufc_frame_queue_* left
+ * them, rate[c].now_ms and rate[c].rtt_ms (ufc_rate_step_*'s result: the flush's now_ms and rtt_ms, mod.rs:197),
+ * flags[c] (nullable: 0) and flushes[c], the data flush the pack will get.  Per connection, in this order:
+ *   1. Ack propagation.  For every position r in [tx_tail, tx_head) with ref_acked[r] != 0 (r < refs_cap; ref_acked
+ *      nullable): ref_acked[r] = 0 (the frame queue never clears it: this call consumes it), and if the ref has
+ *      UFC_TX_RESEND and its packet is in the window ((sequence_id - base_id) & 0xFFFFF < (next_id - base_id) &
+ *      0xFFFFF: Weak::upgrade succeeds) its ack byte is set (acknowledge_fragment).  A ref is matched to its packet
+ *      by id and window position alone: a ref still in the ring when its id has come round 2^20 packets later would
+ *      mark the new packet.  The frame queue forgets a frame 4 RTTs after it was sent, so that takes 2^20 packets
+ *      within 4 RTTs on one connection; the reference's weak pointer cannot be fooled this way.  Then tx_tail moves to the
+ *      ref_first of the frame at the queue's log_base_id, or to tx_head if the log is empty.
+ *   2. acknowledge(f[1]) for every ok UFC_FRAME_ACK frame of the range in arrival order, literally :242-275: ignored
+ *      when delta > span; else alloc, window_bytes, the window parent and the channel parents are updated and
+ *      base_id moves.  An f[1] above 0xFFFFF, which no sender writes, is ignored too (the reference walks past
+ *      next_id and panics on an empty window slot).
+ *      handle_ack_frame interleaves the frame queue's work and acknowledge frame by frame; the two states meet only
+ *      through the ack flags and the weak pointers, and those are read at flush time only (a fragment marked on a
+ *      packet that a later acknowledge of the same tick frees is never looked at again), so running all of
+ *      ufc_frame_queue_* first and every acknowledge after it gives the same state.
+ *   3. Unless UFC_RS_NO_DATA_FLUSH: the resend loop (:351-383).  While the heap is not empty, for its top entry:
+ *      packet gone ((sequence_id - base_id) & 0xFFFFF >= (next_id - base_id) & 0xFFFFF): pop, continue; fragment
+ *      acknowledged: pop, continue; resend_time_ms > now_ms: break; else dfe.push, which is the pack's rule (steps 1-4
+ *      of the ufc_flush comment) run over flushes[c] as a state machine of four variables (alloc, frames, the size
+ *      and count of the frame in progress): WINDOW_LIMITED and SIZE_LIMITED end the loop with that stop; on success
+ *      the fragment becomes the stage's next item (as the emit makes items, from the packet table's slot), the entry
+ *      is popped and pushed again as {now_ms + rtt_ms * (1 << send_count), min(send_count + 1, 2)} (wrapping u64, the
+ *      shift amount & 63, a wrapping u8 add).  With rtt_ms == 0 the entry is due again at once and is resent until
+ *      the flush is limited, as in the reference.  A full stage stops the loop STAGE_FULL.
+ *   4. If the loop was not limited: a pending front whose packet is gone or whose ack byte is set stops REF_HANG: the
+ *      reference pops the *resend* queue and `continue`s with the same pending front for ever (an ack frame with
+ *      packet_window_base_id = next_id, from a hostile or broken peer, gets there).  The connection keeps what the
+ *      reference had done when it entered that loop and the flush ends there: the frame in progress goes out, the
+ *      heap is not drained, no pending fragment and no new packet is sent, and every later tick stops the same way
+ *      until the caller gives the connection up.  Otherwise
+ *      all pending fragments are staged behind the resent ones, unjudged: the pack decides how many go.  If they do
+ *      not fit the stage none is staged and the stop is STAGE_FULL.
+ *   5. senders_out[c] (required, may be `senders`) = the sender with acknowledge's changes, reserve_items = the
+ *      staged count, and take = 0 unless the stop is DONE and a data flush takes place (the reference's flush ends
+ *      there); states_out[c] (required, may be `states`); results[c].
+ * Sizing the stage: with rtt_ms > 0 and times that do not wrap, an entry is resent once per tick, so heap_len + the
+ * fragments of the longest packet the caller sends is enough, and that is the sizing to use (24 bytes an item);
+ * heap_cap + 65536 covers any packet but is 1.5 MB a connection.  The exception is the u64 wrap: when now_ms +
+ * rtt_ms * (1 << send_count) wraps, the re-pushed entry lies in the past, is due again at once and is resent until
+ * the flush is limited, as with rtt_ms == 0; STAGE_FULL is then one of the ways that flush ends.
+ * UFC_RS_BAD_STATE follows the frame queue's convention: the state is copied through and nothing else is touched; the
+ * sender is copied with take = 0 and reserve_items = 0, so that the emit sends nothing for it.  It covers: pkt_cap,
+ * frag_cap or tx_cap not a power of two, or below the bounds above (window_size 0 or above 2^20); a region outside its arena (n_tx > 2^32); heap_len > heap_cap; tx_head - tx_tail > tx_cap; the queue's
+ * log_cap not a power of two or its ring outside [0, n_log); a reversed or outlying frame range.
+ * Counts: n < 2^31 - 1; n == 0 returns UFC_OK whatever the pointers; a NULL frame_first, queues, rate, flushes,
+ * states, senders, results, states_out or senders_out, a NULL infos with n_frames != 0, or a NULL arena with a nonzero
+ * size is UFC_ERR_INVALID_ARG. */
+int ufc_resend_begin_host(const ufc_frame_info* infos, size_t n_frames, const uint64_t* frame_first,
+                          const ufc_frame_queue* queues, const ufc_sent_frame* log, size_t n_log,
+                          const ufc_rate_result* rate, const uint32_t* flags, const ufc_flush* flushes,
+                          const ufc_resend* states, const ufc_sender* senders, size_t n, ufc_resend_entry* heap,
+                          size_t n_heap, const ufc_sent_packet* pkts, size_t n_pkts, uint8_t* frag_acked, size_t n_frag,
+                          const ufc_tx_ref* tx, size_t n_tx, uint8_t* ref_acked, size_t refs_cap, ufc_item* stage,
+                          size_t n_stage, ufc_resend_result* results, ufc_resend* states_out, ufc_sender* senders_out,
+                          int nthreads);
+
+/* ufc_resend_place_*: behind the emit.  Copies connection c's staged items (begin_results[c].n_resent +
+ * n_pending_staged of them, from its stage) into items[flush_first[c] ..), the reserve_items slots the emit left, at
+ * most flush_first[c + 1] - flush_first[c] of them and none at an index >= items_cap.  A copy: on the device one wave
+ * per connection with a lane per staged item of that connection (not one lane per staged item over the whole batch
+ * with the sender searched in flush_first, as the emit's item kernel does it: with less than one staged item a
+ * connection most waves have one live lane; 0.06 ms for 250,000 connections, the smallest of the three calls).
+ * n == 0 returns UFC_OK; a NULL states, begin_results or flush_first, NULL stage with n_stage != 0 or NULL items with
+ * items_cap != 0 is UFC_ERR_INVALID_ARG. */
+int ufc_resend_place_host(const ufc_resend* states, const ufc_resend_result* begin_results, size_t n,
+                          const ufc_item* stage, size_t n_stage, const uint64_t* flush_first, ufc_item* items,
+                          size_t items_cap, int nthreads);
+
+/* ufc_resend_commit_*: behind the pack of the data flushes (flush c = connection c, over the emit's flush_first)
+ * and the build's size pass.  Inputs per connection: flush_results[c] and its frames infos[frame_first ..+
+ * frame_count) with their sizes out_offsets[g + 1] - out_offsets[g]; the first emit's packet_results and
+ * sender_results[c] over packets[packet_first[c] .. packet_first[c + 1]); begin_results[c]; rate[c] as in begin;
+ * senders[c] as begin wrote it.  In this order:
+ *   - items_packed >= n_resent must hold, because begin ran the pack's rule; otherwise BAD_STATE.
+ *   - The packed pending fragments leave the pending queue; with pending_resend each is pushed {now_ms + rtt_ms, 1},
+ *     in order (:417-421).
+ *   - If pending fragments are left, the reference emitted no new packet: take = 0.  Otherwise p = the packet that
+ *     owns the first unpacked new item.  Packets 0..p were emitted by the reference (:387-395): they enter the packet
+ *     table, their ack bytes are taken from frag_next and zeroed, window_bytes grows by their lengths; the packed
+ *     fragments of resend packets are pushed {now_ms + rtt_ms, 1} in item order; p's unpacked fragments become the
+ *     pending queue; take = p's index in the range + 1.  When every item was packed, take = the first emit's
+ *     packets_consumed and every emitted packet enters.
+ *   - retake[c] (required, may be `senders`) = senders[c] with that take and reserve_items = 0: the second emit's
+ *     input.
+ *   - Every packed item's ufc_tx_ref is appended (UFC_TX_RESEND from its packet's resend) and the frames' records are
+ *     written to sent[g], g the frame's index in infos: send_time_ms = now_ms, size, ref_first / ref_count,
+ *     UFC_SENT_NONCE from aux.  sent_first[c] = frame_first and sent_first[n] = *frames_used: the next tick's input
+ *     to ufc_frame_queue_*.  Records at an index >= sent_cap are not written.
+ *   - next_extra_flags[c] (nullable): UFC_FQ_MARK_RATE_LIMITED is set when the pack's stop or begin's stop was
+ *     SIZE_LIMITED and cleared otherwise; the other bits stay.  It is the next tick's extra_flags of
+ *     ufc_rate_begin_*: the frame queue sets its pending mark behind this tick's pushes, as emit.rs:67 and :85 do.
+ *   - A push that finds heap_len == heap_cap is dropped and counted, and the stop is HEAP_FULL: that fragment is not
+ *     resent.  Entries of departed packets leave only at the top of the heap, so no static bound on its length
+ *     exists; the live fragments of Persistent and Reliable packets plus a margin for the departed is a sizing.
+ * BAD_STATE (begin's rules, begin's stop BAD_STATE, items_packed < n_resent or beyond the flush, frames outside
+ * [0, n_infos), items outside [0, n_items), a reversed or outlying packet range, fewer item slots than staged items):
+ * the state is copied through, retake[c] has take = 0, and the flush's frames get records with ref_count = 0.
+ * Counts and NULL rules as begin's; n_packets < 2^31 - 1. */
+int ufc_resend_commit_host(const ufc_flush_result* flush_results, const ufc_frame_info* infos, size_t n_infos,
+                           const uint64_t* out_offsets, const uint64_t* frames_used, const ufc_item* items,
+                           size_t n_items, const uint64_t* flush_first, const ufc_packet* packets, size_t n_packets,
+                           const uint64_t* packet_first, const ufc_packet_result* packet_results,
+                           const ufc_sender_result* sender_results, const ufc_resend_result* begin_results,
+                           const ufc_rate_result* rate, const ufc_resend* states, const ufc_sender* senders, size_t n,
+                           ufc_resend_entry* heap, size_t n_heap, ufc_sent_packet* pkts, size_t n_pkts,
+                           uint8_t* frag_acked, size_t n_frag, ufc_tx_ref* tx, size_t n_tx, ufc_sent_frame* sent,
+                           size_t sent_cap, uint64_t* sent_first, uint32_t* next_extra_flags,
+                           ufc_resend_commit_result* results, ufc_resend* states_out, ufc_sender* retake, int nthreads);
+
+/* The same three on the GPU (gfx950 kernels, resend.hip): every pointer device memory, asynchronous on `stream`,
+ * nothing allocated per call, no scratch.  One launch per call.  Below 16,384 connections one wave per connection (one
+ * wave per workgroup, as the frame queue); from there on begin and commit give every connection a lane, 64 heap walks
+ * in flight per wave (measured: DESIGN 5.14).  In the wave form the whole wave takes the
+ * live refs (64 per pass), the slots acknowledge frees (wave sums of alloc_size and data_len, a ballot for the
+ * window parent), the pending fragments' items, and commit's table entries, ack bytes and refs; the heap operations
+ * and the pack rule are a dependent chain and run in one lane. */
+int ufc_resend_begin_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const uint64_t* d_frame_first,
+                            const ufc_frame_queue* d_queues, const ufc_sent_frame* d_log, size_t n_log,
+                            const ufc_rate_result* d_rate, const uint32_t* d_flags, const ufc_flush* d_flushes,
+                            const ufc_resend* d_states, const ufc_sender* d_senders, size_t n, ufc_resend_entry* d_heap,
+                            size_t n_heap, const ufc_sent_packet* d_pkts, size_t n_pkts, uint8_t* d_frag_acked,
+                            size_t n_frag, const ufc_tx_ref* d_tx, size_t n_tx, uint8_t* d_ref_acked, size_t refs_cap,
+                            ufc_item* d_stage, size_t n_stage, ufc_resend_result* d_results, ufc_resend* d_states_out,
+                            ufc_sender* d_senders_out, void* stream);
+int ufc_resend_place_varlen(ufc_ctx* ctx, const ufc_resend* d_states, const ufc_resend_result* d_begin_results, size_t n,
+                            const ufc_item* d_stage, size_t n_stage, const uint64_t* d_flush_first, ufc_item* d_items,
+                            size_t items_cap, void* stream);
+int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_results, const ufc_frame_info* d_infos,
+                             size_t n_infos, const uint64_t* d_out_offsets, const uint64_t* d_frames_used,
+                             const ufc_item* d_items, size_t n_items, const uint64_t* d_flush_first,
+                             const ufc_packet* d_packets, size_t n_packets, const uint64_t* d_packet_first,
+                             const ufc_packet_result* d_packet_results, const ufc_sender_result* d_sender_results,
+                             const ufc_resend_result* d_begin_results, const ufc_rate_result* d_rate,
+                             const ufc_resend* d_states, const ufc_sender* d_senders, size_t n, ufc_resend_entry* d_heap,
+                             size_t n_heap, ufc_sent_packet* d_pkts, size_t n_pkts, uint8_t* d_frag_acked, size_t n_frag,
+                             ufc_tx_ref* d_tx, size_t n_tx, ufc_sent_frame* d_sent, size_t sent_cap,
+                             uint64_t* d_sent_first, uint32_t* d_next_extra_flags, ufc_resend_commit_result* d_results,
+                             ufc_resend* d_states_out, ufc_sender* d_retake, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 3, 4-per-GPU and 5, the seal and the
 parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GPU box:
-    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,queue,rate,gate_tg,host] [--reps 20]
+    python tools/bench_configs.py [--only varlen,shard,seal,seal_varlen,parse,parse_mtu,build,pack,emit,receive,window,queue,rate,resend,gate_tg,host] [--reps 20]
 
   varlen   config 3: 10M frames, lengths U[64,1500] (splitmix64, seed 0x5EED0002), CSR offsets,
            device-resident; every frame checked against the oracle; CPU baseline of the same loop
@@ -39,6 +39,9 @@ parse), one JSON line each.  Not the driver's bench (bench.py is); run on the GP
            and of 2,048 connections in a mix of modes, most with feedback; the call, ufc_rate_step_host with 1 and 16
            threads and a device-to-device copy of the bytes the call reads and writes; one line per grouping, also
            written to profiles/rate_configs.jsonl.  Run with --only rate.
+  resend   the three resend calls of one tick (begin, place, commit) for 250,000 and 2,048 connections with heaps that
+           earlier ticks filled, each timed on the device and on the host, against a copy of the bytes they move;
+           written to profiles/resend_configs.jsonl.  Run with --only resend.
   host     config 5's GPU leg: 1M x 1472-B frames (uflow's MAX_FRAME_SIZE) that start and end in
            host memory -> ufc_validate_host_varlen (H2D + CRC + D2H) from pinned and from pageable
            buffers; GiB/s of frame bytes including the copies.
@@ -1061,6 +1064,203 @@ def rate(eng, dev, reps, n=None):
     return out
 
 
+RESEND_OUT = os.path.join(REPO, "profiles", "resend_configs.jsonl")
+RESEND_GROUPINGS = (("250,000", 250_000), ("2,048", 2048))
+
+
+def resend(eng, dev, reps):
+    """The three resend calls of one tick, ufc_resend_begin_varlen, ufc_resend_place_varlen and
+    ufc_resend_commit_varlen, for 250,000 and for 2,048 connections.  The state is what earlier ticks leave: every
+    connection has 8 one-fragment Persistent packets of 200 bytes in a window of 16, their 8 entries in its heap (a
+    quarter due, a quarter of the fragments acknowledged, independently), 16 live refs in its transmission ring with a
+    quarter of their ref_acked marks set, one ack frame that frees two packets, and two new Reliable packets of 300
+    bytes in its queue.  Between the calls the emit, the pack and the size pass run on the host once, untimed; the
+    device calls take their outputs.  begin changes the heap, the ack bytes and ref_acked and commit the heap, so
+    those are restored from pristine copies in front of every call, outside the timed span: an event pair around each
+    call on the device, wall clock around each call on the host (1 and 16 threads, median of 3).  The floor is one
+    device-to-device copy of (bytes read + bytes written) / 2 of the three calls together, counted from the records:
+    per connection the state, sender, queue, flush, rate and result records in and out, its heap entries twice, its
+    live refs and marks, its touched table slots and ack bytes, and its items, refs and sent records.  Per grouping
+    one JSON line, also written to profiles/resend_configs.jsonl, with every output of the device calls against the
+    host calls'."""
+    import ctypes
+    from uflow_amd import _native as N, frame as fr
+    lib = N.lib()
+    out = []
+    W, K, LIVE, NEW = 16, 8, 16, 2
+    for name, nq in RESEND_GROUPINGS:
+        rng = np.random.default_rng(29)
+        now, rtt = 100_000, 40
+        states, A = fr.new_resend_states(nq, W, W * 1448, 2, 1, heap_cap=16, stage_cap=16)
+        base = rng.integers(0, 1 << 20, nq).astype(np.uint32)
+        senders = np.zeros(nq, dtype=fr.SENDER_DTYPE)
+        senders["base_id"], senders["next_id"], senders["window_size"] = base, (base + K) & 0xFFFFF, W
+        senders["alloc"], senders["max_alloc"], senders["window_parent_id"] = K * 200, W * 1448, fr.NO_PARENT
+        senders["channel_parent_id"], senders["take"] = fr.NO_PARENT, 0xFFFFFFFF
+        k = np.arange(K, dtype=np.uint32)
+        seq = (base[:, None] + k[None, :]) & 0xFFFFF
+        slot = (states["pkt_first"][:, None] + (seq & (W - 1))).astype(np.int64)
+        pk = A["pkts"]
+        pk["data_offset"][slot], pk["data_len"][slot], pk["frag_first"][slot] = seq * 200 % (1 << 31), 200, k[None, :]
+        pk["sequence_id"][slot], pk["resend"][slot] = seq, 1
+        A["frag_acked"][(states["frag_first"][:, None] + k[None, :]).astype(np.int64)] = rng.random((nq, K)) < 0.25
+        states["frag_next"], states["heap_len"], states["window_bytes"] = K, K, K * 200
+        times = np.sort(np.where(rng.random((nq, K)) < 0.25, now - rng.integers(0, 30, (nq, K)), now + rng.integers(1, 150, (nq, K))), axis=1)
+        order = np.argsort(rng.random((nq, K)), axis=1).astype(np.uint32)   # which packet holds which heap slot
+        hs = (states["heap_first"][:, None] + k[None, :]).astype(np.int64)
+        A["heap"]["resend_time_ms"][hs], A["heap"]["send_count"][hs] = times, 1
+        A["heap"]["sequence_id"][hs] = (base[:, None] + order) & 0xFFFFF
+        j = np.arange(LIVE, dtype=np.uint32)
+        ts = (states["tx_first"][:, None] + j[None, :]).astype(np.int64)
+        A["tx"]["sequence_id"][ts], A["tx"]["flags"][ts] = (base[:, None] + j[None, :] % K) & 0xFFFFF, fr.TX_RESEND
+        A["ref_acked"][ts] = rng.random((nq, LIVE)) < 0.25
+        states["tx_head"] = LIVE
+        queues, log = fr.new_frame_queues(nq, 2, 1)
+        queues["log_next_id"] = 1
+        log["ref_first"][queues["log_first"].astype(np.int64)] = states["tx_first"]
+        infos = np.zeros(nq, dtype=fr.FRAME_INFO_DTYPE)
+        infos["kind"], infos["ok"] = fr.ACK, 1
+        infos["f"][:, 1] = (base + 2) & 0xFFFFF
+        frame_first = np.arange(nq + 1, dtype=np.uint64)
+        rate_r = np.zeros(nq, dtype=fr.RATE_RESULT_DTYPE)
+        rate_r["now_ms"], rate_r["rtt_ms"] = now, rtt
+        flushes = np.zeros(nq, dtype=fr.FLUSH_DTYPE)
+        flushes["flush_alloc"], flushes["kind"], flushes["window_room"], flushes["id0"] = 1 << 30, fr.DATA, 2, 1
+        packets = np.zeros(nq * NEW, dtype=fr.PACKET_DTYPE)
+        packets["data_offset"], packets["data_len"], packets["mode"] = np.arange(nq * NEW) * 300 % (1 << 31), 300, fr.SEND_RELIABLE
+        packet_first = np.arange(nq + 1, dtype=np.uint64) * NEW
+        pristine = {n_: A[n_].copy() for n_ in ("heap", "frag_acked", "ref_acked")}
+
+        def restore_host():
+            for n_, v in pristine.items():
+                np.copyto(A[n_], v)
+
+        host_ms = {}
+        for T in (1, 16):
+            ts_ = {"begin": [], "place": [], "commit": []}
+            for _ in range(3):
+                restore_host()
+                t0 = time.perf_counter()
+                b = fr.resend_begin_host(infos, frame_first, queues, log, rate_r, flushes, states, senders, A, nthreads=T)
+                ts_["begin"].append(time.perf_counter() - t0)
+                items, flush_first, pres, sres, _, used = fr.emit_packets_host(packets, packet_first, b["senders_out"], nthreads=16)
+                t0 = time.perf_counter()
+                fr.resend_place_host(b["states_out"], b["results"], A, flush_first, items, nthreads=T)
+                ts_["place"].append(time.perf_counter() - t0)
+                frames, fres, frames_used = fr.pack_host(items, flush_first, flushes, nthreads=16)
+                frames = frames[:frames_used]
+                offs = np.zeros(frames_used + 1, dtype=np.uint64)
+                assert lib.ufc_build_sizes_host(frames.ctypes.data, items.ctypes.data, items.size, None, 1 << 40, frames_used,
+                                                offs.ctypes.data, None, 16) == 0
+                heap_mid = A["heap"].copy()
+                t0 = time.perf_counter()
+                cm = fr.resend_commit_host(fres, frames, offs, frames_used, items, flush_first, packets, packet_first, pres, sres,
+                                           b["results"], rate_r, b["states_out"], b["senders_out"], A, nthreads=T)
+                ts_["commit"].append(time.perf_counter() - t0)
+            host_ms[T] = {k_: float(np.median(v)) * 1e3 for k_, v in ts_.items()}
+        br, cr = b["results"], cm["results"]
+        n_items = int(used)
+        read = nq * (104 + 304 + 192 + 24 + 56 + 32 + 8) + LIVE * nq * 9 + K * nq * (16 + 24 + 1) + \
+            n_items * 24 * 3 + nq * (104 + 304 + 48 + 24 + 32 + 56) + nq * NEW * 32 + frames_used * 40 + K * nq * 16
+        written = nq * (104 + 304 + 48) + LIVE * nq + K * nq * 16 * 2 + n_items * 24 * 2 + nq * (104 + 304 + 40 + 8) + \
+            nq * NEW * 25 + n_items * 8 + frames_used * 24
+        t = lambda a, w=None: torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a).view(np.uint8).reshape(-1, w) if w  # noqa: E731
+                                               else (a.view(np.int64) if a.dtype == np.uint64 else a).copy()).to(dev)
+        host_final = {n_: A[n_].copy() for n_ in pristine}   # (what the host calls left, before the state goes up pristine)
+        restore_host()
+        g = {"heap": t(A["heap"], 16), "pkts": t(A["pkts"], 24), "frag_acked": t(A["frag_acked"]), "tx": t(A["tx"], 8),
+             "ref_acked": t(A["ref_acked"]), "stage": t(A["stage"], 24)}
+        g0 = {n_: g[n_].clone() for n_ in ("heap", "frag_acked", "ref_acked")}
+        d = {"infos": t(infos, 32), "ff": t(frame_first), "queues": t(queues, 192), "log": t(log, 24), "rate": t(rate_r, 56),
+             "flushes": t(flushes, 24), "states": t(states, 104), "senders": t(senders, 304), "packets": t(packets, 16),
+             "pf": t(packet_first), "pres": t(pres, 16), "sres": t(sres, 32), "fres": t(fres, 24), "frames": t(frames, 32),
+             "offs": t(offs), "used": torch.tensor([frames_used], dtype=torch.int64, device=dev), "flush_first": t(flush_first)}
+        restore = lambda: [g[n_].copy_(v) for n_, v in g0.items()]  # noqa: E731
+        rb = eng.resend_begin(d["infos"], d["ff"], d["queues"], d["log"], d["rate"], d["flushes"], d["states"], d["senders"], g)
+        items_d = t(E_fill(items, flush_first, br), 24)   # (the reserved slots empty, as the emit leaves them)
+        f_begin = lambda: eng.resend_begin(d["infos"], d["ff"], d["queues"], d["log"], d["rate"], d["flushes"], d["states"],  # noqa: E731
+                                           d["senders"], g, results=rb["results"], states_out=rb["states_out"],
+                                           senders_out=rb["senders_out"])
+        f_place = lambda: eng.resend_place(rb["states_out"], rb["results"], g, d["flush_first"], items_d)  # noqa: E731
+        torch.cuda.synchronize()
+        heap_mid_d = g["heap"].clone()
+        rc = eng.resend_commit(d["fres"], d["frames"], d["offs"], d["used"], t(items, 24), d["flush_first"], d["packets"], d["pf"],
+                               d["pres"], d["sres"], rb["results"], d["rate"], rb["states_out"], rb["senders_out"], g)
+        items_full = t(items, 24)
+        f_commit = lambda: eng.resend_commit(d["fres"], d["frames"], d["offs"], d["used"], items_full, d["flush_first"],  # noqa: E731
+                                             d["packets"], d["pf"], d["pres"], d["sres"], rb["results"], d["rate"],
+                                             rb["states_out"], rb["senders_out"], g, sent=rc["sent"], results=rc["results"],
+                                             states_out=rc["states_out"], retake=rc["retake"])
+        f_place()
+        torch.cuda.synchronize()
+        extra = {}
+        if CHECK:
+            same = lambda a, b_: bool(np.array_equal(a.cpu().numpy().reshape(-1), np.ascontiguousarray(b_).view(np.uint8).reshape(-1)))  # noqa: E731
+            pairs = (("begin results", rb["results"], br), ("begin states", rb["states_out"], b["states_out"]),
+                     ("begin senders", rb["senders_out"], b["senders_out"]), ("placed items", items_d, items),
+                     ("commit results", rc["results"], cr), ("commit states", rc["states_out"], cm["states_out"]),
+                     ("retake", rc["retake"], cm["retake"]), ("sent", rc["sent"], cm["sent"]), ("heap", g["heap"], host_final["heap"]),
+                     ("packet table", g["pkts"], A["pkts"]), ("ack bytes", g["frag_acked"], host_final["frag_acked"]),
+                     ("tx ring", g["tx"], A["tx"]), ("ref_acked", g["ref_acked"], host_final["ref_acked"]),
+                     ("heap after begin", heap_mid_d, heap_mid))
+            differs = [n_ for n_, x, y in pairs if not same(x, y)]
+            extra["equals_host"] = not differs
+            if differs:
+                extra["differs"] = differs
+        src = torch.zeros((read + written) // 2, dtype=torch.uint8, device=dev)
+        dst = torch.zeros_like(src)
+        restore_commit = lambda: g["heap"].copy_(heap_mid_d)  # noqa: E731
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.5:                             # (out of idle clocks)
+            restore()
+            f_begin()
+            f_place()
+            f_commit()
+            dst.copy_(src)
+            torch.cuda.synchronize()
+        s = torch.cuda.current_stream()
+        timed = {}
+        for what, f, pre in (("begin", f_begin, restore), ("place", f_place, lambda: None), ("commit", f_commit, restore_commit),
+                             ("copy", lambda: dst.copy_(src), lambda: None)):
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for e0, e1 in evs:
+                pre()
+                e0.record(s)
+                f()
+                e1.record(s)
+            torch.cuda.synchronize()
+            timed[what] = float(np.median([a.elapsed_time(b_) for a, b_ in evs]))
+        total = timed["begin"] + timed["place"] + timed["commit"]
+        out.append({"config": f"f11: device resend calls of one tick, {name} connections (8 heap entries each, a quarter due, "
+                              "a quarter acknowledged, a quarter of 16 live refs marked, one ack frame freeing 2 packets)",
+                    "connections": nq, "resent": int(br["n_resent"].sum()), "popped_dead": int(br["heap_popped_dead"].sum()),
+                    "popped_acked": int(br["heap_popped_acked"].sum()), "refs_acked": int(br["refs_acked"].sum()),
+                    "packets_freed": int(br["packets_freed"].sum()), "heap_pushed": int(cr["heap_pushed"].sum()),
+                    "items": n_items, "frames": int(frames_used), "stopped": int((br["stop"] != 0).sum() + (cr["stop"] != 0).sum()),
+                    "bytes_read": int(read), "bytes_written": int(written),
+                    "begin_ms": round(timed["begin"], 4), "place_ms": round(timed["place"], 4), "commit_ms": round(timed["commit"], 4),
+                    "three_calls_ms": round(total, 4), "ns_per_connection": round(total * 1e6 / nq, 3),
+                    "copy_ms": round(timed["copy"], 4), "calls_over_copy": round(total / timed["copy"], 2),
+                    "host_1t_ms": {k_: round(v, 3) for k_, v in host_ms[1].items()},
+                    "host_16t_ms": {k_: round(v, 3) for k_, v in host_ms[16].items()},
+                    "timing": "an event pair around each call, the heap, ack bytes and marks restored in front of it", **extra})
+        del g, g0, d, src, dst
+        torch.cuda.empty_cache()
+    with open(RESEND_OUT, "w") as f:
+        for r in out:
+            f.write(json.dumps(r) + "\n")
+    return out
+
+
+def E_fill(items, flush_first, begin_results):
+    """The emit's items with the reserved slots zeroed: what the device place call starts from."""
+    a = items.copy()
+    for c in np.nonzero(begin_results["n_resent"] + begin_results["n_pending_staged"])[0]:
+        f0 = int(flush_first[c])
+        a[f0: f0 + int(begin_results["n_resent"][c]) + int(begin_results["n_pending_staged"][c])] = 0
+    return a
+
+
 def host(eng, reps=5, n=1_000_000, L=1472):
     res = []
     for kind in ("pinned", "pageable"):
@@ -1110,7 +1310,7 @@ def main():
         if what == "host":
             for r in host(eng):
                 print(json.dumps(r), flush=True)
-        elif what in ("pack", "emit", "receive", "window", "queue", "rate"):
+        elif what in ("pack", "emit", "receive", "window", "queue", "rate", "resend"):
             for r in globals()[what](eng, dev, a.reps):
                 print(json.dumps(r), flush=True)
         else:

@@ -71,6 +71,18 @@ _RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, 
 _FW_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V]
 _FQ_ARGS = [_V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V]
 _RATE_BEGIN_ARGS = [_V, _V, _V, _Z, _V, _V]
+# ufc_resend_begin_*: infos, n_frames, frame_first, queues, log, n_log, rate, flags, flushes, states, senders, n, heap,
+# n_heap, pkts, n_pkts, frag_acked, n_frag, tx, n_tx, ref_acked, refs_cap, stage, n_stage, results, states_out,
+# senders_out
+_RS_BEGIN_ARGS = [_V, _Z, _V, _V, _V, _Z, _V, _V, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _V,
+                  _V]
+# ufc_resend_place_*: states, begin_results, n, stage, n_stage, flush_first, items, items_cap
+_RS_PLACE_ARGS = [_V, _V, _Z, _V, _Z, _V, _V, _Z]
+# ufc_resend_commit_*: flush_results, infos, n_infos, out_offsets, frames_used, items, n_items, flush_first, packets,
+# n_packets, packet_first, packet_results, sender_results, begin_results, rate, states, senders, n, heap, n_heap, pkts,
+# n_pkts, frag_acked, n_frag, tx, n_tx, sent, sent_cap, sent_first, next_extra_flags, results, states_out, retake
+_RS_COMMIT_ARGS = [_V, _V, _Z, _V, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _Z,
+                   _V, _Z, _V, _V, _V, _V, _V]
 _RATE_STEP_ARGS = [_V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
@@ -198,6 +210,13 @@ _SIGNATURES = {
     # flush_index, results, states_out, then nthreads (host) / ctx first and stream last (device)
     "ufc_rate_step_host": (ctypes.c_int, _RATE_STEP_ARGS + [ctypes.c_int]),
     "ufc_rate_step_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RATE_STEP_ARGS + [ctypes.c_void_p]),
+    # then nthreads (host) / ctx first and stream last (device)
+    "ufc_resend_begin_host": (ctypes.c_int, _RS_BEGIN_ARGS + [ctypes.c_int]),
+    "ufc_resend_begin_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RS_BEGIN_ARGS + [ctypes.c_void_p]),
+    "ufc_resend_place_host": (ctypes.c_int, _RS_PLACE_ARGS + [ctypes.c_int]),
+    "ufc_resend_place_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RS_PLACE_ARGS + [ctypes.c_void_p]),
+    "ufc_resend_commit_host": (ctypes.c_int, _RS_COMMIT_ARGS + [ctypes.c_int]),
+    "ufc_resend_commit_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RS_COMMIT_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 
@@ -350,6 +369,47 @@ class RateResult(ctypes.Structure):
                 ("rtt_ms", ctypes.c_uint64), ("rto_ms", ctypes.c_uint64), ("flush_alloc", ctypes.c_int64),
                 ("send_rate", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("inv_iterations", ctypes.c_uint32),
                 ("recv_count", ctypes.c_uint32)]
+
+
+class ResendEntry(ctypes.Structure):
+    _fields_ = [("resend_time_ms", ctypes.c_uint64), ("sequence_id", ctypes.c_uint32), ("fragment_id", ctypes.c_uint16),
+                ("send_count", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class SentPacket(ctypes.Structure):
+    _fields_ = [("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32), ("frag_first", ctypes.c_uint32),
+                ("sequence_id", ctypes.c_uint32), ("window_parent_lead", ctypes.c_uint16),
+                ("channel_parent_lead", ctypes.c_uint16), ("channel_id", ctypes.c_uint8), ("resend", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16)]
+
+
+class TxRef(ctypes.Structure):
+    _fields_ = [("sequence_id", ctypes.c_uint32), ("fragment_id", ctypes.c_uint16), ("flags", ctypes.c_uint16)]
+
+
+class Resend(ctypes.Structure):
+    _fields_ = [("heap_first", ctypes.c_uint64), ("heap_cap", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
+                ("pkt_first", ctypes.c_uint64), ("pkt_cap", ctypes.c_uint32), ("frag_next", ctypes.c_uint32),
+                ("frag_first", ctypes.c_uint64), ("frag_cap", ctypes.c_uint32), ("tx_cap", ctypes.c_uint32),
+                ("tx_first", ctypes.c_uint64), ("tx_head", ctypes.c_uint32), ("tx_tail", ctypes.c_uint32),
+                ("stage_first", ctypes.c_uint64), ("stage_cap", ctypes.c_uint32), ("pending_seq", ctypes.c_uint32),
+                ("pending_next", ctypes.c_uint32), ("pending_count", ctypes.c_uint32),
+                ("pending_resend", ctypes.c_uint8), ("reserved0", ctypes.c_uint8), ("reserved1", ctypes.c_uint16),
+                ("reserved2", ctypes.c_uint32), ("window_bytes", ctypes.c_uint64)]
+
+
+class ResendResult(ctypes.Structure):
+    _fields_ = [("stop", ctypes.c_uint32), ("n_resent", ctypes.c_uint32), ("n_pending_staged", ctypes.c_uint32),
+                ("heap_popped_dead", ctypes.c_uint32), ("heap_popped_acked", ctypes.c_uint32),
+                ("packets_freed", ctypes.c_uint32), ("refs_acked", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
+                ("pending_count", ctypes.c_uint32), ("acks_ignored", ctypes.c_uint32), ("bytes_freed", ctypes.c_uint64)]
+
+
+class ResendCommitResult(ctypes.Structure):
+    _fields_ = [("stop", ctypes.c_uint32), ("pending_packed", ctypes.c_uint32), ("packets_entered", ctypes.c_uint32),
+                ("heap_pushed", ctypes.c_uint32), ("heap_dropped", ctypes.c_uint32), ("refs_written", ctypes.c_uint32),
+                ("frames", ctypes.c_uint32), ("take", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
+                ("pending_count", ctypes.c_uint32)]
 
 
 class Builder(ctypes.Structure):

@@ -537,6 +537,131 @@ class FrameCrcEngine:
               "ufc_rate_step_varlen")
         return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
 
+    # ---- the resend calls around the emit and the pack, on the device (uflow_frame_codec.h) ----
+    _RS_ARENA_WIDTH = (("heap", 16), ("pkts", 24), ("frag_acked", 1), ("tx", 8), ("ref_acked", 1), ("stage", 24))
+
+    def _rs_arenas(self, arenas):
+        """(pointer, record count) of every resend arena, uint8 device tensors, in the C calls' order."""
+        out = {}
+        for name, width in self._RS_ARENA_WIDTH:
+            t = arenas.get(name)
+            self._check(name, t, (torch.uint8,), 0)
+            count = 0 if t is None else t.numel() // width
+            out[name] = (_ptr(t) if count else None, count)
+        return out
+
+    def resend_begin(self, infos, frame_first, queues, log, rate, flushes, states, senders, arenas, flags=None,
+                     results=None, states_out=None, senders_out=None, stream=None):
+        """ufc_resend_begin_varlen: behind rate_step, in front of emit_packets.  Ack propagation from ref_acked,
+        PacketSender::acknowledge for the ack frames, the resend loop (the heap and the pack's rule) and the pending
+        fragments' staging for every connection.  infos uint8[n_frames, 32], frame_first int64[n + 1], queues
+        uint8[n, 192] and log uint8[n_log, 24] as frame_queue left them, rate uint8[n, 56] (rate_step's results),
+        flushes uint8[n, 24] (the data flushes the pack gets), states uint8[n, 104], senders uint8[n, 304], arenas a
+        dict of uint8 tensors heap [., 16], pkts [., 24], frag_acked, tx [., 8], ref_acked, stage [., 24] (updated in
+        place), flags int32[n] or None.  Returns a dict: results uint8[n, 48], states_out, senders_out (may be given
+        as `states`, `senders`).  Layouts: uflow_amd.frame's RESEND_DTYPE and RESEND_RESULT_DTYPE."""
+        n_frames, n, n_log = infos.shape[0], states.shape[0], log.shape[0]
+        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._check("frame_first", frame_first, (torch.int64,), n + 1)
+        self._check("queues", queues, (torch.uint8,), 192 * n)
+        self._check("log", log, (torch.uint8,), 24 * n_log)
+        self._check("rate", rate, (torch.uint8,), 56 * n)
+        self._check("flushes", flushes, (torch.uint8,), 24 * n)
+        self._check("states", states, (torch.uint8,), 104 * n)
+        self._check("senders", senders, (torch.uint8,), 304 * n)
+        self._check("flags", flags, (torch.int32, torch.uint32), n)
+        self._check("results", results, (torch.uint8,), 48 * n)
+        self._check("states_out", states_out, (torch.uint8,), 104 * n)
+        self._check("senders_out", senders_out, (torch.uint8,), 304 * n)
+        A = self._rs_arenas(arenas)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if results is None:
+                results = torch.zeros((n, 48), dtype=torch.uint8, device=self.device)
+            if states_out is None:
+                states_out = torch.zeros((n, 104), dtype=torch.uint8, device=self.device)
+            if senders_out is None:
+                senders_out = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
+        check(lib().ufc_resend_begin_varlen(
+            self._ctx, _ptr(infos) if n_frames else None, n_frames, _ptr(frame_first), _ptr(queues) if n else None,
+            _ptr(log) if n_log else None, n_log, _ptr(rate) if n else None, _ptr(flags) if n else None,
+            _ptr(flushes) if n else None, _ptr(states) if n else None, _ptr(senders) if n else None, n, *A["heap"],
+            *A["pkts"], *A["frag_acked"], *A["tx"], *A["ref_acked"], *A["stage"], _ptr(results) if n else None,
+            _ptr(states_out) if n else None, _ptr(senders_out) if n else None, self._stream(stream)),
+            "ufc_resend_begin_varlen")
+        return {"results": results, "states_out": states_out, "senders_out": senders_out}
+
+    def resend_place(self, states, begin_results, arenas, flush_first, items, stream=None):
+        """ufc_resend_place_varlen: behind emit_packets.  Every connection's staged items into items[flush_first[c]
+        ..], the slots the emit reserved; items uint8[items_cap, 24] is written in place and returned."""
+        n = states.shape[0]
+        self._check("states", states, (torch.uint8,), 104 * n)
+        self._check("begin_results", begin_results, (torch.uint8,), 48 * n)
+        self._check("flush_first", flush_first, (torch.int64,), n + 1)
+        self._check("items", items, (torch.uint8,), 0)
+        A = self._rs_arenas(arenas)
+        items_cap = items.numel() // 24
+        check(lib().ufc_resend_place_varlen(self._ctx, _ptr(states) if n else None, _ptr(begin_results) if n else None,
+                                            n, *A["stage"], _ptr(flush_first), _ptr(items) if items_cap else None,
+                                            items_cap, self._stream(stream)), "ufc_resend_place_varlen")
+        return items
+
+    def resend_commit(self, flush_results, infos, out_offsets, frames_used, items, flush_first, packets, packet_first,
+                      packet_results, sender_results, begin_results, rate, states, senders, arenas, sent=None,
+                      next_extra_flags=None, results=None, states_out=None, retake=None, stream=None):
+        """ufc_resend_commit_varlen: behind pack_flushes over the data flushes (flush c = connection c) and
+        build_sizes.  flush_results uint8[n, 24], infos uint8[n_infos, 32] (the pack's frames), out_offsets
+        int64[n_infos + 1] (the size pass), frames_used int64[1] (the pack's), items uint8[n_items, 24], flush_first
+        int64[n + 1], packets uint8[n_packets, 16], packet_first int64[n + 1], packet_results uint8[n_packets, 16] and
+        sender_results uint8[n, 32] (the first emit's), begin_results uint8[n, 48], rate uint8[n, 56], states
+        uint8[n, 104], senders uint8[n, 304] (as resend_begin wrote them), arenas as in resend_begin (updated in
+        place), next_extra_flags int32[n] or None (in place).  Returns a dict: results uint8[n, 40], states_out, retake
+        (the second emit's senders), sent uint8[n_infos, 24], sent_first int64[n + 1], next_extra_flags."""
+        n, n_infos, n_items, n_packets = states.shape[0], infos.shape[0], items.shape[0], packets.shape[0]
+        self._check("flush_results", flush_results, (torch.uint8,), 24 * n)
+        self._check("infos", infos, (torch.uint8,), 32 * n_infos)
+        self._check("out_offsets", out_offsets, (torch.int64,), n_infos + 1)
+        self._check("frames_used", frames_used, (torch.int64,), 1)
+        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._check("flush_first", flush_first, (torch.int64,), n + 1)
+        self._check("packets", packets, (torch.uint8,), 16 * n_packets)
+        self._check("packet_first", packet_first, (torch.int64,), n + 1)
+        self._check("packet_results", packet_results, (torch.uint8,), 16 * n_packets)
+        self._check("sender_results", sender_results, (torch.uint8,), 32 * n)
+        self._check("begin_results", begin_results, (torch.uint8,), 48 * n)
+        self._check("rate", rate, (torch.uint8,), 56 * n)
+        self._check("states", states, (torch.uint8,), 104 * n)
+        self._check("senders", senders, (torch.uint8,), 304 * n)
+        self._check("sent", sent, (torch.uint8,), 0)
+        self._check("next_extra_flags", next_extra_flags, (torch.int32, torch.uint32), n)
+        self._check("results", results, (torch.uint8,), 40 * n)
+        self._check("states_out", states_out, (torch.uint8,), 104 * n)
+        self._check("retake", retake, (torch.uint8,), 304 * n)
+        A = self._rs_arenas(arenas)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            if sent is None:
+                sent = torch.zeros((n_infos, 24), dtype=torch.uint8, device=self.device)
+            if results is None:
+                results = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
+            if states_out is None:
+                states_out = torch.zeros((n, 104), dtype=torch.uint8, device=self.device)
+            if retake is None:
+                retake = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
+            sent_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        sent_cap = sent.numel() // 24
+        check(lib().ufc_resend_commit_varlen(
+            self._ctx, _ptr(flush_results) if n else None, _ptr(infos) if n_infos else None, n_infos, _ptr(out_offsets),
+            _ptr(frames_used), _ptr(items) if n_items else None, n_items, _ptr(flush_first),
+            _ptr(packets) if n_packets else None, n_packets, _ptr(packet_first),
+            _ptr(packet_results) if n_packets else None, _ptr(sender_results) if n else None,
+            _ptr(begin_results) if n else None, _ptr(rate) if n else None, _ptr(states) if n else None,
+            _ptr(senders) if n else None, n, *A["heap"], *A["pkts"], *A["frag_acked"], *A["tx"],
+            _ptr(sent) if sent_cap else None, sent_cap, _ptr(sent_first),
+            _ptr(next_extra_flags) if next_extra_flags is not None and n else None, _ptr(results) if n else None,
+            _ptr(states_out) if n else None, _ptr(retake) if n else None, self._stream(stream)),
+            "ufc_resend_commit_varlen")
+        return {"results": results, "states_out": states_out, "retake": retake, "sent": sent, "sent_first": sent_first,
+                "next_extra_flags": next_extra_flags}
+
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):
         """Seal every frame of a host CSR batch in place (GPU CRC, host trailer write); returns the CRCs."""

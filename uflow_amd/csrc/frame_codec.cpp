@@ -755,4 +755,73 @@ int ufc_rate_step_host(const ufc_rate_state* states, const ufc_rate_tick* ticks,
   return UFC_OK;
 }
 
+// ---- batched host resend ----
+int ufc_resend_begin_host(const ufc_frame_info* infos, size_t n_frames, const uint64_t* frame_first,
+                          const ufc_frame_queue* queues, const ufc_sent_frame* log, size_t n_log,
+                          const ufc_rate_result* rate, const uint32_t* flags, const ufc_flush* flushes,
+                          const ufc_resend* states, const ufc_sender* senders, size_t n, ufc_resend_entry* heap,
+                          size_t n_heap, const ufc_sent_packet* pkts, size_t n_pkts, uint8_t* frag_acked, size_t n_frag,
+                          const ufc_tx_ref* tx, size_t n_tx, uint8_t* ref_acked, size_t refs_cap, ufc_item* stage,
+                          size_t n_stage, ufc_resend_result* results, ufc_resend* states_out, ufc_sender* senders_out,
+                          int nthreads) {
+  if (n == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!frame_first || !queues || !rate || !flushes || !states || !senders || !results || !states_out || !senders_out ||
+      (!infos && n_frames) || (!log && n_log) || (!heap && n_heap) || (!pkts && n_pkts) || (!frag_acked && n_frag) ||
+      (!tx && n_tx) || (!stage && n_stage) || n >= lim || n_frames >= lim)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RsBeginArgs a{infos, n_frames, frame_first, queues, log, n_log, rate, flags, flushes, states, senders,
+                                 n, heap, n_heap, pkts, n_pkts, frag_acked, n_frag, tx, n_tx, ref_acked, refs_cap, stage,
+                                 n_stage, results, states_out, senders_out};
+  // The step the device runs; a connection touches its own regions and records, so the connections run in parallel.
+  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+    ufc_codec::RsWaveShared sh;
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_begin(ufc_codec::RsHostWave{}, sh, a, c);
+  });
+  return UFC_OK;
+}
+
+int ufc_resend_place_host(const ufc_resend* states, const ufc_resend_result* begin_results, size_t n,
+                          const ufc_item* stage, size_t n_stage, const uint64_t* flush_first, ufc_item* items,
+                          size_t items_cap, int nthreads) {
+  if (n == 0) return UFC_OK;
+  if (!states || !begin_results || !flush_first || (!stage && n_stage) || (!items && items_cap) ||
+      n >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RsPlaceArgs a{states, begin_results, n, stage, n_stage, flush_first, items, items_cap};
+  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_place(ufc_codec::RsHostWave{}, a, c);
+  });
+  return UFC_OK;
+}
+
+int ufc_resend_commit_host(const ufc_flush_result* flush_results, const ufc_frame_info* infos, size_t n_infos,
+                           const uint64_t* out_offsets, const uint64_t* frames_used, const ufc_item* items,
+                           size_t n_items, const uint64_t* flush_first, const ufc_packet* packets, size_t n_packets,
+                           const uint64_t* packet_first, const ufc_packet_result* packet_results,
+                           const ufc_sender_result* sender_results, const ufc_resend_result* begin_results,
+                           const ufc_rate_result* rate, const ufc_resend* states, const ufc_sender* senders, size_t n,
+                           ufc_resend_entry* heap, size_t n_heap, ufc_sent_packet* pkts, size_t n_pkts,
+                           uint8_t* frag_acked, size_t n_frag, ufc_tx_ref* tx, size_t n_tx, ufc_sent_frame* sent,
+                           size_t sent_cap, uint64_t* sent_first, uint32_t* next_extra_flags,
+                           ufc_resend_commit_result* results, ufc_resend* states_out, ufc_sender* retake, int nthreads) {
+  if (n == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!flush_results || !out_offsets || !frames_used || !flush_first || !packet_first || !sender_results ||
+      !begin_results || !rate || !states || !senders || !sent_first || !results || !states_out || !retake ||
+      (!infos && n_infos) || (!items && n_items) || (!packets && n_packets) || (!packet_results && n_packets) ||
+      (!heap && n_heap) || (!pkts && n_pkts) || (!frag_acked && n_frag) || (!tx && n_tx) || (!sent && sent_cap) ||
+      n >= lim || n_packets >= lim || n_items >= lim || n_infos >= lim)
+    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RsCommitArgs a{flush_results, infos, n_infos, out_offsets, frames_used, items, n_items, flush_first,
+                                  packets, n_packets, packet_first, packet_results, sender_results, begin_results, rate,
+                                  states, senders, n, heap, n_heap, pkts, n_pkts, frag_acked, n_frag, tx, n_tx, sent,
+                                  sent_cap, sent_first, next_extra_flags, results, states_out, retake};
+  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+    ufc_codec::RsWaveShared sh;
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_commit(ufc_codec::RsHostWave{}, sh, a, c);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

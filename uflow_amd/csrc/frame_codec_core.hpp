@@ -2612,4 +2612,719 @@ inline __host__ __device__ void rate_begin(ufc_rate_state& S, uint64_t now, uint
   S.reset_loss_rate = 0.0;
 }
 
+// ---- batched resend (ufc_resend_begin_*, ufc_resend_place_*, ufc_resend_commit_*) ----
+// PacketSender::acknowledge (packet_sender.rs:242-275), the resend queue (resend_queue.rs over std's BinaryHeap),
+// the pending queue and emit_data_frames (half_connection/mod.rs:335-432); the rules are in
+// include/uflow_frame_codec.h.  Written once against a wave policy, as fq_step is, with two additions:
+//   Wv::sum(f)   the sum of f(lane) over the 64 lanes, the same in every lane
+//   Wv::sync()   what Wv::one wrote (to memory or to `sh`) is visible to every lane after it
+// One wave runs a connection.  The running state (ids, alloc, counters) is the same in every lane; the heap and the
+// pack rule are a dependent chain and run inside Wv::one; everything that touches a run of records takes a lane per
+// record: the live refs, the slots acknowledge frees, the pending fragments' items, commit's table entries, ack
+// bytes and refs.
+
+// DataFrameEmitter::push and finalize as a state machine (emit.rs:47-125; steps 1-4 of the ufc_flush comment): what
+// the batched packs compute in closed form, item by item, for a caller that has to decide after each push.
+struct PackRun {
+  int64_t alloc;   // flush_alloc
+  uint64_t s;      // the frame in progress with its overhead; 0 = none
+  uint32_t frames; // frames finalized
+  uint32_t cnt;    // items in the frame in progress
+};
+UFC_HD PackRun pack_run_begin(const ufc_flush& fl) { return PackRun{fl.flush_alloc, 0, 0, 0}; }
+UFC_HD void pack_finalize(PackRun& r) {
+  if (r.s == 0) return;
+  r.frames++;
+  r.alloc = (int64_t)((uint64_t)r.alloc - r.s);
+  r.s = 0;
+  r.cnt = 0;
+}
+// UFC_PACK_DONE when the item (e encoded bytes) went in, else why the flush stops at it.
+UFC_HD uint32_t pack_push(PackRun& r, const ufc_flush& fl, bool ack, uint64_t e) {
+  if (r.s) {
+    if (r.alloc < (int64_t)r.s) {  // :64-68
+      pack_finalize(r);
+      return UFC_PACK_SIZE_LIMITED;
+    }
+    if (pack_frame_takes(r.s, r.cnt, e, pack_max_count(ack))) {
+      r.s += e;
+      r.cnt++;
+      return UFC_PACK_DONE;
+    }
+    pack_finalize(r);  // :69-71
+  }
+  if (r.alloc < 0) return UFC_PACK_SIZE_LIMITED;                       // :83-87
+  if (!ack && r.frames >= fl.window_room) return UFC_PACK_WINDOW_LIMITED;  // :89-92
+  r.s = pack_overhead(ack) + e;
+  r.cnt = 1;
+  return UFC_PACK_DONE;
+}
+
+// std's BinaryHeap over d[0 .. len), Ord reversed on resend_time (resend_queue.rs:20-38): "a <= b".
+UFC_HD bool rs_le(const ufc_resend_entry& x, const ufc_resend_entry& y) { return x.resend_time_ms >= y.resend_time_ms; }
+inline __host__ __device__ void rs_sift_up(ufc_resend_entry* d, uint32_t start, uint32_t pos) {
+  const ufc_resend_entry elem = d[pos];
+  while (pos > start) {
+    const uint32_t parent = (pos - 1) / 2;
+    if (rs_le(elem, d[parent])) break;
+    d[pos] = d[parent];
+    pos = parent;
+  }
+  d[pos] = elem;
+}
+inline __host__ __device__ void rs_heap_push(ufc_resend_entry* d, uint32_t& len, const ufc_resend_entry& x) {
+  d[len] = x;
+  len++;
+  rs_sift_up(d, 0, len - 1);
+}
+inline __host__ __device__ ufc_resend_entry rs_heap_pop(ufc_resend_entry* d, uint32_t& len) {  // len > 0
+  len--;
+  ufc_resend_entry item = d[len];
+  if (len > 0) {
+    const ufc_resend_entry root = d[0];
+    // sift_down_to_bottom(0) of the old last entry, then sift_up
+    const uint32_t end = len;
+    uint32_t pos = 0, child = 1;
+    while (child + 1 < end) {
+      child += rs_le(d[child], d[child + 1]) ? 1u : 0u;
+      d[pos] = d[child];
+      pos = child;
+      child = 2 * pos + 1;
+    }
+    if (child == end - 1) {
+      d[pos] = d[child];
+      pos = child;
+    }
+    d[pos] = item;
+    rs_sift_up(d, 0, pos);
+    item = root;
+  }
+  return item;
+}
+UFC_HD ufc_resend_entry rs_entry(uint64_t t, uint32_t seq, uint32_t frag, uint8_t count) {
+  ufc_resend_entry e{};
+  e.resend_time_ms = t;
+  e.sequence_id = seq;
+  e.fragment_id = (uint16_t)frag;
+  e.send_count = count;
+  return e;
+}
+
+struct RsBeginArgs {
+  const ufc_frame_info* infos;
+  uint64_t n_frames;
+  const uint64_t* frame_first;
+  const ufc_frame_queue* queues;
+  const ufc_sent_frame* log;
+  uint64_t n_log;
+  const ufc_rate_result* rate;
+  const uint32_t* flags;
+  const ufc_flush* flushes;
+  const ufc_resend* states;
+  const ufc_sender* senders;
+  uint64_t n;
+  ufc_resend_entry* heap;
+  uint64_t n_heap;
+  const ufc_sent_packet* pkts;
+  uint64_t n_pkts;
+  uint8_t* frag_acked;
+  uint64_t n_frag;
+  const ufc_tx_ref* tx;
+  uint64_t n_tx;
+  uint8_t* ref_acked;
+  uint64_t refs_cap;
+  ufc_item* stage;
+  uint64_t n_stage;
+  ufc_resend_result* results;
+  ufc_resend* states_out;
+  ufc_sender* senders_out;
+};
+
+struct RsPlaceArgs {
+  const ufc_resend* states;
+  const ufc_resend_result* begin_results;
+  uint64_t n;
+  const ufc_item* stage;
+  uint64_t n_stage;
+  const uint64_t* flush_first;
+  ufc_item* items;
+  uint64_t items_cap;
+};
+
+struct RsCommitArgs {
+  const ufc_flush_result* flush_results;
+  const ufc_frame_info* infos;
+  uint64_t n_infos;
+  const uint64_t* out_offsets;
+  const uint64_t* frames_used;
+  const ufc_item* items;
+  uint64_t n_items;
+  const uint64_t* flush_first;
+  const ufc_packet* packets;
+  uint64_t n_packets;
+  const uint64_t* packet_first;
+  const ufc_packet_result* packet_results;
+  const ufc_sender_result* sender_results;
+  const ufc_resend_result* begin_results;
+  const ufc_rate_result* rate;
+  const ufc_resend* states;
+  const ufc_sender* senders;
+  uint64_t n;
+  ufc_resend_entry* heap;
+  uint64_t n_heap;
+  ufc_sent_packet* pkts;
+  uint64_t n_pkts;
+  uint8_t* frag_acked;
+  uint64_t n_frag;
+  ufc_tx_ref* tx;
+  uint64_t n_tx;
+  ufc_sent_frame* sent;
+  uint64_t sent_cap;
+  uint64_t* sent_first;
+  uint32_t* next_extra_flags;
+  ufc_resend_commit_result* results;
+  ufc_resend* states_out;
+  ufc_sender* retake;
+};
+
+struct RsWaveShared {
+  uint32_t chan_parent[UFC_MAX_CHANNELS];
+  // written by Wv::one, read by all behind Wv::sync
+  uint32_t stop, n_resent, dead, acked, heap_len, pushed, dropped;
+};
+
+UFC_HD bool rs_pow2(uint32_t v) { return v != 0 && (v & (v - 1)) == 0; }
+UFC_HD bool rs_region_ok(uint64_t first, uint64_t cap, uint64_t n) { return first <= n && n - first >= cap; }
+// The checks of the header comment that begin and commit share.
+UFC_HD bool rs_state_ok(const ufc_resend& R, const ufc_sender& S, uint64_t n_heap, uint64_t n_pkts, uint64_t n_frag,
+                        uint64_t n_tx, uint64_t n_stage, bool with_stage) {
+  if (!rs_pow2(R.pkt_cap) || !rs_pow2(R.frag_cap) || !rs_pow2(R.tx_cap)) return false;
+  if (S.window_size == 0 || S.window_size > kPacketIdMask + 1 || R.pkt_cap < S.window_size) return false;
+  if (emit_max_alloc(S.max_alloc) / UFC_MAX_FRAGMENT_SIZE + S.window_size > R.frag_cap) return false;
+  if (n_tx > 0x100000000ull) return false;
+  if (!rs_region_ok(R.heap_first, R.heap_cap, n_heap) || !rs_region_ok(R.pkt_first, R.pkt_cap, n_pkts) ||
+      !rs_region_ok(R.frag_first, R.frag_cap, n_frag) || !rs_region_ok(R.tx_first, R.tx_cap, n_tx) ||
+      (with_stage && !rs_region_ok(R.stage_first, R.stage_cap, n_stage)))
+    return false;
+  if (R.heap_len > R.heap_cap || R.tx_head - R.tx_tail > R.tx_cap) return false;
+  return true;
+}
+// One Entry of the frame log as commit hands it to the next tick's push (written field by field: no record on the
+// stack).
+UFC_HD void rs_put_sent(ufc_sent_frame& o, uint64_t now, uint32_t size, uint32_t ref_first, uint32_t ref_count, uint32_t aux) {
+  o.send_time_ms = now;
+  o.size = size;
+  o.ref_first = ref_first;
+  o.ref_count = ref_count;
+  o.flags = (aux & 1) ? UFC_SENT_NONCE : 0;
+  o.reserved[0] = 0;
+  o.reserved[1] = 0;
+  o.reserved[2] = 0;
+}
+// A state record written field by field (a whole-record copy keeps its untouched bytes on the stack).
+UFC_HD void rs_put_state(ufc_resend& o, const ufc_resend& r) {
+  o.heap_first = r.heap_first;
+  o.heap_cap = r.heap_cap;
+  o.heap_len = r.heap_len;
+  o.pkt_first = r.pkt_first;
+  o.pkt_cap = r.pkt_cap;
+  o.frag_next = r.frag_next;
+  o.frag_first = r.frag_first;
+  o.frag_cap = r.frag_cap;
+  o.tx_cap = r.tx_cap;
+  o.tx_first = r.tx_first;
+  o.tx_head = r.tx_head;
+  o.tx_tail = r.tx_tail;
+  o.stage_first = r.stage_first;
+  o.stage_cap = r.stage_cap;
+  o.pending_seq = r.pending_seq;
+  o.pending_next = r.pending_next;
+  o.pending_count = r.pending_count;
+  o.pending_resend = r.pending_resend;
+  o.reserved0 = r.reserved0;
+  o.reserved1 = r.reserved1;
+  o.reserved2 = r.reserved2;
+  o.window_bytes = r.window_bytes;
+}
+// A ufc_sender without its channel parents (they go lane by lane).
+struct RsSenderHead {
+  uint32_t base_id, next_id, window_size, flush_id;
+  uint64_t alloc, max_alloc;
+  uint32_t window_parent_id, take, reserve_items, reserved;
+};
+UFC_HD void rs_put_sender(ufc_sender& O, const RsSenderHead& h) {
+  O.base_id = h.base_id;
+  O.next_id = h.next_id;
+  O.window_size = h.window_size;
+  O.flush_id = h.flush_id;
+  O.alloc = h.alloc;
+  O.max_alloc = h.max_alloc;
+  O.window_parent_id = h.window_parent_id;
+  O.take = h.take;
+  O.reserve_items = h.reserve_items;
+  O.reserved = h.reserved;
+}
+// PendingPacket::datagram of a table packet (pending_packet.rs:84-103), as the emit makes its items.
+UFC_HD ufc_item rs_item(const ufc_sent_packet& k, uint32_t seq, uint32_t f) {
+  ufc_packet p{};
+  p.data_offset = k.data_offset;
+  p.data_len = k.data_len;
+  p.channel_id = k.channel_id;
+  return emit_item(p, seq, k.window_parent_lead, k.channel_parent_lead, f, emit_fragment_count(k.data_len) - 1);
+}
+
+template <class Wv>
+inline __host__ __device__ void rs_begin(const Wv& wv, RsWaveShared& sh, const RsBeginArgs& a, uint64_t c) {
+  // (read in place: the outputs, which may be the inputs, are written last, behind every read)
+  const ufc_resend R = a.states[c];
+  const ufc_sender& S = a.senders[c];
+  const ufc_frame_queue& Q = a.queues[c];
+  const uint64_t ff0 = a.frame_first[c], ff1 = a.frame_first[c + 1];
+  const uint32_t window_size = S.window_size, flush_id = S.flush_id, in_take = S.take, s_reserved = S.reserved;
+  const uint64_t max_alloc = S.max_alloc;
+  uint32_t base = S.base_id, wparent = S.window_parent_id;
+  const uint32_t next = S.next_id;
+  uint64_t alloc = S.alloc;
+  wv.lanes([&](uint32_t lane) { sh.chan_parent[lane] = S.channel_parent_id[lane]; });
+  bool ok = rs_state_ok(R, S, a.n_heap, a.n_pkts, a.n_frag, a.n_tx, a.n_stage, true) && ff0 <= ff1 && ff1 <= a.n_frames &&
+            rs_pow2(Q.log_cap) && rs_region_ok(Q.log_first, Q.log_cap, a.n_log) &&
+            ((uint64_t)Q.window_size + Q.tail_size + 1) * UFC_DATA_FRAME_MAX_DATAGRAM_COUNT <= R.tx_cap;
+  if (!ok) {  // (every lane takes this branch or none)
+    wv.lanes([&](uint32_t lane) { a.senders_out[c].channel_parent_id[lane] = sh.chan_parent[lane]; });
+    wv.one([&]() {
+      ufc_resend_result res{};
+      res.stop = UFC_RS_BAD_STATE;
+      a.results[c] = res;
+      rs_put_state(a.states_out[c], R);
+      rs_put_sender(a.senders_out[c], RsSenderHead{base, next, window_size, flush_id, alloc, max_alloc, wparent, 0, 0, s_reserved});
+    });
+    return;
+  }
+  const uint32_t pmask = R.pkt_cap - 1, fmask = R.frag_cap - 1, tmask = R.tx_cap - 1;
+  const ufc_sent_packet* pk = a.pkts + R.pkt_first;
+  uint8_t* fa = a.frag_acked + R.frag_first;
+  // 1. ack propagation over the live refs, then the tail
+  uint32_t refs_acked = 0;
+  const uint32_t live = R.tx_head - R.tx_tail;
+  if (a.ref_acked) {
+    const uint32_t span0 = packet_id_sub(next, base);
+    for (uint32_t t = 0; t < live; t += 64)
+      refs_acked += (uint32_t)wv.sum([&](uint32_t lane) -> uint64_t {
+        const uint32_t j = t + lane;
+        if (j >= live) return 0;
+        const uint64_t r = R.tx_first + ((R.tx_tail + j) & tmask);
+        if (r >= a.refs_cap || a.ref_acked[r] == 0) return 0;
+        a.ref_acked[r] = 0;
+        const ufc_tx_ref ref = a.tx[r];
+        if (!(ref.flags & UFC_TX_RESEND) || packet_id_sub(ref.sequence_id, base) >= span0) return 0;
+        const ufc_sent_packet k = pk[ref.sequence_id & pmask];
+        if (ref.fragment_id >= emit_fragment_count(k.data_len)) return 0;
+        fa[(k.frag_first + ref.fragment_id) & fmask] = 1;
+        return 1;
+      });
+  }
+  uint32_t tail = R.tx_head;
+  if (Q.log_next_id != Q.log_base_id) {
+    const uint64_t rf = a.log[Q.log_first + (Q.log_base_id & (Q.log_cap - 1))].ref_first;
+    tail = (rf >= R.tx_first && rf - R.tx_first < R.tx_cap) ? R.tx_head - ((R.tx_head - (uint32_t)(rf - R.tx_first)) & tmask)
+                                                           : R.tx_tail;
+  }
+  // 2. acknowledge for the ack frames in arrival order
+  uint32_t freed = 0, ignored = 0;
+  uint64_t bytes_freed = 0, window_bytes = R.window_bytes;
+  for (uint64_t t0 = ff0; t0 < ff1; t0 += 64) {
+    const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
+    unsigned long long acks = wv.ballot([&](uint32_t lane) { return lane < nv && fq_is_ack(a.infos[t0 + lane]); });
+    for (; acks; acks &= acks - 1) {
+      const uint32_t rb = a.infos[t0 + fw_low_bit(acks)].f[1];
+      const uint32_t delta = packet_id_sub(rb, base), span = packet_id_sub(next, base);
+      if (rb > kPacketIdMask || delta > span) {  // :246
+        ignored++;
+        continue;
+      }
+      for (uint32_t t = 0; t < delta; t += 64) {
+        const uint32_t m = delta - t < 64 ? delta - t : 64u, first = packet_id_add(base, t);
+        if (wv.ballot([&](uint32_t lane) { return lane < m && wparent == packet_id_add(first, lane); })) wparent = UFC_NO_PARENT;
+        alloc -= wv.sum([&](uint32_t lane) -> uint64_t {
+          return lane < m ? emit_alloc_size(pk[packet_id_add(first, lane) & pmask].data_len) : 0;
+        });
+        const uint64_t len = wv.sum([&](uint32_t lane) -> uint64_t {
+          return lane < m ? pk[packet_id_add(first, lane) & pmask].data_len : 0;
+        });
+        window_bytes -= len;
+        bytes_freed += len;
+        wv.lanes([&](uint32_t lane) {  // (one id matches a channel's parent at most)
+          if (lane >= m) return;
+          const uint32_t id = packet_id_add(first, lane), ch = pk[id & pmask].channel_id & (UFC_MAX_CHANNELS - 1);
+          if (sh.chan_parent[ch] == id) sh.chan_parent[ch] = UFC_NO_PARENT;
+        });
+      }
+      freed += delta;
+      base = rb;
+    }
+  }
+  // 3. the resend loop, in one lane
+  const bool no_flush = a.flags && (a.flags[c] & UFC_RS_NO_DATA_FLUSH);
+  const uint64_t now = a.rate[c].now_ms, rtt = a.rate[c].rtt_ms;
+  const uint32_t span = packet_id_sub(next, base);
+  ufc_item* stage = a.stage + R.stage_first;
+  wv.one([&]() {
+    ufc_resend_entry* d = a.heap + R.heap_first;
+    const ufc_flush fl = a.flushes[c];
+    PackRun run = pack_run_begin(fl);
+    uint32_t len = R.heap_len, n = 0, stop = UFC_RS_DONE, dead = 0, acked = 0;
+    while (!no_flush && len > 0) {
+      const ufc_resend_entry e = d[0];
+      if (packet_id_sub(e.sequence_id, base) >= span) {  // Weak::upgrade fails, :379-382
+        rs_heap_pop(d, len);
+        dead++;
+        continue;
+      }
+      const ufc_sent_packet k = pk[e.sequence_id & pmask];
+      if (fa[(k.frag_first + e.fragment_id) & fmask]) {  // :355-358
+        rs_heap_pop(d, len);
+        acked++;
+        continue;
+      }
+      if (e.resend_time_ms > now) break;  // :360
+      if (n >= R.stage_cap) {
+        stop = UFC_RS_STAGE_FULL;
+        break;
+      }
+      const ufc_item it = rs_item(k, e.sequence_id, e.fragment_id);
+      const uint32_t st = pack_push(run, fl, false, datagram_encoded_size(it));
+      if (st != UFC_PACK_DONE) {
+        stop = st == UFC_PACK_SIZE_LIMITED ? UFC_RS_SIZE_LIMITED : UFC_RS_WINDOW_LIMITED;
+        break;
+      }
+      stage[n++] = it;
+      ufc_resend_entry x = rs_heap_pop(d, len);  // :371-378
+      x.resend_time_ms = now + rtt * ((uint64_t)1 << (x.send_count & 63u));
+      const uint8_t up = (uint8_t)(x.send_count + 1);
+      x.send_count = up < 2 ? up : (uint8_t)2;
+      rs_heap_push(d, len, x);
+    }
+    sh.stop = stop;
+    sh.n_resent = n;
+    sh.dead = dead;
+    sh.acked = acked;
+    sh.heap_len = len;
+  });
+  wv.sync();
+  uint32_t stop = sh.stop, n_pending = 0;
+  const uint32_t n_resent = sh.n_resent;
+  // 4. the pending front, then the pending fragments' items
+  if (stop == UFC_RS_DONE && !no_flush && R.pending_count) {
+    const ufc_sent_packet k = pk[R.pending_seq & pmask];
+    if (packet_id_sub(R.pending_seq, base) >= span || fa[(k.frag_first + R.pending_next) & fmask]) {
+      stop = UFC_RS_REF_HANG;
+    } else if ((uint64_t)n_resent + R.pending_count > R.stage_cap) {
+      stop = UFC_RS_STAGE_FULL;
+    } else {
+      n_pending = R.pending_count;
+      for (uint32_t t = 0; t < n_pending; t += 64)
+        wv.lanes([&](uint32_t lane) {
+          const uint32_t j = t + lane;
+          if (j < n_pending) stage[n_resent + j] = rs_item(k, R.pending_seq, R.pending_next + j);
+        });
+    }
+  }
+  // 5. the outputs
+  wv.lanes([&](uint32_t lane) { a.senders_out[c].channel_parent_id[lane] = sh.chan_parent[lane]; });
+  wv.one([&]() {
+    ufc_resend_result res{};
+    res.stop = stop;
+    res.n_resent = n_resent;
+    res.n_pending_staged = n_pending;
+    res.heap_popped_dead = sh.dead;
+    res.heap_popped_acked = sh.acked;
+    res.packets_freed = freed;
+    res.refs_acked = refs_acked;
+    res.heap_len = sh.heap_len;
+    res.pending_count = R.pending_count;
+    res.acks_ignored = ignored;
+    res.bytes_freed = bytes_freed;
+    a.results[c] = res;
+    ufc_resend& O = a.states_out[c];
+    rs_put_state(O, R);
+    O.heap_len = sh.heap_len;
+    O.tx_tail = tail;
+    O.window_bytes = window_bytes;
+    rs_put_sender(a.senders_out[c], RsSenderHead{base, next, window_size, flush_id, alloc, max_alloc, wparent,
+                                                 (stop == UFC_RS_DONE && !no_flush) ? in_take : 0u, n_resent + n_pending,
+                                                 s_reserved});
+  });
+}
+
+// One connection's staged items into the slots the emit reserved; lanes over the items.
+template <class Wv>
+inline __host__ __device__ void rs_place(const Wv& wv, const RsPlaceArgs& a, uint64_t c) {
+  const ufc_resend& R = a.states[c];
+  const ufc_resend_result& B = a.begin_results[c];
+  if (B.stop == UFC_RS_BAD_STATE || !rs_region_ok(R.stage_first, R.stage_cap, a.n_stage)) return;
+  const uint64_t f0 = a.flush_first[c], f1 = a.flush_first[c + 1];
+  if (f1 < f0) return;
+  uint64_t n = (uint64_t)B.n_resent + B.n_pending_staged;
+  if (n > R.stage_cap) n = R.stage_cap;
+  if (n > f1 - f0) n = f1 - f0;
+  for (uint64_t t = 0; t < n; t += 64)
+    wv.lanes([&](uint32_t lane) {
+      const uint64_t j = t + lane;
+      if (j < n && f0 + j < a.items_cap) a.items[f0 + j] = a.stage[R.stage_first + j];
+    });
+}
+
+template <class Wv>
+inline __host__ __device__ void rs_commit(const Wv& wv, RsWaveShared& sh, const RsCommitArgs& a, uint64_t c) {
+  const ufc_resend R = a.states[c];
+  const ufc_sender& S = a.senders[c];
+  const ufc_resend_result B = a.begin_results[c];
+  // (scalars, not the record: a record that lambdas capture stays on the stack)
+  const uint32_t f_first = a.flush_results[c].frame_first, f_count = a.flush_results[c].frame_count;
+  const uint32_t f_packed = a.flush_results[c].items_packed, f_stop = a.flush_results[c].stop;
+  const ufc_sender_result SR = a.sender_results[c];
+  const uint64_t pf0 = a.packet_first[c], pf1 = a.packet_first[c + 1], if0 = a.flush_first[c], if1 = a.flush_first[c + 1];
+  const uint64_t now = a.rate[c].now_ms, rtt = a.rate[c].rtt_ms;
+  const uint32_t staged = B.n_resent + B.n_pending_staged;
+  const bool frames_ok = (uint64_t)f_first + f_count <= a.n_infos;
+  bool ok = rs_state_ok(R, S, a.n_heap, a.n_pkts, a.n_frag, a.n_tx, 0, false) && B.stop != UFC_RS_BAD_STATE && frames_ok &&
+            pf0 <= pf1 && pf1 <= a.n_packets && SR.packets_consumed <= pf1 - pf0 && if0 <= if1 && if1 <= a.n_items &&
+            staged <= if1 - if0 && f_packed >= B.n_resent && f_packed <= if1 - if0 &&
+            B.n_pending_staged <= R.pending_count;
+  const uint32_t m = ok ? f_packed - B.n_resent : 0;
+  const uint32_t pp = m < B.n_pending_staged ? m : B.n_pending_staged, q = m - pp;
+  const uint32_t pending_left = R.pending_count - (ok ? pp : 0);
+  if (ok && pending_left && q) ok = false;  // new items packed behind unpacked pending ones
+  // retake: the sender as begin left it, with the take the reference's loop got to
+  wv.lanes([&](uint32_t lane) { sh.chan_parent[lane] = S.channel_parent_id[lane]; });
+  // (the fixed fields; the parents go through sh)
+  RsSenderHead T{S.base_id, S.next_id, S.window_size, S.flush_id, S.alloc, S.max_alloc, S.window_parent_id, 0, 0, S.reserved};
+  const auto put_sender = [&]() {
+    wv.lanes([&](uint32_t lane) { a.retake[c].channel_parent_id[lane] = sh.chan_parent[lane]; });
+    wv.one([&]() { rs_put_sender(a.retake[c], T); });
+  };
+  wv.one([&]() {
+    a.sent_first[c] = f_first;
+    if (c + 1 == a.n) a.sent_first[a.n] = *a.frames_used;
+  });
+  const bool limited = f_stop == UFC_PACK_SIZE_LIMITED || B.stop == UFC_RS_SIZE_LIMITED;
+  if (!ok) {
+    if (frames_ok)
+      for (uint32_t t = 0; t < f_count; t += 64)
+        wv.lanes([&](uint32_t lane) {
+          const uint64_t g = (uint64_t)f_first + t + lane;
+          if (t + lane >= f_count || g >= a.sent_cap) return;
+          rs_put_sent(a.sent[g], now, (uint32_t)(a.out_offsets[g + 1] - a.out_offsets[g]), 0, 0, a.infos[g].aux);
+        });
+    put_sender();
+    wv.one([&]() {
+      ufc_resend_commit_result res{};
+      res.stop = UFC_RS_BAD_STATE;
+      res.heap_len = R.heap_len;
+      res.pending_count = R.pending_count;
+      a.results[c] = res;
+      rs_put_state(a.states_out[c], R);
+      if (a.next_extra_flags)
+        a.next_extra_flags[c] = (a.next_extra_flags[c] & ~(uint32_t)UFC_FQ_MARK_RATE_LIMITED) |
+                                (limited ? (uint32_t)UFC_FQ_MARK_RATE_LIMITED : 0u);
+    });
+    return;
+  }
+  const uint32_t pmask = R.pkt_cap - 1, fmask = R.frag_cap - 1, tmask = R.tx_cap - 1;
+  ufc_sent_packet* pk = a.pkts + R.pkt_first;
+  uint8_t* fa = a.frag_acked + R.frag_first;
+  const uint64_t new0 = if0 + staged, first_unpacked = new0 + q;
+  // the stopping packet p and the packets that enter the table
+  uint32_t take = 0, entered = 0, frag_next = R.frag_next;
+  uint32_t pend_seq = R.pending_seq, pend_next = R.pending_next + pp, pend_count = pending_left;
+  uint8_t pend_resend = R.pending_resend;
+  uint64_t window_bytes = R.window_bytes;
+  if (pending_left == 0) {
+    take = SR.packets_consumed;
+    uint64_t enter_end = if1;
+    if (first_unpacked < if1) {
+      for (uint32_t t = 0; t < SR.packets_consumed; t += 64) {
+        const unsigned long long hit = wv.ballot([&](uint32_t lane) {
+          if (t + lane >= SR.packets_consumed) return false;
+          const ufc_packet_result r = a.packet_results[pf0 + t + lane];
+          return r.status == UFC_PACKET_EMITTED && (uint64_t)r.item_first + r.item_count > first_unpacked;
+        });
+        if (hit) {
+          const uint32_t p = t + fw_low_bit(hit);
+          const ufc_packet_result r = a.packet_results[pf0 + p];
+          take = p + 1;
+          enter_end = (uint64_t)r.item_first + r.item_count;
+          pend_seq = r.sequence_id;
+          pend_next = (uint32_t)(first_unpacked - r.item_first);
+          pend_count = (uint32_t)(enter_end - first_unpacked);
+          pend_resend = r.resend ? 1 : 0;
+          break;
+        }
+      }
+    }
+    if (pend_count == 0) {
+      pend_seq = 0;
+      pend_next = 0;
+      pend_resend = 0;
+    }
+    for (uint32_t t = 0; t < take; t += 64) {
+      // (status NOT_REACHED = 0 marks a lane with no packet to enter)
+      const auto emitted = [&](uint32_t lane) {
+        ufc_packet_result r{};
+        if (t + lane >= take) return r;
+        r = a.packet_results[pf0 + t + lane];
+        if (r.status != UFC_PACKET_EMITTED || r.item_first < new0 || (uint64_t)r.item_first + r.item_count > enter_end)
+          r.status = UFC_PACKET_NOT_REACHED;
+        return r;
+      };
+      entered += (uint32_t)wv.sum([&](uint32_t lane) -> uint64_t { return emitted(lane).status ? 1 : 0; });
+      window_bytes += wv.sum([&](uint32_t lane) -> uint64_t {
+        return emitted(lane).status ? a.packets[pf0 + t + lane].data_len : 0;
+      });
+      wv.lanes([&](uint32_t lane) {
+        const ufc_packet_result r = emitted(lane);
+        if (!r.status) return;
+        const ufc_packet p = a.packets[pf0 + t + lane];
+        const ufc_item& it = a.items[r.item_first];  // (read in place: only the leads are used)
+        ufc_sent_packet& k = pk[r.sequence_id & pmask];  // (field by field: no record on the stack)
+        k.data_offset = p.data_offset;
+        k.data_len = p.data_len;
+        k.frag_first = R.frag_next + (uint32_t)(r.item_first - new0);
+        k.sequence_id = r.sequence_id;
+        k.window_parent_lead = it.window_parent_lead;
+        k.channel_parent_lead = it.channel_parent_lead;
+        k.channel_id = p.channel_id;
+        k.resend = r.resend ? 1 : 0;
+        k.reserved = 0;
+      });
+    }
+    const uint32_t nfrag = (uint32_t)(enter_end - new0);
+    for (uint32_t t = 0; t < nfrag; t += 64)
+      wv.lanes([&](uint32_t lane) {
+        if (t + lane < nfrag) fa[(R.frag_next + t + lane) & fmask] = 0;
+      });
+    frag_next = R.frag_next + nfrag;
+  } else {
+    wv.sync();
+  }
+  // the pushes, in one lane: the packed pending fragments, then the packed new fragments of resend packets
+  wv.one([&]() {
+    ufc_resend_entry* d = a.heap + R.heap_first;
+    uint32_t len = R.heap_len, pushed = 0, dropped = 0;
+    const uint64_t due = now + rtt;
+    const uint32_t from_pending = R.pending_resend ? pp : 0;
+    for (uint64_t i = 0; i < (uint64_t)from_pending + q; i++) {  // (one loop: one copy of the push)
+      uint32_t seq = R.pending_seq, f = R.pending_next + (uint32_t)i;
+      if (i >= from_pending) {
+        const ufc_item& it = a.items[new0 + (i - from_pending)];
+        seq = it.id;
+        f = it.fragment_id;
+        if (!pk[seq & pmask].resend) continue;
+      }
+      if (len >= R.heap_cap) {
+        dropped++;
+        continue;
+      }
+      rs_heap_push(d, len, rs_entry(due, seq, f, 1));
+      pushed++;
+    }
+    sh.heap_len = len;
+    sh.pushed = pushed;
+    sh.dropped = dropped;
+  });
+  wv.sync();
+  // the refs and the sent records: the positions are a chain over the frames, every lane walks it
+  uint32_t head = R.tx_head, refs_written = 0;
+  for (uint32_t kf = 0; kf < f_count; kf++) {
+    const uint64_t g = (uint64_t)f_first + kf;
+    const uint32_t item_first = a.infos[g].item_first, aux = a.infos[g].aux;
+    uint32_t cnt = a.infos[g].item_count;
+    if (cnt > UFC_DATA_FRAME_MAX_DATAGRAM_COUNT || (uint64_t)item_first + cnt > a.n_items) cnt = 0;
+    if ((head & tmask) + cnt > R.tx_cap) head += R.tx_cap - (head & tmask);
+    const uint64_t ref_first = R.tx_first + (head & tmask);
+    wv.lanes([&](uint32_t lane) {
+      for (uint32_t j = lane; j < cnt; j += 64) {
+        const ufc_item& it = a.items[(uint64_t)item_first + j];
+        ufc_tx_ref& ref = a.tx[ref_first + j];
+        ref.sequence_id = it.id;
+        ref.fragment_id = it.fragment_id;
+        ref.flags = pk[it.id & pmask].resend ? UFC_TX_RESEND : 0;
+      }
+    });
+    wv.one([&]() {
+      if (g >= a.sent_cap) return;
+      rs_put_sent(a.sent[g], now, (uint32_t)(a.out_offsets[g + 1] - a.out_offsets[g]), (uint32_t)ref_first, cnt, aux);
+    });
+    head += cnt;
+    refs_written += cnt;
+  }
+  T.take = take;
+  put_sender();
+  wv.one([&]() {
+    ufc_resend_commit_result res{};
+    res.stop = sh.dropped ? UFC_RS_HEAP_FULL : UFC_RS_DONE;
+    res.pending_packed = pp;
+    res.packets_entered = entered;
+    res.heap_pushed = sh.pushed;
+    res.heap_dropped = sh.dropped;
+    res.refs_written = refs_written;
+    res.frames = f_count;
+    res.take = take;
+    res.heap_len = sh.heap_len;
+    res.pending_count = pend_count;
+    a.results[c] = res;
+    ufc_resend& O = a.states_out[c];
+    rs_put_state(O, R);
+    O.heap_len = sh.heap_len;
+    O.frag_next = frag_next;
+    O.tx_head = head;
+    O.pending_seq = pend_seq;
+    O.pending_next = pend_next;
+    O.pending_count = pend_count;
+    O.pending_resend = pend_resend;
+    O.window_bytes = window_bytes;
+    if (a.next_extra_flags)
+      a.next_extra_flags[c] = (a.next_extra_flags[c] & ~(uint32_t)UFC_FQ_MARK_RATE_LIMITED) |
+                              (limited ? (uint32_t)UFC_FQ_MARK_RATE_LIMITED : 0u);
+  });
+}
+
+// The wave policy as host code (ufc_resend_*_host and tests/c/resend_host_check.hip).
+struct RsHostWave : FqHostWave {
+  template <class F>
+  uint64_t sum(const F& f) const {
+    uint64_t s = 0;
+    for (uint32_t l = 0; l < 64; l++) s += f(l);
+    return s;
+  }
+  void sync() const {}
+};
+
+// The lanes of a phase in the opposite order, which must not matter (tests/c/resend_host_check.hip compares the
+// two).
+struct RsReverseWave {
+  template <class F>
+  void lanes(const F& f) const {
+    for (uint32_t l = 64; l-- > 0;) f(l);
+  }
+  template <class F>
+  void one(const F& f) const {
+    f();
+  }
+  template <class F>
+  unsigned long long ballot(const F& f) const {
+    unsigned long long m = 0;
+    for (uint32_t l = 64; l-- > 0;)
+      if (f(l)) m |= 1ull << l;
+    return m;
+  }
+  template <class F>
+  uint64_t sum(const F& f) const {
+    uint64_t s = 0;
+    for (uint32_t l = 64; l-- > 0;) s += f(l);
+    return s;
+  }
+  void sync() const {}
+};
+
 }  // namespace ufc_codec

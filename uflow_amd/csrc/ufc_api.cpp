@@ -24,6 +24,7 @@
 #include "frame_window.hpp"
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
+#include "resend.hpp"
 #include "send_rate.hpp"
 #include "ufc_internal.hpp"
 
@@ -1114,6 +1115,78 @@ int ufc_rate_step_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ufc
   const ufc_codec::RateArgs a{d_states, d_ticks, d_fq, n, d_entries, n_entries, d_flush_results, n_flush_results,
                               d_result_index, d_flushes, n_flushes, d_flush_index, d_results, d_states_out};
   if ((e = ufc_dev::rate_step_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched resend (resend.hip) ----
+int ufc_resend_begin_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n_frames, const uint64_t* d_frame_first,
+                            const ufc_frame_queue* d_queues, const ufc_sent_frame* d_log, size_t n_log,
+                            const ufc_rate_result* d_rate, const uint32_t* d_flags, const ufc_flush* d_flushes,
+                            const ufc_resend* d_states, const ufc_sender* d_senders, size_t n, ufc_resend_entry* d_heap,
+                            size_t n_heap, const ufc_sent_packet* d_pkts, size_t n_pkts, uint8_t* d_frag_acked,
+                            size_t n_frag, const ufc_tx_ref* d_tx, size_t n_tx, uint8_t* d_ref_acked, size_t refs_cap,
+                            ufc_item* d_stage, size_t n_stage, ufc_resend_result* d_results, ufc_resend* d_states_out,
+                            ufc_sender* d_senders_out, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!d_frame_first || !d_queues || !d_rate || !d_flushes || !d_states || !d_senders || !d_results || !d_states_out ||
+      !d_senders_out || (!d_infos && n_frames) || (!d_log && n_log) || (!d_heap && n_heap) || (!d_pkts && n_pkts) ||
+      (!d_frag_acked && n_frag) || (!d_tx && n_tx) || (!d_stage && n_stage) || n >= lim || n_frames >= lim)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  // (one launch, no scan: the call needs none of the context's per-stream scratch)
+  const ufc_codec::RsBeginArgs a{d_infos, n_frames, d_frame_first, d_queues, d_log, n_log, d_rate, d_flags, d_flushes,
+                                 d_states, d_senders, n, d_heap, n_heap, d_pkts, n_pkts, d_frag_acked, n_frag, d_tx, n_tx,
+                                 d_ref_acked, refs_cap, d_stage, n_stage, d_results, d_states_out, d_senders_out};
+  if ((e = ufc_dev::resend_begin_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+int ufc_resend_place_varlen(ufc_ctx* ctx, const ufc_resend* d_states, const ufc_resend_result* d_begin_results, size_t n,
+                            const ufc_item* d_stage, size_t n_stage, const uint64_t* d_flush_first, ufc_item* d_items,
+                            size_t items_cap, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  if (!d_states || !d_begin_results || !d_flush_first || (!d_stage && n_stage) || (!d_items && items_cap) ||
+      n >= ((size_t)1 << 31) - 1)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const ufc_codec::RsPlaceArgs a{d_states, d_begin_results, n, d_stage, n_stage, d_flush_first, d_items, items_cap};
+  if ((e = ufc_dev::resend_place_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_results, const ufc_frame_info* d_infos,
+                             size_t n_infos, const uint64_t* d_out_offsets, const uint64_t* d_frames_used,
+                             const ufc_item* d_items, size_t n_items, const uint64_t* d_flush_first,
+                             const ufc_packet* d_packets, size_t n_packets, const uint64_t* d_packet_first,
+                             const ufc_packet_result* d_packet_results, const ufc_sender_result* d_sender_results,
+                             const ufc_resend_result* d_begin_results, const ufc_rate_result* d_rate,
+                             const ufc_resend* d_states, const ufc_sender* d_senders, size_t n, ufc_resend_entry* d_heap,
+                             size_t n_heap, ufc_sent_packet* d_pkts, size_t n_pkts, uint8_t* d_frag_acked, size_t n_frag,
+                             ufc_tx_ref* d_tx, size_t n_tx, ufc_sent_frame* d_sent, size_t sent_cap,
+                             uint64_t* d_sent_first, uint32_t* d_next_extra_flags, ufc_resend_commit_result* d_results,
+                             ufc_resend* d_states_out, ufc_sender* d_retake, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  const size_t lim = ((size_t)1 << 31) - 1;
+  if (!d_flush_results || !d_out_offsets || !d_frames_used || !d_flush_first || !d_packet_first || !d_sender_results ||
+      !d_begin_results || !d_rate || !d_states || !d_senders || !d_sent_first || !d_results || !d_states_out ||
+      !d_retake || (!d_infos && n_infos) || (!d_items && n_items) || (!d_packets && n_packets) ||
+      (!d_packet_results && n_packets) || (!d_heap && n_heap) || (!d_pkts && n_pkts) || (!d_frag_acked && n_frag) ||
+      (!d_tx && n_tx) || (!d_sent && sent_cap) || n >= lim || n_packets >= lim || n_items >= lim || n_infos >= lim)
+    return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  const ufc_codec::RsCommitArgs a{d_flush_results, d_infos, n_infos, d_out_offsets, d_frames_used, d_items, n_items,
+                                  d_flush_first, d_packets, n_packets, d_packet_first, d_packet_results,
+                                  d_sender_results, d_begin_results, d_rate, d_states, d_senders, n, d_heap, n_heap,
+                                  d_pkts, n_pkts, d_frag_acked, n_frag, d_tx, n_tx, d_sent, sent_cap, d_sent_first,
+                                  d_next_extra_flags, d_results, d_states_out, d_retake};
+  if ((e = ufc_dev::resend_commit_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
 

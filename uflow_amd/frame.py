@@ -27,6 +27,9 @@ and the batched receive-side parse that follows the batched CRC gate:
                                                <- SendRateComp::step / notify_frame_sent with RecvRateSet,
                                                   src/half_connection/send_rate.rs and recv_rate_set.rs, and
                                                   HalfConnection::step / fill_flush_alloc (mod.rs:165-215)
+    resend_begin_host / resend_place_host / resend_commit_host
+                                               <- PacketSender::acknowledge (packet_sender.rs:242-275), the resend and
+                                                  pending queues and emit_data_frames (half_connection/mod.rs:335-432)
     (device-resident: uflow_amd.batch.FrameCrcEngine.parse_varlen)
 
 None plays the role of Rust's None: a frame the reference rejects is returned as None, never
@@ -41,8 +44,8 @@ import numpy as np
 
 from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameQueue, FrameQueueResult, FrameQueueStep,
                       FrameWindow, FrameWindowResult, Item, Packet, PacketResult, RateResult, RateState, RateTick,
-                      Receiver, ReceiverResult, RecvRateEntry, RxPacket, RxSlot, SentFrame, Sender, SenderResult, check,
-                      lib, UFC_ERR_NOMEM)
+                      Receiver, ReceiverResult, RecvRateEntry, Resend, ResendCommitResult, ResendEntry, ResendResult,
+                      RxPacket, RxSlot, SentFrame, SentPacket, Sender, SenderResult, TxRef, check, lib, UFC_ERR_NOMEM)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -170,6 +173,74 @@ RATE_FRAME_SENT = 1
 RATE_DONE, RATE_BAD_STATE, RATE_REF_PANIC, RATE_RECV_FULL = 0, 1, 2, 3
 RATE_FEEDBACK, RATE_NOFEEDBACK, RATE_RESET_ISSUED, RATE_ENTERED_EQN, RATE_INV_STALLED = 1, 2, 4, 8, 16
 NO_INDEX = 0xFFFFFFFF  # UFC_NO_PARENT in result_index / flush_index: no gather for this connection
+# ufc_resend_entry / ufc_sent_packet / ufc_tx_ref / ufc_resend / ufc_resend_result / ufc_resend_commit_result
+RESEND_ENTRY_DTYPE = np.dtype([("resend_time_ms", "<u8"), ("sequence_id", "<u4"), ("fragment_id", "<u2"),
+                               ("send_count", "u1"), ("reserved", "u1")])
+SENT_PACKET_DTYPE = np.dtype([("data_offset", "<u4"), ("data_len", "<u4"), ("frag_first", "<u4"), ("sequence_id", "<u4"),
+                              ("window_parent_lead", "<u2"), ("channel_parent_lead", "<u2"), ("channel_id", "u1"),
+                              ("resend", "u1"), ("reserved", "<u2")])
+TX_REF_DTYPE = np.dtype([("sequence_id", "<u4"), ("fragment_id", "<u2"), ("flags", "<u2")])
+RESEND_DTYPE = np.dtype([("heap_first", "<u8"), ("heap_cap", "<u4"), ("heap_len", "<u4"), ("pkt_first", "<u8"),
+                         ("pkt_cap", "<u4"), ("frag_next", "<u4"), ("frag_first", "<u8"), ("frag_cap", "<u4"),
+                         ("tx_cap", "<u4"), ("tx_first", "<u8"), ("tx_head", "<u4"), ("tx_tail", "<u4"),
+                         ("stage_first", "<u8"), ("stage_cap", "<u4"), ("pending_seq", "<u4"), ("pending_next", "<u4"),
+                         ("pending_count", "<u4"), ("pending_resend", "u1"), ("reserved0", "u1"), ("reserved1", "<u2"),
+                         ("reserved2", "<u4"), ("window_bytes", "<u8")])
+RESEND_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("n_resent", "<u4"), ("n_pending_staged", "<u4"),
+                                ("heap_popped_dead", "<u4"), ("heap_popped_acked", "<u4"), ("packets_freed", "<u4"),
+                                ("refs_acked", "<u4"), ("heap_len", "<u4"), ("pending_count", "<u4"),
+                                ("acks_ignored", "<u4"), ("bytes_freed", "<u8")])
+RESEND_COMMIT_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("pending_packed", "<u4"), ("packets_entered", "<u4"),
+                                       ("heap_pushed", "<u4"), ("heap_dropped", "<u4"), ("refs_written", "<u4"),
+                                       ("frames", "<u4"), ("take", "<u4"), ("heap_len", "<u4"), ("pending_count", "<u4")])
+assert RESEND_ENTRY_DTYPE.itemsize == ctypes.sizeof(ResendEntry) == 16
+assert SENT_PACKET_DTYPE.itemsize == ctypes.sizeof(SentPacket) == 24
+assert TX_REF_DTYPE.itemsize == ctypes.sizeof(TxRef) == 8
+assert RESEND_DTYPE.itemsize == ctypes.sizeof(Resend) == 104
+assert RESEND_RESULT_DTYPE.itemsize == ctypes.sizeof(ResendResult) == 48
+assert RESEND_COMMIT_RESULT_DTYPE.itemsize == ctypes.sizeof(ResendCommitResult) == 40
+TX_RESEND = 1
+RS_NO_DATA_FLUSH = 1
+RS_DONE, RS_SIZE_LIMITED, RS_WINDOW_LIMITED, RS_REF_HANG, RS_BAD_STATE, RS_STAGE_FULL, RS_HEAP_FULL = range(7)
+# The arenas of the resend state, in the order the C calls take them: name, record dtype.
+RESEND_ARENAS = (("heap", RESEND_ENTRY_DTYPE), ("pkts", SENT_PACKET_DTYPE), ("frag_acked", np.dtype(np.uint8)),
+                 ("tx", TX_REF_DTYPE), ("ref_acked", np.dtype(np.uint8)), ("stage", ITEM_DTYPE))
+
+
+def _pow2_at_least(v: int) -> int:
+    c = 1
+    while c < v:
+        c *= 2
+    return c
+
+
+def new_resend_states(n: int, window_size, max_alloc, frame_window_size, frame_tail_size, heap_cap: int,
+                      stage_cap=None, pkt_cap=None, frag_cap=None, tx_cap=None):
+    """n ufc_resend records of a new HalfConnection (empty heap, empty pending queue, nothing sent) and their arenas:
+    returns (states, arenas), arenas a dict of numpy arrays heap, pkts, frag_acked, tx, ref_acked (one byte per tx
+    record: what frame_queue marks) and stage.  Every connection's regions have the same capacities and lie back to
+    back.  The defaults are the smallest capacities the header's bounds allow for a sender with window_size and
+    max_alloc whose frame queue has frame_window_size and frame_tail_size.  stage_cap defaults to heap_cap + 65536,
+    which covers a packet of any length but is 1.5 MB a connection: give heap_cap + the fragments of the longest
+    packet that is sent (the header's sizing) wherever there are many connections."""
+    frag = 1448
+    rounded = (int(max_alloc) + frag - 1) // frag * frag
+    pkt_cap = _pow2_at_least(int(window_size)) if pkt_cap is None else int(pkt_cap)
+    frag_cap = _pow2_at_least(rounded // frag + int(window_size)) if frag_cap is None else int(frag_cap)
+    tx_cap = _pow2_at_least((int(frame_window_size) + int(frame_tail_size) + 1) * 127) if tx_cap is None else int(tx_cap)
+    stage_cap = int(heap_cap) + 65536 if stage_cap is None else int(stage_cap)
+    s = np.zeros(n, dtype=RESEND_DTYPE)
+    idx = np.arange(n, dtype=np.uint64)
+    for name, cap in (("heap", heap_cap), ("pkt", pkt_cap), ("frag", frag_cap), ("tx", tx_cap), ("stage", stage_cap)):
+        s[name + "_cap"] = cap
+        s[name + "_first"] = idx * np.uint64(cap)
+    arenas = {"heap": np.zeros(n * int(heap_cap), dtype=RESEND_ENTRY_DTYPE),
+              "pkts": np.zeros(n * pkt_cap, dtype=SENT_PACKET_DTYPE),
+              "frag_acked": np.zeros(n * frag_cap, dtype=np.uint8),
+              "tx": np.zeros(n * tx_cap, dtype=TX_REF_DTYPE),
+              "ref_acked": np.zeros(n * tx_cap, dtype=np.uint8),
+              "stage": np.zeros(n * stage_cap, dtype=ITEM_DTYPE)}
+    return s, arenas
 
 
 def new_rate_states(n: int, max_send_rate, recv_cap: int):
@@ -879,3 +950,135 @@ def rate_step_host(states: np.ndarray, ticks: np.ndarray, fq_results: np.ndarray
                                    results.ctypes.data if n else None, states_out.ctypes.data if n else None, nthreads),
           "ufc_rate_step_host")
     return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
+
+
+def _rs_arenas(arenas):
+    out = {}
+    for name, dt in RESEND_ARENAS:
+        a = arenas.get(name)
+        if a is None:
+            a = np.zeros(0, dtype=dt)
+        if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"arena {name} must be a writable contiguous {dt} array")
+        out[name] = a
+    return out
+
+
+def _rs_ptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _rs_in(arr, dt):
+    if arr.dtype != dt or not arr.flags.c_contiguous:
+        arr = np.ascontiguousarray(arr, dtype=dt)
+    return arr
+
+
+def resend_begin_host(infos: np.ndarray, frame_first: np.ndarray, queues: np.ndarray, log: np.ndarray,
+                      rate: np.ndarray, flushes: np.ndarray, states: np.ndarray, senders: np.ndarray, arenas: dict,
+                      flags: Optional[np.ndarray] = None, nthreads: int = 1, results: Optional[np.ndarray] = None,
+                      states_out: Optional[np.ndarray] = None, senders_out: Optional[np.ndarray] = None):
+    """ufc_resend_begin_host: ack propagation, PacketSender::acknowledge for the ack frames among
+    infos[frame_first[c] : frame_first[c + 1]], the resend loop and the pending fragments' staging for every
+    connection (RESEND_DTYPE states with SENDER_DTYPE senders; queues and log as frame_queue_host left them; rate
+    the RATE_RESULT_DTYPE records of rate_step_host; flushes the data FLUSH_DTYPE records the pack will get).  The
+    arenas (the dict new_resend_states returns) are updated in place.  Returns a dict: results (RESEND_RESULT_DTYPE),
+    states_out and senders_out (may be given as `states` and `senders`)."""
+    infos = _rs_in(infos, FRAME_INFO_DTYPE)
+    frame_first = _rs_in(frame_first, np.dtype(np.uint64))
+    queues = _rs_in(queues, FRAME_QUEUE_DTYPE)
+    log = _rs_in(log, SENT_FRAME_DTYPE)
+    rate = _rs_in(rate, RATE_RESULT_DTYPE)
+    flushes = _rs_in(flushes, FLUSH_DTYPE)
+    states = _rs_in(states, RESEND_DTYPE)
+    senders = _rs_in(senders, SENDER_DTYPE)
+    n = states.size
+    if min(queues.size, rate.size, flushes.size, senders.size) < n or frame_first.size < n + 1:
+        raise ValueError("queues, rate, flushes and senders must hold one record per state, frame_first one more")
+    if flags is not None:
+        flags = _rs_in(flags, np.dtype(np.uint32))
+        if flags.size < n:
+            raise ValueError("flags must hold one entry per state")
+    A = _rs_arenas(arenas)
+    results = _rate_inout("results", results, n, RESEND_RESULT_DTYPE)
+    states_out = _rate_inout("states_out", states_out, n, RESEND_DTYPE)
+    senders_out = _rate_inout("senders_out", senders_out, n, SENDER_DTYPE)
+    check(lib().ufc_resend_begin_host(_rs_ptr(infos), infos.size, frame_first.ctypes.data, _rs_ptr(queues), _rs_ptr(log),
+                                      log.size, _rs_ptr(rate), _rs_ptr(flags), _rs_ptr(flushes), _rs_ptr(states),
+                                      _rs_ptr(senders), n, _rs_ptr(A["heap"]), A["heap"].size, _rs_ptr(A["pkts"]),
+                                      A["pkts"].size, _rs_ptr(A["frag_acked"]), A["frag_acked"].size, _rs_ptr(A["tx"]),
+                                      A["tx"].size, _rs_ptr(A["ref_acked"]), A["ref_acked"].size, _rs_ptr(A["stage"]),
+                                      A["stage"].size, _rs_ptr(results), _rs_ptr(states_out), _rs_ptr(senders_out),
+                                      nthreads), "ufc_resend_begin_host")
+    return {"results": results, "states_out": states_out, "senders_out": senders_out}
+
+
+def resend_place_host(states: np.ndarray, begin_results: np.ndarray, arenas: dict, flush_first: np.ndarray,
+                      items: np.ndarray, nthreads: int = 1):
+    """ufc_resend_place_host: every connection's staged items into items[flush_first[c] ..], the slots the emit
+    reserved; items (ITEM_DTYPE) is written in place and returned."""
+    states = _rs_in(states, RESEND_DTYPE)
+    begin_results = _rs_in(begin_results, RESEND_RESULT_DTYPE)
+    flush_first = _rs_in(flush_first, np.dtype(np.uint64))
+    n = states.size
+    if begin_results.size < n or flush_first.size < n + 1:
+        raise ValueError("begin_results must hold one record per state, flush_first one more")
+    if items.dtype != ITEM_DTYPE or not items.flags.c_contiguous or not items.flags.writeable:
+        raise ValueError("items must be a writable contiguous ITEM_DTYPE array")
+    stage = _rs_arenas(arenas)["stage"]
+    check(lib().ufc_resend_place_host(_rs_ptr(states), _rs_ptr(begin_results), n, _rs_ptr(stage), stage.size,
+                                      flush_first.ctypes.data, _rs_ptr(items), items.size, nthreads),
+          "ufc_resend_place_host")
+    return items
+
+
+def resend_commit_host(flush_results: np.ndarray, infos: np.ndarray, out_offsets: np.ndarray, frames_used: int,
+                       items: np.ndarray, flush_first: np.ndarray, packets: np.ndarray, packet_first: np.ndarray,
+                       packet_results: np.ndarray, sender_results: np.ndarray, begin_results: np.ndarray,
+                       rate: np.ndarray, states: np.ndarray, senders: np.ndarray, arenas: dict,
+                       sent: Optional[np.ndarray] = None, next_extra_flags: Optional[np.ndarray] = None,
+                       nthreads: int = 1, results: Optional[np.ndarray] = None, states_out: Optional[np.ndarray] = None,
+                       retake: Optional[np.ndarray] = None):
+    """ufc_resend_commit_host: behind pack_host over the data flushes (flush c = connection c) and build_sizes_host:
+    what the reference's flush did to the pending queue, the packet table, the resend heap and the transmission ring,
+    the frames' SENT_FRAME_DTYPE records for the next frame_queue_host call, and the second emit's senders.  Returns a
+    dict: results (RESEND_COMMIT_RESULT_DTYPE), states_out (may be given as `states`), retake (SENDER_DTYPE, may be
+    given as `senders`), sent (one record per frame of infos unless given), sent_first, next_extra_flags."""
+    flush_results = _rs_in(flush_results, FLUSH_RESULT_DTYPE)
+    infos = _rs_in(infos, FRAME_INFO_DTYPE)
+    out_offsets = _rs_in(out_offsets, np.dtype(np.uint64))
+    items = _rs_in(items, ITEM_DTYPE)
+    flush_first = _rs_in(flush_first, np.dtype(np.uint64))
+    packets = _rs_in(packets, PACKET_DTYPE)
+    packet_first = _rs_in(packet_first, np.dtype(np.uint64))
+    packet_results = _rs_in(packet_results, PACKET_RESULT_DTYPE)
+    sender_results = _rs_in(sender_results, SENDER_RESULT_DTYPE)
+    begin_results = _rs_in(begin_results, RESEND_RESULT_DTYPE)
+    rate = _rs_in(rate, RATE_RESULT_DTYPE)
+    states = _rs_in(states, RESEND_DTYPE)
+    senders = _rs_in(senders, SENDER_DTYPE)
+    n = states.size
+    if min(flush_results.size, sender_results.size, begin_results.size, rate.size, senders.size) < n or \
+            min(flush_first.size, packet_first.size) < n + 1 or out_offsets.size < infos.size + 1 or \
+            packet_results.size < packets.size:
+        raise ValueError("one record per state (one more in the CSRs), out_offsets one more than infos")
+    A = _rs_arenas(arenas)
+    used = np.array([frames_used], dtype=np.uint64)
+    sent = _rate_inout("sent", sent, infos.size, SENT_FRAME_DTYPE)
+    sent_first = np.zeros(n + 1, dtype=np.uint64)
+    if next_extra_flags is not None:
+        next_extra_flags = _rate_inout("next_extra_flags", next_extra_flags, n, np.dtype(np.uint32))
+    results = _rate_inout("results", results, n, RESEND_COMMIT_RESULT_DTYPE)
+    states_out = _rate_inout("states_out", states_out, n, RESEND_DTYPE)
+    retake = _rate_inout("retake", retake, n, SENDER_DTYPE)
+    check(lib().ufc_resend_commit_host(_rs_ptr(flush_results), _rs_ptr(infos), infos.size, out_offsets.ctypes.data,
+                                       used.ctypes.data, _rs_ptr(items), items.size, flush_first.ctypes.data,
+                                       _rs_ptr(packets), packets.size, packet_first.ctypes.data, _rs_ptr(packet_results),
+                                       _rs_ptr(sender_results), _rs_ptr(begin_results), _rs_ptr(rate), _rs_ptr(states),
+                                       _rs_ptr(senders), n, _rs_ptr(A["heap"]), A["heap"].size, _rs_ptr(A["pkts"]),
+                                       A["pkts"].size, _rs_ptr(A["frag_acked"]), A["frag_acked"].size, _rs_ptr(A["tx"]),
+                                       A["tx"].size, _rs_ptr(sent), sent.size, sent_first.ctypes.data,
+                                       _rs_ptr(next_extra_flags), _rs_ptr(results), _rs_ptr(states_out), _rs_ptr(retake),
+                                       nthreads), "ufc_resend_commit_host")
+    return {"results": results, "states_out": states_out, "retake": retake, "sent": sent, "sent_first": sent_first,
+            "next_extra_flags": next_extra_flags}
