@@ -382,10 +382,43 @@ class Config:
         del self.__dict__["self"]
 
 
-class Pipeline:
-    """n connections through the batched calls, with one HalfTx model each."""
+def marked_refs_of_lane(state, ref_acked, lane=63):
+    """How many of a connection's live refs that begin's ack propagation gives to `lane` (the j-th live ref goes to
+    lane j % 64) the frame queue has marked: work that only a pass over all 64 lanes does."""
+    live, mask = (int(state["tx_head"]) - int(state["tx_tail"])) & 0xFFFFFFFF, int(state["tx_cap"]) - 1
+    first, tail = int(state["tx_first"]), int(state["tx_tail"])
+    return sum(1 for j in range(lane, live, 64) if ref_acked[first + ((tail + j) & mask)])
 
-    def __init__(self, configs, backend=None):
+
+def idle_config():
+    """An idle filler: the smallest legal capacities (about 3 KB of arena), no packets and no acks ever."""
+    return Config(window_size=1, max_alloc=1448, frame_window=1, frame_tail=0, heap_cap=1, stage_cap=1)
+
+
+def padding_layout(n, replicas, fillers, tail_replicas=0):
+    """The kinds of the padding connections in batch order, True a replica and False an idle filler: `replicas` spread
+    evenly over the padding slots among the first 256 connections (so that no wave of 64 there holds idle fillers only,
+    and the modelled connections share theirs with replicas), those that do not fit there right behind, the idle
+    fillers, and `tail_replicas` more replicas at the highest indices."""
+    head = max(min(256 - n, replicas + fillers), 0)
+    in_head = min(replicas, head)
+    kinds = [(k + 1) * in_head // head != k * in_head // head for k in range(head)]
+    kinds += [True] * (replicas - in_head) + [False] * (fillers - (head - in_head)) + [True] * tail_replicas
+    assert len(kinds) == replicas + fillers + tail_replicas and sum(kinds) == replicas + tail_replicas
+    return kinds
+
+
+class Pipeline:
+    """n connections through the batched calls, with one HalfTx model each.
+
+    Padding: `replicas` + `tail_replicas` + `fillers` more connections behind the n modelled ones, in the same arrays
+    and arenas (guards between all regions), laid out by padding_layout; every call of a tick gets the whole batch.
+    The k-th replica in batch order has the Config of modelled connection k % n and gets its packets, acks,
+    flush_alloc, flags and take every tick; an idle filler has idle_config() and gets nothing.  The models, `compare`
+    and tick's return value cover the first n; what the calls did to the padding is for the backend to check (against
+    the host calls: tests/test_gpu_resend.py's CheckedBackend), and `pad_totals` sums some of its result fields."""
+
+    def __init__(self, configs, backend=None, replicas=0, fillers=0, tail_replicas=0):
         self.backend = backend or HostBackend()
         self.cfg = configs
         n = self.n = len(configs)
@@ -394,37 +427,60 @@ class Pipeline:
                 c.stage_cap = c.heap_cap + 200
         self.models = [HalfTx(c.window_size, c.base_id, c.max_alloc, c.frame_window, c.frame_tail, c.frame_base,
                               heap_cap=c.heap_cap, stage_cap=c.stage_cap) for c in configs]
-        self.senders = np.zeros(n, dtype=fr.SENDER_DTYPE)
-        self.queues = np.zeros(n, dtype=fr.FRAME_QUEUE_DTYPE)
-        self.states = np.zeros(n, dtype=fr.RESEND_DTYPE)
-        sizes = {"heap": 0, "pkts": 0, "frag_acked": 0, "tx": 0, "stage": 0, "log": 0}
-        for c, cf in enumerate(configs):
-            E.Tx(cf.window_size, cf.base_id, cf.max_alloc).to_record(self.senders[c])
-            q, _ = fr.new_frame_queues(1, cf.frame_window, cf.frame_tail, cf.frame_base)
-            q["log_first"] = sizes["log"] + 3   # (regions need not start at 0 nor lie back to back)
-            sizes["log"] += int(q["log_cap"][0]) + 3
-            self.queues[c] = q[0]
-            s, _ = fr.new_resend_states(1, cf.window_size, cf.max_alloc, cf.frame_window, cf.frame_tail, cf.heap_cap,
-                                        stage_cap=cf.stage_cap,
-                                        pkt_cap=cf.pkt_cap, frag_cap=cf.frag_cap, tx_cap=cf.tx_cap)
-            for name, key in (("heap", "heap"), ("pkt", "pkts"), ("frag", "frag_acked"), ("tx", "tx"), ("stage", "stage")):
-                s[name + "_first"] = sizes[key] + 1
-                sizes[key] += int(s[name + "_cap"][0]) + 2
-            self.states[c] = s[0]
+        kinds = padding_layout(n, replicas, fillers, tail_replicas)
+        total = self.total = n + len(kinds)
+        # src[c]: the modelled connection whose traffic batch index c gets; -1 an idle filler
+        self.src = np.arange(total, dtype=np.int64)
+        self.src[n:] = -1
+        rep = n + np.flatnonzero(kinds)
+        self.src[rep] = np.arange(rep.size) % max(n, 1)
+        self.active = np.flatnonzero(self.src >= 0)   # batch indices with traffic, ascending
+        # one record of each kind per distinct config, then every connection's copy
+        idle = idle_config()
+        kind_cfg = list(configs) + [idle]
+        t_senders = np.zeros(n + 1, dtype=fr.SENDER_DTYPE)
+        t_queues = np.zeros(n + 1, dtype=fr.FRAME_QUEUE_DTYPE)
+        t_states = np.zeros(n + 1, dtype=fr.RESEND_DTYPE)
+        for k, cf in enumerate(kind_cfg):
+            E.Tx(cf.window_size, cf.base_id, cf.max_alloc).to_record(t_senders[k])
+            t_queues[k] = fr.new_frame_queues(1, cf.frame_window, cf.frame_tail, cf.frame_base)[0][0]
+            t_states[k] = fr.new_resend_states(1, cf.window_size, cf.max_alloc, cf.frame_window, cf.frame_tail, cf.heap_cap,
+                                               stage_cap=cf.stage_cap, pkt_cap=cf.pkt_cap, frag_cap=cf.frag_cap,
+                                               tx_cap=cf.tx_cap)[0][0]
+        kind = np.where(self.src >= 0, self.src, n)
+        self.senders, self.queues, self.states = t_senders[kind], t_queues[kind], t_states[kind]
+        # (regions need not start at 0 nor lie back to back: three records before every log ring, one before and one
+        # behind every other region)
+        step = self.queues["log_cap"].astype(np.uint64) + np.uint64(3)
+        ends = np.cumsum(step, dtype=np.uint64)
+        self.queues["log_first"] = ends - self.queues["log_cap"]
+        sizes = {"log": int(ends[-1]) if total else 0}
+        self.guard_at = {}
+        for name, key in (("heap", "heap"), ("pkt", "pkts"), ("frag", "frag_acked"), ("tx", "tx"), ("stage", "stage")):
+            cap = self.states[name + "_cap"].astype(np.uint64)
+            ends = np.cumsum(cap + np.uint64(2), dtype=np.uint64)
+            first = ends - cap - np.uint64(1)
+            self.states[name + "_first"] = first
+            sizes[key] = int(ends[-1]) if total else 0
+            self.guard_at[key] = np.concatenate([first - np.uint64(1), first + cap]).astype(np.int64)
+        self.guard_at["ref_acked"] = self.guard_at["tx"]
+        self.layout = self.states.copy()
         self.log = np.zeros(sizes["log"], dtype=fr.SENT_FRAME_DTYPE)
         self.arenas = {"heap": np.zeros(sizes["heap"], fr.RESEND_ENTRY_DTYPE), "pkts": np.zeros(sizes["pkts"], fr.SENT_PACKET_DTYPE),
                        "frag_acked": np.zeros(sizes["frag_acked"], np.uint8), "tx": np.zeros(sizes["tx"], fr.TX_REF_DTYPE),
                        "ref_acked": np.zeros(sizes["tx"], np.uint8), "stage": np.zeros(sizes["stage"], fr.ITEM_DTYPE)}
         self.arenas["frag_acked"][:] = 0x5A   # (an ack byte must be zeroed when its packet enters, not before)
-        self.guard = {k: v.copy() for k, v in self.arenas.items()}
+        self.guard = {k: v[self.guard_at[k]].copy() for k, v in self.arenas.items()}
         self.sent = np.zeros(0, dtype=fr.SENT_FRAME_DTYPE)
-        self.sent_first = np.zeros(n + 1, dtype=np.uint64)
-        self.extra = np.zeros(n, dtype=np.uint32)
+        self.sent_first = np.zeros(total + 1, dtype=np.uint64)
+        self.extra = np.zeros(total, dtype=np.uint32)
         self.backlog = [[] for _ in range(n)]   # PACKET_DTYPE records not yet consumed
         self.flush_id = 0
         self.seen_stops = set()
         self.seen = set()
         self.arena_len = 0
+        self.pad_totals = {"packets_freed": 0, "refs_acked": 0, "n_resent": 0, "heap_pushed": 0}
+        self.last = {}   # the last tick's begin and commit results and placed items, the whole batch
 
     def enqueue(self, c, size, channel=0, mode=E.RELIABLE):
         p, _ = E.pkt(size, channel, mode, flush_id=self.flush_id, offset=self.arena_len)
@@ -432,30 +488,40 @@ class Pipeline:
         self.backlog[c].append(p)
         self.models[c].queue.append(p)
 
+    def spread(self, values, idle, dtype):
+        """One value per modelled connection (or one for all) as one per connection of the batch."""
+        values = np.broadcast_to(np.asarray(values, dtype=dtype), (self.n,))
+        out = np.full(self.total, idle, dtype=dtype)
+        out[self.active] = values[self.src[self.active]]
+        return out
+
     def tick(self, now_ms, rtt_ms, flush_alloc, acks, flags=None, take=None):
         """acks[c]: [(frame_window_base_id, packet_window_base_id, [(base_id, bitfield, nonce)])] in arrival order.
         flush_alloc: one value or one per connection.  Returns the frames each connection sent, from the batched
         calls: [[(frame id, [(seq, fragment)])]], after every record was compared with the model's."""
-        n, be = self.n, self.backend
+        n, total_n, be, src = self.n, self.total, self.backend, self.src
         self.now_ms = now_ms
         self.flush_id = (self.flush_id + 1) & 0xFFFFFFFF
         flush_alloc = np.broadcast_to(np.asarray(flush_alloc, dtype=np.int64), (n,))
         flags = np.zeros(n, dtype=np.uint32) if flags is None else np.asarray(flags, dtype=np.uint32)
         # the ack frames
-        infos, groups, frame_first = [], [], [0]
-        for c in range(n):
-            for fw, pw, gs in acks[c]:
+        infos, groups = [], []
+        frame_count = np.zeros(total_n, dtype=np.uint64)
+        for c in self.active:
+            for fw, pw, gs in acks[src[c]]:
                 info = Q.ack_info(fw, len(groups), len(gs))
                 info["f"][1] = pw
                 infos.append(info)
                 groups.extend(Q.group_item(*g) for g in gs)
-            frame_first.append(len(infos))
+            frame_count[c] = len(acks[src[c]])
         infos = np.array(infos, dtype=fr.FRAME_INFO_DTYPE) if infos else np.zeros(0, fr.FRAME_INFO_DTYPE)
         groups = np.array(groups, dtype=fr.ITEM_DTYPE) if groups else np.zeros(0, fr.ITEM_DTYPE)
-        frame_first = np.array(frame_first, dtype=np.uint64)
+        frame_first = np.zeros(total_n + 1, dtype=np.uint64)
+        frame_first[1:] = np.cumsum(frame_count, dtype=np.uint64)
         thresh = max(now_ms - 4 * rtt_ms, 0)
-        steps = np.array([Q.make_step(fr.FQ_FORGET | fr.FQ_HAS_RTT | int(self.extra[c]), rtt_ms, thresh, now_ms)
-                          for c in range(n)], dtype=fr.FRAME_QUEUE_STEP_DTYPE)
+        steps = np.zeros(total_n, dtype=fr.FRAME_QUEUE_STEP_DTYPE)
+        steps["flags"] = np.uint32(fr.FQ_FORGET | fr.FQ_HAS_RTT) | self.extra
+        steps["rtt_ms"], steps["thresh_ms"], steps["now_ms"] = rtt_ms, thresh, now_ms
         # the model, as the reference interleaves it
         logs = []
         for c, m in enumerate(self.models):
@@ -465,24 +531,29 @@ class Pipeline:
                 m.handle_ack_frame(fw, pw, gs, rtt_ms)
             m.fq.forget_frames(thresh, rtt_ms)
             logs.append(m.flush(now_ms, rtt_ms, self.flush_id, int(flush_alloc[c]), no_flush=bool(flags[c] & 1)))
+        flush_alloc, flags = self.spread(flush_alloc, 0, np.int64), self.spread(flags, 0, np.uint32)
         # the batched calls
         fq_res = be.frame_queue(infos, groups, frame_first, self.sent, self.sent_first, self.queues, steps, self.log,
                                 self.arenas["ref_acked"])
         assert (fq_res["stop"] == fr.FQ_DONE).all() and (fq_res["pushes_refused"] == 0).all()
-        rate = np.zeros(n, dtype=fr.RATE_RESULT_DTYPE)
+        if any(marked_refs_of_lane(self.states[c], self.arenas["ref_acked"]) for c in range(n)):
+            self.seen.add("ref_acked_lane_63")
+        rate = np.zeros(total_n, dtype=fr.RATE_RESULT_DTYPE)
         rate["now_ms"], rate["rtt_ms"] = now_ms, rtt_ms
-        flushes = np.zeros(n, dtype=fr.FLUSH_DTYPE)
+        flushes = np.zeros(total_n, dtype=fr.FLUSH_DTYPE)
         flushes["flush_alloc"], flushes["kind"] = flush_alloc, fr.DATA
         flushes["window_room"], flushes["id0"] = fq_res["window_room"], self.queues["log_next_id"]
         self.senders["flush_id"] = self.flush_id
-        self.senders["take"] = 0xFFFFFFFF if take is None else take
+        self.senders["take"] = self.spread(0xFFFFFFFF if take is None else take, 0xFFFFFFFF, np.uint32)
         self.senders["reserve_items"] = 0
         begin = be.resend_begin(infos, frame_first, self.queues, self.log, rate, flushes, self.states, self.senders,
                                 self.arenas, flags)
-        packets = [p for q in self.backlog for p in q]
+        packets = [p for c in self.active for p in self.backlog[src[c]]]
         packets = np.array(packets, dtype=fr.PACKET_DTYPE) if packets else np.zeros(0, fr.PACKET_DTYPE)
-        packet_first = np.zeros(n + 1, dtype=np.uint64)
-        packet_first[1:] = np.cumsum([len(q) for q in self.backlog])
+        packet_count = np.zeros(total_n, dtype=np.uint64)
+        packet_count[self.active] = [len(self.backlog[src[c]]) for c in self.active]
+        packet_first = np.zeros(total_n + 1, dtype=np.uint64)
+        packet_first[1:] = np.cumsum(packet_count, dtype=np.uint64)
         pre = self.senders.copy()
         total = int(self.senders["reserve_items"].sum()) + sum(E.fragments(int(p["data_len"])).__len__() for p in packets)
         items = E.filled_items(total + 4)
@@ -499,6 +570,15 @@ class Pipeline:
         commit, retake, self.sent, self.sent_first = r["results"], r["retake"], r["sent"][:frames_used], r["sent_first"]
         self.extra = r["next_extra_flags"]
         sr2, self.senders = be.emit_state(packets, packet_first, retake)
+        # (a replica shares its connection's backlog, so it must have consumed as many; an idle filler does nothing)
+        taken = sr2["packets_consumed"].astype(np.int64)
+        assert np.array_equal(taken[self.active], taken[src[self.active]]), "a replica consumed another count"
+        idle = src < 0
+        assert not taken[idle].any() and not begin["n_resent"][idle].any() and not commit["frames"][idle].any()
+        for fld, res in (("packets_freed", begin), ("refs_acked", begin), ("n_resent", begin), ("heap_pushed", commit)):
+            self.pad_totals[fld] += int(res[fld][n:].sum())
+        self.last = {"begin": begin, "commit": commit, "items": items, "flush_first": flush_first,
+                     "window_room": fq_res["window_room"] - flush_results["frame_count"]}   # (what is left of it)
         out = []
         for c in range(n):
             consumed = int(sr2[c]["packets_consumed"])
@@ -612,17 +692,14 @@ class Pipeline:
         return out
 
     def check_guards(self):
-        """Nothing outside the connections' regions was written."""
-        mask = {k: np.ones(v.size, dtype=bool) for k, v in self.arenas.items()}
-        for c in range(self.n):
-            s = self.states[c]
-            for name, keys in (("heap", ("heap",)), ("pkt", ("pkts",)), ("frag", ("frag_acked",)), ("tx", ("tx", "ref_acked")),
-                               ("stage", ("stage",))):
-                a = int(s[name + "_first"])
-                for key in keys:
-                    mask[key][a: a + int(s[name + "_cap"])] = False
+        """Nothing outside the connections' regions was written, the padding's regions included: the regions stay
+        where they were laid out, and the record before and the record behind each (all there is between them) are as
+        they were."""
+        for name in ("heap", "pkt", "frag", "tx", "stage"):
+            for fld in (name + "_first", name + "_cap"):
+                assert np.array_equal(self.states[fld], self.layout[fld]), ("a region moved", fld)
         for k, v in self.arenas.items():
-            assert np.array_equal(v[mask[k]], self.guard[k][mask[k]]), ("wrote outside a region", k)
+            assert np.array_equal(v[self.guard_at[k]], self.guard[k]), ("wrote outside a region", k)
 
 
 # ---- a lossy link and its peer ----
@@ -687,6 +764,7 @@ def run_lossy(pipeline, rng, ticks, loss=0.25, rtt_ms=40, tick_ms=25, alloc=(300
         sent = pipeline.tick(now, rtt_ms, fa, acks)
         acks = [links[c].deliver(sent[c]) for c in range(n)]
         now += tick_ms
+    pipeline.next_acks, pipeline.next_ms = acks, now   # (what the next tick would get)
     return links
 
 

@@ -109,6 +109,31 @@ def test_threads_agree():
         assert a.arenas[k].tobytes() == b.arenas[k].tobytes(), k
 
 
+def test_padding_changes_nothing():
+    """The padding of resend_expect.Pipeline (what puts the GPU tests' launches into the lane form): the six
+    connections with six replicas and sixty idle fillers in the same arrays and arenas send the same frames, tick by
+    tick, and see the same events as the six alone."""
+    def frames(**kw):
+        p = R.Pipeline(lossy_configs(), R.HostBackend(2), **kw)
+        out, tick = [], p.tick
+        p.tick = lambda *a, **k: (out.append(tick(*a, **k)), out[-1])[1]
+        R.run_lossy(p, random.Random(5), 40, loss=0.3)
+        return p, out
+
+    plain, want = frames()
+    padded, got = frames(replicas=6, fillers=60)
+    assert padded.total == 72 and plain.total == plain.n == 6
+    assert list(padded.src[:6]) == list(range(6)) and sorted(padded.src[6:])[60:] == list(range(6))
+    assert got == want and len(got) == 40 and any(f for t in got for f in t)
+    assert padded.seen == plain.seen and padded.seen_stops == plain.seen_stops
+    # the replicas did the same work as their connections, the idle fillers none
+    assert padded.pad_totals["heap_pushed"] > 0 and padded.pad_totals["n_resent"] > 0 and plain.pad_totals["n_resent"] == 0
+    for c in np.flatnonzero(padded.src[6:] >= 0) + 6:
+        s, m = padded.states[c], padded.states[padded.src[c]]
+        assert (int(s["heap_len"]), int(s["tx_head"]), int(s["frag_next"])) == (int(m["heap_len"]), int(m["tx_head"]), int(m["frag_next"]))
+    assert plain.states.tobytes() == padded.states[:6].tobytes()   # (the first regions lie where they lay)
+
+
 def one_connection(**kw):
     p = R.Pipeline([R.Config(**kw)])
     for _ in range(3):
