@@ -288,7 +288,7 @@ void run_both(Batch& b, bool with_refs) {
   for (uint64_t c = n; c-- > 0;) {  // (the connections in any order: last first here)
     FqWaveShared sh;
     std::memset((void*)&sh, 0xCD, sizeof sh);
-    fq_step(FqHostWave{}, sh, a, c);
+    fq_step(SerialWave{}, sh, a, c);
   }
   a.results = r2.data();
   a.queues_out = q2.data();

@@ -97,15 +97,6 @@ struct Counts {
   uint64_t packets, out, carry;
 };
 
-// The wave policy of rx_receive_tiles as host code: a phase is a loop over the 64 lanes.
-struct HostWave {
-  template <class F>
-  void lanes(const F& f) const {
-    for (uint32_t l = 0; l < 64; l++) f(l);
-  }
-  static void or64(unsigned long long* p, unsigned long long v) { *p |= v; }
-  static void add64(unsigned long long* p, unsigned long long v) { *p += v; }
-};
 bool g_tiled = false;  // run_step takes the device form's parts instead of the serial walk
 
 // One step the way the device form runs it; the caps are the vectors' sizes.
@@ -149,7 +140,7 @@ Counts run_step(const std::vector<ufc_frame_info>& infos, const std::vector<ufc_
       std::memset((void*)&sh, 0xCD, sizeof sh);
       uint32_t d;
       uint64_t o, c[3];
-      rx_receive_tiles(HostWave{}, sh, a, r, plans.data(), d, o);
+      rx_receive_tiles(SerialWave{}, sh, a, r, plans.data(), d, o);
       rx_walk_end(a, r, d, o, c);
       c0[r] = c[0], c1[r] = c[1], c2[r] = c[2];
     }

@@ -9,7 +9,7 @@
 //   - chained ticks of one connection, begin -> a scalar emit -> place -> a scalar pack -> commit, with random acks
 //     of sent refs, packet window acks (some beyond the span, some of next_id while fragments are pending), random
 //     flush allocations, a small frame window, rings that wrap, ids through 2^20: run twice, the lanes of every phase
-//     forwards (RsHostWave) and backwards (RsReverseWave), and every state, result, arena byte and output compared.
+//     forwards (SerialWave) and backwards (ReverseWave), and every state, result, arena byte and output compared.
 // Prints "ok: <checks>" and exits 0; any difference or sanitizer report stops the program.
 #include <algorithm>
 #include <cstdint>
@@ -161,6 +161,32 @@ struct Tick {
   int64_t alloc;
   uint32_t room, flags;
   uint64_t now, rtt;
+};
+
+// The lanes of a phase in the opposite order to SerialWave's, which must not matter.
+struct ReverseWave {
+  template <class F>
+  void lanes(const F& f) const {
+    for (uint32_t l = 64; l-- > 0;) f(l);
+  }
+  template <class F>
+  void one(const F& f) const {
+    f();
+  }
+  template <class F>
+  unsigned long long ballot(const F& f) const {
+    unsigned long long m = 0;
+    for (uint32_t l = 64; l-- > 0;)
+      if (f(l)) m |= 1ull << l;
+    return m;
+  }
+  template <class F>
+  uint64_t sum(const F& f) const {
+    uint64_t s = 0;
+    for (uint32_t l = 64; l-- > 0;) s += f(l);
+    return s;
+  }
+  void sync() const {}
 };
 
 template <class Wv>
@@ -334,8 +360,8 @@ void check_ticks() {
         t.acks.push_back(f);
       }
       std::vector<uint8_t> ta, tb;
-      run_tick<RsHostWave>(a, t, ta);
-      run_tick<RsReverseWave>(b, t, tb);
+      run_tick<SerialWave>(a, t, ta);
+      run_tick<ReverseWave>(b, t, tb);
       if (ta != tb) fail("lane order changes the result", conn, tick, (long)ta.size());
       ufc_resend_result br;
       std::memcpy(&br, ta.data(), sizeof br);

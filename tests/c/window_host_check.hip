@@ -37,19 +37,6 @@ uint32_t rnd() {  // splitmix64
   return (uint32_t)((z ^ (z >> 31)) >> 16);
 }
 
-// The wave policy of fw_walk_tiles as host code: a phase is a loop over the 64 lanes.
-struct HostWave {
-  template <class F>
-  void lanes(const F& f) const {
-    for (uint32_t l = 0; l < 64; l++) f(l);
-  }
-  template <class F>
-  void one(const F& f) const {
-    f();
-  }
-  static void or64(unsigned long long* p, unsigned long long v) { *p |= v; }
-};
-
 struct Out {
   std::vector<uint8_t> accept;
   std::vector<ufc_item> groups;
@@ -78,7 +65,7 @@ void run(bool tiled, const std::vector<ufc_frame_info>& infos, const std::vector
     if (!tiled) return fw_walk_serial(a, r, write, gfirst);
     FwWaveShared sh;
     std::memset((void*)&sh, 0xCD, sizeof sh);
-    return fw_walk_tiles(HostWave{}, sh, a, r, write, gfirst);
+    return fw_walk_tiles(SerialWave{}, sh, a, r, write, gfirst);
   };
   for (uint64_t r = 0; r < n; r++) counts[r] = walk(r, false, 0);
   uint64_t total = 0;

@@ -122,6 +122,32 @@ def test_argument_checks(engine):
     engine.receive_packets(**a0)   # no receivers: UFC_OK
 
 
+def test_slot_count_limit_of_the_device_entry(engine):
+    """The device entry alone scans 2 n_slots + 1 chunk counts with a 32-bit count, so it takes n_slots below
+    (2^31 - 1) // 2 where the host entry takes them below 2^31 - 1: that many slots are refused before any launch,
+    with every pointer set; the same arguments with the receiver's own 4 slots are accepted."""
+    import ctypes
+    V = ctypes.c_void_p
+    r = fr.new_receivers(1, 4)
+    d = {"receivers": _t(r, 560), "slots": _t(np.zeros(4, fr.RX_SLOT_DTYPE), 32),
+         "frame_first": _t(np.zeros(2, np.uint64)), "slot_first": _t(np.array([0, 4], np.uint64))}
+    buf = torch.zeros(4096, dtype=torch.uint8, device=DEV)
+    at = lambda off: V(buf.data_ptr() + off)   # noqa: E731
+    st = V(torch.cuda.current_stream().cuda_stream)
+
+    def call(n_slots):
+        return fr.lib().ufc_receive_packets_varlen(
+            engine._ctx, None, 0, None, None, 0, None, None, 0, V(d["frame_first"].data_ptr()),
+            V(d["receivers"].data_ptr()), 1, V(d["slots"].data_ptr()), V(d["slot_first"].data_ptr()), n_slots, None, 0,
+            None, 0, at(64), at(128), None, 0, at(256), at(136), None, 0, at(144), None, at(512), at(1024), st)
+
+    assert call(((1 << 31) - 1) // 2) == T.UFC_ERR_INVALID_ARG
+    assert call(4) == 0
+    torch.cuda.synchronize()
+    res = buf[512:592].cpu().numpy().view(fr.RECEIVER_RESULT_DTYPE)
+    assert int(res["stop"][0]) == 0
+
+
 def big_fragment_steps(rng):
     """Two steps for three receivers: window 4096 with the ring wrapped and packets of 2, 64, 65 and 130 fragments
     (bitfield word edges) whose fragments arrive reversed, some withheld until the second step, beside more small

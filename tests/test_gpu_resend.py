@@ -664,7 +664,7 @@ def clone(p):
 
 
 def test_lane_lossy_traffic(lane_lossy):
-    """16,406 connections, so rs_begin_lane_kernel and rs_commit_lane_kernel (RsLaneWave) with a part-full last block:
+    """16,406 connections, so rs_begin_lane_kernel and rs_commit_lane_kernel (SerialWave) with a part-full last block:
     the lossy traffic of test_lossy_traffic_small_rings with ack frames every tick, in every wave of the first 256
     connections; the padding's acknowledge, ack propagation and heap pushes had work to do."""
     p = ran(lane_lossy)
@@ -672,27 +672,27 @@ def test_lane_lossy_traffic(lane_lossy):
     assert {R.DONE, R.SIZE_LIMITED, R.WINDOW_LIMITED, R.REF_HANG, R.STAGE_FULL, R.HEAP_FULL} <= p.seen_stops
     assert R.BAD_STATE not in p.seen_stops
     assert {"dead_pop", "acked_pop", "resent", "partial_packet", "frag_wrap", "id_wrap", "hang"} <= p.seen
-    assert "ref_acked_lane_63" in p.seen   # (RsLaneWave::sum's 64th turn had a ref to propagate)
+    assert "ref_acked_lane_63" in p.seen   # (SerialWave::sum's 64th turn had a ref to propagate)
     assert p.pad_totals["packets_freed"] > 0 and p.pad_totals["refs_acked"] > 0 and p.pad_totals["heap_pushed"] > 0, p.pad_totals
 
 
 @pytest.mark.parametrize("k,replicas", [(64, 0), (65, 64), (1000, 0)])
 def test_lane_heap_sizes(engine, k, replicas):
     """16,400 connections (lane form): test_heap_sizes' k pops and pushes through a heap of k entries inside one lane
-    of RsLaneWave, beside idle fillers (k = 65: and 64 replicas)."""
+    of SerialWave, beside idle fillers (k = 65: and 64 replicas)."""
     p = heap_pipeline(checked(engine), k, **padded(1, 16400, replicas))
     assert p.total == 16400 and p.total % 64 and (not replicas or p.pad_totals["n_resent"] == replicas * k)
 
 
 def test_lane_130_fragment_packet(engine):
-    """16,401 connections (lane form): the 129 pending fragments are staged by the three passes of RsLaneWave::lanes'
+    """16,401 connections (lane form): the 129 pending fragments are staged by the three passes of SerialWave::lanes'
     own loop, in the modelled connection and in 64 replicas."""
     p = fragments_pipeline(checked(engine), **padded(1, 16401, 64))
     assert p.total == 16401 and p.total % 64 and p.pad_totals["heap_pushed"] == 64 * 130
 
 
 def test_lane_acknowledge_frees_0_1_64_65_packets(engine):
-    """16,402 connections (lane form): RsLaneWave::ballot and ::sum over acknowledge deltas of 0, 1, 64 and 65 packets,
+    """16,402 connections (lane form): SerialWave::ballot and ::sum over acknowledge deltas of 0, 1, 64 and 65 packets,
     in the modelled connection and in 64 replicas."""
     p = acknowledge_pipeline(checked(engine), **padded(1, 16402, 64))
     assert p.total == 16402 and p.total % 64 and p.pad_totals["packets_freed"] == 64 * 130
@@ -757,7 +757,7 @@ def region_bytes(states, arenas, c):
 
 
 def test_lane_bad_state_among_good_ones(lane_lossy):
-    """16,406 connections (lane form): a BAD_STATE lane of RsLaneWave returns early while its 63 neighbours go on.
+    """16,406 connections (lane form): a BAD_STATE lane of SerialWave returns early while its 63 neighbours go on.
     The connections at batch indices 0, 31, 63, 64, the last one and the modelled connection 4 are broken after the
     lossy ticks; they stop BAD_STATE in begin and in commit with their state and arena bytes untouched, and every
     other connection equals the host, with resends among the broken ones' wave neighbours."""
@@ -854,8 +854,8 @@ def switch_pass(be, B, m):
 
 
 def test_form_switch_16383_against_16384(engine, switch_batch):
-    """The same connections at 16,383 (the last wave-form count: rs_begin_kernel, rs_commit_kernel, RsDevWave) and at
-    16,384 (the first lane-form count: the _lane_ kernels, RsLaneWave, every block full), with a tick's ack frames so
+    """The same connections at 16,383 (the last wave-form count: rs_begin_kernel, rs_commit_kernel, DevWave) and at
+    16,384 (the first lane-form count: the _lane_ kernels, SerialWave, every block full), with a tick's ack frames so
     that acknowledge runs: each pass equals the host, and the first 16,383 connections come out the same from both."""
     be, B = checked(engine), switch_batch
     a, b = switch_pass(be, B, 16383), switch_pass(be, B, 16384)

@@ -273,6 +273,37 @@ def test_caps_below_need_and_argument_rules():
     assert fr.lib().ufc_receive_packets_host(*a) == 0   # no receivers: UFC_OK whatever the pointers
 
 
+def test_argument_table():
+    """Every pointer and every limited count of ufc_receive_packets_host, over one new receiver with a frame that
+    did not parse and an item no frame holds: a required pointer that is NULL, an array that is NULL beside its
+    non-zero count, and a count of 2^31 - 1 are UFC_ERR_INVALID_ARG; the three nullable arguments may be NULL."""
+    import ctypes
+    infos, items = np.zeros(1, dtype=fr.FRAME_INFO_DTYPE), np.zeros(1, dtype=fr.ITEM_DTYPE)
+    r, ro, slots = fr.new_receivers(1, 4), fr.new_receivers(1, 4), np.zeros(4, dtype=fr.RX_SLOT_DTYPE)
+    accept, base, status = np.ones(1, np.uint8), np.zeros(1, np.uint64), np.zeros(1, np.uint8)
+    payload, out = np.zeros(8, np.uint8), np.zeros(8, np.uint8)
+    carry_in, carry_out = np.zeros(1, np.uint64), np.zeros(1, np.uint64)   # (8-byte aligned, as the call demands)
+    ff, sf = np.array([0, 1], np.uint64), np.array([0, 4], np.uint64)
+    cf, pf = np.zeros(2, np.uint64), np.zeros(2, np.uint64)
+    packets, res = np.zeros(1, dtype=fr.RX_PACKET_DTYPE), np.zeros(1, dtype=fr.RECEIVER_RESULT_DTYPE)
+    u = [ctypes.c_uint64(0) for _ in range(3)]
+    p = lambda a: a.ctypes.data   # noqa: E731
+    ok = [p(infos), 1, p(accept), p(items), 1, p(base), p(payload), 8, p(ff), p(r), 1, p(slots), p(sf), 4, p(carry_in), 8,
+          p(carry_out), 8, p(cf), ctypes.addressof(u[0]), p(packets), 1, p(pf), ctypes.addressof(u[1]), p(out), 8,
+          ctypes.addressof(u[2]), p(status), p(res), p(ro), 1]
+    call = fr.lib().ufc_receive_packets_host
+    assert call(*ok) == 0
+    counts = (1, 4, 10, 13)                                   # n_frames, n_items, n_receivers, n_slots
+    for k in (8, 9, 12, 18, 19, 22, 23, 26, 28, 29) + (0, 3, 6, 11, 14, 16, 20, 24) + counts:
+        bad = list(ok)
+        bad[k] = (1 << 31) - 1 if k in counts else None
+        assert call(*bad) == UFC_ERR_INVALID_ARG, k
+    for k in (2, 5, 27):                                      # frame_accept, src_base, item_status
+        fine = list(ok)
+        fine[k] = None
+        assert call(*fine) == 0, k
+
+
 def lib_call_null_payload(r, s, z):
     import ctypes
     res = np.zeros(1, dtype=fr.RECEIVER_RESULT_DTYPE)

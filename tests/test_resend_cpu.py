@@ -265,6 +265,48 @@ def test_null_and_zero_count_rules():
     assert L.ufc_resend_place_host(p.states.ctypes.data, None, 1, None, 0, ff.ctypes.data, None, 0, 1) == UFC_ERR_INVALID_ARG
 
 
+def check_argument_table(call, ok, required, counted, counts, nullable):
+    """`ok` is accepted; NULL in place of a required pointer, NULL for an array whose count is not zero and a count of
+    2^31 - 1 are UFC_ERR_INVALID_ARG; NULL for a nullable argument is accepted."""
+    assert call(*ok) == UFC_OK
+    for k in required + counted + counts:
+        bad = list(ok)
+        bad[k] = (1 << 31) - 1 if k in counts else None
+        assert call(*bad) == UFC_ERR_INVALID_ARG, k
+    for k in nullable:
+        fine = list(ok)
+        fine[k] = None
+        assert call(*fine) == UFC_OK, k
+
+
+def test_place_and_commit_argument_rules():
+    """Every pointer and every limited count of ufc_resend_place_host and ufc_resend_commit_host, over one connection
+    that begin refused (UFC_RS_BAD_STATE: place leaves it alone, commit copies it through), so that one record per
+    array is enough."""
+    def rec(dtype, n=1):
+        return np.zeros(n, dtype=dtype)
+    states, begin = rec(fr.RESEND_DTYPE), rec(fr.RESEND_RESULT_DTYPE)
+    begin["stop"] = fr.RS_BAD_STATE
+    stage, items, first = rec(fr.ITEM_DTYPE), rec(fr.ITEM_DTYPE), rec(np.uint64, 2)
+    p = lambda a: a.ctypes.data   # noqa: E731
+    check_argument_table(lib().ufc_resend_place_host,
+                         [p(states), p(begin), 1, p(stage), 1, p(first), p(items), 1, 1],
+                         required=(0, 1, 5), counted=(3, 6), counts=(2,), nullable=())
+    keep = [rec(d) for d in (fr.FLUSH_RESULT_DTYPE, fr.FRAME_INFO_DTYPE, fr.PACKET_DTYPE, fr.PACKET_RESULT_DTYPE,
+                             fr.SENDER_RESULT_DTYPE, fr.RATE_RESULT_DTYPE, fr.SENDER_DTYPE, fr.RESEND_ENTRY_DTYPE,
+                             fr.SENT_PACKET_DTYPE, np.uint8, fr.TX_REF_DTYPE, fr.SENT_FRAME_DTYPE, np.uint32,
+                             fr.RESEND_COMMIT_RESULT_DTYPE, fr.RESEND_DTYPE, fr.SENDER_DTYPE)]
+    (flush_results, infos, packets, packet_results, sender_results, rate, senders, heap, pkts, frag, tx, sent, extra,
+     results, states_out, retake) = keep
+    offsets, used, sent_first = rec(np.uint64, 2), rec(np.uint64), rec(np.uint64, 2)
+    ok = [p(flush_results), p(infos), 1, p(offsets), p(used), p(items), 1, p(first), p(packets), 1, p(first),
+          p(packet_results), p(sender_results), p(begin), p(rate), p(states), p(senders), 1, p(heap), 1, p(pkts), 1,
+          p(frag), 1, p(tx), 1, p(sent), 1, p(sent_first), p(extra), p(results), p(states_out), p(retake), 1]
+    check_argument_table(lib().ufc_resend_commit_host, ok,
+                         required=(0, 3, 4, 7, 10, 12, 13, 14, 15, 16, 28, 30, 31, 32),
+                         counted=(1, 5, 8, 11, 18, 20, 22, 24, 26), counts=(2, 6, 9, 17), nullable=(29,))
+
+
 def test_core_under_sanitizers():
     """tests/c/resend_host_check.hip: the wave-policy core (rs_begin, rs_place, rs_commit) as host code under
     AddressSanitizer and UBSan, the lanes of a phase forwards and backwards, over exact-size buffers, with the heap

@@ -28,7 +28,6 @@
 // This keeps every store a full aligned 16 bytes per lane, 1 KiB contiguous per wave (DESIGN.md section
 // 5.3 measured sub-64-byte scattered writes as read-modify-writes).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstddef>
@@ -36,6 +35,7 @@
 #include "frame_build.hpp"
 #include "frame_build_piece.hpp"
 #include "frame_codec_core.hpp"
+#include "scan.hpp"
 
 namespace ufc_dev {
 
@@ -171,61 +171,41 @@ __global__ __launch_bounds__(kBuildThreads) void build_write_kernel(BuildArgs a,
   }
 }
 
-struct BuildLayout {  // scratch of a build (256-byte aligned parts)
-  uint64_t dst, flags, owners, temp, end;
-  BuildLayout(uint64_t n, uint64_t n_items, uint64_t spans, size_t temp_bytes) {
-    auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-    dst = 0;
-    flags = dst + up((n_items + 1) * 8);
-    owners = flags + up(n);
-    temp = owners + up((spans + 1) * 4);
-    end = temp + up(temp_bytes);
-  }
-};
-size_t scan_temp_bytes(uint64_t n, uint64_t n_items) {  // one scan over max(n, n_items) + 1 words
-  size_t temp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, temp, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                         (int)(std::max(n, n_items) + 1));
-  return temp;
-}
-
 }  // namespace
 
-size_t build_scratch_bytes(uint64_t n, uint64_t n_items, uint64_t out_len) {
-  return BuildLayout(n, n_items, write_spans(out_len), scan_temp_bytes(n, n_items)).end;
-}
-
-hipError_t build_sizes(const BuildArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  const BuildLayout lay(a.n, a.n_items, 0, scan_temp_bytes(a.n, a.n_items));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
+hipError_t build_sizes(const BuildArgs& a, const ScratchSource& scratch, hipStream_t stream) {
+  const size_t temp_bytes = scan_temp_bytes<uint64_t>(a.n + 1);
+  char* temp;
+  hipError_t e = scratch.get(temp_bytes, &temp);
+  if (e != hipSuccess) return e;
   const unsigned blocks = (unsigned)((a.n + 1 + kBuildThreads - 1) / kBuildThreads);
   build_check_kernel<false><<<blocks, kBuildThreads, 0, stream>>>(a, nullptr, nullptr, 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  size_t temp_bytes = lay.end - lay.temp;
-  return hipcub::DeviceScan::ExclusiveSum((char*)scratch + lay.temp, temp_bytes, a.out_offsets, a.out_offsets,
-                                          (int)(a.n + 1), stream);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return exclusive_sum(temp, temp_bytes, a.out_offsets, a.out_offsets, a.n + 1, stream);
 }
 
-hipError_t build_write(const BuildArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+hipError_t build_write(const BuildArgs& a, const ScratchSource& scratch, hipStream_t stream) {
   // One workgroup per kSpanBytes of the buffer's first out_len bytes (the batch's stream lies inside them;
   // a workgroup past its end returns after reading the two end offsets).
   const uint64_t wblocks = write_spans(a.out_len);
+  const size_t temp_bytes = scan_temp_bytes<uint64_t>(a.n_items + 1);
+  ScratchPlan plan;  // the items' destination offsets, a flag byte per frame, a word per span, the scan's temporaries
+  const uint64_t at_dst = plan.take((a.n_items + 1) * 8);
+  const uint64_t at_flags = plan.take(a.n);
+  const uint64_t at_owners = plan.take((wblocks + 1) * 4);
+  const uint64_t at_temp = plan.take(temp_bytes);
+  char* s;
+  hipError_t e = scratch.get(plan.end, &s);
+  if (e != hipSuccess) return e;
   if (wblocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  const BuildLayout lay(a.n, a.n_items, wblocks, scan_temp_bytes(a.n, a.n_items));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
   if (a.out_len == 0) return hipSuccess;  // no frame fits: nothing is written
-  char* s = (char*)scratch;
-  uint64_t* dst = (uint64_t*)(s + lay.dst);
-  uint8_t* flags = (uint8_t*)(s + lay.flags);
-  uint32_t* owners = (uint32_t*)(s + lay.owners);
-  size_t temp_bytes = lay.end - lay.temp;
+  uint64_t* dst = (uint64_t*)(s + at_dst);
+  uint8_t* flags = (uint8_t*)(s + at_flags);
+  uint32_t* owners = (uint32_t*)(s + at_owners);
   const unsigned iblocks = (unsigned)((a.n_items + 1 + kBuildThreads - 1) / kBuildThreads);
   build_item_sizes_kernel<<<iblocks, kBuildThreads, 0, stream>>>(a.items, a.n_items, dst);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(s + lay.temp, temp_bytes, dst, dst, (int)(a.n_items + 1), stream);
-  if (e != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = exclusive_sum(s + at_temp, temp_bytes, dst, dst, a.n_items + 1, stream)) != hipSuccess) return e;
   const unsigned fblocks = (unsigned)((a.n + 1 + kBuildThreads - 1) / kBuildThreads);
   build_check_kernel<true><<<fblocks, kBuildThreads, 0, stream>>>(a, flags, owners, wblocks);
   if ((e = hipGetLastError()) != hipSuccess) return e;

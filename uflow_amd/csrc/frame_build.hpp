@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/uflow_frame_codec.h"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
@@ -23,12 +24,9 @@ struct BuildArgs {
   uint64_t out_len;
 };
 
-// Device scratch of either call: the scan temporaries and, for the write (out_len > 0), the items'
-// destination offsets (8 (n_items + 1) bytes), one flag byte per frame and one word per 16 KiB of out_len.
-size_t build_scratch_bytes(uint64_t n, uint64_t n_items, uint64_t out_len);
 // out_offsets (exclusive sum of the frames' encoded sizes, 0 for frames not UFC_BUILD_OK) and status.
-hipError_t build_sizes(const BuildArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t build_sizes(const BuildArgs& a, const ScratchSource& scratch, hipStream_t stream);
 // Every frame whose span matches its size, trailer bytes zero.
-hipError_t build_write(const BuildArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t build_write(const BuildArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

@@ -41,15 +41,28 @@ inline void trailer(uint8_t* f, size_t body, int seal) {
 constexpr uint32_t kPacketIdMask = (1u << 20) - 1;  // src/packet_id.rs
 
 // ---- batched host build (the encode of frame_codec_core.hpp, shared with frame_build.hip) ----
+// body(a, b) over contiguous ranges of [0, n) on up to nthreads threads, and no more threads than n / grain
+// rounded up: kRecordGrain where an element is a record's worth of work (a frame, a flush, a sender, a copy
+// segment), kStepGrain where it is a connection's whole step, which is work enough for a thread.
+constexpr size_t kRecordGrain = 1024, kStepGrain = 1;
 template <class F>
-void for_ranges(size_t n, int nthreads, const F& body) {  // body(a, b) over contiguous frame ranges
-  int T = nthreads > 0 ? nthreads : 1;
-  T = (int)std::min<size_t>((size_t)T, (n + 1023) / 1024);
-  if (T < 1) T = 1;
+void for_ranges(size_t n, int nthreads, size_t grain, const F& body) {
+  size_t T = nthreads > 0 ? (size_t)nthreads : 1;
+  T = std::max<size_t>(1, std::min(T, (n + grain - 1) / grain));
   std::vector<std::thread> th;
-  for (int t = 1; t < T; t++) th.emplace_back([&, t] { body(n * t / T, n * (t + 1) / T); });
+  for (size_t t = 1; t < T; t++) th.emplace_back([&, t] { body(n * t / T, n * (t + 1) / T); });
   body(0, n / T);
   for (auto& x : th) x.join();
+}
+// first[1 .. n] hold n counts: first[0 .. n] become their exclusive sum, first[n] the total, which is returned.
+inline uint64_t counts_to_firsts(uint64_t* first, size_t n) {
+  uint64_t total = 0;
+  for (size_t r = 0; r < n; r++) {
+    const uint64_t c = first[r + 1];
+    first[r] = total;
+    total += c;
+  }
+  return first[n] = total;
 }
 inline void put_packed(uint8_t* out, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t nbytes) {
   for (uint32_t j = 0; j < nbytes; j++) out[j] = (uint8_t)ufc_codec::packed_byte(w0, w1, w2, j);
@@ -310,7 +323,7 @@ int ufc_build_sizes_host(const ufc_frame_info* infos, const ufc_item* items, siz
   if (n == 0) return UFC_OK;
   if (!infos || !out_offsets || (!items && n_items) || n >= ((size_t)1 << 31) || n_items >= ((size_t)1 << 31))
     return UFC_ERR_INVALID_ARG;
-  for_ranges(n, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t i = a; i < b; i++) {
       uint64_t size;
       const uint8_t st = ufc_codec::check_frame(infos[i], items, n_items, src_base ? src_base[i] : 0, payload_len, size);
@@ -331,7 +344,7 @@ int ufc_build_batch_host(const ufc_frame_info* infos, const ufc_item* items, siz
       n >= ((size_t)1 << 31) || n_items >= ((size_t)1 << 31))
     return UFC_ERR_INVALID_ARG;
   const uint64_t first = out_offsets[0], last = out_offsets[n];
-  for_ranges(n, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t i = a; i < b; i++) {
       const ufc_frame_info& info = infos[i];
       const uint64_t base = src_base ? src_base[i] : 0;
@@ -428,7 +441,7 @@ int ufc_pack_host(const ufc_item* items, size_t n_items, const uint64_t* flush_f
       n_flushes >= ((size_t)1 << 31) - 1 || n_items >= ((size_t)1 << 31) - 1)
     return UFC_ERR_INVALID_ARG;
   // Pass 1: every flush's result; then frame_first, their exclusive sum; pass 2: the frames.
-  for_ranges(n_flushes, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n_flushes, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t j = a; j < b; j++) {
       results[j].frame_first = 0;
       pack_flush(items, n_items, flush_first[j], flush_first[j + 1], flushes[j], nullptr, nullptr, 0, results[j]);
@@ -441,7 +454,7 @@ int ufc_pack_host(const ufc_item* items, size_t n_items, const uint64_t* flush_f
   }
   *frames_used = total;
   if (!infos) return UFC_OK;
-  for_ranges(n_flushes, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n_flushes, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t j = a; j < b; j++)
       if (results[j].frame_count)
         pack_flush(items, n_items, flush_first[j], flush_first[j + 1], flushes[j], nonce_bits, infos, frames_cap,
@@ -544,21 +557,14 @@ int ufc_emit_packets_host(const ufc_packet* packets, size_t n_packets, const uin
       (!items && items_cap) || n_senders >= ((size_t)1 << 31) - 1 || n_packets >= ((size_t)1 << 31) - 1)
     return UFC_ERR_INVALID_ARG;
   // Pass 1: every sender's item count, into flush_first; then their exclusive sum; pass 2: the outputs.
-  for_ranges(n_senders, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n_senders, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t s = a; s < b; s++)
       flush_first[s + 1] = emit_sender(packets, n_packets, packet_first[s], packet_first[s + 1], senders[s], false, 0,
                                        nullptr, 0, nullptr, nullptr, nullptr);
   });
-  uint64_t total = 0;
-  for (size_t s = 0; s < n_senders; s++) {
-    const uint64_t c = flush_first[s + 1];
-    flush_first[s] = total;
-    total += c;
-  }
-  flush_first[n_senders] = total;
-  *items_used = total;
+  const uint64_t total = *items_used = counts_to_firsts(flush_first, n_senders);
   if (total >= ((uint64_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
-  for_ranges(n_senders, nthreads, [&](size_t a, size_t b) {
+  for_ranges(n_senders, nthreads, kRecordGrain, [&](size_t a, size_t b) {
     for (size_t s = a; s < b; s++)
       emit_sender(packets, n_packets, packet_first[s], packet_first[s + 1], senders[s], true, flush_first[s], items,
                   items_cap, packet_results, &sender_results[s], senders_out ? &senders_out[s] : nullptr);
@@ -570,16 +576,6 @@ int ufc_emit_packets_host(const ufc_packet* packets, size_t n_packets, const uin
 
 // ---- batched host receive ----
 namespace {
-// body(a, b) over contiguous receiver ranges, up to nthreads of them (a receiver's walk is work enough).
-template <class F>
-void for_receivers(size_t n, int nthreads, const F& body) {
-  size_t T = nthreads > 0 ? (size_t)nthreads : 1;
-  T = std::max<size_t>(1, std::min(T, n));
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < T; t++) th.emplace_back([&, t] { body(n * t / T, n * (t + 1) / T); });
-  body(0, n / T);
-  for (auto& x : th) x.join();
-}
 // One copy segment, clipped at its destination's cap.
 void rx_copy(const ufc_codec::RxArgs& a, const ufc_codec::RxSegment& sg) {
   if (!sg.len) return;
@@ -604,17 +600,11 @@ int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const
                              uint64_t* out_used, uint8_t* item_status, ufc_receiver_result* results,
                              ufc_receiver* receivers_out, int nthreads) {
   if (n_receivers == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!frame_first || !receivers || !receivers_out || !slot_first || !carry_first || !carry_used || !packet_first ||
-      !packets_used || !out_used || !results || (!infos && n_frames) || (!items && n_items) ||
-      (!payload && payload_len) || (!slots && n_slots) || (!carry_in && carry_in_len) || (!carry_out && carry_cap) ||
-      (!packets && packets_cap) || (!out_bytes && out_cap) || n_frames >= lim || n_items >= lim || n_receivers >= lim ||
-      n_slots >= lim || ((uintptr_t)carry_in & 7) || ((uintptr_t)carry_out & 7))  // (the bit words are read as uint64)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::RxArgs a{infos, n_frames, frame_accept, items, n_items, src_base, payload, payload_len, frame_first,
                             receivers, n_receivers, slots, slot_first, n_slots, carry_in, carry_in_len, carry_out,
                             carry_cap, carry_first, carry_used, packets, packets_cap, packet_first, packets_used,
                             out_bytes, out_cap, out_used, item_status, results, receivers_out};
+  if (!ufc_codec::rx_args_ok(a)) return UFC_ERR_INVALID_ARG;
   std::vector<ufc_codec::RxPlan> plans(n_slots);
   std::vector<uint8_t> own_status(item_status ? 0 : n_items);
   uint8_t* status = item_status ? item_status : own_status.data();
@@ -622,7 +612,7 @@ int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const
   const ufc_codec::RxDupSet dups{table.data(), table.size() - 1};
   std::vector<uint64_t> out_first(n_receivers + 1);
   // Pass 1: every receiver's step; its counts into the three CSR arrays, then their exclusive sums.
-  for_receivers(n_receivers, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n_receivers, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t r = lo; r < hi; r++) {
       if (receivers_out != receivers) receivers_out[r] = receivers[r];
       uint64_t c[3];
@@ -632,31 +622,18 @@ int ufc_receive_packets_host(const ufc_frame_info* infos, size_t n_frames, const
       carry_first[r + 1] = c[2];
     }
   });
-  uint64_t np = 0, nb = 0, nc = 0;
-  for (size_t r = 0; r < n_receivers; r++) {
-    const uint64_t c0 = packet_first[r + 1], c1 = out_first[r + 1], c2 = carry_first[r + 1];
-    packet_first[r] = np;
-    out_first[r] = nb;
-    carry_first[r] = nc;
-    np += c0;
-    nb += c1;
-    nc += c2;
-  }
-  packet_first[n_receivers] = np;
-  out_first[n_receivers] = nb;
-  carry_first[n_receivers] = nc;
-  *packets_used = np;
-  *out_used = nb;
-  *carry_used = nc;
+  *packets_used = counts_to_firsts(packet_first, n_receivers);
+  *out_used = counts_to_firsts(out_first.data(), n_receivers);
+  *carry_used = counts_to_firsts(carry_first, n_receivers);
   // Pass 2: records, layout, bits and segments; then the copies, the slots' before the datagrams'.
   std::vector<ufc_codec::RxSegment> segs(2 * n_slots + n_items);
-  for_receivers(n_receivers, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n_receivers, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t r = lo; r < hi; r++) ufc_codec::rx_finish(a, r, plans.data(), status, out_first[r], segs.data(), nullptr);
   });
-  for_ranges(2 * n_slots, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(2 * n_slots, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; k++) rx_copy(a, segs[k]);
   });
-  for_ranges(n_items, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n_items, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; k++) rx_copy(a, segs[2 * n_slots + k]);
   });
   return UFC_OK;
@@ -668,25 +645,15 @@ int ufc_frame_window_host(const ufc_frame_info* infos, size_t n_frames, const ui
                           ufc_item* groups, size_t groups_cap, uint64_t* group_first, uint64_t* groups_used,
                           ufc_frame_window_result* results, ufc_frame_window* windows_out, int nthreads) {
   if (n_windows == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!frame_first || !windows || !windows_out || !frame_accept || !group_first || !groups_used || !results ||
-      (!infos && n_frames) || (!groups && groups_cap) || n_frames >= lim || n_windows >= lim)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::FwArgs a{infos, n_frames, frame_first, windows, n_windows, frame_accept, groups, groups_cap,
                             group_first, groups_used, results, windows_out};
+  if (!ufc_codec::fw_args_ok(a)) return UFC_ERR_INVALID_ARG;
   // Pass 1: every connection's group count, into group_first; then their exclusive sum; pass 2: the outputs.
-  for_receivers(n_windows, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n_windows, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t r = lo; r < hi; r++) group_first[r + 1] = ufc_codec::fw_walk_serial(a, r, false, 0);
   });
-  uint64_t total = 0;
-  for (size_t r = 0; r < n_windows; r++) {
-    const uint64_t c = group_first[r + 1];
-    group_first[r] = total;
-    total += c;
-  }
-  group_first[n_windows] = total;
-  *groups_used = total;
-  for_receivers(n_windows, nthreads, [&](size_t lo, size_t hi) {
+  *groups_used = counts_to_firsts(group_first, n_windows);
+  for_ranges(n_windows, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t r = lo; r < hi; r++) ufc_codec::fw_walk_serial(a, r, true, group_first[r]);
   });
   return UFC_OK;
@@ -699,18 +666,14 @@ int ufc_frame_queue_host(const ufc_frame_info* infos, size_t n_frames, const ufc
                          size_t n_queues, ufc_sent_frame* log, size_t n_log, uint8_t* ref_acked, size_t refs_cap,
                          ufc_frame_queue_result* results, ufc_frame_queue* queues_out, int nthreads) {
   if (n_queues == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!frame_first || !sent_first || !queues || !steps || !results || !queues_out || (!infos && n_frames) ||
-      (!items && n_items) || (!sent && n_sent) || (!log && n_log) || n_frames >= lim || n_items >= lim ||
-      n_sent >= lim || n_queues >= lim)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::FqArgs a{infos, n_frames, items, n_items, frame_first, sent, n_sent, sent_first, queues, steps,
                             n_queues, log, n_log, ref_acked, refs_cap, results, queues_out};
+  if (!ufc_codec::fq_args_ok(a)) return UFC_ERR_INVALID_ARG;
   // The step the device runs, the lanes of a phase one after the other; a connection touches its own ring, its
   // own records and (with ranges that do not overlap) its own fragment marks, so the connections run in parallel.
-  for_receivers(n_queues, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n_queues, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     ufc_codec::FqWaveShared sh;
-    for (size_t c = lo; c < hi; c++) ufc_codec::fq_step(ufc_codec::FqHostWave{}, sh, a, c);
+    for (size_t c = lo; c < hi; c++) ufc_codec::fq_step(ufc_codec::SerialWave{}, sh, a, c);
   });
   return UFC_OK;
 }
@@ -719,8 +682,9 @@ int ufc_frame_queue_host(const ufc_frame_info* infos, size_t n_frames, const ufc
 int ufc_rate_begin_host(const ufc_rate_state* states, const uint64_t* now_ms, const uint32_t* extra_flags, size_t n,
                         ufc_frame_queue_step* steps, ufc_rate_state* states_out, int nthreads) {
   if (n == 0) return UFC_OK;
-  if (!states || !now_ms || !steps || !states_out || n >= ((size_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
-  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+  const ufc_codec::RateBeginArgs a{states, now_ms, extra_flags, n, steps, states_out};
+  if (!ufc_codec::rate_begin_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t c = lo; c < hi; c++) {
       ufc_rate_state S = states[c];
       ufc_frame_queue_step Q;
@@ -737,13 +701,11 @@ int ufc_rate_step_host(const ufc_rate_state* states, const ufc_rate_tick* ticks,
                        size_t n_flush_results, const uint32_t* result_index, ufc_flush* flushes, size_t n_flushes,
                        const uint32_t* flush_index, ufc_rate_result* results, ufc_rate_state* states_out, int nthreads) {
   if (n == 0) return UFC_OK;
-  if (!states || !ticks || !fq || !results || !states_out || (!entries && n_entries) ||
-      (flush_results && !result_index) || (flushes && !flush_index) || n >= ((size_t)1 << 31) - 1)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::RateArgs a{states, ticks, fq, n, entries, n_entries, flush_results, n_flush_results, result_index,
                               flushes, n_flushes, flush_index, results, states_out};
+  if (!ufc_codec::rate_args_ok(a)) return UFC_ERR_INVALID_ARG;
   // The step the device gives a lane; a connection touches its own records, its own entries and its own flush.
-  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     for (size_t c = lo; c < hi; c++) {
       ufc_rate_state S = states[c];
       ufc_rate_result R;
@@ -765,18 +727,14 @@ int ufc_resend_begin_host(const ufc_frame_info* infos, size_t n_frames, const ui
                           size_t n_stage, ufc_resend_result* results, ufc_resend* states_out, ufc_sender* senders_out,
                           int nthreads) {
   if (n == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!frame_first || !queues || !rate || !flushes || !states || !senders || !results || !states_out || !senders_out ||
-      (!infos && n_frames) || (!log && n_log) || (!heap && n_heap) || (!pkts && n_pkts) || (!frag_acked && n_frag) ||
-      (!tx && n_tx) || (!stage && n_stage) || n >= lim || n_frames >= lim)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::RsBeginArgs a{infos, n_frames, frame_first, queues, log, n_log, rate, flags, flushes, states, senders,
                                  n, heap, n_heap, pkts, n_pkts, frag_acked, n_frag, tx, n_tx, ref_acked, refs_cap, stage,
                                  n_stage, results, states_out, senders_out};
+  if (!ufc_codec::rs_begin_args_ok(a)) return UFC_ERR_INVALID_ARG;
   // The step the device runs; a connection touches its own regions and records, so the connections run in parallel.
-  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     ufc_codec::RsWaveShared sh;
-    for (size_t c = lo; c < hi; c++) ufc_codec::rs_begin(ufc_codec::RsHostWave{}, sh, a, c);
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_begin(ufc_codec::SerialWave{}, sh, a, c);
   });
   return UFC_OK;
 }
@@ -785,12 +743,10 @@ int ufc_resend_place_host(const ufc_resend* states, const ufc_resend_result* beg
                           const ufc_item* stage, size_t n_stage, const uint64_t* flush_first, ufc_item* items,
                           size_t items_cap, int nthreads) {
   if (n == 0) return UFC_OK;
-  if (!states || !begin_results || !flush_first || (!stage && n_stage) || (!items && items_cap) ||
-      n >= ((size_t)1 << 31) - 1)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::RsPlaceArgs a{states, begin_results, n, stage, n_stage, flush_first, items, items_cap};
-  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
-    for (size_t c = lo; c < hi; c++) ufc_codec::rs_place(ufc_codec::RsHostWave{}, a, c);
+  if (!ufc_codec::rs_place_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_place(ufc_codec::SerialWave{}, a, c);
   });
   return UFC_OK;
 }
@@ -806,20 +762,14 @@ int ufc_resend_commit_host(const ufc_flush_result* flush_results, const ufc_fram
                            size_t sent_cap, uint64_t* sent_first, uint32_t* next_extra_flags,
                            ufc_resend_commit_result* results, ufc_resend* states_out, ufc_sender* retake, int nthreads) {
   if (n == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!flush_results || !out_offsets || !frames_used || !flush_first || !packet_first || !sender_results ||
-      !begin_results || !rate || !states || !senders || !sent_first || !results || !states_out || !retake ||
-      (!infos && n_infos) || (!items && n_items) || (!packets && n_packets) || (!packet_results && n_packets) ||
-      (!heap && n_heap) || (!pkts && n_pkts) || (!frag_acked && n_frag) || (!tx && n_tx) || (!sent && sent_cap) ||
-      n >= lim || n_packets >= lim || n_items >= lim || n_infos >= lim)
-    return UFC_ERR_INVALID_ARG;
   const ufc_codec::RsCommitArgs a{flush_results, infos, n_infos, out_offsets, frames_used, items, n_items, flush_first,
                                   packets, n_packets, packet_first, packet_results, sender_results, begin_results, rate,
                                   states, senders, n, heap, n_heap, pkts, n_pkts, frag_acked, n_frag, tx, n_tx, sent,
                                   sent_cap, sent_first, next_extra_flags, results, states_out, retake};
-  for_receivers(n, nthreads, [&](size_t lo, size_t hi) {
+  if (!ufc_codec::rs_commit_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
     ufc_codec::RsWaveShared sh;
-    for (size_t c = lo; c < hi; c++) ufc_codec::rs_commit(ufc_codec::RsHostWave{}, sh, a, c);
+    for (size_t c = lo; c < hi; c++) ufc_codec::rs_commit(ufc_codec::SerialWave{}, sh, a, c);
   });
   return UFC_OK;
 }

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "../../include/uflow_frame_codec.h"
+#include "wave.hpp"
 
 namespace ufc_codec {
 
@@ -621,6 +622,21 @@ struct RxArgs {
   ufc_receiver_result* results;
   ufc_receiver* receivers_out;
 };
+// The argument contracts of the batched calls from here on, each stated once for its host entry (frame_codec.cpp)
+// and its device entry (ufc_api.cpp): a required pointer is set, an array with a non-zero count is set, and every
+// count that is scanned or indexed with 32 bits lies below kCountLim.  Host code.  An entry asks after its own two
+// answers: a missing context is an error (device entries), and an empty batch is UFC_OK whatever the pointers.
+constexpr uint64_t kCountLim = ((uint64_t)1 << 31) - 1;
+inline bool rx_args_ok(const RxArgs& a) {
+  const bool bad = !a.frame_first || !a.receivers || !a.receivers_out || !a.slot_first || !a.carry_first ||
+                   !a.carry_used || !a.packet_first || !a.packets_used || !a.out_used || !a.results ||
+                   (!a.infos && a.n_frames) || (!a.items && a.n_items) || (!a.payload && a.payload_len) ||
+                   (!a.slots && a.n_slots) || (!a.carry_in && a.carry_in_len) || (!a.carry_out && a.carry_cap) ||
+                   (!a.packets && a.packets_cap) || (!a.out_bytes && a.out_cap) || a.n_frames >= kCountLim ||
+                   a.n_items >= kCountLim || a.n_receivers >= kCountLim || a.n_slots >= kCountLim ||
+                   ((uintptr_t)a.carry_in & 7) || ((uintptr_t)a.carry_out & 7);  // (the bit words are read as uint64)
+  return !bad;
+}
 
 // What the copy needs to know of a slot (48 bytes).
 enum RxPlanFlags : uint32_t {
@@ -1014,21 +1030,6 @@ struct RxWaveShared {
   unsigned long long deliv_mask, entry_mask, entry_fail, ready_bits, alloc_sub, out_bytes;
   uint32_t delivered, new_base, stop;
 };
-UFC_HD uint32_t rx_high_bit(unsigned long long m) {
-  uint32_t b = 0;
-  while (m >>= 1) b++;
-  return b;
-}
-UFC_HD uint32_t rx_low_bit(unsigned long long m) {
-  uint32_t b = 0;
-  while (!(m & 1)) m >>= 1, b++;
-  return b;
-}
-UFC_HD uint32_t rx_popc(unsigned long long m) {
-  uint32_t n = 0;
-  for (; m; m &= m - 1) n++;
-  return n;
-}
 template <class Wv>
 inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh, const RxArgs& a, uint64_t r, RxPlan* plans,
                                                  uint32_t& delivered, uint64_t& out_bytes) {
@@ -1080,7 +1081,7 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
       if (!(s.rx_flags & UFC_RX_SLOT_DATA)) return;
       const uint32_t c = s.rx_channel_id;
       const unsigned long long m = sh.chan_mask[c] & below(lane);
-      const uint32_t cb = m ? packet_id_add(seq_of(rx_high_bit(m)), 1) : (sh.chan_base[c] != UFC_NO_PARENT ? sh.chan_base[c] : base);
+      const uint32_t cb = m ? packet_id_add(seq_of(high_bit(m)), 1) : (sh.chan_base[c] != UFC_NO_PARENT ? sh.chan_base[c] : base);
       if (!lead_clears(s.rx_channel_parent_lead, packet_id_sub(seq_of(lane), cb))) Wv::or64(&sh.chan_fail[c], 1ull << lane);
     });
     wv.lanes([&](uint32_t lane) {
@@ -1088,7 +1089,7 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
       const ufc_rx_slot& s = slots[seq_of(lane) & mask];
       if (!(s.rx_flags & UFC_RX_SLOT_DATA)) return;
       const uint32_t c = s.rx_channel_id, count = sh.chan_count[c];
-      const uint32_t rank = rx_popc(sh.chan_mask[c] & below(lane));
+      const uint32_t rank = popc(sh.chan_mask[c] & below(lane));
       if (sh.chan_ready[c] && !(sh.chan_fail[c] & (below(lane) | 1ull << lane)) && (count == 0 || rank < count)) {
         Wv::or64(&sh.deliv_mask, 1ull << lane);
         sh.lane_len[lane] = (s.rx_flags & UFC_RX_SLOT_DUD) ? 0u : s.data_len;
@@ -1101,7 +1102,7 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
       const bool dud = (s.rx_flags & UFC_RX_SLOT_DUD) != 0;
       uint64_t at = sh.out_bytes;
       for (uint32_t l = 0; l < lane; l++) at += sh.lane_len[l];
-      p.deliver_idx = sh.delivered + rx_popc(sh.deliv_mask & below(lane));
+      p.deliver_idx = sh.delivered + popc(sh.deliv_mask & below(lane));
       p.seq = seq_of(lane);
       p.len = sh.lane_len[lane];
       p.channel = s.rx_channel_id;
@@ -1114,21 +1115,21 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
       const unsigned long long M = sh.chan_mask[c], F = sh.chan_fail[c];
       if (sh.chan_ready[c] && M) {
         const uint32_t count = sh.chan_count[c];
-        const uint32_t clear = F ? rx_popc(M & below(rx_low_bit(F))) : rx_popc(M);  // DATA lanes before the first failing one
+        const uint32_t clear = F ? popc(M & below(low_bit(F))) : popc(M);  // DATA lanes before the first failing one
         const uint32_t nd = (count != 0 && clear > count) ? count : clear;
         if ((count != 0 && nd == count) || (F && (count == 0 || clear < count))) sh.chan_ready[c] = 0;
         sh.chan_count[c] = count - nd;
         if (nd) {
           unsigned long long m = M;
           for (uint32_t k = 1; k < nd; k++) m &= m - 1;  // drop the nd - 1 lowest: the nd-th DATA lane is the lowest left
-          sh.chan_base[c] = packet_id_add(seq_of(rx_low_bit(m)), 1);
+          sh.chan_base[c] = packet_id_add(seq_of(low_bit(m)), 1);
         }
       }
       sh.chan_mask[c] = sh.chan_fail[c] = 0;
     });
     wv.lanes([&](uint32_t lane) {
       if (lane != 0) return;
-      sh.delivered += rx_popc(sh.deliv_mask);
+      sh.delivered += popc(sh.deliv_mask);
       for (uint32_t l = 0; l < 64; l++) sh.out_bytes += sh.lane_len[l];
       sh.deliv_mask = 0;
     });
@@ -1159,7 +1160,7 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
     wv.lanes([&](uint32_t lane) {
       if (!((sh.entry_mask >> lane) & 1u)) return;
       const unsigned long long m = sh.entry_mask & below(lane);
-      const uint32_t nb = m ? packet_id_add(seq_of(rx_high_bit(m)), 1) : sh.new_base;
+      const uint32_t nb = m ? packet_id_add(seq_of(high_bit(m)), 1) : sh.new_base;
       if (!lead_clears(slots[seq_of(lane) & mask].rx_window_parent_lead, packet_id_sub(seq_of(lane), nb)))
         Wv::or64(&sh.entry_fail, 1ull << lane);
     });
@@ -1167,10 +1168,10 @@ inline __host__ __device__ void rx_receive_tiles(const Wv& wv, RxWaveShared& sh,
       if (lane != 0) return;
       unsigned long long E = sh.entry_mask;
       if (sh.entry_fail) {
-        E &= below(rx_low_bit(sh.entry_fail));
+        E &= below(low_bit(sh.entry_fail));
         sh.stop = 1;
       }
-      if (E) sh.new_base = packet_id_add(seq_of(rx_high_bit(E)), 1);
+      if (E) sh.new_base = packet_id_add(seq_of(high_bit(E)), 1);
       sh.entry_mask = sh.entry_fail = 0;
     });
     if (sh.stop) break;  // (read by every lane after the phase: uniform)
@@ -1344,6 +1345,12 @@ struct FwArgs {
   ufc_frame_window_result* results;
   ufc_frame_window* windows_out;
 };
+inline bool fw_args_ok(const FwArgs& a) {  // (the n_windows + 1 group counts are scanned with a 32-bit count)
+  const bool bad = !a.frame_first || !a.windows || !a.windows_out || !a.frame_accept || !a.group_first ||
+                   !a.groups_used || !a.results || (!a.infos && a.n_frames) || (!a.groups && a.groups_cap) ||
+                   a.n_frames >= kCountLim || a.n_windows >= kCountLim;
+  return !bad;
+}
 
 constexpr uint32_t kFwMaxSize = 0x80000000u;
 // What a frame is to the window.
@@ -1519,9 +1526,6 @@ struct FwWaveShared {
   uint32_t target[64];
   uint8_t cls[64];
 };
-UFC_HD uint32_t fw_high_bit(unsigned long long m) { return 63u - (uint32_t)__builtin_clzll(m); }
-UFC_HD uint32_t fw_low_bit(unsigned long long m) { return (uint32_t)__builtin_ctzll(m); }
-UFC_HD uint32_t fw_popc(unsigned long long m) { return (uint32_t)__builtin_popcountll(m); }
 
 template <class Wv>
 inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh, const FwArgs& a, uint64_t r, bool write,
@@ -1572,22 +1576,22 @@ inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh
       wv.lanes([&](uint32_t lane) {
         if (lane < from || !((live >> lane) & 1u)) return;
         const unsigned long long m = live & below(lane);
-        const uint32_t b = m ? sh.target[fw_high_bit(m)] : s.base;
+        const uint32_t b = m ? sh.target[high_bit(m)] : s.base;
         if (!fw_passes(sh.cls[lane], sh.target[lane], b, size)) Wv::or64(&sh.fail[k], 1ull << lane);
       });
       const unsigned long long F = sh.fail[k];
       if (!F) break;
-      const uint32_t f = fw_low_bit(F);
+      const uint32_t f = low_bit(F);
       failed |= 1ull << f;
       from = f + 1;
     }
     const unsigned long long passing = cand & ~failed, acc = data & passing;
-    if (passing) s.base = sh.target[fw_high_bit(passing)];
-    s.accepted += fw_popc(acc);
-    s.refused += fw_popc(data & ~acc);
-    s.syncs += fw_popc(syncs);
-    if (psyncs && !s.psyncs) s.first_psync = (uint32_t)(t0 + fw_low_bit(psyncs));
-    s.psyncs += fw_popc(psyncs);
+    if (passing) s.base = sh.target[high_bit(passing)];
+    s.accepted += popc(acc);
+    s.refused += popc(data & ~acc);
+    s.syncs += popc(syncs);
+    if (psyncs && !s.psyncs) s.first_psync = (uint32_t)(t0 + low_bit(psyncs));
+    s.psyncs += popc(psyncs);
     if (syncs) s.reply = 1;
     if (write)
       wv.lanes([&](uint32_t lane) {
@@ -1597,7 +1601,7 @@ inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh
     unsigned long long rem = acc;
     for (uint32_t k = 0; rem; k++) {
       if (!s.has) {  // the first lane left opens a group
-        const uint32_t o = fw_low_bit(rem);
+        const uint32_t o = low_bit(rem);
         s.ge = sh.target[o] - 1;
         s.gb = 1;
         s.gn = (sh.cls[o] & kFwNonce) ? 1u : 0u;
@@ -1609,10 +1613,10 @@ inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh
         if (!((rem >> lane) & 1u)) return;
         const uint32_t off = sh.target[lane] - 1 - s.ge;
         const unsigned long long m = rem & below(lane);
-        if (off >= 32 || (m && sh.target[fw_high_bit(m)] - 1 - s.ge >= off)) Wv::or64(&sh.stop[k], 1ull << lane);
+        if (off >= 32 || (m && sh.target[high_bit(m)] - 1 - s.ge >= off)) Wv::or64(&sh.stop[k], 1ull << lane);
       });
       const unsigned long long S = sh.stop[k];
-      const unsigned long long fold = S ? rem & below(fw_low_bit(S)) : rem;
+      const unsigned long long fold = S ? rem & below(low_bit(S)) : rem;
       if (fold) {
         wv.lanes([&](uint32_t lane) {
           if (!((fold >> lane) & 1u)) return;
@@ -1621,10 +1625,10 @@ inline __host__ __device__ uint64_t fw_walk_tiles(const Wv& wv, FwWaveShared& sh
           if (!(s.gb & bit) && (sh.cls[lane] & kFwNonce)) Wv::or64(&sh.par[k], 1ull << lane);
         });
         s.gb |= (uint32_t)sh.bits[k];
-        s.gn ^= fw_popc(sh.par[k]) & 1u;
+        s.gn ^= popc(sh.par[k]) & 1u;
         rem &= ~fold;
       }
-      if (rem && sh.target[fw_low_bit(rem)] - 1 - s.ge >= 32) {  // the next lane closes the group
+      if (rem && sh.target[low_bit(rem)] - 1 - s.ge >= 32) {  // the next lane closes the group
         const uint64_t at = gfirst + s.groups;
         if (write) wv.one([&]() { fw_put_group(a, at, s.ge, s.gb, s.gn); });
         s.groups++;
@@ -1677,6 +1681,13 @@ struct FqArgs {
   ufc_frame_queue_result* results;
   ufc_frame_queue* queues_out;
 };
+inline bool fq_args_ok(const FqArgs& a) {
+  const bool bad = !a.frame_first || !a.sent_first || !a.queues || !a.steps || !a.results || !a.queues_out ||
+                   (!a.infos && a.n_frames) || (!a.items && a.n_items) || (!a.sent && a.n_sent) ||
+                   (!a.log && a.n_log) || a.n_frames >= kCountLim || a.n_items >= kCountLim || a.n_sent >= kCountLim ||
+                   a.n_queues >= kCountLim;
+  return !bad;
+}
 
 constexpr uint64_t kFqInitialRttMs = 100;         // FeedbackGen::INITIAL_RTT_MS, frame_queue.rs:111
 constexpr uint32_t kFqMaxIntervals = 9;           // loss_rate.rs:72
@@ -1792,7 +1803,7 @@ inline __host__ __device__ void fq_nacks(const Wv& wv, FqWaveShared& sh, const F
         const uint64_t end = s.li_end;
         const unsigned long long M =
             wv.ballot([&](uint32_t lane) { return lane >= pos && lane < nv && sh.tile_time[lane] >= end; });
-        f = M ? fw_low_bit(M) : nv;
+        f = M ? low_bit(M) : nv;
         const uint32_t adds = f - pos;  // they fall under the front interval (:75)
         if (adds) wv.one([&]() { sh.li_len[0] = fq_sat_add(sh.li_len[0], adds); });
         if (f >= nv) break;
@@ -1945,7 +1956,7 @@ inline __host__ __device__ void fq_group(const Wv& wv, FqWaveShared& sh, const F
   const unsigned long long claimed = bits;
   const unsigned long long odd =
       wv.ballot([&](uint32_t lane) { return lane < n && ((claimed >> lane) & 1u) && (sh.group_flags[lane] & UFC_SENT_NONCE); });
-  if ((fw_popc(odd) & 1u) != nonce) {  // (:313)
+  if ((popc(odd) & 1u) != nonce) {  // (:313)
     wv.one([&]() { sh.res.groups_bad_nonce++; });
     return;
   }
@@ -1966,7 +1977,7 @@ inline __host__ __device__ void fq_group(const Wv& wv, FqWaveShared& sh, const F
     return false;
   });
   for (unsigned long long w = wide; w; w &= w - 1) {  // a frame with many fragments: all lanes mark them
-    const uint32_t o = fw_low_bit(w);
+    const uint32_t o = low_bit(w);
     const uint64_t first = sh.group_ref_first[o], end = ref_end(o);
     wv.lanes([&](uint32_t lane) {
       for (uint64_t j = first + lane; j < end; j += 64) a.ref_acked[j] = 1;
@@ -1974,7 +1985,7 @@ inline __host__ __device__ void fq_group(const Wv& wv, FqWaveShared& sh, const F
   }
   uint64_t last = 0, total = 0;
   for (unsigned long long w = fresh; w; w &= w - 1) {
-    const uint32_t o = fw_low_bit(w), id = base + o;
+    const uint32_t o = low_bit(w), id = base + o;
     const uint64_t t = sh.group_time[o];
     last = last > t ? last : t;
     total += sh.group_size[o];
@@ -2089,7 +2100,7 @@ inline __host__ __device__ void fq_step(const Wv& wv, FqWaveShared& sh, const Fq
     const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
     unsigned long long acks = wv.ballot([&](uint32_t lane) { return lane < nv && fq_is_ack(a.infos[t0 + lane]); });
     for (; acks; acks &= acks - 1) {
-      const ufc_frame_info f = a.infos[t0 + fw_low_bit(acks)];
+      const ufc_frame_info f = a.infos[t0 + low_bit(acks)];
       wv.one([&]() { sh.res.ack_frames++; });
       for (uint64_t g = f.item_first, ge = (uint64_t)f.item_first + f.item_count; g < ge; g++) fq_group(wv, sh, a, s, a.items[g]);
       // advance_transfer_window (:357-380)
@@ -2111,7 +2122,7 @@ inline __host__ __device__ void fq_step(const Wv& wv, FqWaveShared& sh, const Fq
       const unsigned long long kept = wv.ballot(
           [&](uint32_t lane) { return lane < nv && a.log[fq_slot(s, s.log_base + t + lane)].send_time_ms >= S.thresh_ms; });
       if (kept) {
-        expired += fw_low_bit(kept);
+        expired += low_bit(kept);
         break;
       }
       expired += nv;
@@ -2158,26 +2169,6 @@ inline __host__ __device__ void fq_step(const Wv& wv, FqWaveShared& sh, const Fq
   });
 }
 
-// The wave policy as host code: a phase is a loop over the 64 lanes (ufc_frame_queue_host and
-// tests/c/queue_host_check.hip).
-struct FqHostWave {
-  template <class F>
-  void lanes(const F& f) const {
-    for (uint32_t l = 0; l < 64; l++) f(l);
-  }
-  template <class F>
-  void one(const F& f) const {
-    f();
-  }
-  template <class F>
-  unsigned long long ballot(const F& f) const {
-    unsigned long long m = 0;
-    for (uint32_t l = 0; l < 64; l++)
-      if (f(l)) m |= 1ull << l;
-    return m;
-  }
-};
-
 // ---- batched send rate control (ufc_rate_begin_*, ufc_rate_step_*) ----
 // SendRateComp and RecvRateSet (src/half_connection/send_rate.rs, recv_rate_set.rs) with HalfConnection's
 // fill_flush_alloc, one connection per call of rate_step: the host entry loops over it, the kernel gives it a lane.
@@ -2206,6 +2197,14 @@ struct RateBeginArgs {
   ufc_frame_queue_step* steps;
   ufc_rate_state* states_out;
 };
+inline bool rate_begin_args_ok(const RateBeginArgs& a) {
+  return a.states && a.now_ms && a.steps && a.states_out && a.n < kCountLim;
+}
+inline bool rate_args_ok(const RateArgs& a) {
+  const bool bad = !a.states || !a.ticks || !a.fq || !a.results || !a.states_out || (!a.entries && a.n_entries) ||
+                   (a.flush_results && !a.result_index) || (a.flushes && !a.flush_index) || a.n >= kCountLim;
+  return !bad;
+}
 
 constexpr uint32_t kRateMinimum = UFC_MAX_FRAME_SIZE / 64;  // MINIMUM_RATE
 constexpr uint32_t kRateInitialWindow = 4380;               // INITIAL_TCP_WINDOW
@@ -2786,6 +2785,28 @@ struct RsCommitArgs {
   ufc_resend* states_out;
   ufc_sender* retake;
 };
+inline bool rs_begin_args_ok(const RsBeginArgs& a) {
+  const bool bad = !a.frame_first || !a.queues || !a.rate || !a.flushes || !a.states || !a.senders || !a.results ||
+                   !a.states_out || !a.senders_out || (!a.infos && a.n_frames) || (!a.log && a.n_log) ||
+                   (!a.heap && a.n_heap) || (!a.pkts && a.n_pkts) || (!a.frag_acked && a.n_frag) || (!a.tx && a.n_tx) ||
+                   (!a.stage && a.n_stage) || a.n >= kCountLim || a.n_frames >= kCountLim;
+  return !bad;
+}
+inline bool rs_place_args_ok(const RsPlaceArgs& a) {
+  const bool bad = !a.states || !a.begin_results || !a.flush_first || (!a.stage && a.n_stage) ||
+                   (!a.items && a.items_cap) || a.n >= kCountLim;
+  return !bad;
+}
+inline bool rs_commit_args_ok(const RsCommitArgs& a) {
+  const bool bad = !a.flush_results || !a.out_offsets || !a.frames_used || !a.flush_first || !a.packet_first ||
+                   !a.sender_results || !a.begin_results || !a.rate || !a.states || !a.senders || !a.sent_first ||
+                   !a.results || !a.states_out || !a.retake || (!a.infos && a.n_infos) || (!a.items && a.n_items) ||
+                   (!a.packets && a.n_packets) || (!a.packet_results && a.n_packets) || (!a.heap && a.n_heap) ||
+                   (!a.pkts && a.n_pkts) || (!a.frag_acked && a.n_frag) || (!a.tx && a.n_tx) ||
+                   (!a.sent && a.sent_cap) || a.n >= kCountLim || a.n_packets >= kCountLim || a.n_items >= kCountLim ||
+                   a.n_infos >= kCountLim;
+  return !bad;
+}
 
 struct RsWaveShared {
   uint32_t chan_parent[UFC_MAX_CHANNELS];
@@ -2936,7 +2957,7 @@ inline __host__ __device__ void rs_begin(const Wv& wv, RsWaveShared& sh, const R
     const uint32_t nv = ff1 - t0 < 64 ? (uint32_t)(ff1 - t0) : 64u;
     unsigned long long acks = wv.ballot([&](uint32_t lane) { return lane < nv && fq_is_ack(a.infos[t0 + lane]); });
     for (; acks; acks &= acks - 1) {
-      const uint32_t rb = a.infos[t0 + fw_low_bit(acks)].f[1];
+      const uint32_t rb = a.infos[t0 + low_bit(acks)].f[1];
       const uint32_t delta = packet_id_sub(rb, base), span = packet_id_sub(next, base);
       if (rb > kPacketIdMask || delta > span) {  // :246
         ignored++;
@@ -3150,7 +3171,7 @@ inline __host__ __device__ void rs_commit(const Wv& wv, RsWaveShared& sh, const 
           return r.status == UFC_PACKET_EMITTED && (uint64_t)r.item_first + r.item_count > first_unpacked;
         });
         if (hit) {
-          const uint32_t p = t + fw_low_bit(hit);
+          const uint32_t p = t + low_bit(hit);
           const ufc_packet_result r = a.packet_results[pf0 + p];
           take = p + 1;
           enter_end = (uint64_t)r.item_first + r.item_count;
@@ -3288,43 +3309,5 @@ inline __host__ __device__ void rs_commit(const Wv& wv, RsWaveShared& sh, const 
                               (limited ? (uint32_t)UFC_FQ_MARK_RATE_LIMITED : 0u);
   });
 }
-
-// The wave policy as host code (ufc_resend_*_host and tests/c/resend_host_check.hip).
-struct RsHostWave : FqHostWave {
-  template <class F>
-  uint64_t sum(const F& f) const {
-    uint64_t s = 0;
-    for (uint32_t l = 0; l < 64; l++) s += f(l);
-    return s;
-  }
-  void sync() const {}
-};
-
-// The lanes of a phase in the opposite order, which must not matter (tests/c/resend_host_check.hip compares the
-// two).
-struct RsReverseWave {
-  template <class F>
-  void lanes(const F& f) const {
-    for (uint32_t l = 64; l-- > 0;) f(l);
-  }
-  template <class F>
-  void one(const F& f) const {
-    f();
-  }
-  template <class F>
-  unsigned long long ballot(const F& f) const {
-    unsigned long long m = 0;
-    for (uint32_t l = 64; l-- > 0;)
-      if (f(l)) m |= 1ull << l;
-    return m;
-  }
-  template <class F>
-  uint64_t sum(const F& f) const {
-    uint64_t s = 0;
-    for (uint32_t l = 64; l-- > 0;) s += f(l);
-    return s;
-  }
-  void sync() const {}
-};
 
 }  // namespace ufc_codec

@@ -22,13 +22,14 @@
 // Walking the chain twice keeps the scratch at 9 bytes per item and needs no per-item flags or ranks in
 // global memory.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstddef>
 
 #include "frame_codec_core.hpp"
 #include "frame_pack.hpp"
+#include "scan.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -60,13 +61,6 @@ __global__ __launch_bounds__(kPackThreads) void pack_hops_kernel(const uint64_t*
   if (i >= n_items) return;
   // (the hop reads P(i .. i + 127), capped at n_items: indices below kPackThreads + kHopWindow)
   hops[i] = (uint8_t)ufc_codec::pack_data_hop([&](uint64_t k) -> uint64_t { return sP[k - base]; }, i, n_items);
-}
-
-// The lanes of one wave meet: what each wrote to LDS before is what the others read after.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // kEmit false: results (frame_first left 0) and counts[j] = frame_count, counts[n_flushes] = 0.
@@ -195,48 +189,28 @@ __global__ __launch_bounds__(kPackThreads) void pack_chain_kernel(PackArgs a, co
   }
 }
 
-struct PackLayout {  // scratch of a pack (256-byte aligned parts)
-  uint64_t psum, hops, counts, firsts, temp, end;
-  PackLayout(uint64_t n_flushes, uint64_t n_items, size_t temp_bytes) {
-    auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-    psum = 0;
-    hops = psum + up((n_items + 1) * 8);
-    counts = hops + up(n_items);
-    firsts = counts + up((n_flushes + 1) * 4);
-    temp = firsts + up((n_flushes + 1) * 4);
-    end = temp + up(temp_bytes);
-  }
-};
-size_t pack_temp_bytes(uint64_t n_flushes, uint64_t n_items) {  // the larger of the two scans' temporaries
-  size_t t_items = 0, t_flushes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t_items, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n_items + 1));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t_flushes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                         (int)(n_flushes + 1));
-  return std::max(t_items, t_flushes);
-}
-
 }  // namespace
 
-size_t pack_scratch_bytes(uint64_t n_flushes, uint64_t n_items) {
-  return PackLayout(n_flushes, n_items, pack_temp_bytes(n_flushes, n_items)).end;
-}
-
-hipError_t pack_batch(const PackArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  const PackLayout lay(a.n_flushes, a.n_items, pack_temp_bytes(a.n_flushes, a.n_items));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
-  char* s = (char*)scratch;
-  uint64_t* P = (uint64_t*)(s + lay.psum);
-  uint8_t* hops = (uint8_t*)(s + lay.hops);
-  uint32_t* counts = (uint32_t*)(s + lay.counts);
-  uint32_t* firsts = (uint32_t*)(s + lay.firsts);
-  const size_t temp_cap = lay.end - lay.temp;
+hipError_t pack_batch(const PackArgs& a, const ScratchSource& scratch, hipStream_t stream) {
+  // the larger of the two scans' temporaries
+  const size_t temp_bytes = std::max(scan_temp_bytes<uint64_t>(a.n_items + 1), scan_temp_bytes<uint32_t>(a.n_flushes + 1));
+  ScratchPlan plan;
+  const uint64_t at_psum = plan.take((a.n_items + 1) * 8);
+  const uint64_t at_hops = plan.take(a.n_items);
+  const uint64_t at_counts = plan.take((a.n_flushes + 1) * 4);
+  const uint64_t at_firsts = plan.take((a.n_flushes + 1) * 4);
+  const uint64_t at_temp = plan.take(temp_bytes);
+  char* s;
   hipError_t e;
+  if ((e = scratch.get(plan.end, &s)) != hipSuccess) return e;
+  uint64_t* P = (uint64_t*)(s + at_psum);
+  uint8_t* hops = (uint8_t*)(s + at_hops);
+  uint32_t* counts = (uint32_t*)(s + at_counts);
+  uint32_t* firsts = (uint32_t*)(s + at_firsts);
   const unsigned iblocks = (unsigned)((a.n_items + 1 + kPackThreads - 1) / kPackThreads);
   pack_item_sizes_kernel<<<iblocks, kPackThreads, 0, stream>>>(a.items, a.n_items, P);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t temp_bytes = temp_cap;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(s + lay.temp, temp_bytes, P, P, (int)(a.n_items + 1), stream)) != hipSuccess)
-    return e;
+  if ((e = exclusive_sum(s + at_temp, temp_bytes, P, P, a.n_items + 1, stream)) != hipSuccess) return e;
   if (a.n_items) {
     pack_hops_kernel<<<(unsigned)((a.n_items + kPackThreads - 1) / kPackThreads), kPackThreads, 0, stream>>>(P, a.n_items,
                                                                                                            hops);
@@ -245,10 +219,7 @@ hipError_t pack_batch(const PackArgs& a, void* scratch, size_t scratch_bytes, hi
   const unsigned cblocks = (unsigned)((a.n_flushes + 1 + kPackWaves - 1) / kPackWaves);
   pack_chain_kernel<false><<<cblocks, kPackThreads, 0, stream>>>(a, P, hops, counts, nullptr);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  temp_bytes = temp_cap;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(s + lay.temp, temp_bytes, counts, firsts, (int)(a.n_flushes + 1), stream)) !=
-      hipSuccess)
-    return e;
+  if ((e = exclusive_sum(s + at_temp, temp_bytes, counts, firsts, a.n_flushes + 1, stream)) != hipSuccess) return e;
   pack_chain_kernel<true><<<cblocks, kPackThreads, 0, stream>>>(a, P, hops, nullptr, firsts);
   return hipGetLastError();
 }

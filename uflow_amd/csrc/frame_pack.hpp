@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/uflow_frame_codec.h"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
@@ -25,9 +26,8 @@ struct PackArgs {
   uint64_t* frames_used;
 };
 
-// Device scratch of a pack: the items' size prefix sums (8 (n_items + 1) bytes), one hop byte per item, two
+// The scratch of a pack: the items' size prefix sums (8 (n_items + 1) bytes), one hop byte per item, two
 // words per flush (frame counts and their exclusive sum) and the scan temporaries.
-size_t pack_scratch_bytes(uint64_t n_flushes, uint64_t n_items);
-hipError_t pack_batch(const PackArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t pack_batch(const PackArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

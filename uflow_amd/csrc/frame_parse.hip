@@ -21,7 +21,6 @@
 // store sat in the same vmcnt queue as the walk's next header load, and the stores of a wave
 // scattered over 64 frames' item ranges.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstddef>
@@ -29,6 +28,7 @@
 
 #include "frame_codec_core.hpp"
 #include "frame_parse.hpp"
+#include "scan.hpp"
 
 namespace ufc_dev {
 
@@ -398,63 +398,43 @@ __global__ __launch_bounds__(kParseThreads) void parse_emit_kernel(
 
 }  // namespace
 
-namespace {
-struct ParseLayout {  // the scratch of a parse of n frames (256-byte aligned parts)
-  uint64_t counts, wg_counts, wg_firsts, modes, cursor, bases, slots, temp, end, seg_cap;
-  ParseLayout(uint64_t n, uint64_t items_cap, size_t temp_bytes) {
-    auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-    const uint64_t blocks = (n + kParseThreads - 1) / kParseThreads;
-    // u16 header slots; below 2^32 - 1 so that every segment fits 32-bit offsets and no segment base
-    // can equal the overflow sentinel 0xFFFFFFFF (frames past the cap are walked again, kItemsWalk)
-    seg_cap = std::min<uint64_t>(std::min<uint64_t>(n * kPosSlots, std::max<uint64_t>(items_cap, 1)),
-                                 0xFFFFFFFEull - kSegWords);
-    counts = 0;
-    wg_counts = counts + up(n * 4);  // items per workgroup of 256 frames, then their exclusive sum
-    wg_firsts = wg_counts + up(blocks * 4);
-    modes = wg_firsts + up(blocks * 4);
-    cursor = modes + up(n);
-    bases = cursor + 256;
-    slots = bases + up(blocks * 4);
-    temp = slots + up(seg_cap * 2);
-    end = temp + up(temp_bytes);
-  }
-};
-size_t scan_temp_bytes(uint64_t n) {  // the scan over the workgroups' item counts
-  const uint64_t blocks = (n + kParseThreads - 1) / kParseThreads;
-  size_t temp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, temp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)blocks);
-  return temp;
-}
-}  // namespace
-
-size_t parse_scratch_bytes(uint64_t n, uint64_t items_cap) {
-  return ParseLayout(n, items_cap, scan_temp_bytes(n)).end;
-}
-
-hipError_t parse_batch(const ParseArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
+hipError_t parse_batch(const ParseArgs& a, const ScratchSource& scratch, hipStream_t stream) {
   const uint64_t n = a.n;
   const uint64_t blocks = (n + kParseThreads - 1) / kParseThreads;
-  const ParseLayout lay(n, a.items_cap, scan_temp_bytes(n));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
-  char* s = (char*)scratch;
-  uint32_t* counts = (uint32_t*)(s + lay.counts);
-  uint32_t* wg_counts = (uint32_t*)(s + lay.wg_counts);
-  uint32_t* wg_firsts = (uint32_t*)(s + lay.wg_firsts);
-  uint8_t* modes = (uint8_t*)(s + lay.modes);
-  unsigned long long* cursor = (unsigned long long*)(s + lay.cursor);
-  uint32_t* bases = (uint32_t*)(s + lay.bases);
-  uint16_t* pos_seg = (uint16_t*)(s + lay.slots);
-  void* temp = s + lay.temp;
-  size_t temp_bytes = lay.end - lay.temp;
-  hipError_t e = hipMemsetAsync(cursor, 0, 8, stream);
+  // u16 header slots for min(64 n, items_cap) datagrams (the walk's workgroups take their slot segments from a bump
+  // counter, and a workgroup that finds no room left leaves its frames to the emit step's re-walk); below 2^32 - 1
+  // so that every segment fits 32-bit offsets and no segment base can equal the overflow sentinel 0xFFFFFFFF
+  // (frames past the cap are walked again, kItemsWalk)
+  const uint64_t seg_cap = std::min<uint64_t>(std::min<uint64_t>(n * kPosSlots, std::max<uint64_t>(a.items_cap, 1)),
+                                              0xFFFFFFFEull - kSegWords);
+  const size_t temp_bytes = scan_temp_bytes<uint32_t>(blocks);  // the scan over the workgroups' item counts
+  ScratchPlan plan;
+  const uint64_t at_counts = plan.take(n * 4);
+  const uint64_t at_wg_counts = plan.take(blocks * 4);  // items per workgroup of 256 frames, then their exclusive sum
+  const uint64_t at_wg_firsts = plan.take(blocks * 4);
+  const uint64_t at_modes = plan.take(n);
+  const uint64_t at_cursor = plan.take(256);
+  const uint64_t at_bases = plan.take(blocks * 4);
+  const uint64_t at_slots = plan.take(seg_cap * 2);
+  const uint64_t at_temp = plan.take(temp_bytes);
+  char* s;
+  hipError_t e = scratch.get(plan.end, &s);
+  if (e != hipSuccess) return e;
+  uint32_t* counts = (uint32_t*)(s + at_counts);
+  uint32_t* wg_counts = (uint32_t*)(s + at_wg_counts);
+  uint32_t* wg_firsts = (uint32_t*)(s + at_wg_firsts);
+  uint8_t* modes = (uint8_t*)(s + at_modes);
+  unsigned long long* cursor = (unsigned long long*)(s + at_cursor);
+  uint32_t* bases = (uint32_t*)(s + at_bases);
+  uint16_t* pos_seg = (uint16_t*)(s + at_slots);
+  e = hipMemsetAsync(cursor, 0, 8, stream);
   if (e != hipSuccess) return e;
   parse_walk_pool_kernel<<<(unsigned)blocks, kParseThreads, 0, stream>>>(a.bytes, a.offsets, n, a.valid, a.infos, counts,
-                                                                         modes, pos_seg, cursor, bases, lay.seg_cap,
-                                                                         wg_counts);
+                                                                         modes, pos_seg, cursor, bases, seg_cap, wg_counts);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   // each workgroup's first item (the emit adds the frames' own counts within the workgroup)
-  e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, wg_counts, wg_firsts, (int)blocks, stream);
+  e = exclusive_sum(s + at_temp, temp_bytes, wg_counts, wg_firsts, blocks, stream);
   if (e != hipSuccess) return e;
   // One item per thread per round, one non-temporal 16-byte load per header, non-temporal record
   // stores (the measured alternatives in profiles/EXPERIMENTS.md).  (A one-launch

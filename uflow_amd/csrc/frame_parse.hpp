@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/uflow_frame_codec.h"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
@@ -26,11 +27,6 @@ struct ParseArgs {
   uint64_t* items_used;    // device word, nullable
 };
 
-// Device scratch of a parse of n frames with room for at most items_cap items (item counts, first
-// indices, modes, scan temporaries, and header slots for min(64 n, items_cap) datagrams: the walk's
-// workgroups take their slot segments from a bump counter, and a workgroup that finds no room left
-// leaves its frames to the emit step's re-walk).
-size_t parse_scratch_bytes(uint64_t n, uint64_t items_cap);
-hipError_t parse_batch(const ParseArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t parse_batch(const ParseArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

@@ -17,6 +17,7 @@
 
 #include "frame_codec_core.hpp"
 #include "frame_queue.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -29,38 +30,11 @@ static_assert(sizeof(ufc_sent_frame) == 24 && sizeof(ufc_frame_queue) == 192 && 
                   sizeof(ufc_frame_queue_result) == 80,
               "record layouts");
 
-// The wave policy of fq_step on the device: every lane runs each phase, a wave barrier in between.
-struct FqDevWave {
-  static __device__ __forceinline__ void sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  template <class F>
-  __device__ __forceinline__ void lanes(const F& f) const {
-    f(threadIdx.x & 63u);
-    sync();
-  }
-  template <class F>
-  __device__ __forceinline__ void one(const F& f) const {
-    if ((threadIdx.x & 63u) == 0) f();
-  }
-  template <class F>
-  __device__ __forceinline__ unsigned long long ballot(const F& f) const {
-    const unsigned long long m = __ballot(f(threadIdx.x & 63u) ? 1 : 0);
-    sync();
-    return m;
-  }
-};
-
-// One wave per connection.  The 17 arguments are read where they are needed, from the kernel-argument segment (the
-// one by-value argument lies at its start), not held in 34 scalar registers for the whole step: with them held the
-// compiler spilled 21 scalar registers.
+// One wave per connection.  The 17 arguments are read from the kernel-argument segment (wave_dev.hpp).
 __global__ __launch_bounds__(64) void fq_step_kernel(FqArgs) {
   __shared__ ufc_codec::FqWaveShared sh;
-  typedef const FqArgs __attribute__((address_space(4))) * KernArgs;
-  const FqArgs& a = *(const FqArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  for (uint64_t c = blockIdx.x; c < a.n_queues; c += gridDim.x) ufc_codec::fq_step(FqDevWave{}, sh, a, c);
+  const FqArgs& a = kernargs<FqArgs>();
+  for (uint64_t c = blockIdx.x; c < a.n_queues; c += gridDim.x) ufc_codec::fq_step(DevWave{}, sh, a, c);
 }
 
 }  // namespace

@@ -6,12 +6,10 @@
 #include <cstdint>
 
 #include "frame_codec_core.hpp"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
-// Device scratch of a frame window call: a group count per connection (8 bytes, + 1 entry) and the scan's
-// temporaries, each part rounded up to 256.
-size_t window_scratch_bytes(uint64_t n_windows);
-hipError_t window_batch(const ufc_codec::FwArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t window_batch(const ufc_codec::FwArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

@@ -28,13 +28,14 @@
 //      sender's consumed packets by their first items, skips slots that belong to no packet (reserved ones) and
 //      writes one 24-byte record; consecutive lanes write consecutive records.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstddef>
 
 #include "frame_codec_core.hpp"
 #include "packet_emit.hpp"
+#include "scan.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -47,13 +48,6 @@ static_assert(kEmitTile == 64 && UFC_MAX_CHANNELS == 64, "one lane per packet of
 static_assert(sizeof(ufc_packet) == 16 && sizeof(ufc_sender) == 304 && sizeof(ufc_packet_result) == 16 &&
                   sizeof(ufc_sender_result) == 32, "record layouts");
 
-// The lanes of one wave meet: what each wrote to LDS before is what the others read after.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Inclusive sum over the wave's lanes.
 template <class T>
 __device__ __forceinline__ T wave_inclusive_sum(T v, uint32_t lane) {
@@ -64,8 +58,6 @@ __device__ __forceinline__ T wave_inclusive_sum(T v, uint32_t lane) {
   }
   return v;
 }
-
-__device__ __forceinline__ uint32_t high_bit(uint64_t m) { return 63u - (uint32_t)__clzll((long long)m); }
 
 __global__ __launch_bounds__(kEmitThreads) void emit_senders_kernel(EmitArgs a, uint32_t* rel_first, uint2* meta,
                                                                     uint64_t* counts) {
@@ -157,25 +149,25 @@ __global__ __launch_bounds__(kEmitThreads) void emit_senders_kernel(EmitArgs a, 
     const bool reliable = emitted && pk.mode == UFC_SEND_RELIABLE;
     const uint64_t rel_mask = __ballot(reliable);
     const uint64_t rel_below = rel_mask & lanes_below;
-    const uint32_t wp = rel_below ? seq_of(high_bit(rel_below)) : wparent;
+    const uint32_t wp = rel_below ? seq_of(ufc_codec::high_bit(rel_below)) : wparent;
     // (an emitted packet's channel_id is below 64: its class is not bad)
     if (reliable) atomicOr(&mask[pk.channel_id], 1ull << lane);
     wave_sync();
     uint32_t cp = UFC_NO_PARENT;
     if (emitted) {
       const uint64_t m = mask[pk.channel_id] & lanes_below;
-      cp = m ? seq_of(high_bit(m)) : parent[pk.channel_id];
+      cp = m ? seq_of(ufc_codec::high_bit(m)) : parent[pk.channel_id];
     }
     wave_sync();  // every lane has read its channel's mask and carried parent
     {
       const uint64_t m = mask[lane];  // lane c: channel c
       if (m) {
-        parent[lane] = seq_of(high_bit(m));
+        parent[lane] = seq_of(ufc_codec::high_bit(m));
         mask[lane] = 0;
       }
     }
     wave_sync();
-    if (rel_mask) wparent = seq_of(high_bit(rel_mask));  // (uniform)
+    if (rel_mask) wparent = seq_of(ufc_codec::high_bit(rel_mask));  // (uniform)
     if (lane < nv) {
       if (in_prefix) rel_first[idx] = (uint32_t)item_rel;
       if (emitted)
@@ -290,44 +282,25 @@ __global__ __launch_bounds__(kEmitThreads) void emit_items_kernel(EmitArgs a, co
   }
 }
 
-struct EmitLayout {  // scratch of an emit (256-byte aligned parts)
-  uint64_t rel_first, meta, counts, temp, end;
-  EmitLayout(uint64_t n_senders, uint64_t n_packets, size_t temp_bytes) {
-    auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-    rel_first = 0;
-    meta = rel_first + up(n_packets * 4);
-    counts = meta + up(n_packets * 8);
-    temp = counts + up((n_senders + 1) * 8);
-    end = temp + up(temp_bytes);
-  }
-};
-size_t emit_temp_bytes(uint64_t n_senders) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n_senders + 1));
-  return t;
-}
-
 }  // namespace
 
-size_t emit_scratch_bytes(uint64_t n_senders, uint64_t n_packets) {
-  return EmitLayout(n_senders, n_packets, emit_temp_bytes(n_senders)).end;
-}
-
-hipError_t emit_batch(const EmitArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  const EmitLayout lay(a.n_senders, a.n_packets, emit_temp_bytes(a.n_senders));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
-  char* sc = (char*)scratch;
-  uint32_t* rel_first = (uint32_t*)(sc + lay.rel_first);
-  uint2* meta = (uint2*)(sc + lay.meta);
-  uint64_t* counts = (uint64_t*)(sc + lay.counts);
+hipError_t emit_batch(const EmitArgs& a, const ScratchSource& scratch, hipStream_t stream) {
+  const size_t temp_bytes = scan_temp_bytes<uint64_t>(a.n_senders + 1);
+  ScratchPlan plan;
+  const uint64_t at_rel_first = plan.take(a.n_packets * 4);
+  const uint64_t at_meta = plan.take(a.n_packets * 8);
+  const uint64_t at_counts = plan.take((a.n_senders + 1) * 8);
+  const uint64_t at_temp = plan.take(temp_bytes);
+  char* sc;
   hipError_t e;
+  if ((e = scratch.get(plan.end, &sc)) != hipSuccess) return e;
+  uint32_t* rel_first = (uint32_t*)(sc + at_rel_first);
+  uint2* meta = (uint2*)(sc + at_meta);
+  uint64_t* counts = (uint64_t*)(sc + at_counts);
   const unsigned sblocks = (unsigned)((a.n_senders + 1 + kEmitWaves - 1) / kEmitWaves);
   emit_senders_kernel<<<sblocks, kEmitThreads, 0, stream>>>(a, rel_first, meta, counts);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t temp_bytes = lay.end - lay.temp;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(sc + lay.temp, temp_bytes, counts, a.flush_first, (int)(a.n_senders + 1),
-                                            stream)) != hipSuccess)
-    return e;
+  if ((e = exclusive_sum(sc + at_temp, temp_bytes, counts, a.flush_first, a.n_senders + 1, stream)) != hipSuccess) return e;
   if (a.n_packets <= 16 * a.n_senders)
     emit_finish_kernel<8><<<(unsigned)((a.n_senders + 1 + 31) / 32), kEmitThreads, 0, stream>>>(a);
   else

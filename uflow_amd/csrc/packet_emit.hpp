@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/uflow_frame_codec.h"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
@@ -27,9 +28,8 @@ struct EmitArgs {
   uint64_t* items_used;
 };
 
-// Device scratch of an emit: per packet its first item relative to the sender's range (4 bytes) and its
+// The scratch of an emit: per packet its first item relative to the sender's range (4 bytes) and its
 // sequence id and leads (8 bytes), one 8-byte item count per sender (+ 1) and the scan's temporaries.
-size_t emit_scratch_bytes(uint64_t n_senders, uint64_t n_packets);
-hipError_t emit_batch(const EmitArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t emit_batch(const EmitArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

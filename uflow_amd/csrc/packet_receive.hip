@@ -27,13 +27,14 @@
 // Either side of a copy has any byte alignment: the destination is written in aligned 8-byte words between a
 // head and a tail of single bytes, the source read with unaligned 8-byte loads.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstddef>
 
 #include "frame_codec_core.hpp"
 #include "packet_receive.hpp"
+#include "scan.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -53,23 +54,6 @@ constexpr uint32_t kCopyBlocksMax = 16384;  // the copy kernels stride over what
 constexpr uint32_t kItemLanes = 16;       // lanes per datagram in the item copy
 static_assert(sizeof(ufc_receiver) == 560 && sizeof(ufc_rx_slot) == 32 && sizeof(ufc_rx_packet) == 24 &&
                   sizeof(ufc_receiver_result) == 80, "record layouts");
-
-// The lanes of one wave meet: what each wrote before is what the others read after.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// The wave policy of rx_receive_tiles on the device: every lane runs each phase, a barrier in between.
-struct RxDevWave {
-  template <class F>
-  __device__ __forceinline__ void lanes(const F& f) const {
-    f(threadIdx.x & 63u);
-    wave_sync();
-  }
-  static __device__ __forceinline__ void or64(unsigned long long* p, unsigned long long v) { atomicOr(p, v); }
-  static __device__ __forceinline__ void add64(unsigned long long* p, unsigned long long v) { atomicAdd(p, v); }
-};
 
 // begin: one lane per receiver (the state check, the plan records, resynchronize).
 __global__ __launch_bounds__(kRxThreads) void rx_begin_kernel(RxArgs a, RxPlan* plans) {
@@ -114,7 +98,7 @@ __global__ __launch_bounds__(64) void rx_receive_kernel(RxArgs a, RxPlan* plans,
   }
   uint32_t delivered;
   uint64_t out_bytes;
-  ufc_codec::rx_receive_tiles(RxDevWave{}, sh, a, r, plans, delivered, out_bytes);
+  ufc_codec::rx_receive_tiles(DevWave{}, sh, a, r, plans, delivered, out_bytes);
   uint64_t carry = 0;
   const bool done = a.results[r].stop == UFC_RX_DONE;
   if (done) {
@@ -215,56 +199,35 @@ __global__ __launch_bounds__(kCopyThreads) void rx_copy_items_kernel(RxArgs a, c
   }
 }
 
-struct RxLayout {  // scratch of a receive (256-byte aligned parts)
-  uint64_t plans, segs, chunks, chunk_first, status, verdicts, dups, counts, temp, end;
-  uint64_t dup_entries, zero_from, zero_to;  // [segs, status) is zeroed as one range, the table as another
-  RxLayout(uint64_t n_receivers, uint64_t n_items, uint64_t n_slots, size_t temp_bytes) {
-    auto up = [](uint64_t b) { return (b + 255) / 256 * 256; };
-    dup_entries = ufc_codec::rx_dup_entries(n_items);
-    plans = 0;
-    segs = plans + up(n_slots * sizeof(RxPlan));
-    chunks = segs + up((2 * n_slots + n_items) * sizeof(RxSegment));
-    chunk_first = chunks + up((2 * n_slots + 1) * 4);
-    status = chunk_first + up((2 * n_slots + 1) * 4);
-    verdicts = status + up(n_items);
-    dups = verdicts + up(n_items);
-    counts = dups + up(dup_entries * 8);
-    temp = counts + up(6 * (n_receivers + 1) * 8);
-    end = temp + up(temp_bytes);
-    zero_from = segs;
-    zero_to = chunk_first;
-  }
-};
-size_t rx_temp_bytes(uint64_t n_receivers, uint64_t n_slots) {
-  size_t t0 = 0, t1 = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t0, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n_receivers + 1));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(2 * n_slots + 1));
-  return std::max(t0, t1);
-}
-
 }  // namespace
 
-size_t receive_scratch_bytes(uint64_t n_receivers, uint64_t n_items, uint64_t n_slots) {
-  return RxLayout(n_receivers, n_items, n_slots, rx_temp_bytes(n_receivers, n_slots)).end;
-}
-
-hipError_t receive_batch(const RxArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  const RxLayout lay(a.n_receivers, a.n_items, a.n_slots, rx_temp_bytes(a.n_receivers, a.n_slots));
-  if (lay.end > scratch_bytes) return hipErrorInvalidValue;
-  char* sc = (char*)scratch;
-  RxPlan* plans = (RxPlan*)(sc + lay.plans);
-  RxSegment* segs = (RxSegment*)(sc + lay.segs);
-  uint32_t* chunks = (uint32_t*)(sc + lay.chunks);
-  uint32_t* chunk_first = (uint32_t*)(sc + lay.chunk_first);
-  uint8_t* status = a.item_status ? a.item_status : (uint8_t*)(sc + lay.status);
-  uint8_t* verdicts = (uint8_t*)(sc + lay.verdicts);
-  const RxDupSet dups{(unsigned long long*)(sc + lay.dups), lay.dup_entries - 1};
-  uint64_t* counts = (uint64_t*)(sc + lay.counts);
-  const uint64_t n1 = a.n_receivers + 1;
-  uint64_t *c_packets = counts, *c_out = counts + n1, *c_carry = counts + 2 * n1, *out_first = counts + 3 * n1;
+hipError_t receive_batch(const RxArgs& a, const ScratchSource& scratch, hipStream_t stream) {
+  const uint64_t n1 = a.n_receivers + 1, n_segs = 2 * a.n_slots, dup_entries = ufc_codec::rx_dup_entries(a.n_items);
+  const size_t temp_bytes = std::max(scan_temp_bytes<uint64_t>(n1), scan_temp_bytes<uint32_t>(n_segs + 1));
+  ScratchPlan plan;  // (the segments and the chunk counts are zeroed as one range, the table as another)
+  const uint64_t at_plans = plan.take(a.n_slots * sizeof(RxPlan));
+  const uint64_t at_segs = plan.take((n_segs + a.n_items) * sizeof(RxSegment));
+  const uint64_t at_chunks = plan.take((n_segs + 1) * 4);
+  const uint64_t at_chunk_first = plan.take((n_segs + 1) * 4);
+  const uint64_t at_status = plan.take(a.n_items);
+  const uint64_t at_verdicts = plan.take(a.n_items);
+  const uint64_t at_dups = plan.take(dup_entries * 8);
+  const uint64_t at_counts = plan.take(6 * n1 * 8);
+  const uint64_t at_temp = plan.take(temp_bytes);
+  char* sc;
   hipError_t e;
-  if ((e = hipMemsetAsync(sc + lay.zero_from, 0, lay.zero_to - lay.zero_from, stream)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(sc + lay.dups, 0, lay.dup_entries * 8, stream)) != hipSuccess) return e;
+  if ((e = scratch.get(plan.end, &sc)) != hipSuccess) return e;
+  RxPlan* plans = (RxPlan*)(sc + at_plans);
+  RxSegment* segs = (RxSegment*)(sc + at_segs);
+  uint32_t* chunks = (uint32_t*)(sc + at_chunks);
+  uint32_t* chunk_first = (uint32_t*)(sc + at_chunk_first);
+  uint8_t* status = a.item_status ? a.item_status : (uint8_t*)(sc + at_status);
+  uint8_t* verdicts = (uint8_t*)(sc + at_verdicts);
+  const RxDupSet dups{(unsigned long long*)(sc + at_dups), dup_entries - 1};
+  uint64_t* counts = (uint64_t*)(sc + at_counts);
+  uint64_t *c_packets = counts, *c_out = counts + n1, *c_carry = counts + 2 * n1, *out_first = counts + 3 * n1;
+  if ((e = hipMemsetAsync(sc + at_segs, 0, at_chunk_first - at_segs, stream)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(sc + at_dups, 0, dup_entries * 8, stream)) != hipSuccess) return e;
   const unsigned rthreads = n1 < kRxFew ? kRxThreadsFew : kRxThreads;
   const unsigned rblocks = (unsigned)((n1 + rthreads - 1) / rthreads);
   rx_begin_kernel<<<rblocks, rthreads, 0, stream>>>(a, plans);
@@ -279,18 +242,14 @@ hipError_t receive_batch(const RxArgs& a, void* scratch, size_t scratch_bytes, h
   if ((e = hipGetLastError()) != hipSuccess) return e;
   rx_receive_kernel<<<(unsigned)n1, 64, 0, stream>>>(a, plans, c_packets, c_out, c_carry);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t temp_bytes = lay.end - lay.temp;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(sc + lay.temp, temp_bytes, c_packets, a.packet_first, (int)n1, stream)) != hipSuccess ||
-      (e = hipcub::DeviceScan::ExclusiveSum(sc + lay.temp, temp_bytes, c_out, out_first, (int)n1, stream)) != hipSuccess ||
-      (e = hipcub::DeviceScan::ExclusiveSum(sc + lay.temp, temp_bytes, c_carry, a.carry_first, (int)n1, stream)) != hipSuccess)
+  if ((e = exclusive_sum(sc + at_temp, temp_bytes, c_packets, a.packet_first, n1, stream)) != hipSuccess ||
+      (e = exclusive_sum(sc + at_temp, temp_bytes, c_out, out_first, n1, stream)) != hipSuccess ||
+      (e = exclusive_sum(sc + at_temp, temp_bytes, c_carry, a.carry_first, n1, stream)) != hipSuccess)
     return e;
   rx_finish_kernel<<<rblocks, rthreads, 0, stream>>>(a, plans, status, out_first, segs, chunks);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (a.n_slots) {
-    const uint64_t n_segs = 2 * a.n_slots;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(sc + lay.temp, temp_bytes, chunks, chunk_first, (int)(n_segs + 1), stream)) !=
-        hipSuccess)
-      return e;
+    if ((e = exclusive_sum(sc + at_temp, temp_bytes, chunks, chunk_first, n_segs + 1, stream)) != hipSuccess) return e;
     const uint64_t blocks = (n_segs + 3) / 4;  // a wave per segment where every segment is one chunk
     rx_copy_slots_kernel<<<(unsigned)std::min<uint64_t>(blocks, kCopyBlocksMax), kCopyThreads, 0, stream>>>(
         a, segs, chunk_first, n_segs);

@@ -6,17 +6,17 @@
 #include <cstdint>
 
 #include "frame_codec_core.hpp"
+#include "scratch.hpp"
 
 namespace ufc_dev {
 
 // Bytes of a slot's copy segment that one wave moves (packet_receive.hip): larger segments are split.
 constexpr uint32_t kRxChunk = 2048;
 
-// Device scratch of a receive: a plan record per slot (48 bytes); a copy segment per datagram and two per slot
+// The scratch of a receive: a plan record per slot (48 bytes); a copy segment per datagram and two per slot
 // (24 bytes each); a chunk count and its prefix per slot segment (4 + 4 bytes, + 1 entry); a status and a verdict byte per
 // datagram; the duplicate table (8 bytes per entry, the power of two at or above 2 n_items, at least 64); six
 // 8-byte counts per receiver (+ 1); the scans' temporaries.
-size_t receive_scratch_bytes(uint64_t n_receivers, uint64_t n_items, uint64_t n_slots);
-hipError_t receive_batch(const ufc_codec::RxArgs& a, void* scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t receive_batch(const ufc_codec::RxArgs& a, const ScratchSource& scratch, hipStream_t stream);
 
 }  // namespace ufc_dev

@@ -15,6 +15,7 @@
 
 #include "frame_codec_core.hpp"
 #include "resend.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -29,55 +30,21 @@ static_assert(sizeof(ufc_resend_entry) == 16 && sizeof(ufc_sent_packet) == 24 &&
                   sizeof(ufc_resend) == 104 && sizeof(ufc_resend_result) == 48 && sizeof(ufc_resend_commit_result) == 40,
               "record layouts");
 
-// The wave policy of rs_begin and rs_commit on the device: every lane runs each phase, a wave barrier in between.
-struct RsDevWave {
-  static __device__ __forceinline__ void sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  template <class F>
-  __device__ __forceinline__ void lanes(const F& f) const {
-    f(threadIdx.x & 63u);
-    sync();
-  }
-  template <class F>
-  __device__ __forceinline__ void one(const F& f) const {
-    if ((threadIdx.x & 63u) == 0) f();
-  }
-  template <class F>
-  __device__ __forceinline__ unsigned long long ballot(const F& f) const {
-    const unsigned long long m = __ballot(f(threadIdx.x & 63u) ? 1 : 0);
-    sync();
-    return m;
-  }
-  template <class F>
-  __device__ __forceinline__ uint64_t sum(const F& f) const {
-    unsigned long long v = f(threadIdx.x & 63u);
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    sync();
-    return v;
-  }
-};
-
-// The arguments are read where they are needed, from the kernel-argument segment (the one by-value argument lies at
-// its start), as fq_step_kernel reads its own.
+// The arguments are read from the kernel-argument segment (wave_dev.hpp), as fq_step_kernel reads its own.
 __global__ __launch_bounds__(64) void rs_begin_kernel(RsBeginArgs) {
   __shared__ ufc_codec::RsWaveShared sh;
-  typedef const RsBeginArgs __attribute__((address_space(4))) * KernArgs;
-  const RsBeginArgs& a = *(const RsBeginArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_begin(RsDevWave{}, sh, a, c);
+  const RsBeginArgs& a = kernargs<RsBeginArgs>();
+  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_begin(DevWave{}, sh, a, c);
 }
 
 __global__ __launch_bounds__(64) void rs_place_kernel(RsPlaceArgs a) {
-  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_place(RsDevWave{}, a, c);
+  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_place(DevWave{}, a, c);
 }
 
 __global__ __launch_bounds__(64) void rs_commit_kernel(RsCommitArgs) {
   __shared__ ufc_codec::RsWaveShared sh;
-  typedef const RsCommitArgs __attribute__((address_space(4))) * KernArgs;
-  const RsCommitArgs& a = *(const RsCommitArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_commit(RsDevWave{}, sh, a, c);
+  const RsCommitArgs& a = kernargs<RsCommitArgs>();
+  for (uint64_t c = blockIdx.x; c < a.n; c += gridDim.x) ufc_codec::rs_commit(DevWave{}, sh, a, c);
 }
 
 // The other grouping of the same steps: a lane per connection.  A phase is a loop in the lane, as on the host, so a
@@ -85,46 +52,19 @@ __global__ __launch_bounds__(64) void rs_commit_kernel(RsCommitArgs) {
 // of LDS) and lanes that diverge.  Measured (profiles/EXPERIMENTS.md): 3.7 times faster at 250,000 connections, where
 // the wave form leaves 63 lanes of every wave waiting on one chain; twice slower at 2,048, which are 32 waves on 256
 // CUs.  So the launch takes this form from kRsLaneFrom connections on; -DUFC_RS_FORM=1 / =2 builds a library with
-// the wave / the lane form alone (tools/build_variant.py, for the A/B).
-struct RsLaneWave {
-  __device__ __forceinline__ void sync() const {}
-  template <class F>
-  __device__ __forceinline__ void lanes(const F& f) const {
-    for (uint32_t l = 0; l < 64; l++) f(l);
-  }
-  template <class F>
-  __device__ __forceinline__ void one(const F& f) const {
-    f();
-  }
-  template <class F>
-  __device__ __forceinline__ unsigned long long ballot(const F& f) const {
-    unsigned long long m = 0;
-    for (uint32_t l = 0; l < 64; l++)
-      if (f(l)) m |= 1ull << l;
-    return m;
-  }
-  template <class F>
-  __device__ __forceinline__ uint64_t sum(const F& f) const {
-    uint64_t v = 0;
-    for (uint32_t l = 0; l < 64; l++) v += f(l);
-    return v;
-  }
-};
-
+// the wave / the lane form alone (tools/build_variant.py, for the A/B).  The policy is the serial one (wave.hpp).
 __global__ __launch_bounds__(64) void rs_begin_lane_kernel(RsBeginArgs) {
   __shared__ ufc_codec::RsWaveShared sh[64];
-  typedef const RsBeginArgs __attribute__((address_space(4))) * KernArgs;
-  const RsBeginArgs& a = *(const RsBeginArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const RsBeginArgs& a = kernargs<RsBeginArgs>();
   for (uint64_t c = (uint64_t)blockIdx.x * 64 + threadIdx.x; c < a.n; c += (uint64_t)gridDim.x * 64)
-    ufc_codec::rs_begin(RsLaneWave{}, sh[threadIdx.x], a, c);
+    ufc_codec::rs_begin(ufc_codec::SerialWave{}, sh[threadIdx.x], a, c);
 }
 
 __global__ __launch_bounds__(64) void rs_commit_lane_kernel(RsCommitArgs) {
   __shared__ ufc_codec::RsWaveShared sh[64];
-  typedef const RsCommitArgs __attribute__((address_space(4))) * KernArgs;
-  const RsCommitArgs& a = *(const RsCommitArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const RsCommitArgs& a = kernargs<RsCommitArgs>();
   for (uint64_t c = (uint64_t)blockIdx.x * 64 + threadIdx.x; c < a.n; c += (uint64_t)gridDim.x * 64)
-    ufc_codec::rs_commit(RsLaneWave{}, sh[threadIdx.x], a, c);
+    ufc_codec::rs_commit(ufc_codec::SerialWave{}, sh[threadIdx.x], a, c);
 }
 
 #if !defined(UFC_RS_FORM)

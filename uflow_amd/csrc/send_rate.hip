@@ -19,6 +19,7 @@
 
 #include "frame_codec_core.hpp"
 #include "send_rate.hpp"
+#include "wave_dev.hpp"
 
 namespace ufc_dev {
 
@@ -88,11 +89,10 @@ struct Staged {
 // One wave per block and a tile of 64 connections per round.  The state rows serve states_out and the frame
 // queue result rows the results on the way back; a tile is read completely before any of it is written, and the
 // tiles are disjoint, so states_out may be `states`.
-// The 14 arguments are read where they are needed, from the kernel-argument segment (the one by-value argument
-// lies at its start), as fq_step_kernel reads its own: held in scalar registers through the step they spilled.
+// The 14 arguments are read from the kernel-argument segment (wave_dev.hpp): held in scalar registers through the
+// step they spilled.
 __global__ __launch_bounds__(64) void rate_step_kernel(RateArgs) {
-  typedef const RateArgs __attribute__((address_space(4))) * KernArgs;
-  const RateArgs& a = *(const RateArgs*)(KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const RateArgs& a = kernargs<RateArgs>();
   __shared__ Staged<ufc_rate_state> st;
   __shared__ Staged<ufc_rate_tick> tk;
   __shared__ union {

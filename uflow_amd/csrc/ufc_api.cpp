@@ -42,12 +42,11 @@ struct ufc_ctx {
   uint8_t* d_stage = nullptr;
   size_t d_stage_cap = 0;
   uint64_t* d_off = nullptr;
-  size_t d_off_cap = 0;  // entries
+  size_t d_off_cap = 0;  // entries, of d_off and of h_off_pinned
   uint32_t* d_crc = nullptr;
   uint8_t* d_valid = nullptr;
   size_t d_out_cap = 0;  // frames
   uint64_t* h_off_pinned = nullptr;
-  size_t h_off_cap = 0;
   hipStream_t streams[2] = {nullptr, nullptr};
   // Claim counters of the lean fixed kernel: kCtrSlots slots of ncu * kCtrWordsPerBlock words,
   // zeroed at creation and reset by each launch's last wave; launches take slots round-robin, so
@@ -291,7 +290,47 @@ int launch_varlen_any(ufc_ctx* ctx, bool seal, bool pairs, ufc_dev::KernelParams
 
 using ufc_internal::kMaxFrameLen;
 
+// The staging of the host-buffer calls, two slots of each, grow-only: stage_bytes for the frames, off_entries
+// offsets on the device and as many pinned on the host, out_frames CRC words and valid bytes.  (The calls wait for
+// their streams before they return, so nothing uses a buffer that is freed here.)
+hipError_t grow_staging(ufc_ctx* ctx, size_t stage_bytes, size_t off_entries, size_t out_frames) {
+  hipError_t e;
+  if (ctx->d_stage_cap < stage_bytes) {
+    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    ctx->d_stage = nullptr;
+    ctx->d_stage_cap = 0;
+    if ((e = hipMalloc(&ctx->d_stage, stage_bytes)) != hipSuccess) return e;
+    ctx->d_stage_cap = stage_bytes;
+  }
+  if (ctx->d_off_cap < off_entries) {
+    if (ctx->d_off) (void)hipFree(ctx->d_off);
+    if (ctx->h_off_pinned) (void)hipHostFree(ctx->h_off_pinned);
+    ctx->d_off = nullptr;
+    ctx->h_off_pinned = nullptr;
+    ctx->d_off_cap = 0;
+    if ((e = hipMalloc(&ctx->d_off, off_entries * 8)) != hipSuccess) return e;
+    if ((e = hipHostMalloc(&ctx->h_off_pinned, off_entries * 8, hipHostMallocDefault)) != hipSuccess) return e;
+    ctx->d_off_cap = off_entries;
+  }
+  if (ctx->d_out_cap < out_frames) {
+    if (ctx->d_crc) (void)hipFree(ctx->d_crc);
+    if (ctx->d_valid) (void)hipFree(ctx->d_valid);
+    ctx->d_crc = nullptr;
+    ctx->d_valid = nullptr;
+    ctx->d_out_cap = 0;
+    if ((e = hipMalloc(&ctx->d_crc, out_frames * 4)) != hipSuccess) return e;
+    if ((e = hipMalloc(&ctx->d_valid, out_frames)) != hipSuccess) return e;
+    ctx->d_out_cap = out_frames;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
+
+// This stream's own scratch of the kind (it grows on the first or a larger batch only).
+hipError_t ufc_dev::ScratchSource::get(size_t bytes, char** out) const {
+  return stream_scratch(ctx, kind, stream, bytes, (void**)out);
+}
 
 extern "C" {
 
@@ -618,36 +657,8 @@ static int validate_host_varlen_impl(ufc_ctx* ctx, const uint8_t* h_bytes, const
     cuts.push_back(b);
   }
   (void)total;
-  // Grow staging (2 slots each).
-  if (ctx->d_stage_cap < 2 * max_chunk_bytes + 64) {
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    ctx->d_stage = nullptr;
-    ctx->d_stage_cap = 0;
-    if ((e = hipMalloc(&ctx->d_stage, 2 * max_chunk_bytes + 64)) != hipSuccess) return hip_fail(ctx, e);
-    ctx->d_stage_cap = 2 * max_chunk_bytes + 64;
-  }
-  const size_t need_off = 2 * (max_chunk_frames + 1);
-  if (ctx->d_off_cap < need_off) {
-    if (ctx->d_off) (void)hipFree(ctx->d_off);
-    if (ctx->h_off_pinned) (void)hipHostFree(ctx->h_off_pinned);
-    ctx->d_off = nullptr;
-    ctx->h_off_pinned = nullptr;
-    ctx->d_off_cap = ctx->h_off_cap = 0;
-    if ((e = hipMalloc(&ctx->d_off, need_off * 8)) != hipSuccess) return hip_fail(ctx, e);
-    if ((e = hipHostMalloc(&ctx->h_off_pinned, need_off * 8, hipHostMallocDefault)) != hipSuccess)
-      return hip_fail(ctx, e);
-    ctx->d_off_cap = ctx->h_off_cap = need_off;
-  }
-  if (ctx->d_out_cap < 2 * max_chunk_frames) {
-    if (ctx->d_crc) (void)hipFree(ctx->d_crc);
-    if (ctx->d_valid) (void)hipFree(ctx->d_valid);
-    ctx->d_crc = nullptr;
-    ctx->d_valid = nullptr;
-    ctx->d_out_cap = 0;
-    if ((e = hipMalloc(&ctx->d_crc, 2 * max_chunk_frames * 4)) != hipSuccess) return hip_fail(ctx, e);
-    if ((e = hipMalloc(&ctx->d_valid, 2 * max_chunk_frames)) != hipSuccess) return hip_fail(ctx, e);
-    ctx->d_out_cap = 2 * max_chunk_frames;
-  }
+  if ((e = grow_staging(ctx, 2 * max_chunk_bytes + 64, 2 * (max_chunk_frames + 1), 2 * max_chunk_frames)) != hipSuccess)
+    return hip_fail(ctx, e);
   for (size_t k = 0; k + 1 < cuts.size(); k++) {
     const int slot = (int)(k & 1);
     hipStream_t s = ctx->streams[slot];
@@ -714,33 +725,7 @@ static int validate_host_slots_impl(ufc_ctx* ctx, const uint8_t* h_slots, size_t
   const size_t per = std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, ((size_t)64 << 20) / slot_stride));
   const size_t cf = std::min(per, n);
   const size_t cb = cf * slot_stride;
-  if (ctx->d_stage_cap < 2 * cb + 64) {
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    ctx->d_stage = nullptr;
-    ctx->d_stage_cap = 0;
-    if ((e = hipMalloc(&ctx->d_stage, 2 * cb + 64)) != hipSuccess) return hip_fail(ctx, e);
-    ctx->d_stage_cap = 2 * cb + 64;
-  }
-  if (ctx->d_off_cap < 4 * cf) {
-    if (ctx->d_off) (void)hipFree(ctx->d_off);
-    if (ctx->h_off_pinned) (void)hipHostFree(ctx->h_off_pinned);
-    ctx->d_off = nullptr;
-    ctx->h_off_pinned = nullptr;
-    ctx->d_off_cap = ctx->h_off_cap = 0;
-    if ((e = hipMalloc(&ctx->d_off, 4 * cf * 8)) != hipSuccess) return hip_fail(ctx, e);
-    if ((e = hipHostMalloc(&ctx->h_off_pinned, 4 * cf * 8, hipHostMallocDefault)) != hipSuccess) return hip_fail(ctx, e);
-    ctx->d_off_cap = ctx->h_off_cap = 4 * cf;
-  }
-  if (ctx->d_out_cap < 2 * cf) {
-    if (ctx->d_crc) (void)hipFree(ctx->d_crc);
-    if (ctx->d_valid) (void)hipFree(ctx->d_valid);
-    ctx->d_crc = nullptr;
-    ctx->d_valid = nullptr;
-    ctx->d_out_cap = 0;
-    if ((e = hipMalloc(&ctx->d_crc, 2 * cf * 4)) != hipSuccess) return hip_fail(ctx, e);
-    if ((e = hipMalloc(&ctx->d_valid, 2 * cf)) != hipSuccess) return hip_fail(ctx, e);
-    ctx->d_out_cap = 2 * cf;
-  }
+  if ((e = grow_staging(ctx, 2 * cb + 64, 4 * cf, 2 * cf)) != hipSuccess) return hip_fail(ctx, e);
   size_t k = 0;
   for (size_t a = 0; a < n; a += cf, k++) {
     const int slot = (int)(k & 1);
@@ -784,13 +769,13 @@ static int validate_host_slots_async_impl(ufc_ctx* ctx, const uint8_t* h_slots, 
   if (n > (((size_t)1 << 31) - ((size_t)1 << 20)) / slot_stride) return UFC_ERR_INVALID_ARG;
   for (size_t i = 0; i < n; i++)
     if (h_lens[i] > slot_stride) return UFC_ERR_INVALID_ARG;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t bytes = (n - 1) * slot_stride + h_lens[n - 1];  // the slab may end at the last datagram
-  const size_t o_lens = up(bytes + 64), o_pairs = o_lens + up(4 * n), o_crc = o_pairs + up(16 * n),
-               o_valid = o_crc + up(4 * n), need = o_valid + up(n);
+  ufc_dev::ScratchPlan plan;
+  plan.take(bytes + 64);  // (the slots' bytes, at the scratch's start)
+  const size_t o_lens = plan.take(4 * n), o_pairs = plan.take(16 * n), o_crc = plan.take(4 * n), o_valid = plan.take(n);
   void* sp = nullptr;
   hipError_t e;
-  if ((e = stream_scratch(ctx, kScratchAsyncSlots, stream, need, &sp)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = stream_scratch(ctx, kScratchAsyncSlots, stream, plan.end, &sp)) != hipSuccess) return hip_fail(ctx, e);
   uint8_t* s = (uint8_t*)sp;
   uint32_t* d_lens = (uint32_t*)(s + o_lens);
   uint64_t* d_pairs = (uint64_t*)(s + o_pairs);
@@ -887,13 +872,10 @@ int ufc_parse_batch_varlen(ufc_ctx* ctx, const uint8_t* d_bytes, const uint64_t*
   if (!d_bytes || !d_offsets || !d_valid || !d_infos || n >= ((size_t)1 << 31)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const size_t need = ufc_dev::parse_scratch_bytes(n, d_items ? (uint64_t)items_cap : 0);
-  void* scratch = nullptr;  // this stream's own scratch (grows on the first or a larger batch only)
-  if ((e = stream_scratch(ctx, kScratchParse, (hipStream_t)stream, need, &scratch)) != hipSuccess)
-    return hip_fail(ctx, e);
   ufc_dev::ParseArgs a{d_bytes, d_offsets, (uint64_t)n, d_valid, d_infos, d_items, (uint64_t)(d_items ? items_cap : 0),
                        d_items_used};
-  if ((e = ufc_dev::parse_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = ufc_dev::parse_batch(a, {ctx, kScratchParse, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -915,12 +897,10 @@ int ufc_build_sizes_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const uf
   if (!build_args_ok(d_infos, d_items, n_items, n, d_out_offsets)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const size_t need = ufc_dev::build_scratch_bytes(n, n_items, 0);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchBuild, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
   ufc_dev::BuildArgs a{d_infos, d_items, (uint64_t)n_items, d_src_base, nullptr, (uint64_t)payload_len, (uint64_t)n,
                        d_out_offsets, d_status, nullptr, 0};
-  if ((e = ufc_dev::build_sizes(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = ufc_dev::build_sizes(a, {ctx, kScratchBuild, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -935,12 +915,10 @@ int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const uf
     return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const size_t need = ufc_dev::build_scratch_bytes(n, n_items, out_len);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchBuild, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
   ufc_dev::BuildArgs a{d_infos, d_items, (uint64_t)n_items, d_src_base, d_payload, (uint64_t)payload_len, (uint64_t)n,
                        const_cast<uint64_t*>(d_out_offsets), nullptr, d_out_bytes, (uint64_t)out_len};
-  if ((e = ufc_dev::build_write(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = ufc_dev::build_write(a, {ctx, kScratchBuild, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   if (!seal || !d_out_bytes) return UFC_OK;
   // The trailers: the variable-length seal over the batch just written, next on the stream (spans shorter
   // than 4 bytes, the skipped frames' length-0 ones among them, get none: frame_crc_varlen8.hip).
@@ -966,12 +944,10 @@ int ufc_pack_varlen(ufc_ctx* ctx, const ufc_item* d_items, size_t n_items, const
     return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const size_t need = ufc_dev::pack_scratch_bytes(n_flushes, n_items);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchPack, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
   ufc_dev::PackArgs a{d_items, (uint64_t)n_items, d_flush_first, d_flushes, (uint64_t)n_flushes, d_nonce_bits,
                       d_infos, (uint64_t)frames_cap, d_results, d_frames_used};
-  if ((e = ufc_dev::pack_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = ufc_dev::pack_batch(a, {ctx, kScratchPack, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -991,13 +967,11 @@ int ufc_emit_packets_varlen(ufc_ctx* ctx, const ufc_packet* d_packets, size_t n_
     return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const size_t need = ufc_dev::emit_scratch_bytes(n_senders, n_packets);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchEmit, (hipStream_t)stream, need, &scratch)) != hipSuccess) return hip_fail(ctx, e);
   ufc_dev::EmitArgs a{d_packets, (uint64_t)n_packets, d_packet_first, d_senders, (uint64_t)n_senders, d_items,
                       (uint64_t)items_cap, d_flush_first, d_packet_results, d_sender_results, d_senders_out,
                       d_items_used};
-  if ((e = ufc_dev::emit_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if ((e = ufc_dev::emit_batch(a, {ctx, kScratchEmit, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -1014,27 +988,18 @@ int ufc_receive_packets_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size
                                ufc_receiver_result* d_results, ufc_receiver* d_receivers_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n_receivers == 0) return UFC_OK;
-  // (the counts and the chunk counts are scanned with 32-bit counts)
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!d_frame_first || !d_receivers || !d_receivers_out || !d_slot_first || !d_carry_first || !d_carry_used ||
-      !d_packet_first || !d_packets_used || !d_out_used || !d_results || (!d_infos && n_frames) ||
-      (!d_items && n_items) || (!d_payload && payload_len) || (!d_slots && n_slots) || (!d_carry_in && carry_in_len) ||
-      (!d_carry_out && carry_cap) || (!d_packets && packets_cap) || (!d_out_bytes && out_cap) || n_frames >= lim ||
-      n_items >= lim || n_receivers >= lim || n_slots >= lim / 2 || ((uintptr_t)d_carry_in & 7) ||
-      ((uintptr_t)d_carry_out & 7))
-    return UFC_ERR_INVALID_ARG;
-  DeviceGuard g(ctx->device);
-  hipError_t e;
-  const size_t need = ufc_dev::receive_scratch_bytes(n_receivers, n_items, n_slots);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchReceive, (hipStream_t)stream, need, &scratch)) != hipSuccess)
-    return hip_fail(ctx, e);
   const ufc_codec::RxArgs a{d_infos, n_frames, d_frame_accept, d_items, n_items, d_src_base, d_payload, payload_len,
                             d_frame_first, d_receivers, n_receivers, d_slots, d_slot_first, n_slots, d_carry_in,
                             carry_in_len, d_carry_out, carry_cap, d_carry_first, d_carry_used, d_packets, packets_cap,
                             d_packet_first, d_packets_used, d_out_bytes, out_cap, d_out_used, d_item_status, d_results,
                             d_receivers_out};
-  if ((e = ufc_dev::receive_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  // The device alone also scans the 2 n_slots + 1 chunk counts of the slots' copy segments with a 32-bit count
+  // (packet_receive.hip); the host entry copies without chunks and takes n_slots up to the shared limit.
+  if (!ufc_codec::rx_args_ok(a) || n_slots >= ufc_codec::kCountLim / 2) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  if ((e = ufc_dev::receive_batch(a, {ctx, kScratchReceive, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -1045,20 +1010,13 @@ int ufc_frame_window_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
                             ufc_frame_window_result* d_results, ufc_frame_window* d_windows_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n_windows == 0) return UFC_OK;
-  // (the n_windows + 1 group counts are scanned with a 32-bit count)
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!d_frame_first || !d_windows || !d_windows_out || !d_frame_accept || !d_group_first || !d_groups_used ||
-      !d_results || (!d_infos && n_frames) || (!d_groups && groups_cap) || n_frames >= lim || n_windows >= lim)
-    return UFC_ERR_INVALID_ARG;
-  DeviceGuard g(ctx->device);
-  hipError_t e;
-  const size_t need = ufc_dev::window_scratch_bytes(n_windows);
-  void* scratch = nullptr;
-  if ((e = stream_scratch(ctx, kScratchWindow, (hipStream_t)stream, need, &scratch)) != hipSuccess)
-    return hip_fail(ctx, e);
   const ufc_codec::FwArgs a{d_infos, n_frames, d_frame_first, d_windows, n_windows, d_frame_accept, d_groups,
                             groups_cap, d_group_first, d_groups_used, d_results, d_windows_out};
-  if ((e = ufc_dev::window_batch(a, scratch, need, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  if (!ufc_codec::fw_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  if ((e = ufc_dev::window_batch(a, {ctx, kScratchWindow, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 
@@ -1071,16 +1029,12 @@ int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n
                            ufc_frame_queue* d_queues_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n_queues == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!d_frame_first || !d_sent_first || !d_queues || !d_steps || !d_results || !d_queues_out ||
-      (!d_infos && n_frames) || (!d_items && n_items) || (!d_sent && n_sent) || (!d_log && n_log) || n_frames >= lim ||
-      n_items >= lim || n_sent >= lim || n_queues >= lim)
-    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::FqArgs a{d_infos, n_frames, d_items, n_items, d_frame_first, d_sent, n_sent, d_sent_first, d_queues,
+                            d_steps, n_queues, d_log, n_log, d_ref_acked, refs_cap, d_results, d_queues_out};
+  if (!ufc_codec::fq_args_ok(a)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
   // (one launch and no scan: the call needs none of the context's per-stream scratch)
-  const ufc_codec::FqArgs a{d_infos, n_frames, d_items, n_items, d_frame_first, d_sent, n_sent, d_sent_first, d_queues,
-                            d_steps, n_queues, d_log, n_log, d_ref_acked, refs_cap, d_results, d_queues_out};
   if ((e = ufc_dev::queue_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
@@ -1091,10 +1045,10 @@ int ufc_rate_begin_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ui
                           ufc_rate_state* d_states_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n == 0) return UFC_OK;
-  if (!d_states || !d_now_ms || !d_steps || !d_states_out || n >= ((size_t)1 << 31) - 1) return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RateBeginArgs a{d_states, d_now_ms, d_extra_flags, n, d_steps, d_states_out};
+  if (!ufc_codec::rate_begin_args_ok(a)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const ufc_codec::RateBeginArgs a{d_states, d_now_ms, d_extra_flags, n, d_steps, d_states_out};
   if ((e = ufc_dev::rate_begin_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
@@ -1106,14 +1060,12 @@ int ufc_rate_step_varlen(ufc_ctx* ctx, const ufc_rate_state* d_states, const ufc
                          ufc_rate_result* d_results, ufc_rate_state* d_states_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n == 0) return UFC_OK;
-  if (!d_states || !d_ticks || !d_fq || !d_results || !d_states_out || (!d_entries && n_entries) ||
-      (d_flush_results && !d_result_index) || (d_flushes && !d_flush_index) || n >= ((size_t)1 << 31) - 1)
-    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RateArgs a{d_states, d_ticks, d_fq, n, d_entries, n_entries, d_flush_results, n_flush_results,
+                              d_result_index, d_flushes, n_flushes, d_flush_index, d_results, d_states_out};
+  if (!ufc_codec::rate_args_ok(a)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
   // (one launch, no scan: the call needs none of the context's per-stream scratch)
-  const ufc_codec::RateArgs a{d_states, d_ticks, d_fq, n, d_entries, n_entries, d_flush_results, n_flush_results,
-                              d_result_index, d_flushes, n_flushes, d_flush_index, d_results, d_states_out};
   if ((e = ufc_dev::rate_step_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
@@ -1129,17 +1081,13 @@ int ufc_resend_begin_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t 
                             ufc_sender* d_senders_out, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!d_frame_first || !d_queues || !d_rate || !d_flushes || !d_states || !d_senders || !d_results || !d_states_out ||
-      !d_senders_out || (!d_infos && n_frames) || (!d_log && n_log) || (!d_heap && n_heap) || (!d_pkts && n_pkts) ||
-      (!d_frag_acked && n_frag) || (!d_tx && n_tx) || (!d_stage && n_stage) || n >= lim || n_frames >= lim)
-    return UFC_ERR_INVALID_ARG;
-  DeviceGuard g(ctx->device);
-  hipError_t e;
-  // (one launch, no scan: the call needs none of the context's per-stream scratch)
   const ufc_codec::RsBeginArgs a{d_infos, n_frames, d_frame_first, d_queues, d_log, n_log, d_rate, d_flags, d_flushes,
                                  d_states, d_senders, n, d_heap, n_heap, d_pkts, n_pkts, d_frag_acked, n_frag, d_tx, n_tx,
                                  d_ref_acked, refs_cap, d_stage, n_stage, d_results, d_states_out, d_senders_out};
+  if (!ufc_codec::rs_begin_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  // (one launch, no scan: the call needs none of the context's per-stream scratch)
   if ((e = ufc_dev::resend_begin_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
@@ -1149,12 +1097,10 @@ int ufc_resend_place_varlen(ufc_ctx* ctx, const ufc_resend* d_states, const ufc_
                             size_t items_cap, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n == 0) return UFC_OK;
-  if (!d_states || !d_begin_results || !d_flush_first || (!d_stage && n_stage) || (!d_items && items_cap) ||
-      n >= ((size_t)1 << 31) - 1)
-    return UFC_ERR_INVALID_ARG;
+  const ufc_codec::RsPlaceArgs a{d_states, d_begin_results, n, d_stage, n_stage, d_flush_first, d_items, items_cap};
+  if (!ufc_codec::rs_place_args_ok(a)) return UFC_ERR_INVALID_ARG;
   DeviceGuard g(ctx->device);
   hipError_t e;
-  const ufc_codec::RsPlaceArgs a{d_states, d_begin_results, n, d_stage, n_stage, d_flush_first, d_items, items_cap};
   if ((e = ufc_dev::resend_place_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
@@ -1172,20 +1118,14 @@ int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_resul
                              ufc_resend* d_states_out, ufc_sender* d_retake, void* stream) {
   if (!ctx) return UFC_ERR_INVALID_ARG;
   if (n == 0) return UFC_OK;
-  const size_t lim = ((size_t)1 << 31) - 1;
-  if (!d_flush_results || !d_out_offsets || !d_frames_used || !d_flush_first || !d_packet_first || !d_sender_results ||
-      !d_begin_results || !d_rate || !d_states || !d_senders || !d_sent_first || !d_results || !d_states_out ||
-      !d_retake || (!d_infos && n_infos) || (!d_items && n_items) || (!d_packets && n_packets) ||
-      (!d_packet_results && n_packets) || (!d_heap && n_heap) || (!d_pkts && n_pkts) || (!d_frag_acked && n_frag) ||
-      (!d_tx && n_tx) || (!d_sent && sent_cap) || n >= lim || n_packets >= lim || n_items >= lim || n_infos >= lim)
-    return UFC_ERR_INVALID_ARG;
-  DeviceGuard g(ctx->device);
-  hipError_t e;
   const ufc_codec::RsCommitArgs a{d_flush_results, d_infos, n_infos, d_out_offsets, d_frames_used, d_items, n_items,
                                   d_flush_first, d_packets, n_packets, d_packet_first, d_packet_results,
                                   d_sender_results, d_begin_results, d_rate, d_states, d_senders, n, d_heap, n_heap,
                                   d_pkts, n_pkts, d_frag_acked, n_frag, d_tx, n_tx, d_sent, sent_cap, d_sent_first,
                                   d_next_extra_flags, d_results, d_states_out, d_retake};
+  if (!ufc_codec::rs_commit_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
   if ((e = ufc_dev::resend_commit_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
   return UFC_OK;
 }
