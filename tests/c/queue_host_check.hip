@@ -1,13 +1,17 @@
 // The frame queue's core (uflow_amd/csrc/frame_codec_core.hpp: fq_step, the form the device runs, one wave per
 // connection with a lane per log entry) as host code under AddressSanitizer and UBSan: the lanes of a phase run one
-// after the other, the shared block starts as garbage.  Checked against a scalar loop in this file that follows the
+// after the other -- forwards, backwards and in a fresh seeded permutation per phase (lane_orders.hpp) -- and the
+// shared block starts as garbage, fresh for every step or, in a fourth pass, one block carried from connection to
+// connection as the kernel's grid-stride loop and the host entry carry it.  Checked against a scalar loop in this file that follows the
 // reference entry by entry (push, acknowledge_group, ReorderBuffer::put and advance with a callback per id,
 // push_ack and push_nack one at a time, find_expiration_cutoff frame by frame) and stops where the reference would
 // panic: results, states, every log byte and ref_acked must be equal byte for byte.  Seeded traffic: connections
 // chained over several calls (frames pushed at rising times or at times all over, a receiver that loses frames and
 // acknowledges in groups, in order or not, twice, with a bad nonce, empty or far away; window bases that advance;
 // forgets, feedbacks, resets), windows of 1 to 4096 with rings that wrap, ids through 2^32, random states that pass
-// the check, and states that do not.  All buffers have their exact sizes.
+// the check, and states that do not.  All buffers have their exact sizes.  In front of the seeded traffic, directed
+// cases that put every ballot's deciding lane on lane 0, on lane 63 and across a tile seam (DESIGN.md 5.15;
+// tests/test_queue_cpu.py has the same cases as scenarios), each with its expectation spelled out.
 // Prints "ok: <checks>" and exits 0; any difference or sanitizer report stops the program.
 #include <cstdint>
 #include <cstdio>
@@ -16,6 +20,7 @@
 #include <vector>
 
 #include "../../uflow_amd/csrc/frame_codec_core.hpp"
+#include "lane_orders.hpp"
 
 namespace {
 
@@ -271,41 +276,53 @@ struct Batch {
 
 long total_nacks = 0, total_acked = 0, total_bad = 0, total_unknown = 0, total_badnonce = 0, total_feedback = 0, total_culled = 0;
 
-// Runs the batch tiled and scalar, compares, and moves the batch's state on (queues, log, refs).
+// The forms the wave step runs in: three lane orders on a fresh garbage block, and forwards on a carried one.
+enum Form { kForwards, kBackwards, kShuffled, kCarried, kForms };
+FqWaveShared carried_block;  // (garbage once, in main)
+ufc_frame_queue_result last_result;  // connection 0's, of the last batch
+
+// Runs the batch in every wave form and scalar, compares, and moves the batch's state on (queues, log, refs).
 void run_both(Batch& b, bool with_refs) {
   const size_t n = b.queues.size();
   std::vector<ufc_frame_queue_result> r1(n), r2(n);
   std::vector<ufc_frame_queue> q1(n), q2(n);
-  std::memset((void*)r1.data(), 0xA5, n * sizeof r1[0]);
   std::memset((void*)r2.data(), 0xA5, n * sizeof r2[0]);
-  std::memset((void*)q1.data(), 0xA5, n * sizeof q1[0]);
   std::memset((void*)q2.data(), 0xA5, n * sizeof q2[0]);
-  std::vector<ufc_sent_frame> log1 = b.log, log2 = b.log;
-  std::vector<uint8_t> refs1 = b.refs, refs2 = b.refs;
+  std::vector<ufc_sent_frame> log1, log2 = b.log;
+  std::vector<uint8_t> refs1, refs2 = b.refs;
   FqArgs a{b.infos.data(), b.infos.size(), b.items.data(), b.items.size(), b.frame_first.data(), b.sent.data(), b.sent.size(),
-           b.sent_first.data(), b.queues.data(), b.steps.data(), n, log1.data(), log1.size(),
-           with_refs ? refs1.data() : nullptr, refs1.size(), r1.data(), q1.data()};
-  for (uint64_t c = n; c-- > 0;) {  // (the connections in any order: last first here)
-    FqWaveShared sh;
-    std::memset((void*)&sh, 0xCD, sizeof sh);
-    fq_step(SerialWave{}, sh, a, c);
-  }
-  a.results = r2.data();
-  a.queues_out = q2.data();
+           b.sent_first.data(), b.queues.data(), b.steps.data(), n, log2.data(), log2.size(),
+           with_refs ? refs2.data() : nullptr, refs2.size(), r2.data(), q2.data()};
   for (uint64_t c = 0; c < n; c++) scalar_step(a, c, log2.data(), with_refs ? refs2.data() : nullptr);
-  if (std::memcmp((void*)r1.data(), (void*)r2.data(), n * sizeof r1[0])) {
-    for (size_t c = 0; c < n; c++)
-      if (std::memcmp((void*)&r1[c], (void*)&r2[c], sizeof r1[0])) fail("results", (long)c, r1[c].li_nacks, r2[c].li_nacks);
+  for (int form = 0; form < kForms; form++) {
+    std::memset((void*)r1.data(), 0xA5, n * sizeof r1[0]);
+    std::memset((void*)q1.data(), 0xA5, n * sizeof q1[0]);
+    log1 = b.log, refs1 = b.refs;
+    a.log = log1.data(), a.ref_acked = with_refs ? refs1.data() : nullptr, a.results = r1.data(), a.queues_out = q1.data();
+    for (uint64_t c = n; c-- > 0;) {  // (the connections in any order: last first here)
+      FqWaveShared fresh;
+      std::memset((void*)&fresh, 0xCD, sizeof fresh);
+      FqWaveShared& sh = form == kCarried ? carried_block : fresh;
+      if (form == kBackwards) fq_step(lane_orders::ReverseWave{}, sh, a, c);
+      else if (form == kShuffled) fq_step(lane_orders::ShuffledWave{}, sh, a, c);
+      else fq_step(SerialWave{}, sh, a, c);
+    }
+    if (std::memcmp((void*)r1.data(), (void*)r2.data(), n * sizeof r1[0])) {
+      for (size_t c = 0; c < n; c++)
+        if (std::memcmp((void*)&r1[c], (void*)&r2[c], sizeof r1[0])) fail("results", (long)c, form, r1[c].li_nacks * 100000L + r2[c].li_nacks);
+    }
+    if (std::memcmp((void*)q1.data(), (void*)q2.data(), n * sizeof q1[0])) fail("queues_out", form, 0, 0);
+    if (!log1.empty() && std::memcmp((void*)log1.data(), (void*)log2.data(), log1.size() * sizeof log1[0])) fail("log", form, 0, 0);
+    if (refs1 != refs2) fail("ref_acked", form, 0, 0);
+    checks++;
   }
-  if (std::memcmp((void*)q1.data(), (void*)q2.data(), n * sizeof q1[0])) fail("queues_out", 0, 0, 0);
-  if (!log1.empty() && std::memcmp((void*)log1.data(), (void*)log2.data(), log1.size() * sizeof log1[0])) fail("log", 0, 0, 0);
-  if (refs1 != refs2) fail("ref_acked", 0, 0, 0);
   for (size_t c = 0; c < n; c++) {
     total_nacks += r1[c].li_nacks, total_acked += r1[c].frames_acked, total_bad += r1[c].stop == UFC_FQ_BAD_STATE;
     total_unknown += r1[c].groups_unknown, total_badnonce += r1[c].groups_bad_nonce, total_feedback += r1[c].has_feedback;
     total_culled += r1[c].log_culled;
     checks++;
   }
+  if (n) last_result = r1[0];
   b.queues = q1;
   b.log = log1;
   b.refs = refs1;
@@ -549,9 +566,125 @@ void bad_states() {
   }
 }
 
+// The ballots of fq_step with their deciding lane on lane 0, on lane 63 and across a tile seam (the same cases, with
+// the same numbers, are scenarios of tests/test_queue_cpu.py).  One connection, window 256 / tail 256 / a ring of 512
+// at ids through 2^32; a first call pushes 200 frames, the second is the case.  The expectation is written out here
+// and must also be what the scalar loop gives (run_both).
+constexpr uint32_t kBase = 0xFFFFFFC0u;
+
+Batch pushed(const std::vector<uint64_t>& times) {
+  Batch b;
+  b.queues.push_back(new_queue(256, 256, kBase, 512, 0));
+  b.log.assign(512, ufc_sent_frame{});
+  std::memset((void*)b.log.data(), 0x5A, b.log.size() * sizeof b.log[0]);
+  for (size_t k = 0; k < times.size(); k++) {
+    ufc_sent_frame s{};
+    s.send_time_ms = times[k], s.size = 100 + (uint32_t)k, s.ref_first = (uint32_t)k, s.ref_count = 1, s.flags = (uint8_t)(k & 1);
+    b.sent.push_back(s);
+  }
+  b.frame_first = {0, 0}, b.sent_first = {0, times.size()};
+  b.steps.assign(1, ufc_frame_queue_step{});
+  b.refs.assign(times.size(), 0);
+  run_both(b, true);
+  if (last_result.pushes_taken != times.size()) fail("directed: the pushes", last_result.pushes_taken, 0, 0);
+  b.sent.clear(), b.sent_first = {0, 0};
+  return b;
+}
+
+// 130 frames of which the ok ack frames sit at 63, 64 and 129, three ids each; the others are not acks or not ok
+// and carry item ranges that must never be looked at.  bad_at: that ack frame's item range runs past the items.
+void ack_frames_at_63_64_129(int bad_at) {
+  std::vector<uint64_t> times;
+  for (uint32_t k = 0; k < 200; k++) times.push_back(10 * k);
+  Batch b = pushed(times);
+  b.infos.clear();
+  for (uint32_t i = 0; i < 130; i++) {
+    ufc_frame_info f{};
+    if (i == 63 || i == 64 || i == 129) {
+      const uint32_t g = i == 63 ? 0 : i == 64 ? 1 : 2;
+      f.kind = UFC_FRAME_ACK, f.ok = 1, f.crc_ok = 1;
+      f.f[0] = i == 129 ? kBase + 9 : kBase;
+      f.item_first = g, f.item_count = (int)i == bad_at ? 4 - g : 1;
+      b.items.push_back(group_item(kBase + 3 * g, 7, g == 1 ? 0 : 1));  // (nonces k & 1: 0 1 0 | 1 0 1 | 0 1 0)
+    } else {
+      f.kind = i % 2 ? UFC_FRAME_DATA : UFC_FRAME_ACK;
+      f.ok = f.kind == UFC_FRAME_DATA;
+      f.item_first = 0xFFFFFFF0u, f.item_count = 100;
+    }
+    b.infos.push_back(f);
+  }
+  b.frame_first = {0, 130};
+  run_both(b, true);
+  const ufc_frame_queue_result& r = last_result;
+  if (bad_at >= 0) {
+    if (r.stop != UFC_FQ_BAD_STATE || b.queues[0].window_base_id != kBase) fail("directed: a bad item range", bad_at, r.stop, 0);
+    return;
+  }
+  if (r.stop != UFC_FQ_DONE || r.ack_frames != 3 || r.groups != 3 || r.frames_acked != 9 || r.li_acks != 9 || r.window_advanced != 9)
+    fail("directed: ack frames at 63, 64, 129", r.ack_frames, r.frames_acked, r.window_advanced);
+  for (uint32_t k = 0; k < 200; k++)
+    if (b.refs[k] != (k < 9)) fail("directed: ack frames at 63, 64, 129: ref_acked", k, 0, 0);
+}
+
+// A nack run of 140 ids over a log whose send times go up and down (a forget whose first kept entry is `lead` + 140,
+// the first `lead` ids acknowledged in the same call so that the run starts there).  rtt 50: the run's entry 0 opens
+// an interval (none is open), entries 1..62 fall under it, entry 63 (number 63 of the first nack tile) is the first
+// at or after its end and opens the next, entry 64 (number 0 of the next tile) the next, entry 128 (number 0 of the
+// third) the last.
+void nack_run(uint32_t lead) {
+  std::vector<uint64_t> times;
+  for (uint32_t k = 0; k < lead; k++) times.push_back(500 + k);
+  for (uint32_t k = 0; k < 140; k++) {
+    const uint64_t wobble = (k * 7) % 50;
+    times.push_back(k == 0 ? 1000 : k < 63 ? 1049 - wobble : k == 63 ? 1050 : k == 64 ? 1100 : k < 128 ? 1149 - wobble
+                    : k == 128 ? 1150 : 1199 - wobble);
+  }
+  while (times.size() < 200) times.push_back(3000);
+  Batch b = pushed(times);
+  ufc_frame_info f{};
+  f.kind = UFC_FRAME_ACK, f.ok = 1, f.f[0] = kBase;
+  f.item_first = 0, f.item_count = lead;
+  for (uint32_t k = 0; k < lead; k++) b.items.push_back(group_item(kBase + k, 1, k & 1));
+  b.infos.assign(1, f);
+  b.frame_first = {0, 1};
+  b.steps[0].flags = UFC_FQ_FORGET | UFC_FQ_HAS_RTT;
+  b.steps[0].rtt_ms = 50, b.steps[0].thresh_ms = 2000;
+  run_both(b, true);
+  const ufc_frame_queue_result& r = last_result;
+  const ufc_frame_queue& q = b.queues[0];
+  static const uint32_t want_len[4] = {12, 64, 1, 63};
+  static const uint64_t want_end[4] = {1200, 1150, 1100, 1050};
+  if (r.stop != UFC_FQ_DONE || r.li_nacks != 140 || r.li_acks != lead || r.log_culled != lead + 140 || q.li_count != 4)
+    fail("directed: the nack run", r.li_nacks, r.log_culled, q.li_count);
+  for (uint32_t k = 0; k < 4; k++)
+    if (q.li_length[k] != want_len[k] || q.li_end_time_ms[k] != want_end[k]) fail("directed: the nack run's intervals", lead, k, q.li_length[k]);
+}
+
+// A forget whose first kept entry is log index `kept`: 63 (the last lane of the first expiry tile) or 64 (the first
+// of the next).
+void forget_kept_at(uint32_t kept) {
+  std::vector<uint64_t> times;
+  for (uint32_t k = 0; k < 200; k++) times.push_back(10 * k);
+  Batch b = pushed(times);
+  b.steps[0].flags = UFC_FQ_FORGET;
+  b.steps[0].thresh_ms = 10 * kept;
+  run_both(b, true);
+  if (last_result.log_culled != kept || last_result.li_nacks != kept || b.queues[0].log_base_id != kBase + kept)
+    fail("directed: forget", kept, last_result.log_culled, last_result.li_nacks);
+}
+
+void directed_cases() {
+  ack_frames_at_63_64_129(-1);
+  for (int bad_at : {63, 64, 129}) ack_frames_at_63_64_129(bad_at);
+  for (uint32_t lead : {0u, 5u}) nack_run(lead);
+  for (uint32_t kept : {63u, 64u, 128u}) forget_kept_at(kept);
+}
+
 }  // namespace
 
 int main() {
+  std::memset((void*)&carried_block, 0xCD, sizeof carried_block);
+  directed_cases();
   bad_states();
   chained(3, 4, 4, 8, 0xFFFFFFF0u, 40, true, 6);        // the ring wraps every other call; ids through 2^32
   chained(2, 1, 1, 2, 5, 30, true, 3);

@@ -15,8 +15,12 @@
 // Every step of both parts also runs the device form's parts as host code -- rx_walk_begin, the item-parallel
 // verdicts (rx_frame_verdicts, frames in reverse order), rx_walk_items on what they let through, and
 // rx_receive_tiles (the per-channel delivery prefixes and the window-advance prefix over 64-lane masks, the
-// lanes of a phase run one after the other) -- against the serial rx_walk: headers, slots, results, records,
-// delivered bytes and the carry must be equal byte for byte, on hostile state too.
+// lanes of a phase run one after the other: forwards, backwards and in a fresh seeded permutation per phase,
+// lane_orders.hpp; the shared block garbage, fresh for every receiver or, in a fourth pass, one block carried from
+// receiver to receiver) -- against the serial rx_walk: headers, slots, results, records, delivered bytes and the
+// carry must be equal byte for byte, on hostile state too.  In front of all that, directed cases that put every
+// cross-lane read of rx_receive_tiles on lane 63 and on lane 0 of the second tile (DESIGN.md 5.15;
+// tests/test_receive_cpu.py has the same cases as scenarios), each with its expectation spelled out.
 // Prints "ok: <checks>" and exits 0; any difference or sanitizer report stops the program.
 #include <algorithm>
 #include <cstdint>
@@ -27,6 +31,7 @@
 #include <vector>
 
 #include "../../uflow_amd/csrc/frame_codec_core.hpp"
+#include "lane_orders.hpp"
 
 namespace {
 
@@ -97,7 +102,11 @@ struct Counts {
   uint64_t packets, out, carry;
 };
 
-bool g_tiled = false;  // run_step takes the device form's parts instead of the serial walk
+// The forms run_step runs in: the serial walk, or the device form's parts with rx_receive_tiles under three lane
+// orders on a fresh garbage block, and forwards on a carried one.
+enum Form { kWalkSerial, kForwards, kBackwards, kShuffled, kCarried, kForms };
+int g_form = kWalkSerial;
+RxWaveShared carried_block;  // (garbage once, in main)
 
 // One step the way the device form runs it; the caps are the vectors' sizes.
 Counts run_step(const std::vector<ufc_frame_info>& infos, const std::vector<ufc_item>& items, const std::vector<uint8_t>& payload,
@@ -120,7 +129,7 @@ Counts run_step(const std::vector<ufc_frame_info>& infos, const std::vector<ufc_
   std::vector<unsigned long long> table(rx_dup_entries(ni), 0ull);
   const RxDupSet dups{table.data(), table.size() - 1};
   std::vector<uint64_t> c0(nr + 1, 0), c1(nr + 1, 0), c2(nr + 1, 0);
-  if (!g_tiled) {
+  if (g_form == kWalkSerial) {
     for (uint64_t r = 0; r < nr; r++) {
       uint64_t c[3];
       rx_walk(a, r, plans.data(), status.data(), dups, c);
@@ -136,11 +145,14 @@ Counts run_step(const std::vector<ufc_frame_info>& infos, const std::vector<ufc_
         for (uint64_t i = frame_first[r + 1]; i-- > frame_first[r];) rx_frame_verdicts(a, r, i, verdicts.data());
     for (uint64_t r = 0; r < nr; r++) rx_walk_items(a, r, plans.data(), status.data(), dups, verdicts.data());
     for (uint64_t r = 0; r < nr; r++) {
-      RxWaveShared sh;
-      std::memset((void*)&sh, 0xCD, sizeof sh);
+      RxWaveShared fresh;
+      std::memset((void*)&fresh, 0xCD, sizeof fresh);
+      RxWaveShared& sh = g_form == kCarried ? carried_block : fresh;
       uint32_t d;
       uint64_t o, c[3];
-      rx_receive_tiles(SerialWave{}, sh, a, r, plans.data(), d, o);
+      if (g_form == kBackwards) rx_receive_tiles(lane_orders::ReverseWave{}, sh, a, r, plans.data(), d, o);
+      else if (g_form == kShuffled) rx_receive_tiles(lane_orders::ShuffledWave{}, sh, a, r, plans.data(), d, o);
+      else rx_receive_tiles(SerialWave{}, sh, a, r, plans.data(), d, o);
       rx_walk_end(a, r, d, o, c);
       c0[r] = c[0], c1[r] = c[1], c2[r] = c[2];
     }
@@ -196,32 +208,151 @@ void both_ways(int where, const std::vector<ufc_frame_info>& infos, const std::v
                const std::vector<ufc_receiver>& receivers, const std::vector<ufc_rx_slot>& slots,
                const std::vector<uint64_t>& slot_first, const std::vector<uint8_t>& carry, size_t carry_cap, size_t packets_cap,
                size_t out_cap) {
-  std::vector<ufc_receiver> r1 = receivers, r2 = receivers;
-  std::vector<ufc_rx_slot> s1 = slots, s2 = slots;
-  std::vector<ufc_receiver_result> q1(receivers.size()), q2(receivers.size());
-  std::vector<uint8_t> c1(carry_cap), c2(carry_cap), o1(out_cap), o2(out_cap);
-  std::vector<ufc_rx_packet> p1(packets_cap), p2(packets_cap);
-  if (!p1.empty()) {
-    std::memset((void*)p1.data(), 0, p1.size() * sizeof(ufc_rx_packet));
-    std::memset((void*)p2.data(), 0, p2.size() * sizeof(ufc_rx_packet));
-  }
-  g_tiled = false;
+  std::vector<ufc_receiver> r1 = receivers;
+  std::vector<ufc_rx_slot> s1 = slots;
+  std::vector<ufc_receiver_result> q1(receivers.size());
+  std::vector<uint8_t> c1(carry_cap), o1(out_cap);
+  std::vector<ufc_rx_packet> p1(packets_cap);
+  if (!p1.empty()) std::memset((void*)p1.data(), 0, p1.size() * sizeof(ufc_rx_packet));
+  g_form = kWalkSerial;
   const Counts a = run_step(infos, items, payload, frame_first, r1, s1, slot_first, carry, c1, p1, o1, q1);
-  g_tiled = true;
-  const Counts b = run_step(infos, items, payload, frame_first, r2, s2, slot_first, carry, c2, p2, o2, q2);
-  g_tiled = false;
-  if (a.packets != b.packets || a.out != b.out || a.carry != b.carry) fail("tiled: used counts", where, (long)a.out, (long)b.out);
-  if (std::memcmp((void*)r1.data(), (void*)r2.data(), r1.size() * sizeof(ufc_receiver))) fail("tiled: headers", where, 0, 0);
-  if (!s1.empty() && std::memcmp((void*)s1.data(), (void*)s2.data(), s1.size() * sizeof(ufc_rx_slot))) fail("tiled: slots", where, 0, 0);
-  if (std::memcmp((void*)q1.data(), (void*)q2.data(), q1.size() * sizeof(ufc_receiver_result))) fail("tiled: results", where, 0, 0);
-  if (!p1.empty() && std::memcmp((void*)p1.data(), (void*)p2.data(), p1.size() * sizeof(ufc_rx_packet))) fail("tiled: records", where, 0, 0);
-  if (c1 != c2 || o1 != o2) fail("tiled: bytes", where, 0, 0);
-  checks++;
+  for (int form = kForwards; form < kForms; form++) {
+    std::vector<ufc_receiver> r2 = receivers;
+    std::vector<ufc_rx_slot> s2 = slots;
+    std::vector<ufc_receiver_result> q2(receivers.size());
+    std::vector<uint8_t> c2(carry_cap), o2(out_cap);
+    std::vector<ufc_rx_packet> p2(packets_cap);
+    if (!p2.empty()) std::memset((void*)p2.data(), 0, p2.size() * sizeof(ufc_rx_packet));
+    g_form = form;
+    const Counts b = run_step(infos, items, payload, frame_first, r2, s2, slot_first, carry, c2, p2, o2, q2);
+    g_form = kWalkSerial;
+    if (a.packets != b.packets || a.out != b.out || a.carry != b.carry) fail("tiled: used counts", where, form, (long)b.out);
+    if (std::memcmp((void*)r1.data(), (void*)r2.data(), r1.size() * sizeof(ufc_receiver))) fail("tiled: headers", where, form, 0);
+    if (!s1.empty() && std::memcmp((void*)s1.data(), (void*)s2.data(), s1.size() * sizeof(ufc_rx_slot))) fail("tiled: slots", where, form, 0);
+    if (std::memcmp((void*)q1.data(), (void*)q2.data(), q1.size() * sizeof(ufc_receiver_result))) fail("tiled: results", where, form, 0);
+    if (!p1.empty() && std::memcmp((void*)p1.data(), (void*)p2.data(), p1.size() * sizeof(ufc_rx_packet))) fail("tiled: records", where, form, 0);
+    if (c1 != c2 || o1 != o2) fail("tiled: bytes", where, form, 0);
+    checks++;
+  }
+}
+
+// ---- the cross-lane reads of rx_receive_tiles on lane 63 and on lane 0 of the second tile ----
+// One fresh receiver of window W at `base` (the ids wrap inside the window), one-fragment packets at the given
+// leads, one step: every form against the serial walk (both_ways), then the expectation written out here.  The same
+// cases, with the same numbers, are scenarios of tests/test_receive_cpu.py.
+struct Dgm {
+  uint32_t lead, ch, wl, cl, len;
+};
+struct Got {
+  std::vector<uint32_t> leads, lens, offsets;  // the delivered packets, in order
+  ufc_receiver out;
+  ufc_receiver_result res;
+};
+Got directed(int where, uint32_t W, uint32_t base, const std::vector<Dgm>& dgs) {
+  std::vector<ufc_receiver> receivers(1);
+  ufc_receiver h{};
+  h.base_id = h.end_id = base;
+  h.window_size = W;
+  h.deliver = 1;
+  h.resync_id = kNone;
+  h.max_alloc = 1ull << 40;
+  for (auto& c : h.channel_base_id) c = kNone;
+  receivers[0] = h;
+  std::vector<ufc_rx_slot> slots(W);
+  std::memset((void*)slots.data(), 0, slots.size() * sizeof(ufc_rx_slot));
+  const std::vector<uint64_t> slot_first = {0, W}, frame_first = {0, 1};
+  std::vector<ufc_item> items;
+  std::vector<uint8_t> payload(3);
+  for (const Dgm& d : dgs) {
+    ufc_item it{};
+    it.id = (base + d.lead) & kMask;
+    it.channel_id = (uint8_t)d.ch;
+    it.window_parent_lead = (uint16_t)d.wl;
+    it.channel_parent_lead = (uint16_t)d.cl;
+    it.data_len = d.len;
+    it.data_offset = (uint32_t)payload.size();
+    for (uint32_t k = 0; k < d.len; k++) payload.push_back((uint8_t)(d.lead + k));
+    items.push_back(it);
+  }
+  ufc_frame_info f{};
+  f.kind = UFC_FRAME_DATA;
+  f.ok = 1;
+  f.item_count = (uint32_t)items.size();
+  const std::vector<ufc_frame_info> infos(1, f);
+  const std::vector<uint8_t> carry;
+  std::vector<ufc_receiver> rc = receivers;
+  std::vector<ufc_rx_slot> sc = slots;
+  std::vector<ufc_receiver_result> results(1);
+  std::vector<uint8_t> none8;
+  std::vector<ufc_rx_packet> nonep;
+  const Counts need = run_step(infos, items, payload, frame_first, rc, sc, slot_first, carry, none8, nonep, none8, results);
+  both_ways(where, infos, items, payload, frame_first, receivers, slots, slot_first, carry, need.carry, need.packets, need.out);
+  std::vector<uint8_t> carry_out(need.carry), out_bytes(need.out);
+  std::vector<ufc_rx_packet> packets(need.packets);
+  run_step(infos, items, payload, frame_first, receivers, slots, slot_first, carry, carry_out, packets, out_bytes, results);
+  Got g;
+  g.out = receivers[0];
+  g.res = results[0];
+  if (g.res.stop != UFC_RX_DONE || g.res.packet_count != need.packets) fail("directed: stop", where, g.res.stop, 0);
+  for (const ufc_rx_packet& p : packets) {
+    const uint32_t lead = (p.sequence_id - base) & kMask;
+    g.leads.push_back(lead), g.lens.push_back(p.len), g.offsets.push_back((uint32_t)p.out_offset);
+    for (uint32_t k = 0; k < p.len; k++)
+      if (out_bytes[p.out_offset + k] != (uint8_t)(lead + k)) fail("directed: bytes", where, lead, k);
+  }
+  return g;
+}
+
+void directed_cases() {
+  const uint32_t base = 0xFFFFF - 20;  // (the ids wrap at lead 21)
+  const auto want_leads = [](int where, const Got& g, const std::vector<uint32_t>& want) {
+    if (g.leads != want) fail("directed: delivered", where, (long)g.leads.size(), g.leads.empty() ? -1 : (long)g.leads.back());
+  };
+  for (int seam = 0; seam < 2; seam++) {
+    // the event's lead: 63, the last lane of a full tile (window 64), or 64, lane 0 of the second tile (window 128);
+    // the lane before it in its channel or among the entries is lead 60
+    const uint32_t W = seam ? 128 : 64, ev = seam ? 64 : 63, gap = ev - 60;
+    {  // DATA: delivered only against the base lead 60 leaves (61: ev - 61 < gap); against the carried base, none
+       // (measured from the window's base: ev >= gap), it would fail.  (Its window parent, the id before it, never
+       // came: the window stops in front of it.)
+      const Got g = directed(10 + seam, W, base, {{60, 4, 0, 0, 5}, {ev, 4, 1, gap, 6}});
+      want_leads(10 + seam, g, {60, ev});
+      if (g.out.channel_packet_count[4] != 0 || g.out.channel_ready_flags != 0 || g.out.base_id != ((base + 61) & kMask))
+        fail("directed: channel base from the lane before", seam, g.out.channel_packet_count[4], (long)g.out.base_id);
+    }
+    {  // ENTRY: the advance passes only against the new base lead 60 leaves
+      const Got g = directed(20 + seam, W, base, {{60, 4, 0, 0, 5}, {ev, 5, gap, 0, 6}});
+      want_leads(20 + seam, g, {60, ev});
+      if (g.out.base_id != ((base + ev + 1) & kMask) || g.res.advanced != ev + 1 || g.out.alloc != 0)
+        fail("directed: entry prefix from the lane before", seam, (long)g.out.base_id, g.res.advanced);
+    }
+    {  // the event's lane is the only failing lane of its channel (its parent, two before it, never came): not
+       // delivered, the ready flag cleared, one packet left; the window stops in front of it too
+      const Got g = directed(30 + seam, W, base, {{10, 4, 0, 0, 5}, {20, 4, 0, 0, 7}, {ev, 4, 2, 2, 6}, {5, 9, 0, 0, 1}});
+      want_leads(30 + seam, g, {5, 10, 20});
+      if (g.out.channel_packet_count[4] != 1 || g.out.channel_ready_flags != 0 || g.out.base_id != ((base + 21) & kMask) ||
+          g.out.channel_base_id[4] != kNone)
+        fail("directed: the only failing lane", seam, g.out.channel_packet_count[4], (long)g.out.channel_ready_flags);
+    }
+  }
+  {  // 128 ids delivered, lengths 1 but 200 at lead 63 and 77 at lead 64: tile 2's offsets carry lane 63's length
+    std::vector<Dgm> d;
+    for (uint32_t k = 0; k < 128; k++) d.push_back(Dgm{k, 4, k ? 1u : 0u, k ? 1u : 0u, k == 63 ? 200u : k == 64 ? 77u : 1u});
+    const Got g = directed(40, 128, base, d);
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < 128; k++) {
+      if (g.leads.size() != 128 || g.leads[k] != k || g.offsets[k] != at || g.lens[k] != d[k].len) fail("directed: offsets", k, at, 0);
+      at += d[k].len;
+    }
+    if (at != 126 + 277 || g.out.base_id != ((base + 128) & kMask)) fail("directed: 128 delivered", at, 0, 0);
+  }
 }
 
 }  // namespace
 
 int main() {
+  std::memset((void*)&carried_block, 0xCD, sizeof carried_block);
+  directed_cases();
   const uint32_t W = 16, R = 5;
   static const uint32_t sizes[] = {0, 1, 77, kFrag - 1, kFrag, kFrag + 1, 3000, 64 * kFrag, 65 * kFrag - 3};
   std::vector<Peer> peers(R);

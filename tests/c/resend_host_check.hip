@@ -8,8 +8,14 @@
 //     bytes);
 //   - chained ticks of one connection, begin -> a scalar emit -> place -> a scalar pack -> commit, with random acks
 //     of sent refs, packet window acks (some beyond the span, some of next_id while fragments are pending), random
-//     flush allocations, a small frame window, rings that wrap, ids through 2^20: run twice, the lanes of every phase
-//     forwards (SerialWave) and backwards (ReverseWave), and every state, result, arena byte and output compared.
+//     flush allocations, a small frame window, rings that wrap, ids through 2^20: run four times, the lanes of every
+//     phase forwards (SerialWave), backwards (ReverseWave) and in a fresh seeded permutation per phase (ShuffledWave,
+//     tests/c/lane_orders.hpp) on a shared block of fresh garbage, and forwards on one block carried from call to call
+//     as the kernels' grid-stride loops and the host entries carry it; every state, result, arena byte and output
+//     compared;
+//   - directed ticks that put the wave form's cross-lane reads on lane 63 and on lane 0 of the next tile (DESIGN.md
+//     5.15; tests/test_resend_cpu.py has the same cases on the model): the ack frames' ballot, the freed ids' window
+//     and channel parents, the stopping packet of commit; in the same four forms, the expectation written out.
 // Prints "ok: <checks>" and exits 0; any difference or sanitizer report stops the program.
 #include <algorithm>
 #include <cstdint>
@@ -19,6 +25,7 @@
 #include <vector>
 
 #include "../../uflow_amd/csrc/frame_codec_core.hpp"
+#include "lane_orders.hpp"
 
 namespace {
 
@@ -138,7 +145,7 @@ struct World {
     for (auto& c : sd.channel_parent_id) c = UFC_NO_PARENT;
     st.heap_cap = heap_cap;
     st.pkt_cap = window;
-    st.frag_cap = 32;  // >= ceil(20000 / 1448) + window = 14 + window
+    st.frag_cap = window <= 16 ? 32 : 256;  // >= ceil(20000 / 1448) + window = 14 + window
     st.tx_cap = 512;   // >= (2 + 1 + 1) * 127
     st.stage_cap = stage_cap;
     q.window_size = 2;
@@ -163,37 +170,24 @@ struct Tick {
   uint64_t now, rtt;
 };
 
-// The lanes of a phase in the opposite order to SerialWave's, which must not matter.
-struct ReverseWave {
-  template <class F>
-  void lanes(const F& f) const {
-    for (uint32_t l = 64; l-- > 0;) f(l);
-  }
-  template <class F>
-  void one(const F& f) const {
-    f();
-  }
-  template <class F>
-  unsigned long long ballot(const F& f) const {
-    unsigned long long m = 0;
-    for (uint32_t l = 64; l-- > 0;)
-      if (f(l)) m |= 1ull << l;
-    return m;
-  }
-  template <class F>
-  uint64_t sum(const F& f) const {
-    uint64_t s = 0;
-    for (uint32_t l = 64; l-- > 0;) s += f(l);
-    return s;
-  }
-  void sync() const {}
+using lane_orders::ReverseWave;
+using lane_orders::ShuffledWave;
+
+RsWaveShared carried_block;  // (garbage once, in main)
+
+// What a tick's calls said, for the directed cases.
+struct Said {
+  ufc_resend_result begin;
+  ufc_resend_commit_result commit;
+  uint32_t frames;
 };
 
 template <class Wv>
-void run_tick(World& w, const Tick& t, std::vector<uint8_t>& trace) {
+Said run_tick(World& w, const Tick& t, std::vector<uint8_t>& trace, bool carried = false) {
   const auto put = [&](const void* p, size_t n) { trace.insert(trace.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
-  RsWaveShared sh;
-  std::memset(&sh, 0xA5, sizeof sh);
+  RsWaveShared fresh;
+  std::memset(&fresh, 0xA5, sizeof fresh);
+  RsWaveShared& sh = carried ? carried_block : fresh;
   for (uint32_t r : t.ack_refs) w.ref_acked[r] = 1;
   // the frame queue's part that begin reads: the log's base frame
   w.q.log_base_id = 0;
@@ -319,14 +313,37 @@ void run_tick(World& w, const Tick& t, std::vector<uint8_t>& trace) {
   put(w.ref_acked.data(), w.ref_acked.size());
   put(w.tx.data(), w.tx.size() * sizeof(ufc_tx_ref));
   put(&w.extra, sizeof w.extra);
+  return Said{br, cr, (uint32_t)infos.size()};
 }
+
+// One tick in the four forms, on four worlds in the same state; every form's trace must be the first's.
+struct Worlds {
+  World a, b, c, d;
+  Worlds(uint32_t window, uint32_t base, uint32_t heap_cap, uint32_t stage_cap)
+      : a(window, base, heap_cap, stage_cap), b(window, base, heap_cap, stage_cap), c(window, base, heap_cap, stage_cap),
+        d(window, base, heap_cap, stage_cap) {}
+  Said tick(const Tick& t, long where, long when, std::vector<uint8_t>& ta) {
+    std::vector<uint8_t> tb, tc, td;
+    ta.clear();
+    const Said said = run_tick<SerialWave>(a, t, ta);
+    run_tick<ReverseWave>(b, t, tb);
+    run_tick<ShuffledWave>(c, t, tc);
+    run_tick<SerialWave>(d, t, td, true);
+    if (ta != tb) fail("lane order changes the result: backwards", where, when, (long)ta.size());
+    if (ta != tc) fail("lane order changes the result: shuffled", where, when, (long)ta.size());
+    if (ta != td) fail("a carried shared block changes the result", where, when, (long)ta.size());
+    checks += 3;
+    return said;
+  }
+};
 
 void check_ticks() {
   long stops[8] = {0}, commit_stops[8] = {0};
   for (uint32_t conn = 0; conn < 12; conn++) {
     const uint32_t window = conn % 2 ? 8 : 4, base = conn % 3 ? 0xFFFF8u + conn : conn * 1000;
     const uint32_t heap_cap = conn % 4 == 3 ? 5 : 24, stage_cap = conn % 4 == 2 ? 4 : 40;  // (small ones fill)
-    World a(window, base, heap_cap, stage_cap), b(window, base, heap_cap, stage_cap);
+    Worlds ws(window, base, heap_cap, stage_cap);
+    World& a = ws.a;
     uint64_t now = 1000;
     for (uint32_t tick = 0; tick < 120; tick++) {
       Tick t;
@@ -359,10 +376,8 @@ void check_ticks() {
                         : packet_id_add(a.sd.base_id, span ? rnd() % (span + 1) / 2 : 0);
         t.acks.push_back(f);
       }
-      std::vector<uint8_t> ta, tb;
-      run_tick<SerialWave>(a, t, ta);
-      run_tick<ReverseWave>(b, t, tb);
-      if (ta != tb) fail("lane order changes the result", conn, tick, (long)ta.size());
+      std::vector<uint8_t> ta;
+      ws.tick(t, conn, tick, ta);
       ufc_resend_result br;
       std::memcpy(&br, ta.data(), sizeof br);
       ufc_resend_commit_result cr;
@@ -378,12 +393,102 @@ void check_ticks() {
   if (commit_stops[UFC_RS_HEAP_FULL] == 0) fail("the traffic never filled the heap", 0, 0, 0);
 }
 
+// ---- the wave form's cross-lane reads on lane 63 and on lane 0 of the next tile ----
+Tick quiet_tick(uint64_t now, uint32_t room) {
+  Tick t;
+  t.alloc = (int64_t)1 << 30;
+  t.room = room;
+  t.flags = 0;
+  t.now = now;
+  t.rtt = 30;
+  return t;
+}
+ufc_packet a_packet(uint32_t len, uint32_t channel, uint32_t mode) {
+  ufc_packet p{};
+  p.data_offset = 7 * len;
+  p.data_len = len;
+  p.channel_id = (uint8_t)channel;
+  p.mode = (uint8_t)mode;
+  return p;
+}
+ufc_frame_info an_ack(uint32_t packet_window_base) {
+  ufc_frame_info f{};
+  f.kind = UFC_FRAME_ACK;
+  f.ok = 1;
+  f.f[1] = packet_window_base;
+  return f;
+}
+
+void check_directed() {
+  const uint32_t base = 0xFFFF0;  // (the ids pass 2^20 inside every case)
+  const auto id = [&](uint32_t k) { return packet_id_add(base, k); };
+  std::vector<uint8_t> trace;
+  // begin, the freed ids' parents: the window's parent and channel 63's are the id at lane 63 of a tile of freed ids
+  // (64 freed), then at lane 0 of the next (65 freed); that id's packet is the only long one (the sums' lane too)
+  for (uint32_t at : {63u, 64u}) {
+    Worlds ws(128, base, 256, 300);
+    Tick t = quiet_tick(1000, 3);
+    uint64_t bytes = 0;
+    for (uint32_t k = 0; k < 70; k++) {
+      t.packets.push_back(k == at ? a_packet(1000, 63, UFC_SEND_RELIABLE) : a_packet(1 + k % 5, k % 3, UFC_SEND_UNRELIABLE));
+      if (k <= at) bytes += t.packets.back().data_len;
+    }
+    Said said = ws.tick(t, 100 + at, 0, trace);
+    if (said.commit.take != 70 || ws.a.sd.window_parent_id != id(at) || ws.a.sd.channel_parent_id[63] != id(at))
+      fail("directed: the parents' packet", at, said.commit.take, ws.a.sd.window_parent_id);
+    t = quiet_tick(1020, 3);
+    t.acks.push_back(an_ack(id(at + 1)));
+    said = ws.tick(t, 100 + at, 1, trace);
+    if (said.begin.packets_freed != at + 1 || said.begin.bytes_freed != bytes || ws.a.sd.base_id != id(at + 1) ||
+        ws.a.sd.window_parent_id != UFC_NO_PARENT || ws.a.sd.channel_parent_id[63] != UFC_NO_PARENT)
+      fail("directed: parents freed", at, said.begin.packets_freed, ws.a.sd.window_parent_id);
+  }
+  {  // begin, the ack frames' ballot: the ack that frees sits at frame 63; the one behind it is stale only if it ran.
+     // Then at frame 64 (lane 0 of the second tile), and a last one at 129 (lane 1 of the third).
+    Worlds ws(128, base, 256, 300);
+    Tick t = quiet_tick(1000, 3);
+    for (uint32_t k = 0; k < 20; k++) t.packets.push_back(a_packet(2 + k, k % 3, UFC_SEND_UNRELIABLE));
+    ws.tick(t, 200, 0, trace);
+    t = quiet_tick(1020, 3);
+    for (uint32_t i = 0; i < 70; i++) t.acks.push_back(an_ack(i == 63 ? id(5) : i == 64 ? id(3) : base));
+    t.acks[10].kind = UFC_FRAME_DATA;  // (not an ack: whatever it names)
+    t.acks[10].f[1] = id(9);
+    Said said = ws.tick(t, 200, 1, trace);
+    if (said.begin.packets_freed != 5 || said.begin.acks_ignored != 6 || ws.a.sd.base_id != id(5))
+      fail("directed: the ack at frame 63", said.begin.packets_freed, said.begin.acks_ignored, ws.a.sd.base_id);
+    t = quiet_tick(1040, 3);
+    for (uint32_t i = 0; i < 130; i++) t.acks.push_back(an_ack(i == 64 ? id(9) : i == 65 ? id(7) : i == 129 ? id(11) : i < 64 ? id(5) : base));
+    said = ws.tick(t, 200, 2, trace);
+    if (said.begin.packets_freed != 6 || said.begin.acks_ignored != 64 || ws.a.sd.base_id != id(11))
+      fail("directed: the acks at frames 64 and 129", said.begin.packets_freed, said.begin.acks_ignored, ws.a.sd.base_id);
+  }
+  // commit, the stopping packet: one frame's room; the packets in front of `at` fit it, packet `at` does not, and is
+  // the first whose items lie past the packed ones: lane 63 of the first tile of packets, then lane 0 of the second
+  for (uint32_t at : {63u, 64u}) {
+    Worlds ws(128, base, 256, 300);
+    Tick t = quiet_tick(1000, 1);
+    for (uint32_t k = 0; k < 70; k++) t.packets.push_back(a_packet(k == at ? 1400 : 1, k % 3, UFC_SEND_PERSISTENT));
+    Said said = ws.tick(t, 300 + at, 0, trace);
+    const ufc_resend_commit_result& cr = said.commit;
+    if (said.frames != 1 || cr.take != at + 1 || cr.packets_entered != at + 1 || cr.pending_count != 1 || cr.heap_pushed != at ||
+        ws.a.st.pending_seq != id(at) || ws.a.st.window_bytes != at + 1400 || ws.a.sd.next_id != id(at + 1))
+      fail("directed: the stopping packet", at, cr.take, cr.packets_entered);
+    t.packets.erase(t.packets.begin(), t.packets.begin() + cr.take);
+    t.now = 1010, t.room = 3;
+    said = ws.tick(t, 300 + at, 1, trace);
+    if (said.commit.pending_packed != 1 || said.commit.take != 69 - at || said.commit.pending_count != 0 || ws.a.st.heap_len != 70)
+      fail("directed: behind the stopping packet", at, said.commit.take, ws.a.st.heap_len);
+  }
+}
+
 }  // namespace
 
 int main() {
+  std::memset(&carried_block, 0xA5, sizeof carried_block);
   check_heap();
   check_pack_rule();
   check_ticks();
+  check_directed();
   std::printf("ok: %ld checks\n", checks);
   return 0;
 }

@@ -103,6 +103,13 @@ def test_frames_of_0_and_161_groups(engine, monkeypatch):
     assert got["ref_acked"][:161].all() and not got["ref_acked"][161:].any()
 
 
+@pytest.mark.parametrize("scenario", T.LANE_SCENARIOS, ids=lambda f: f.__name__[9:])
+def test_lane_scenarios(engine, monkeypatch, scenario):
+    """The step's ballots with their deciding lane on lane 0, on lane 63 and across a tile seam."""
+    monkeypatch.setattr(T, "host", gpu_call(engine))
+    scenario()
+
+
 @pytest.mark.parametrize("rule", ["ring outside the arena", "held frames out of order", "ack frame's items outside",
                                   "reset with no interval", "log starts more than tail behind the window"])
 def test_state_check(engine, monkeypatch, rule):

@@ -329,6 +329,13 @@ def test_acknowledge_frees_0_1_64_65_packets(engine):
     acknowledge_pipeline(GpuBackend(engine))
 
 
+@pytest.mark.parametrize("pipeline", T.LANE_PIPELINES)
+def test_lane_63_and_tile_seam(engine, pipeline):
+    """The wave form's cross-lane reads on lane 63 and on lane 0 of the next tile: the freed ids' window and channel
+    parents, the ack frames' ballot, the stopping packet of commit (one connection each: the wave form)."""
+    pipeline(GpuBackend(engine))
+
+
 def test_two_streams(engine):
     s1, s2 = torch.cuda.Stream(DEV), torch.cuda.Stream(DEV)
     try:

@@ -527,9 +527,133 @@ def test_random_states_never_panic():
     assert nacks > 200 and acked > 200, (nacks, acked)
 
 
+# ---- the step's ballots with their deciding lane on lane 0, on lane 63 and across a tile seam.  The
+# same cases, with the same numbers, run in tests/c/queue_host_check.hip under three lane orders.  One connection,
+# window 256 / tail 256 at ids through 2^32; a first call pushes 200 frames, the second is the case.  Every case
+# asserts on the model's side that its event sits where it was meant to. ----
+LANE_BASE = 0xFFFFFFC0
+
+
+def pushed(times):
+    q, log = fr.new_frame_queues(1, 256, 256, LANE_BASE)
+    refs = np.zeros(len(times), dtype=np.uint8)
+    got, want = run(one_call(q[0], [E.sent_frame(100 + k, t, k & 1, k, 1) for k, t in enumerate(times)]), q, log, refs)
+    assert int(want["results"][0]["pushes_taken"]) == len(times)
+    return got["queues_out"][:1].copy(), got["log"], got["ref_acked"]
+
+
+def ack_frames_at_63_64_129(bad_at=None):
+    """130 frames of which the ok ack frames sit at 63, 64 and 129, three ids each; the others are not acks or not
+    ok, with item ranges that must never be looked at.  bad_at: that ack frame's item range runs past the items."""
+    q, log, refs = pushed([10 * k for k in range(200)])
+    infos = np.zeros(130, dtype=fr.FRAME_INFO_DTYPE)
+    items = []
+    for i in range(130):
+        if i in (63, 64, 129):
+            g = (63, 64, 129).index(i)
+            infos[i] = E.ack_info(LANE_BASE + 9 if i == 129 else LANE_BASE, g, 4 - g if i == bad_at else 1)
+            items.append(E.group_item(LANE_BASE + 3 * g, 7, 0 if g == 1 else 1))   # (nonces k & 1: 0 1 0 | 1 0 1 | 0 1 0)
+        else:
+            infos[i]["kind"], infos[i]["ok"] = (fr.DATA, 1) if i % 2 else (fr.ACK, 0)
+            infos[i]["item_first"], infos[i]["item_count"] = 0xFFFFFFF0, 100
+    call = one_call(q[0])
+    call["infos"], call["items"] = infos, np.array(items, dtype=fr.ITEM_DTYPE)
+    call["frame_first"] = np.array([0, 130], dtype=np.uint64)
+    assert np.flatnonzero((infos["kind"] == fr.ACK) & (infos["ok"] != 0)).tolist() == [63, 64, 129]
+    got, want = run(call, q, log, refs)
+    r = want["results"][0]
+    if bad_at is not None:
+        assert int(r["stop"]) == fr.FQ_BAD_STATE and not want["ref_acked"].any()
+        return
+    assert (int(r["stop"]), int(r["ack_frames"]), int(r["groups"]), int(r["frames_acked"]), int(r["li_acks"]),
+            int(r["window_advanced"])) == (fr.FQ_DONE, 3, 3, 9, 9, 9)
+    assert want["ref_acked"].tolist() == [1] * 9 + [0] * 191
+
+
+def scenario_ack_frames_at_63_64_129():
+    ack_frames_at_63_64_129()
+
+
+def scenario_bad_item_range_at_63():
+    ack_frames_at_63_64_129(63)
+
+
+def scenario_bad_item_range_at_64_and_129():
+    ack_frames_at_63_64_129(64)
+    ack_frames_at_63_64_129(129)
+
+
+def nack_run_times(lead):
+    times = [500 + k for k in range(lead)]
+    for k in range(140):
+        wobble = (k * 7) % 50
+        times.append(1000 if k == 0 else 1049 - wobble if k < 63 else 1050 if k == 63 else 1100 if k == 64 else
+                     1149 - wobble if k < 128 else 1150 if k == 128 else 1199 - wobble)
+    return times + [3000] * (200 - len(times))
+
+
+def nack_run(lead):
+    """A nack run of 140 ids over a log whose send times go up and down: a forget whose first kept entry is lead +
+    140, the first `lead` ids acknowledged in the same call so that the run starts there.  rtt 50: the run's entry 0
+    opens an interval (none is open), entries 1..62 fall under it, entry 63 (number 63 of the first nack tile) is
+    the first at or after its end and opens the next, entry 64 (number 0 of the next tile) the next, entry 128 the
+    last."""
+    times = nack_run_times(lead)
+    run_times = times[lead:lead + 140]
+    assert any(a > b for a, b in zip(run_times, run_times[1:])) and any(a < b for a, b in zip(run_times, run_times[1:]))
+    q, log, refs = pushed(times)
+    call = one_call(q[0], acks=[(None, [[LANE_BASE + k, 1, k & 1] for k in range(lead)])], flags=fr.FQ_FORGET, rtt_ms=50,
+                    thresh_ms=2000)
+    # on the model's side: which entries of the run open an interval
+    li = E.LossIntervalQueue()
+    openers = []
+    for k, t in enumerate(run_times):
+        before = len(li.entries)
+        li.push_nack(t, 50)
+        if len(li.entries) != before:
+            openers.append(k)
+    assert openers == [0, 63, 64, 128]
+    got, want = run(call, q, log, refs)
+    r, out = want["results"][0], want["queues_out"][0]
+    assert (int(r["li_nacks"]), int(r["li_acks"]), int(r["log_culled"]), int(out["li_count"])) == (140, lead, lead + 140, 4)
+    assert out["li_length"][:4].tolist() == [12, 64, 1, 63] and out["li_end_time_ms"][:4].tolist() == [1200, 1150, 1100, 1050]
+
+
+def scenario_nack_run_opens_at_63_and_at_0_of_the_next_tile():
+    nack_run(0)
+
+
+def scenario_nack_run_behind_five_acked_ids():
+    nack_run(5)
+
+
+def forget_kept_at(kept):
+    q, log, refs = pushed([10 * k for k in range(200)])
+    assert E.load_queue(q[0], log).frame_log.find_expiration_cutoff(10 * kept) == (LANE_BASE + kept) & M32
+    _, want = run(one_call(q[0], flags=fr.FQ_FORGET, thresh_ms=10 * kept), q, log, refs)
+    r = want["results"][0]
+    assert (int(r["log_culled"]), int(r["li_nacks"]), int(want["queues_out"][0]["log_base_id"])) == (kept, kept, (LANE_BASE + kept) & M32)
+
+
+def scenario_forget_first_kept_at_63_then_64():
+    """The expiry cutoff at the last lane of the first tile of 64 entries, at the first of the next, and at 128."""
+    for kept in (63, 64, 128):
+        forget_kept_at(kept)
+
+
+LANE_SCENARIOS = [scenario_ack_frames_at_63_64_129, scenario_bad_item_range_at_63, scenario_bad_item_range_at_64_and_129,
+                  scenario_nack_run_opens_at_63_and_at_0_of_the_next_tile, scenario_nack_run_behind_five_acked_ids,
+                  scenario_forget_first_kept_at_63_then_64]
+
+
+@pytest.mark.parametrize("scenario", LANE_SCENARIOS, ids=lambda f: f.__name__[9:])
+def test_lane_scenarios(scenario):
+    scenario()
+
+
 def test_queue_core_under_sanitizers():
     """tests/c/queue_host_check.hip: the wave-policy core of the frame queue (fq_step, the lanes of a phase run one
-    after the other) as host code under AddressSanitizer and UBSan, against a scalar loop that follows the
+    after the other: forwards, backwards, shuffled, and on a carried shared block) as host code under AddressSanitizer and UBSan, against a scalar loop that follows the
     reference entry by entry, on generated traffic and random states over exact-size buffers; a stand-alone program
     (nothing is loaded into Python under a sanitizer)."""
     import subprocess

@@ -539,7 +539,74 @@ def test_window_not_ready_with_deliveries_in_tile_2():
     assert int(o["results"][0]["advanced"]) == 0 and "first_delivery_in_later_tile" in rx.tags
 
 
-TILE_SCENARIOS = [test_stall_in_tile_0_holds_the_later_tiles, test_window_not_ready_with_deliveries_in_tile_2]
+# The cross-lane reads of the tiled receive on lane 63 (a full tile: window 64) and on lane 0 of the second tile
+# (window 128); the same cases, with the same numbers, run in tests/c/receive_host_check.hip under
+# three lane orders.  The event's lead is 63 or 64; the lane before it, in its channel or among the entries, is lead
+# 60.  Every case asserts on the model's side that the event decides what it was meant to decide.
+LANE_BASE = 0xFFFFF - 20    # (the ids wrap at lead 21)
+LANE_EVENTS = [(64, 63), (128, 64)]
+
+
+def lane_step(window, dgs, what):
+    rx = E.PacketReceiver(window, LANE_BASE, 1 << 30)
+    h = E.Harness([rx], host)
+    o, exp = h.step(E.simple_batch([[(E.add(LANE_BASE, k), ch, wl, cl, 0, 0, iota(k, n)) for k, ch, wl, cl, n in dgs]],
+                                   per_frame=64), what=what)
+    return rx, o, [E.sub(d[0], LANE_BASE) for d in exp["delivered"][0]]
+
+
+@pytest.mark.parametrize("window,ev", LANE_EVENTS)
+def test_channel_base_from_the_lane_before(window, ev):
+    """The event's packet names lead 60 as its channel parent: it clears only against the channel base that lead 60
+    leaves (61); measured from the carried base (none: the window's) it would fail.  Its window parent, the id before
+    it, never came: the window stops in front of it."""
+    gap = ev - 60
+    rx, o, leads = lane_step(window, [(60, 4, 0, 0, 5), (ev, 4, 1, gap, 6)], "channel base")
+    assert leads == [60, ev] and not gap > ev and gap > ev - 61   # (lead_clears: lead == 0 or lead > distance)
+    out = o["receivers_out"][0]
+    assert (int(out["channel_packet_count"][4]), int(out["channel_ready_flags"]), int(out["base_id"])) == (0, 0, E.add(LANE_BASE, 61))
+
+
+@pytest.mark.parametrize("window,ev", LANE_EVENTS)
+def test_entry_prefix_from_the_lane_before(window, ev):
+    """The same for the window advance: the event's entry names lead 60 as its window parent and passes only
+    against the new base that lead 60 leaves."""
+    gap = ev - 60
+    rx, o, leads = lane_step(window, [(60, 4, 0, 0, 5), (ev, 5, gap, 0, 6)], "entry prefix")
+    assert leads == [60, ev] and not gap > ev and gap > ev - 61 and "window_stalled" not in rx.tags
+    out = o["receivers_out"][0]
+    assert (int(out["base_id"]), int(o["results"][0]["advanced"]), int(out["alloc"])) == (E.add(LANE_BASE, ev + 1), ev + 1, 0)
+
+
+@pytest.mark.parametrize("window,ev", LANE_EVENTS)
+def test_only_failing_lane_of_its_channel(window, ev):
+    """The event's lane is the only failing lane of its channel (its parent, two before it, never came): not
+    delivered, the ready flag cleared, one packet left; the window stops in front of it too."""
+    rx, o, leads = lane_step(window, [(10, 4, 0, 0, 5), (20, 4, 0, 0, 7), (ev, 4, 2, 2, 6), (5, 9, 0, 0, 1)], "failing lane")
+    assert leads == [5, 10, 20] and "channel_stalled" in rx.tags and "window_stalled" in rx.tags
+    out = o["receivers_out"][0]
+    assert (int(out["channel_packet_count"][4]), int(out["channel_ready_flags"]), int(out["base_id"])) == (1, 0, E.add(LANE_BASE, 21))
+    assert int(out["channel_base_id"][4]) == E.NONE
+
+
+def test_lengths_at_lane_63_and_at_lane_0_of_tile_2():
+    """128 ids delivered, lengths 1 but 200 at lead 63 and 77 at lead 64: tile 2's offsets and the used bytes carry
+    lane 63's length."""
+    size = lambda k: 200 if k == 63 else 77 if k == 64 else 1  # noqa: E731
+    rx, o, leads = lane_step(128, [(k, 4, int(k > 0), int(k > 0), size(k)) for k in range(128)], "lengths")
+    assert leads == list(range(128)) and o["out_used"] == 126 + 277
+    recs = o["packets"][:128]
+    assert recs["len"].tolist() == [size(k) for k in range(128)]
+    assert recs["out_offset"].tolist() == [sum(size(j) for j in range(k)) for k in range(128)]
+    assert rx.base_id == E.add(LANE_BASE, 128)
+
+
+TILE_SCENARIOS = [test_stall_in_tile_0_holds_the_later_tiles, test_window_not_ready_with_deliveries_in_tile_2,
+                  test_lengths_at_lane_63_and_at_lane_0_of_tile_2]
+for _w, _ev in LANE_EVENTS:
+    TILE_SCENARIOS += [pytest.param(lambda f=f, w=_w, ev=_ev: f(w, ev), id=f"{f.__name__[5:]}_{_ev}")
+                       for f in (test_channel_base_from_the_lane_before, test_entry_prefix_from_the_lane_before,
+                                 test_only_failing_lane_of_its_channel)]
 TILE_SCENARIOS += [pytest.param(lambda b=b: test_tile_edge_counts(b), id=f"tile_edge_counts_{b}") for b in (5, 0xFFFFF - 70, 236)]
 TILE_SCENARIOS += [pytest.param(lambda v=v: test_channel_count_across_the_tile_edge(v), id=f"channel_count_{v}")
                    for v in ("all", "part", "count_runs_out")]

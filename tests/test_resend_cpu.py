@@ -134,6 +134,90 @@ def test_padding_changes_nothing():
     assert plain.states.tobytes() == padded.states[:6].tobytes()   # (the first regions lie where they lay)
 
 
+# ---- the wave form's cross-lane reads on lane 63 and on lane 0 of the next tile.  The same cases,
+# with the same numbers, run in tests/c/resend_host_check.hip under three lane orders; tests/test_gpu_resend.py runs
+# these pipelines on the device.  Every case asserts on the model's side that its event sits where it was meant to. ----
+LANE_BASE = 0xFFFF0   # (the ids pass 2^20 inside every case)
+
+
+def lane_id(k):
+    return (LANE_BASE + k) & E.ID_MASK
+
+
+def lane_pipeline(backend, frame_window=64, frame_tail=16):
+    return R.Pipeline([R.Config(window_size=128, max_alloc=1 << 20, frame_window=frame_window, frame_tail=frame_tail, heap_cap=256,
+                                base_id=LANE_BASE)], backend)
+
+
+def parents_pipeline(backend, at):
+    """begin, the freed ids' parents: the window's parent and channel 63's are the id at lane 63 of a tile of freed ids
+    (at = 63: 64 freed), or at lane 0 of the next (at = 64: 65 freed); that id's packet is the only long one, so the
+    sums over the freed ids have their weight on the same lane."""
+    p = lane_pipeline(backend)
+    for k in range(70):
+        if k == at:
+            p.enqueue(0, 1000, 63, E.RELIABLE)
+        else:
+            p.enqueue(0, 1 + k % 5, k % 3, E.UNRELIABLE)
+    p.tick(0, 1000, 1 << 30, [[]])
+    m = p.models[0]
+    assert m.tx.window_parent_id == lane_id(at) and m.tx.channel_parent_id[63] == lane_id(at) and m.tx.next_id == lane_id(70)
+    p.tick(10, 1000, 1 << 30, [[(int(p.queues[0]["window_base_id"]), lane_id(at + 1), [])]])
+    assert m.tx.window_parent_id is None and m.tx.channel_parent_id[63] is None
+    assert (m.freed, m.tx.base_id, m.bytes_freed) == (at + 1, lane_id(at + 1), 1000 + sum(1 + k % 5 for k in range(at)))
+    assert int(p.last["begin"][0]["packets_freed"]) == at + 1
+    return p
+
+
+def ack_frames_pipeline(backend):
+    """begin, the ack frames' ballot: the ack that frees sits at frame 63, and the one behind it is stale only if it
+    ran; then at frame 64 (lane 0 of the second tile), with a last one at 129 (lane 1 of the third)."""
+    p = lane_pipeline(backend)
+    for k in range(20):
+        p.enqueue(0, 2 + k, k % 3, E.UNRELIABLE)
+    p.tick(0, 1000, 1 << 30, [[]])
+    m, fw = p.models[0], int(p.queues[0]["window_base_id"])
+    p.tick(10, 1000, 1 << 30, [[(fw, lane_id(5) if i == 63 else lane_id(3) if i == 64 else LANE_BASE, []) for i in range(70)]])
+    assert (m.freed, m.ignored, m.tx.base_id) == (5, 6, lane_id(5))
+    assert (int(p.last["begin"][0]["packets_freed"]), int(p.last["begin"][0]["acks_ignored"])) == (5, 6)
+    acks = [(fw, lane_id(9) if i == 64 else lane_id(7) if i == 65 else lane_id(11) if i == 129 else lane_id(5) if i < 64 else LANE_BASE, [])
+            for i in range(130)]
+    p.tick(20, 1000, 1 << 30, [acks])
+    assert (m.freed, m.ignored, m.tx.base_id) == (6, 64, lane_id(11))
+    assert (int(p.last["begin"][0]["packets_freed"]), int(p.last["begin"][0]["acks_ignored"])) == (6, 64)
+    return p
+
+
+def stop_packet_pipeline(backend, at):
+    """commit, the stopping packet: a frame window of one frame; the packets in front of `at` fit it, packet `at` (1400
+    bytes) does not and is the first whose items lie past the packed ones: lane 63 of the first tile of packets
+    (at = 63), or lane 0 of the second (at = 64).  The frame is then acknowledged and the rest goes on."""
+    p = lane_pipeline(backend, frame_window=1, frame_tail=0)
+    for k in range(70):
+        p.enqueue(0, 1400 if k == at else 1, k % 3, E.PERSISTENT)
+    sent = p.tick(0, 1000, 1 << 30, [[]])[0]
+    m = p.models[0]
+    assert len(sent) == 1 and [seq for seq, _ in sent[0][1]] == [lane_id(k) for k in range(at)]
+    assert len(m.pending) == 1 and m.pending[0][0].seq == lane_id(at) and m.tx.next_id == lane_id(at + 1)
+    cm = p.last["commit"][0]
+    assert (int(cm["take"]), int(cm["packets_entered"]), int(cm["pending_count"]), int(cm["heap_pushed"])) == (at + 1, at + 1, 1, at)
+    assert int(p.states[0]["window_bytes"]) == at + 1400 == m.window_bytes
+    fid = sent[0][0]
+    sent = p.tick(10, 1000, 1 << 30, [[(fid + 1, LANE_BASE, [(fid, 1, 0)])]])[0]
+    assert len(sent) == 1 and sent[0][1][0] == (lane_id(at), 0) and int(p.last["commit"][0]["pending_packed"]) == 1
+    return p
+
+
+LANE_PIPELINES = [pytest.param(lambda be, f=f, at=at: f(be, at), id=f"{f.__name__[:-9]}_{at}")
+                  for f in (parents_pipeline, stop_packet_pipeline) for at in (63, 64)]
+LANE_PIPELINES.append(pytest.param(ack_frames_pipeline, id="ack_frames_63_64_129"))
+
+
+@pytest.mark.parametrize("pipeline", LANE_PIPELINES)
+def test_lane_63_and_tile_seam(pipeline):
+    pipeline(R.HostBackend())
+
+
 def one_connection(**kw):
     p = R.Pipeline([R.Config(**kw)])
     for _ in range(3):
@@ -309,7 +393,7 @@ def test_place_and_commit_argument_rules():
 
 def test_core_under_sanitizers():
     """tests/c/resend_host_check.hip: the wave-policy core (rs_begin, rs_place, rs_commit) as host code under
-    AddressSanitizer and UBSan, the lanes of a phase forwards and backwards, over exact-size buffers, with the heap
+    AddressSanitizer and UBSan, the lanes of a phase forwards, backwards and shuffled, over exact-size buffers, with the heap
     held against a plain sorted-order oracle; a stand-alone program (nothing is loaded into Python under a
     sanitizer)."""
     import tempfile

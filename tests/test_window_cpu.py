@@ -222,8 +222,120 @@ def scenario_many_connections():
     assert np.array_equal(got["frame_accept"][1:2 * n:2], (step != 0).astype(np.uint8))
 
 
+# ---- the tiled walk's cross-lane reads on lane 0, on lane 63 and across the tile seam.  The same
+# cases, with the same numbers, run in tests/c/window_host_check.hip under three lane orders.  Every case asserts on
+# the model's side (facts) that its event sits where it was meant to. ----
+def run_one(size, base, frames, tail=None):
+    w = fr.new_frame_windows(1, size, base)
+    if tail is not None:
+        w[0]["has_tail"], (w[0]["tail_base_id"], w[0]["tail_bitfield"], w[0]["tail_nonce"]) = 1, tail
+    infos = np.array(frames, dtype=fr.FRAME_INFO_DTYPE)
+    got, want = run(infos, np.array([0, len(infos)], dtype=np.uint64), w)
+    return got, want, want["facts"], want["results"][0]
+
+
+def filler(k):
+    """A frame that is nothing to the window: a data frame that is not ok, an ack frame."""
+    if k % 2:
+        return E.data_info(6, 1, ok=0)
+    f = np.zeros((), dtype=fr.FRAME_INFO_DTYPE)
+    f["kind"], f["ok"], f["crc_ok"] = fr.ACK, 1, 1
+    f["f"][0] = 6
+    return f
+
+
+def scenario_duplicate_at_lane_63_and_over_the_seam():
+    """A duplicate refused at lane 63 (against the candidate of lane 62), and once more at lane 0 of the next tile
+    (against the base carried over the seam)."""
+    frames = [E.data_info(1000 + k, k & 1) for k in range(63)] + [E.data_info(1062, 1), E.data_info(1062, 1), E.data_info(1063, 1)]
+    _, want, facts, res = run_one(4096, 1000, frames)
+    assert facts["refused_at"] == [63, 64] and facts["accepted_at"][-2:] == [62, 65], facts
+    assert (int(res["accepted"]), int(res["refused"]), int(want["windows_out"][0]["base_id"])) == (64, 2, 1064)
+
+
+def scenario_fold_at_lane_63_and_a_group_closed_over_the_seam():
+    """Lane 63 folds into the open group and carries its only nonce; lane 0 of the next tile is 32 ids from the
+    group's base: it closes the group and opens the next."""
+    frames = [E.data_info(1000 + k, int(k == 63)) for k in range(64)] + [E.data_info(1064, 1)]
+    got, want, facts, res = run_one(4096, 1000, frames)
+    assert facts["groups_opened_at"] == [0, 32, 64] and facts["accepted_at"] == list(range(65)), facts
+    assert [(int(g["id"]), int(g["data_offset"]), int(g["channel_id"])) for g in got["groups"][:3]] == \
+        [(1000, 0xFFFFFFFF, 0), (1032, 0xFFFFFFFF, 1), (1064, 1, 1)] and got["groups_used"] == 3
+
+
+def scenario_sync_at_lane_63():
+    """A sync at lane 63 moves the base that lane 0 of the next tile is tested against (refused only against the
+    moved base); packet syncs at lane 5, at lane 63 and at lane 1 of the next tile."""
+    frames, nxt = [], 1000
+    for k in range(63):
+        if k == 5:
+            frames.append(E.sync_info(None, 77))
+        else:
+            frames.append(E.data_info(nxt, k & 1))
+            nxt += 1
+    frames += [E.sync_info(nxt + 100, 78), E.data_info(nxt + 50, 1), E.sync_info(None, 79), E.data_info(nxt + 100, 1)]
+    _, want, facts, res = run_one(4096, 1000, frames)
+    assert facts["sync_moved_at"] == [63] and facts["refused_at"] == [64] and facts["accepted_at"][-1] == 66, facts
+    assert E.ReceiveWindow(nxt, 4096).contains(nxt + 50)          # (what the unmoved base would have let in)
+    assert (int(res["first_packet_sync"]), int(res["packet_syncs"]), int(res["syncs"])) == (5, 3, 3)
+    assert int(want["windows_out"][0]["base_id"]) == nxt + 101
+
+
+def scenario_64_refused_then_one():
+    """Every candidate of a tile refused: 65 window rounds, the 65th on the word behind the 64 lanes' own; then a
+    tile with one refusal."""
+    frames = [E.data_info(999, k & 1) for k in range(64)] + [E.data_info(1000, 1), E.data_info(1000, 0), E.data_info(1001, 1)]
+    got, want, facts, res = run_one(64, 1000, frames)
+    assert facts["max_rounds"] == 65 and facts["tiles_with_rounds"] == 2 and facts["refused_at"] == list(range(64)) + [65], facts
+    assert (int(res["accepted"]), int(res["refused"])) == (2, 65)
+    g = got["groups"][0]
+    assert (int(g["id"]), int(g["data_offset"]), int(g["channel_id"])) == (1000, 3, 0)
+
+
+def scenario_64_groups_in_a_tile():
+    """A carried tail out of reach and 64 accepted frames 40 ids apart: every lane closes the group before it (64
+    group rounds with a stop test each, the most a tile takes); lane 0 of the next tile folds into the group lane 63
+    opened."""
+    frames = [E.data_info(1000 + 40 * k, k & 1) for k in range(64)] + [E.data_info(1000 + 40 * 63 + 31, 1)]
+    got, want, facts, res = run_one(4096, 1000, frames, tail=(900, 1, 1))
+    assert facts["groups_opened_at"] == list(range(64)) and facts["accepted_at"][-1] == 64, facts
+    t, g = got["groups"][0], got["groups"][64]
+    assert (int(t["id"]), int(t["data_offset"]), int(t["channel_id"])) == (900, 1, 1)
+    assert got["groups_used"] == 65 and (int(g["id"]), int(g["data_offset"]), int(g["channel_id"])) == (3520, 0x80000001, 0)
+
+
+def frames_that_come_back(first6):
+    """data 5 | fillers | data 6 at first6 | a sync that moves the base by 2^31 | data 6 again | data 3 (refused)."""
+    return [E.data_info(5, 0)] + [filler(k) for k in range(1, first6)] + \
+        [E.data_info(6, 1), E.sync_info((7 + (1 << 31)) & E.M32, None), E.data_info(6, 1), E.data_info(3, 1)]
+
+
+def ids_that_come_back_at(first6):
+    got, want, facts, res = run_one(1 << 31, 5, frames_that_come_back(first6))
+    assert facts["accepted_at"] == [0, first6, first6 + 2] and facts["groups_opened_at"] == [0], facts
+    assert facts["sync_moved_at"] == [first6 + 1] and facts["refused_at"] == [first6 + 3], facts
+    g = got["groups"][0]
+    # the fold's stop test decides the nonce: with both 6s in one fold both would count as "the bit was clear" (0)
+    assert got["groups_used"] == 1 and (int(g["id"]), int(g["data_offset"]), int(g["channel_id"])) == (5, 3, 1)
+
+
+def scenario_comes_back_at_lane_63():
+    """size = 2^31: the returning id 6 is the accepted lane 63, the lane before it among the accepted (61, the first
+    6) in the same open group: its bit is set already, the nonce stays."""
+    ids_that_come_back_at(61)
+
+
+def scenario_comes_back_at_lane_0_of_the_next_tile():
+    """The same with the first 6 at lane 62, the sync at lane 63 and the returning 6 at lane 0 of the next tile:
+    the open group's bits are carried over the seam."""
+    ids_that_come_back_at(62)
+
+
 SCENARIOS = [scenario_hostile_sizes, scenario_every_other_refused, scenario_ids_that_come_back, scenario_chained_steps,
-             scenario_groups_cap, scenario_bad_state, scenario_many_connections]
+             scenario_groups_cap, scenario_bad_state, scenario_many_connections,
+             scenario_duplicate_at_lane_63_and_over_the_seam, scenario_fold_at_lane_63_and_a_group_closed_over_the_seam,
+             scenario_sync_at_lane_63, scenario_64_refused_then_one,
+             scenario_64_groups_in_a_tile, scenario_comes_back_at_lane_63, scenario_comes_back_at_lane_0_of_the_next_tile]
 
 
 @pytest.mark.parametrize("scenario", SCENARIOS, ids=lambda f: f.__name__[9:])
@@ -273,7 +385,7 @@ def test_argument_rules():
 
 def test_window_core_under_sanitizers():
     """tests/c/window_host_check.hip: the wave-policy core of the frame window (fw_walk_tiles, the lanes of a phase
-    run one after the other) as host code under AddressSanitizer and UBSan, against the serial walk
+    run one after the other: forwards, backwards, shuffled, and on a carried shared block) as host code under AddressSanitizer and UBSan, against the serial walk
     (fw_walk_serial) on ordinary and hostile traffic and on random states, over exact-size buffers; a stand-alone
     program (nothing is loaded into Python under a sanitizer)."""
     import subprocess

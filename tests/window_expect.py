@@ -101,7 +101,9 @@ def expect_connection(window, infos, first):
     verdicts = np.zeros(n, dtype=np.uint8)
     res = dict(group_count=0, accepted=0, refused=0, syncs=0, packet_syncs=0, first_packet_sync=NO_PARENT, advanced=0,
                stop=0)
-    facts = dict(refused=0, sync_moved=0, sync_stayed=0, tail_fold=0, tiles_with_rounds=0, max_rounds=1)
+    # (*_at: the positions within the connection's frames, for the directed cases that want an event on a given lane)
+    facts = dict(refused=0, sync_moved=0, sync_stayed=0, tail_fold=0, tiles_with_rounds=0, max_rounds=1, refused_at=[],
+                 sync_moved_at=[], accepted_at=[], groups_opened_at=[])
     if int(window["size"]) > FW_MAX_SIZE:
         res["stop"] = 1
         return verdicts, [], out, res, facts
@@ -120,14 +122,19 @@ def expect_connection(window, infos, first):
             seq, nonce = int(f["f"][0]), int(f["aux"]) & 1
             only_tail = carried and len(c.frame_ack_queue.entries) == 1
             tail_bits = c.frame_ack_queue.entries[0].bitfield if only_tail else 0
+            n_groups = len(c.frame_ack_queue.entries)
             if c.handle_data_frame(seq, nonce):
                 verdicts[k] = 1
                 res["accepted"] += 1
+                facts["accepted_at"].append(k)
+                if len(c.frame_ack_queue.entries) != n_groups:
+                    facts["groups_opened_at"].append(k)
                 if only_tail and len(c.frame_ack_queue.entries) == 1 and c.frame_ack_queue.entries[0].bitfield != tail_bits:
                     facts["tail_fold"] += 1
             else:
                 res["refused"] += 1
                 facts["refused"] += 1
+                facts["refused_at"].append(k)
                 failed_in_tile[k // 64] = failed_in_tile.get(k // 64, 0) + 1
         elif f["kind"] == SYNC:
             aux = int(f["aux"])
@@ -139,6 +146,8 @@ def expect_connection(window, infos, first):
                 res["packet_syncs"] += 1
             if aux & 1:
                 facts["sync_moved" if moved else "sync_stayed"] += 1
+                if moved:
+                    facts["sync_moved_at"].append(k)
                 if not moved:
                     failed_in_tile[k // 64] = failed_in_tile.get(k // 64, 0) + 1
     facts["tiles_with_rounds"] = len(failed_in_tile)
@@ -191,7 +200,10 @@ def expect_batch(infos, frame_first, windows, groups_cap=None, prefill=None):
         for key, val in res.items():
             results[r][key] = val
         for key, val in fc.items():
-            facts[key] = max(facts.get(key, 0), val) if key == "max_rounds" else facts.get(key, 0) + val
+            if isinstance(val, list):   # (positions: meaningful for a batch of one connection)
+                facts.setdefault(key, []).extend(val)
+            else:
+                facts[key] = max(facts.get(key, 0), val) if key == "max_rounds" else facts.get(key, 0) + val
     group_first[n] = total
     return {"frame_accept": accept, "groups": groups, "group_first": group_first, "groups_used": total,
             "results": results, "windows_out": windows_out, "facts": facts}
