@@ -13,6 +13,7 @@ import oracle
 from oracle import codec as C
 from parse_expect import compare, oracle_records
 from uflow_amd import _native
+from uflow_amd.batch import records, rows
 from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE, build_batch_host
 
 import build_expect as BE
@@ -24,9 +25,8 @@ DEV = "cuda:0"
 
 def _dev(batch):
     infos, items, payload, src = batch.arrays()
-    t = lambda a: torch.from_numpy(a).to(DEV)  # noqa: E731
-    return (t(infos.view(np.uint8).reshape(-1, 32)), t(items.view(np.uint8).reshape(-1, 24)), t(payload),
-            t(src.astype(np.int64)))
+    return (rows(infos, DEV), rows(items, DEV), rows(payload, DEV),
+            rows(src.astype(np.int64), DEV))
 
 
 def _build_and_check(engine, batch, seal=True, **kw):
@@ -61,10 +61,10 @@ def test_codec_batch_roundtrip(engine):
     torch.cuda.synchronize()
     assert np.array_equal(valid2.cpu().numpy() != 0, written)
     assert int(used2.cpu()[0]) == n_items
-    i1 = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    i2 = infos2.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    t1 = items.cpu().numpy().view(ITEM_DTYPE).reshape(-1)[:n_items]
-    t2 = items2.cpu().numpy().view(ITEM_DTYPE).reshape(-1)[:n_items]
+    i1 = records(infos, FRAME_INFO_DTYPE)
+    i2 = records(infos2, FRAME_INFO_DTYPE)
+    t1 = records(items, ITEM_DTYPE)[:n_items]
+    t2 = records(items2, ITEM_DTYPE)[:n_items]
     exp_infos, exp_items = oracle_records(batch.exp)
     compare(i2, t2, exp_infos, exp_items)
     # against the first parse: the infos whole (item_first too: the same frames are accepted); of the items
@@ -274,8 +274,8 @@ def test_two_streams_release_and_empty(engine):
     cur = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     assert lib.ufc_build_sizes_varlen(engine._ctx, None, None, 0, None, 0, 0, None, None, cur) == 0
     assert lib.ufc_build_batch_varlen(engine._ctx, None, None, 0, None, None, 0, 0, None, None, 0, 1, None, cur) == 0
-    none = torch.empty((0, 32), dtype=torch.uint8, device=DEV)
-    out, off, status = engine.build_varlen(none, torch.empty((0, 24), dtype=torch.uint8, device=DEV),
+    none = torch.empty((0, FRAME_INFO_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    out, off, status = engine.build_varlen(none, torch.empty((0, ITEM_DTYPE.itemsize), dtype=torch.uint8, device=DEV),
                                            torch.empty(0, dtype=torch.uint8, device=DEV))
     assert out.numel() == 0 and off.cpu().tolist() == [0] and status.numel() == 0
     assert lib.ufc_build_sizes_varlen(engine._ctx, None, None, 0, None, 0, 5, None, None, cur) == _native.UFC_ERR_INVALID_ARG

@@ -9,7 +9,7 @@ import torch
 
 from oracle import codec as C
 from uflow_amd import _native
-from uflow_amd.batch import EMIT_TILE
+from uflow_amd.batch import EMIT_TILE, records, rows
 from uflow_amd.frame import FLUSH_DTYPE, FRAME_INFO_DTYPE, ITEM_DTYPE, PACKET_DTYPE, SENDER_DTYPE
 
 import emit_expect as EE
@@ -20,13 +20,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _t(a):
-    return torch.from_numpy(a).to(DEV)
-
-
 def _dev(packets, first, senders):
-    return (_t(packets.view(np.uint8).reshape(-1, 16)), _t(first.astype(np.int64)),
-            _t(senders.view(np.uint8).reshape(-1, 304)))
+    return (rows(packets, DEV), rows(first.astype(np.int64), DEV),
+            rows(senders, DEV))
 
 
 def _host(out):
@@ -40,7 +36,7 @@ def _emit(engine, packets, first, senders, exp=None, items_cap=None, slack=16, s
     exp = EE.expect(packets, first, senders) if exp is None else exp
     cap = exp.items_used + slack if items_cap is None else items_cap
     d = _dev(packets, first, senders)
-    items = torch.full((max(cap, exp.items_used) + slack, 24), EE.FILL, dtype=torch.uint8, device=DEV)
+    items = torch.full((max(cap, exp.items_used) + slack, ITEM_DTYPE.itemsize), EE.FILL, dtype=torch.uint8, device=DEV)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
     out = engine.emit_packets(*d, items_cap=cap, items=items, stream=stream, **kw)
@@ -92,7 +88,7 @@ def test_tile_cases(engine):
     d = _dev(packets, first, senders)
     for cap in (0, exp.items_used // 2):
         state = d[2].clone()
-        items = torch.full((exp.items_used + 8, 24), EE.FILL, dtype=torch.uint8, device=DEV)
+        items = torch.full((exp.items_used + 8, ITEM_DTYPE.itemsize), EE.FILL, dtype=torch.uint8, device=DEV)
         out = engine.emit_packets(d[0], d[1], state, items_cap=cap, items=items, senders_out=state)
         torch.cuda.synchronize()
         EE.check(_host(out), exp, items_cap=cap)
@@ -137,9 +133,9 @@ def test_bad_ranges_empty_and_no_senders(engine):
 def test_argument_checks(engine):
     packets, first, senders = EE.Senders().add([EE.pkt(1)]).arrays()
     d = _dev(packets, first, senders)
-    items = torch.zeros((1, 24), dtype=torch.uint8, device=DEV)
+    items = torch.zeros((1, ITEM_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     ff = torch.zeros(2, dtype=torch.int64, device=DEV)
-    sres = torch.zeros((1, 32), dtype=torch.uint8, device=DEV)
+    sres = torch.zeros((1, EE.SENDER_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     used = torch.zeros(1, dtype=torch.int64, device=DEV)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     good = [engine._ctx, p(d[0]), 1, p(d[1]), p(d[2]), 1, p(items), 1, p(ff), None, p(sres), None, p(used), None]
@@ -168,7 +164,7 @@ def test_streams_and_scratch_reuse(engine):
         packets, first, senders = b.arrays()
         exp = EE.expect(packets, first, senders)
         d = _dev(packets, first, senders)
-        items = torch.full((exp.items_used, 24), EE.FILL, dtype=torch.uint8, device=DEV)
+        items = torch.full((exp.items_used, ITEM_DTYPE.itemsize), EE.FILL, dtype=torch.uint8, device=DEV)
         s.wait_stream(torch.cuda.current_stream())
         outs.append((exp, d, engine.emit_packets(*d, items_cap=exp.items_used, items=items, stream=s)))
     s.synchronize()
@@ -197,8 +193,8 @@ def test_emit_pack_build_seal_gate_parse(engine):
 
     d_packets, d_first, d_senders = _dev(packets, first, senders)
     items, ff, pres, sres, sout, used = engine.emit_packets(d_packets, d_first, d_senders, items_cap=exp.items_used)
-    infos, res, frames_used = engine.pack_flushes(items, ff, _t(flushes.view(np.uint8).reshape(-1, 24)))
-    d_payload = _t(payload)
+    infos, res, frames_used = engine.pack_flushes(items, ff, rows(flushes, DEV))
+    d_payload = rows(payload, DEV)
     out, off, status = engine.build_varlen(infos, items, d_payload, seal=True)
     torch.cuda.synchronize()
     EE.check(_host((items, ff, pres, sres, sout, used)), exp)
@@ -219,10 +215,10 @@ def test_emit_pack_build_seal_gate_parse(engine):
     infos2, items2, used2 = engine.parse_varlen(out, d_off, valid)
     torch.cuda.synchronize()
     assert (valid.cpu().numpy() == 1).all()
-    i2 = infos2.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
+    i2 = records(infos2, FRAME_INFO_DTYPE)
     assert (i2["ok"] == 1).all()
     assert int(used2.cpu()[0]) == exp.items_used
-    t2 = items2.cpu().numpy().view(ITEM_DTYPE).reshape(-1)[:exp.items_used]
+    t2 = records(items2, ITEM_DTYPE)[:exp.items_used]
     for fld in ITEM_DTYPE.names:
         if fld != "data_offset":
             assert np.array_equal(t2[fld], exp.items[fld]), fld
@@ -251,7 +247,7 @@ def test_more_items_than_the_item_grid(engine):
     ref = fr.emit_packets_host(packets, first, senders, nthreads=8)
     used, slack = ref[5], 1000
     assert used > E.EMIT_SLOTS_MAX and len(big) * 65536 > E.EMIT_SLOTS_MAX   # the threshold, from the inputs
-    items = torch.full((used + slack, 24), EE.FILL, dtype=torch.uint8, device=DEV)
+    items = torch.full((used + slack, ITEM_DTYPE.itemsize), EE.FILL, dtype=torch.uint8, device=DEV)
     got = _host(engine.emit_packets(*_dev(packets, first, senders), items_cap=used + slack, items=items))
     torch.cuda.synchronize()
     assert got[5] == used and np.array_equal(got[1].astype(np.uint64), ref[1])
@@ -260,7 +256,7 @@ def test_more_items_than_the_item_grid(engine):
     reserved = np.zeros(used, dtype=bool)
     for s in np.flatnonzero(senders["reserve_items"]):
         reserved[int(ref[1][s]): int(ref[1][s]) + int(senders["reserve_items"][s])] = True
-    same = (g_items[:used].view(np.uint8).reshape(-1, 24) == ref[0].view(np.uint8).reshape(-1, 24)).all(axis=1)
+    same = (g_items[:used].view(np.uint8).reshape(used, -1) == ref[0].view(np.uint8).reshape(used, -1)).all(axis=1)
     assert same[~reserved].all(), np.flatnonzero(~same & ~reserved)[:8]
     assert (g_items[:used][reserved].view(np.uint8) == EE.FILL).all() and (g_items[used:].view(np.uint8) == EE.FILL).all()
     for k, dt in ((2, EE.PACKET_RESULT_DTYPE), (3, EE.SENDER_RESULT_DTYPE), (4, SENDER_DTYPE)):

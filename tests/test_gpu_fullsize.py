@@ -215,6 +215,7 @@ def test_parse_bench_workload_full(engine, mtu):
     not ok, no items), and every info and every item of the GPU output is compared with them."""
     import parse_expect
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     n = 1_000_000
     base = _parse_workload_base(mtu)
     lens = np.array([len(base[i % 600]) for i in range(n)], dtype=np.int64)
@@ -230,8 +231,8 @@ def test_parse_bench_workload_full(engine, mtu):
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
     k = int(used.cpu()[0])
-    got_infos = _host(infos).view(FRAME_INFO_DTYPE).reshape(-1)
-    got_items = _host(items[:k]).view(ITEM_DTYPE).reshape(-1)
+    got_infos = records(infos, FRAME_INFO_DTYPE)
+    got_items = records(items[:k], ITEM_DTYPE)
     b_infos, b_items = parse_expect.oracle_records(base)
     assert b_infos["ok"].all()
     dead = np.zeros(n, dtype=bool)
@@ -248,6 +249,7 @@ def test_parse_datagram_validity_flags(engine):
     import random
     from oracle import codec as C
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     rng = random.Random(4321)
     frames = [C.frame_write(C.receive_side_data_frame(rng)) for _ in range(3000)]
     data, offsets = _csr(frames)
@@ -256,8 +258,8 @@ def test_parse_datagram_validity_flags(engine):
     _, valid = engine.crc_varlen(d, o)
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
-    infos = _host(infos).view(FRAME_INFO_DTYPE).reshape(-1)
-    items = _host(items).view(ITEM_DTYPE).reshape(-1)
+    infos = records(infos, FRAME_INFO_DTYPE)
+    items = records(items, ITEM_DTYPE)
     k = 0
     counts = {True: 0, False: 0}
     for i, fb in enumerate(frames):
@@ -314,6 +316,7 @@ def test_parse_large_batch(engine):
     import parse_expect
     from test_gpu_parity import _codec_batch
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE, parse_batch_host
+    from uflow_amd.batch import records
     frames, data, offsets = _codec_batch(10, 600)
     reps = 7200
     lens = np.diff(offsets)
@@ -327,8 +330,8 @@ def test_parse_large_batch(engine):
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
     k = int(used.cpu()[0])
-    got = _host(infos).view(FRAME_INFO_DTYPE).reshape(-1)
-    got_items = _host(items[:k]).view(ITEM_DTYPE).reshape(-1)
+    got = records(infos, FRAME_INFO_DTYPE)
+    got_items = records(items[:k], ITEM_DTYPE)
     b_infos, b_items = parse_expect.oracle_records(frames)
     exp_infos, exp_items = parse_expect.tile_records(b_infos, b_items, np.arange(n) % 600, np.zeros(n, dtype=bool))
     assert k == exp_items.size

@@ -10,7 +10,7 @@ import torch
 
 from oracle import codec as C
 from uflow_amd import _native
-from uflow_amd.batch import PACK_TILE
+from uflow_amd.batch import PACK_TILE, records, rows
 from uflow_amd.frame import FLUSH_DTYPE, FLUSH_RESULT_DTYPE, FRAME_INFO_DTYPE, ITEM_DTYPE
 
 import pack_expect as PE
@@ -20,13 +20,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _t(a):
-    return torch.from_numpy(a).to(DEV)
-
-
 def _dev(items, first, flushes, nonce_bits=None):
-    return (_t(items.view(np.uint8).reshape(-1, 24)), _t(first.astype(np.int64)), _t(flushes.view(np.uint8).reshape(-1, 24)),
-            _t(nonce_bits.view(np.int32)) if nonce_bits is not None else None)
+    return (rows(items, DEV), rows(first.astype(np.int64), DEV), rows(flushes, DEV),
+            rows(nonce_bits.view(np.int32), DEV) if nonce_bits is not None else None)
 
 
 def _pack(engine, items, first, flushes, nonce_bits=None, **kw):
@@ -118,8 +114,8 @@ def test_empty_ends_one_item_and_no_flushes(engine):
 def test_argument_checks(engine):
     items, first, flushes = PE.Flushes().add(PE.DATA, [PE.dgram(1)]).arrays()
     d_items, d_first, d_flushes, _ = _dev(items, first, flushes)
-    infos = torch.zeros((1, 32), dtype=torch.uint8, device=DEV)
-    res = torch.zeros((1, 24), dtype=torch.uint8, device=DEV)
+    infos = torch.zeros((1, FRAME_INFO_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    res = torch.zeros((1, FLUSH_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     used = torch.zeros(1, dtype=torch.int64, device=DEV)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     good = [engine._ctx, p(d_items), 1, p(d_first), p(d_flushes), 1, None, p(infos), 1, p(res), p(used), None]
@@ -159,8 +155,8 @@ def test_frames_cap_and_guard(engine):
     exp = PE.expect(items, first, flushes)
     cap = exp[2] // 2
     d_items, d_first, d_flushes, _ = _dev(items, first, flushes)
-    infos = torch.full((cap + 64, 32), 0xA5, dtype=torch.uint8, device=DEV)
-    res = torch.zeros((flushes.size, 24), dtype=torch.uint8, device=DEV)
+    infos = torch.full((cap + 64, FRAME_INFO_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device=DEV)
+    res = torch.zeros((flushes.size, FLUSH_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     used = torch.zeros(1, dtype=torch.int64, device=DEV)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     torch.cuda.synchronize()
@@ -226,7 +222,7 @@ def test_pack_build_seal_gate_parse(engine):
 
     d_items, d_first, d_flushes, d_nb = _dev(items, first, flushes, nonce_bits)
     infos, res, used = engine.pack_flushes(d_items, d_first, d_flushes, nonce_bits=d_nb)
-    d_payload = _t(payload)
+    d_payload = rows(payload, DEV)
     out, off, status = engine.build_varlen(infos, d_items, d_payload, seal=True)  # the infos as they are
     torch.cuda.synchronize()
     PE.check((infos.cpu().numpy(), res.cpu().numpy(), int(used.cpu()[0])), exp)
@@ -247,13 +243,13 @@ def test_pack_build_seal_gate_parse(engine):
     infos2, items2, used2 = engine.parse_varlen(out, d_off, valid)
     torch.cuda.synchronize()
     assert (valid.cpu().numpy() == 1).all()
-    i2 = infos2.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
+    i2 = records(infos2, FRAME_INFO_DTYPE)
     assert (i2["ok"] == 1).all() and np.array_equal(i2["item_count"], e_infos["item_count"])
     assert np.array_equal(i2["f"][:, 0], e_infos["f"][:, 0]) and np.array_equal(i2["aux"], e_infos["aux"])
     packed = np.concatenate([np.arange(int(first[j]), int(first[j]) + int(e_res["items_packed"][j]))
                              for j in range(flushes.size)])
     assert int(used2.cpu()[0]) == packed.size
-    t2 = items2.cpu().numpy().view(ITEM_DTYPE).reshape(-1)[:packed.size]
+    t2 = records(items2, ITEM_DTYPE)[:packed.size]
     src = items[packed]
     ack = is_ack[packed]
     for fld in ("id", "channel_id"):

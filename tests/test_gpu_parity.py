@@ -314,6 +314,7 @@ def test_parse_varlen_vs_oracle(engine):
     """GPU gate + GPU parse vs the Python codec oracle, frame by frame."""
     from oracle import codec as C
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     from test_codec_cpu import info_to_dict
     frames, data, offsets = _codec_batch(9, 3000)
     d = torch.from_numpy(data).to(DEV)
@@ -321,8 +322,8 @@ def test_parse_varlen_vs_oracle(engine):
     _, valid = engine.crc_varlen(d, o)
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
-    infos = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    items = items.cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+    infos = records(infos, FRAME_INFO_DTYPE)
+    items = records(items, ITEM_DTYPE)
     total = 0
     for i, fb in enumerate(frames):
         cnt = int(infos[i]["item_count"]) if infos[i]["ok"] else 0
@@ -382,6 +383,7 @@ def test_parse_varlen_slow_paths_and_cap(engine):
     through the middle (items past the cap are not written; item_first / items_used unchanged)."""
     from oracle import codec as C
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     from test_codec_cpu import info_to_dict
     frames, data, offsets = _parse_edge_batch(31)
     d = torch.from_numpy(data).to(DEV)
@@ -389,8 +391,8 @@ def test_parse_varlen_slow_paths_and_cap(engine):
     _, valid = engine.crc_varlen(d, o)
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
-    infos = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    items = items.cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+    infos = records(infos, FRAME_INFO_DTYPE)
+    items = records(items, ITEM_DTYPE)
     total, walked = 0, 0
     for i, fb in enumerate(frames):
         cnt = int(infos[i]["item_count"]) if infos[i]["ok"] else 0
@@ -401,7 +403,7 @@ def test_parse_varlen_slow_paths_and_cap(engine):
     assert int(used.cpu()[0]) == total
     assert walked > 100  # the direct-store path ran
     cap = total // 2 + 7
-    fill = torch.full((cap + 100, 24), 0xA5, dtype=torch.uint8, device=DEV)
+    fill = torch.full((cap + 100, ITEM_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device=DEV)
     infos2, _, used2 = engine.parse_varlen(d, o, valid, items_cap=cap)
     # (parse_varlen allocates its own item array; run the capped parse into a sentinel-filled one)
     from uflow_amd import _native as NN
@@ -416,7 +418,7 @@ def test_parse_varlen_slow_paths_and_cap(engine):
     assert rc == 0
     torch.cuda.synchronize()
     assert int(used3.cpu()[0]) == total and int(used2.cpu()[0]) == total
-    assert np.array_equal(infos3.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1), infos)
+    assert np.array_equal(records(infos3, FRAME_INFO_DTYPE), infos)
     got = fill.cpu().numpy()
     assert np.array_equal(got[:cap].view(ITEM_DTYPE).reshape(-1), items[:cap])
     assert (got[cap:] == 0xA5).all()
@@ -431,6 +433,7 @@ def test_parse_varlen_headers_at_span_ends(engine):
     import random
     from oracle import codec as C
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     from test_codec_cpu import info_to_dict
     rng = random.Random(77)
     frames = []
@@ -460,8 +463,8 @@ def test_parse_varlen_headers_at_span_ends(engine):
         assert bool(valid.all())
         infos, items, used = engine.parse_varlen(d, o, valid)
         torch.cuda.synchronize()
-        infos = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-        items = items.cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+        infos = records(infos, FRAME_INFO_DTYPE)
+        items = records(items, ITEM_DTYPE)
         total = 0
         for i, fb in enumerate(frames):
             assert infos[i]["ok"], i
@@ -476,6 +479,7 @@ def test_parse_varlen_vs_host_parse_large(engine):
     oracle/codec.py, expanded over the tiling) and == the host parse gating on its own."""
     import parse_expect
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE, parse_batch_host
+    from uflow_amd.batch import records
     frames, data, offsets = _codec_batch(10, 600)
     reps = 340
     big = np.tile(data, reps)
@@ -489,8 +493,8 @@ def test_parse_varlen_vs_host_parse_large(engine):
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
     k = int(used.cpu()[0])
-    got_infos = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    got_items = items[:k].cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+    got_infos = records(infos, FRAME_INFO_DTYPE)
+    got_items = records(items[:k], ITEM_DTYPE)
     b_infos, b_items = parse_expect.oracle_records(frames)
     exp_infos, exp_items = parse_expect.tile_records(b_infos, b_items, np.arange(n) % 600, np.zeros(n, dtype=bool))
     assert k == exp_items.size

@@ -97,6 +97,7 @@ def test_parse_vs_codec_oracle(engine, spec):
     import random
     from oracle import codec as C
     from uflow_amd.frame import FRAME_INFO_DTYPE, ITEM_DTYPE
+    from uflow_amd.batch import records
     from test_codec_cpu import info_to_dict
     refs = C.reference_test_frames()
     frames = []
@@ -122,8 +123,8 @@ def test_parse_vs_codec_oracle(engine, spec):
     _, valid = engine.crc_varlen(d, o)
     infos, items, used = engine.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
-    infos = infos.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    items = items.cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+    infos = records(infos, FRAME_INFO_DTYPE)
+    items = records(items, ITEM_DTYPE)
     total = 0
     for i, fb in enumerate(frames):
         cnt = int(infos[i]["item_count"]) if infos[i]["ok"] else 0

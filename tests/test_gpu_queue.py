@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from uflow_amd import frame as fr
+from uflow_amd.batch import records, rows
 from uflow_amd.frame import FLUSH_DTYPE, PACKET_DTYPE, SENDER_DTYPE
 
 import queue_expect as E
@@ -23,22 +24,15 @@ U8 = np.uint8
 KEYS = ("results", "queues_out", "log", "ref_acked")
 
 
-def _t(a, width=None):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.astype(np.int64)
-    return torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
-
-
 def _args(call, queues, log, ref_acked):
-    return (_t(call["infos"], 32), _t(call["items"], 24), _t(call["frame_first"]), _t(call["sent"], 24), _t(call["sent_first"]),
-            _t(queues, 192), _t(call["steps"], 40), _t(log, 24), _t(ref_acked) if ref_acked is not None else None)
+    return (rows(call["infos"], DEV), rows(call["items"], DEV), rows(call["frame_first"], DEV), rows(call["sent"], DEV), rows(call["sent_first"], DEV),
+            rows(queues, DEV), rows(call["steps"], DEV), rows(log, DEV), rows(ref_acked, DEV) if ref_acked is not None else None)
 
 
 def _host_out(d):
-    return {"results": d["results"].cpu().numpy().view(fr.FRAME_QUEUE_RESULT_DTYPE).reshape(-1),
-            "queues_out": d["queues_out"].cpu().numpy().view(fr.FRAME_QUEUE_DTYPE).reshape(-1),
-            "log": d["log"].cpu().numpy().view(fr.SENT_FRAME_DTYPE).reshape(-1),
+    return {"results": records(d["results"], fr.FRAME_QUEUE_RESULT_DTYPE),
+            "queues_out": records(d["queues_out"], fr.FRAME_QUEUE_DTYPE),
+            "log": records(d["log"], fr.SENT_FRAME_DTYPE),
             "ref_acked": d["ref_acked"].cpu().numpy() if d["ref_acked"] is not None else None}
 
 
@@ -257,7 +251,7 @@ def test_argument_checks(engine):
     res = buf[:80].cpu().numpy().view(fr.FRAME_QUEUE_RESULT_DTYPE)[0]
     assert int(res["stop"]) == fr.FQ_DONE and int(res["frames_acked"]) == 1 and int(res["pushes_taken"]) == 1
     assert a[8].cpu().numpy().tolist() == [1, 0, 0, 0]
-    d = engine.frame_queue(a[0][:0], a[1][:0], _t(np.zeros(1, np.uint64)), a[3][:0], _t(np.zeros(1, np.uint64)), a[5][:0],
+    d = engine.frame_queue(a[0][:0], a[1][:0], rows(np.zeros(1, np.uint64), DEV), a[3][:0], rows(np.zeros(1, np.uint64), DEV), a[5][:0],
                            a[6][:0], a[7])   # no connections: UFC_OK
     assert d["results"].shape[0] == 0
 
@@ -286,7 +280,7 @@ def test_whole_path_on_the_device(engine):
     pf = np.arange(n + 1) * per
     # 1. emit
     cap = int(np.maximum(1, (sizes + FRAG - 1) // FRAG).sum())
-    items, iff, _, _, _, _ = engine.emit_packets(_t(packets, 16), _t(pf), _t(senders, 304), items_cap=cap)
+    items, iff, _, _, _, _ = engine.emit_packets(rows(packets, DEV), rows(pf, DEV), rows(senders, DEV), items_cap=cap)
     h_items, h_iff, _, _, _, h_used = fr.emit_packets_host(packets, pf.astype(np.uint64), senders)
     same(items, h_items[:h_used], fr.ITEM_DTYPE, "emit: items")
     # 2. pack, with the room and the first id the frame queues give
@@ -296,13 +290,13 @@ def test_whole_path_on_the_device(engine):
     flushes["kind"], flushes["flush_alloc"] = fr.DATA, 1 << 40
     flushes["window_room"], flushes["id0"] = queues["window_size"], queues["log_next_id"]
     nonce_words = rng.integers(0, 1 << 32, 64, dtype=np.uint64).astype(np.uint32)
-    infos, res, frames_used = engine.pack_flushes(items, iff, _t(flushes, 24), nonce_bits=_t(nonce_words.view(np.int32)))
+    infos, res, frames_used = engine.pack_flushes(items, iff, rows(flushes, DEV), nonce_bits=rows(nonce_words.view(np.int32), DEV))
     h_infos, h_res, nfr = fr.pack_host(h_items[:h_used], h_iff, flushes, nonce_bits=nonce_words)
     same(infos, h_infos[:nfr], fr.FRAME_INFO_DTYPE, "pack: infos")
     same(res, h_res, fr.FLUSH_RESULT_DTYPE, "pack: results")
     assert (h_res["frame_count"] == 16).all() and (h_res["stop"] == fr.PACK_WINDOW_LIMITED).all()
     # 3. build and seal; push the packed frames into the queues
-    wire, off, _ = engine.build_varlen(infos, items, _t(payload), seal=True)
+    wire, off, _ = engine.build_varlen(infos, items, rows(payload, DEV), seal=True)
     h_wire, h_off, _, _ = fr.build_batch_host(h_infos[:nfr], h_items[:h_used], payload)
     torch.cuda.synchronize()
     wire_h, off_h = wire.cpu().numpy(), off.cpu().numpy()[:nfr + 1].astype(np.int64)
@@ -317,7 +311,7 @@ def test_whole_path_on_the_device(engine):
     push = {"infos": np.zeros(0, fr.FRAME_INFO_DTYPE), "items": np.zeros(0, fr.ITEM_DTYPE),
             "frame_first": np.zeros(n + 1, np.uint64), "sent": sent, "sent_first": sf, "steps": steps}
     refs = np.zeros(h_used, dtype=U8)
-    d_log, d_refs = _t(log, 24), _t(refs)
+    d_log, d_refs = rows(log, DEV), rows(refs, DEV)
     a = _args(push, queues, log, None)
     fq1 = engine.frame_queue(*a[:7], d_log, d_refs)
     h1 = fr.frame_queue_host(push["infos"], push["items"], push["frame_first"], sent, sf, queues, steps, log, ref_acked=refs)
@@ -332,13 +326,13 @@ def test_whole_path_on_the_device(engine):
     off2 = np.concatenate([[0], np.cumsum([off_h[g + 1] - off_h[g] for g in arrive])]).astype(np.int64)
     wire2 = np.concatenate([wire_h[off_h[g]:off_h[g + 1]] for g in arrive])
     frame_first = np.searchsorted(np.array(owner), np.arange(n + 1)).astype(np.int64)
-    d_wire, d_off = _t(wire2), _t(off2)
+    d_wire, d_off = rows(wire2, DEV), rows(off2, DEV)
     _, valid = engine.crc_varlen(d_wire, d_off)
     infos2, items2, _ = engine.parse_varlen(d_wire, d_off, valid)
     hp_infos, hp_items = fr.parse_batch_host(wire2, off2.astype(np.uint64))
     same(infos2, hp_infos, fr.FRAME_INFO_DTYPE, "parse: infos")
     windows = fr.new_frame_windows(n, 4096, first_ids.astype(np.uint32))
-    fw = engine.frame_window(infos2, _t(frame_first), _t(windows, 24))
+    fw = engine.frame_window(infos2, rows(frame_first, DEV), rows(windows, DEV))
     hw = fr.frame_window_host(hp_infos, frame_first.astype(np.uint64), windows)
     torch.cuda.synchronize()
     used = int(fw["groups_used"].cpu()[0])
@@ -350,7 +344,7 @@ def test_whole_path_on_the_device(engine):
     ack["kind"], ack["flush_alloc"] = fr.ACK, 1 << 40
     ack["id0"], ack["id1"] = hw["windows_out"]["base_id"], 77
     groups = fw["groups"][:used].contiguous()
-    a_infos, a_res, a_used = engine.pack_flushes(groups, fw["group_first"], _t(ack, 24))
+    a_infos, a_res, a_used = engine.pack_flushes(groups, fw["group_first"], rows(ack, DEV))
     ha_infos, ha_res, na = fr.pack_host(hw["groups"][:used], hw["group_first"], ack)
     same(a_infos, ha_infos[:na], fr.FRAME_INFO_DTYPE, "ack pack: infos")
     assert na == n
@@ -371,8 +365,8 @@ def test_whole_path_on_the_device(engine):
     steps2["flags"], steps2["rtt_ms"], steps2["now_ms"] = fr.FQ_FEEDBACK | fr.FQ_HAS_RTT, 30, 500
     af = np.arange(n + 1, dtype=np.uint64)
     none = np.zeros(n + 1, dtype=np.uint64)
-    fq2 = engine.frame_queue(p_infos, p_items[:len(hq_items)].contiguous(), _t(af), _t(sent[:0], 24), _t(none), fq1["queues_out"],
-                             _t(steps2, 40), d_log, d_refs, queues_out=fq1["queues_out"])
+    fq2 = engine.frame_queue(p_infos, p_items[:len(hq_items)].contiguous(), rows(af, DEV), rows(sent[:0], DEV), rows(none, DEV), fq1["queues_out"],
+                             rows(steps2, DEV), d_log, d_refs, queues_out=fq1["queues_out"])
     h2 = fr.frame_queue_host(hq_infos, hq_items, af, sent[:0], none, h1["queues_out"], steps2, h1["log"],
                              ref_acked=h1["ref_acked"])
     torch.cuda.synchronize()
@@ -391,7 +385,7 @@ def test_whole_path_on_the_device(engine):
     assert (r["loss_rate"] > 0).all() and (r["groups_bad_nonce"] == 0).all() and (r["groups_unknown"] == 0).all()
     # the room and the next id go back into the next pack
     flushes["window_room"], flushes["id0"] = r["window_room"], o2["queues_out"]["log_next_id"]
-    infos3, res3, used3 = engine.pack_flushes(items, iff, _t(flushes, 24))
+    infos3, res3, used3 = engine.pack_flushes(items, iff, rows(flushes, DEV))
     h_infos3, h_res3, nfr3 = fr.pack_host(h_items[:h_used], h_iff, flushes)
     same(infos3, h_infos3[:nfr3], fr.FRAME_INFO_DTYPE, "next pack: infos")
     assert (h_res3["frame_count"] == 16).all()

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from uflow_amd import frame as fr
+from uflow_amd.batch import records, rows
 
 import queue_expect as Q
 import rate_expect as E
@@ -19,19 +20,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 U8 = np.uint8
-
-
-def _t(a, width=None):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.view(np.int64)
-    elif a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
-
-
-def _back(t, dtype):
-    return t.cpu().numpy().view(dtype).reshape(-1)
 
 
 def same(got, want, what):
@@ -43,19 +31,19 @@ def same(got, want, what):
 
 def device_step(engine, b, in_place=False, gather_in=True, gather_out=True):
     """ufc_rate_step_varlen on the batch `b` (rate_expect.random_batch's dict); the outputs as host arrays."""
-    states = _t(b["states"], 112)
-    d = engine.rate_step(states, _t(b["ticks"], 32), _t(b["fq"], 80), _t(b["entries"], 16),
-                         flush_results=_t(b["flush_results"], 24) if gather_in else None,
-                         result_index=_t(b["result_index"]) if gather_in else None,
-                         flushes=_t(b["flushes"], 24) if gather_out else None,
-                         flush_index=_t(b["flush_index"]) if gather_out else None,
+    states = rows(b["states"], DEV)
+    d = engine.rate_step(states, rows(b["ticks"], DEV), rows(b["fq"], DEV), rows(b["entries"], DEV),
+                         flush_results=rows(b["flush_results"], DEV) if gather_in else None,
+                         result_index=rows(b["result_index"], DEV) if gather_in else None,
+                         flushes=rows(b["flushes"], DEV) if gather_out else None,
+                         flush_index=rows(b["flush_index"], DEV) if gather_out else None,
                          states_out=states if in_place else None)
     torch.cuda.synchronize()
     if not in_place:
-        same(_back(states, fr.RATE_STATE_DTYPE), b["states"], "states (input)")
-    return {"results": _back(d["results"], fr.RATE_RESULT_DTYPE), "states_out": _back(d["states_out"], fr.RATE_STATE_DTYPE),
-            "entries": _back(d["entries"], fr.RECV_RATE_ENTRY_DTYPE),
-            "flushes": _back(d["flushes"], fr.FLUSH_DTYPE) if gather_out else None}
+        same(records(states, fr.RATE_STATE_DTYPE), b["states"], "states (input)")
+    return {"results": records(d["results"], fr.RATE_RESULT_DTYPE), "states_out": records(d["states_out"], fr.RATE_STATE_DTYPE),
+            "entries": records(d["entries"], fr.RECV_RATE_ENTRY_DTYPE),
+            "flushes": records(d["flushes"], fr.FLUSH_DTYPE) if gather_out else None}
 
 
 def host_step(b, gather_in=True, gather_out=True):
@@ -79,12 +67,12 @@ def compare_step(engine, b, **kw):
 
 def compare_begin(engine, states, now, extra, in_place=False):
     want = fr.rate_begin_host(states, now, extra)
-    d_states = _t(states, 112)
-    d = engine.rate_begin(d_states, _t(now), _t(extra) if extra is not None else None,
+    d_states = rows(states, DEV)
+    d = engine.rate_begin(d_states, rows(now, DEV), rows(extra, DEV) if extra is not None else None,
                           states_out=d_states if in_place else None)
     torch.cuda.synchronize()
-    same(_back(d["steps"], fr.FRAME_QUEUE_STEP_DTYPE), want["steps"], "steps")
-    same(_back(d["states_out"], fr.RATE_STATE_DTYPE), want["states_out"], "states_out")
+    same(records(d["steps"], fr.FRAME_QUEUE_STEP_DTYPE), want["steps"], "steps")
+    same(records(d["states_out"], fr.RATE_STATE_DTYPE), want["states_out"], "states_out")
 
 
 # ---- parity at the tile edges ----
@@ -284,14 +272,14 @@ def test_closed_loop_on_the_device(engine):
     assert flags & 15 == 15 and (np.concatenate(h_rate)["stop"] == fr.RATE_DONE).all()
     assert (np.concatenate(h_fq)["stop"] == fr.FQ_DONE).all()
     # the device: everything uploaded first, then 600 calls queued, then one synchronize
-    up = [{"infos": _t(tr["infos"], 32), "items": _t(tr["items"], 24), "frame_first": _t(tr["frame_first"]),
-           "sent": _t(tr["sent"], 24), "sent_first": _t(tr["sent_first"]), "now": _t(tr["now"]),
-           "ticks": _t(tr["ticks"], 32), "extra": _t(tr["extra"])} for tr in traffic]
-    d_q, d_log, d_s, d_e = _t(queues, 192), _t(log, 24), _t(states, 112), _t(entries, 16)
-    d_fl, d_fi = _t(flushes, 24), _t(flush_index)
-    d_steps = torch.zeros((n, 40), dtype=torch.uint8, device=DEV)
-    d_fq = torch.zeros((ticks, n, 80), dtype=torch.uint8, device=DEV)
-    d_rate = torch.zeros((ticks, n, 56), dtype=torch.uint8, device=DEV)
+    up = [{"infos": rows(tr["infos"], DEV), "items": rows(tr["items"], DEV), "frame_first": rows(tr["frame_first"], DEV),
+           "sent": rows(tr["sent"], DEV), "sent_first": rows(tr["sent_first"], DEV), "now": rows(tr["now"], DEV),
+           "ticks": rows(tr["ticks"], DEV), "extra": rows(tr["extra"], DEV)} for tr in traffic]
+    d_q, d_log, d_s, d_e = rows(queues, DEV), rows(log, DEV), rows(states, DEV), rows(entries, DEV)
+    d_fl, d_fi = rows(flushes, DEV), rows(flush_index, DEV)
+    d_steps = torch.zeros((n, fr.FRAME_QUEUE_STEP_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    d_fq = torch.zeros((ticks, n, fr.FRAME_QUEUE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    d_rate = torch.zeros((ticks, n, fr.RATE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     torch.cuda.synchronize()
     for t, u in enumerate(up):
         engine.rate_begin(d_s, u["now"], u["extra"], steps=d_steps, states_out=d_s)
@@ -300,23 +288,24 @@ def test_closed_loop_on_the_device(engine):
         d_fq[t].copy_(fq["results"])
         engine.rate_step(d_s, u["ticks"], d_fq[t], d_e, flushes=d_fl, flush_index=d_fi, results=d_rate[t], states_out=d_s)
     torch.cuda.synchronize()
-    same(_back(d_s, fr.RATE_STATE_DTYPE), h_s, "states")
-    same(_back(d_q, fr.FRAME_QUEUE_DTYPE), h_q, "queues")
-    same(_back(d_log, fr.SENT_FRAME_DTYPE), h_log, "log")
-    same(_back(d_e, fr.RECV_RATE_ENTRY_DTYPE), h_e, "entries")
-    same(_back(d_fl, fr.FLUSH_DTYPE), h_fl, "flushes")
-    same(_back(d_fq, fr.FRAME_QUEUE_RESULT_DTYPE), np.concatenate(h_fq), "frame queue results")
-    same(_back(d_rate, fr.RATE_RESULT_DTYPE), np.concatenate(h_rate), "rate results")
+    same(records(d_s, fr.RATE_STATE_DTYPE), h_s, "states")
+    same(records(d_q, fr.FRAME_QUEUE_DTYPE), h_q, "queues")
+    same(records(d_log, fr.SENT_FRAME_DTYPE), h_log, "log")
+    same(records(d_e, fr.RECV_RATE_ENTRY_DTYPE), h_e, "entries")
+    same(records(d_fl, fr.FLUSH_DTYPE), h_fl, "flushes")
+    same(records(d_fq, fr.FRAME_QUEUE_RESULT_DTYPE), np.concatenate(h_fq), "frame queue results")
+    same(records(d_rate, fr.RATE_RESULT_DTYPE), np.concatenate(h_rate), "rate results")
 
 
 def test_argument_checks(engine):
     states, entries = fr.new_rate_states(2, 1000, 2)
-    s, e = _t(states, 112), _t(entries, 16)
-    tk, fq = torch.zeros((2, 32), dtype=torch.uint8, device=DEV), torch.zeros((2, 80), dtype=torch.uint8, device=DEV)
+    s, e = rows(states, DEV), rows(entries, DEV)
+    tk = torch.zeros((2, fr.RATE_TICK_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    fq = torch.zeros((2, fr.FRAME_QUEUE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     with pytest.raises(ValueError):
         engine.rate_step(s, tk[:1], fq, e)
     with pytest.raises(ValueError):
-        engine.rate_step(s, tk, fq, e, flushes=torch.zeros((1, 24), dtype=torch.uint8, device=DEV))
+        engine.rate_step(s, tk, fq, e, flushes=rows(np.zeros(1, fr.FLUSH_DTYPE), DEV))
     with pytest.raises(ValueError):
         engine.rate_step(s, tk, fq, e, results=torch.zeros(10, dtype=torch.uint8, device=DEV))
     with pytest.raises(ValueError):
@@ -325,7 +314,7 @@ def test_argument_checks(engine):
     st = V(torch.cuda.current_stream().cuda_stream)
     L = fr.lib()
     p = lambda t: V(t.data_ptr())
-    res = torch.zeros((2, 56), dtype=torch.uint8, device=DEV)
+    res = torch.zeros((2, fr.RATE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
     assert L.ufc_rate_step_varlen(None, p(s), p(tk), p(fq), 2, p(e), 4, None, 0, None, None, 0, None, p(res), p(s), st) != 0
     assert L.ufc_rate_step_varlen(engine._ctx, None, None, None, 0, None, 0, None, 0, None, None, 0, None, None, None, st) == 0
     assert L.ufc_rate_step_varlen(engine._ctx, p(s), p(tk), p(fq), 2, p(e), 4, None, 0, None, None, 0, None, None, p(s), st) != 0

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from uflow_amd import frame as fr
+from uflow_amd.batch import records, rows
 from uflow_amd.frame import FLUSH_DTYPE, PACKET_DTYPE, SENDER_DTYPE
 
 import receive_expect as E
@@ -21,19 +22,11 @@ FRAG = E.FRAG
 U8 = np.uint8
 
 
-def _t(a, width=None):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.astype(np.int64)
-    t = torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
-    return t
-
-
 def _dev_args(infos, items, payload, frame_first, receivers, slots, slot_first, carry_in, src_base, frame_accept):
-    return dict(infos=_t(infos, 32), items=_t(items, 24), payload=_t(payload), frame_first=_t(frame_first),
-                receivers=_t(receivers, 560), slots=_t(slots, 32), slot_first=_t(slot_first), carry_in=_t(carry_in),
-                src_base=None if src_base is None else _t(src_base),
-                frame_accept=None if frame_accept is None else _t(frame_accept))
+    return dict(infos=rows(infos, DEV), items=rows(items, DEV), payload=rows(payload, DEV), frame_first=rows(frame_first, DEV),
+                receivers=rows(receivers, DEV), slots=rows(slots, DEV), slot_first=rows(slot_first, DEV), carry_in=rows(carry_in, DEV),
+                src_base=None if src_base is None else rows(src_base, DEV),
+                frame_accept=None if frame_accept is None else rows(frame_accept, DEV))
 
 
 def _host_out(d, d_slots):
@@ -47,7 +40,7 @@ def _host_out(d, d_slots):
         o[k] = o[k].astype(np.uint64)
     for k in ("packets_used", "out_used", "carry_used"):
         o[k] = int(o[k][0])
-    o["slots"] = d_slots.cpu().numpy().view(fr.RX_SLOT_DTYPE).reshape(-1)
+    o["slots"] = records(d_slots, fr.RX_SLOT_DTYPE)
     return o
 
 
@@ -56,8 +49,8 @@ def gpu_call(engine, stream=None):
     def call(infos, items, payload, frame_first, receivers, slots, slot_first, carry_in, src_base=None, frame_accept=None,
              carry_out=None, out_bytes=None, packets=None, **_):
         a = _dev_args(infos, items, payload, frame_first, receivers, slots, slot_first, carry_in, src_base, frame_accept)
-        opt = lambda x, w=None: None if x is None else _t(x, w)  # noqa: E731  (None: the wrapper's default caps)
-        d = engine.receive_packets(**a, carry_out=opt(carry_out), out_bytes=opt(out_bytes), packets=opt(packets, 24),
+        opt = lambda x: None if x is None else rows(x, DEV)  # noqa: E731  (None: the wrapper's default caps)
+        d = engine.receive_packets(**a, carry_out=opt(carry_out), out_bytes=opt(out_bytes), packets=opt(packets),
                                    stream=stream)
         torch.cuda.synchronize()
         o = _host_out(d, a["slots"])
@@ -96,7 +89,7 @@ def test_argument_checks(engine):
                   np.zeros(4, fr.RX_SLOT_DTYPE), np.array([0, 4], np.uint64), np.zeros(0, U8), None, None)
     o = engine.receive_packets(**a)
     torch.cuda.synchronize()
-    res = o["results"].cpu().numpy().view(fr.RECEIVER_RESULT_DTYPE).reshape(-1)
+    res = records(o["results"], fr.RECEIVER_RESULT_DTYPE)
     assert int(o["packets_used"][0]) == 0 and int(res["stop"][0]) == 0
     with pytest.raises(ValueError):
         engine.receive_packets(**{**a, "slot_first": a["slot_first"][:1]})
@@ -129,8 +122,8 @@ def test_slot_count_limit_of_the_device_entry(engine):
     import ctypes
     V = ctypes.c_void_p
     r = fr.new_receivers(1, 4)
-    d = {"receivers": _t(r, 560), "slots": _t(np.zeros(4, fr.RX_SLOT_DTYPE), 32),
-         "frame_first": _t(np.zeros(2, np.uint64)), "slot_first": _t(np.array([0, 4], np.uint64))}
+    d = {"receivers": rows(r, DEV), "slots": rows(np.zeros(4, fr.RX_SLOT_DTYPE), DEV),
+         "frame_first": rows(np.zeros(2, np.uint64), DEV), "slot_first": rows(np.array([0, 4], np.uint64), DEV)}
     buf = torch.zeros(4096, dtype=torch.uint8, device=DEV)
     at = lambda off: V(buf.data_ptr() + off)   # noqa: E731
     st = V(torch.cuda.current_stream().cuda_stream)
@@ -237,10 +230,10 @@ def test_four_steps_one_stream_no_synchronise(engine, family):
         a = _dev_args(b.infos, b.items, b.payload, b.frame_first, receivers, slots, slot_first, carry, b.src_base,
                       b.frame_accept)
         # the step's inputs in the header: deliver (byte 13) and resync_id (bytes 16..19)
-        a["deliver"] = _t(np.array(b.deliver, dtype=U8))
-        a["resync"] = _t(np.array(b.resync, dtype="<u4").view(U8).reshape(-1, 4))
+        a["deliver"] = rows(np.array(b.deliver, dtype=U8), DEV)
+        a["resync"] = rows(np.array(b.resync, dtype="<u4").view(U8).reshape(-1, 4), DEV)
         plan.append((b, exp, copy.deepcopy(rxs), a))
-    d_recv, d_slots, d_sf, d_carry = _t(receivers, 560), _t(slots, 32), _t(slot_first), _t(carry)
+    d_recv, d_slots, d_sf, d_carry = rows(receivers, DEV), rows(slots, DEV), rows(slot_first, DEV), rows(carry, DEV)
     torch.cuda.synchronize()
     s = torch.cuda.Stream(device=DEV)
     outs = []
@@ -256,13 +249,13 @@ def test_four_steps_one_stream_no_synchronise(engine, family):
                                        d_carry, src_base=a["src_base"], frame_accept=a["frame_accept"],
                                        carry_out=fill(E.carry_bound(b, d_carry.numel(), slots.size)),
                                        out_bytes=fill(d_carry.numel() + b.payload.size),
-                                       packets=fill(b.items.size + slots.size, 24), stream=s)
+                                       packets=fill(b.items.size + slots.size, fr.RX_PACKET_DTYPE.itemsize), stream=s)
             outs.append((d, d_slots.clone(), before))
             d_recv, d_carry = d["receivers_out"], d["carry_out"]   # the swap: the arena as it is, not cut to carry_used
     s.synchronize()
     for (b, exp, rxs_k, _), (d, slots_after, (recv_before, slots_before)) in zip(plan, outs):
-        E.check(_host_out(d, slots_after), exp, rxs_k, b, recv_before.cpu().numpy().view(fr.RECEIVER_DTYPE).reshape(-1),
-                slots_before.cpu().numpy().view(fr.RX_SLOT_DTYPE).reshape(-1), slot_first, what="queued step")
+        E.check(_host_out(d, slots_after), exp, rxs_k, b, records(recv_before, fr.RECEIVER_DTYPE),
+                records(slots_before, fr.RX_SLOT_DTYPE), slot_first, what="queued step")
     engine.release_stream(s)
     if family == "tiles":
         T.assert_tile_condition(set().union(*[rx.tags for rx in rxs]), rxs)
@@ -291,23 +284,23 @@ def test_emit_to_receive_on_the_device(engine):
     senders["window_size"], senders["max_alloc"], senders["take"] = 64, 1 << 30, per
     senders["window_parent_id"] = fr.NO_PARENT
     senders["channel_parent_id"] = fr.NO_PARENT
-    items, ff, _, sres, _, used = engine.emit_packets(_t(packets, 16), _t(np.arange(n + 1) * per), _t(senders, 304),
+    items, ff, _, sres, _, used = engine.emit_packets(rows(packets, DEV), rows(np.arange(n + 1) * per, DEV), rows(senders, DEV),
                                                       items_cap=int(np.maximum(1, (sizes + FRAG - 1) // FRAG).sum()))
     flushes = np.zeros(n, dtype=FLUSH_DTYPE)
     flushes["kind"], flushes["flush_alloc"], flushes["window_room"] = 10, 1 << 40, 1 << 20
-    infos, res, frames_used = engine.pack_flushes(items, ff, _t(flushes, 24))
-    wire, off, status = engine.build_varlen(infos, items, _t(payload), seal=True)
+    infos, res, frames_used = engine.pack_flushes(items, ff, rows(flushes, DEV))
+    wire, off, status = engine.build_varlen(infos, items, rows(payload, DEV), seal=True)
     torch.cuda.synchronize()
     n_frames = int(frames_used.cpu()[0])
     d_off = off[:n_frames + 1].contiguous()
     _, valid = engine.crc_varlen(wire, d_off)
     infos2, items2, used2 = engine.parse_varlen(wire, d_off, valid)
-    fres = res.cpu().numpy().view(fr.FLUSH_RESULT_DTYPE).reshape(-1)
+    fres = records(res, fr.FLUSH_RESULT_DTYPE)
     frame_first = np.concatenate([fres["frame_first"], [n_frames]]).astype(np.int64)
     receivers = fr.new_receivers(n, 64, senders["base_id"])
-    slots = torch.zeros((n * 64, 32), dtype=torch.uint8, device=DEV)
-    o = engine.receive_packets(infos2[:n_frames].contiguous(), items2, wire, _t(frame_first), _t(receivers, 560), slots,
-                               _t(np.arange(n + 1) * 64), torch.zeros(0, dtype=torch.uint8, device=DEV),
+    slots = torch.zeros((n * 64, fr.RX_SLOT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    o = engine.receive_packets(infos2[:n_frames].contiguous(), items2, wire, rows(frame_first, DEV), rows(receivers, DEV), slots,
+                               rows(np.arange(n + 1) * 64, DEV), torch.zeros(0, dtype=torch.uint8, device=DEV),
                                src_base=d_off[:n_frames].contiguous(), frame_accept=valid)
     torch.cuda.synchronize()
     h = _host_out(o, slots)

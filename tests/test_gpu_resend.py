@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from uflow_amd import frame as fr
+from uflow_amd.batch import records, rows
 
 import emit_expect as E
 import resend_expect as R
@@ -28,23 +29,11 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 U8 = np.uint8
-WIDTH = {"heap": 16, "pkts": 24, "frag_acked": None, "tx": 8, "ref_acked": None, "stage": 24}
-
-
-def _t(a, width=None):
-    a = np.ascontiguousarray(a)
-    if a.dtype in (np.uint64, np.uint32):
-        a = a.view(np.int64 if a.dtype == np.uint64 else np.int32)
-    return torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
 
 
 def _back(t, arr):
     """The device tensor's bytes into the host array it was made from."""
-    arr.view(U8).reshape(-1)[:] = t.cpu().numpy().view(U8).reshape(-1)
-
-
-def _np(t, dtype):
-    return t.cpu().numpy().view(U8).reshape(-1).view(dtype).copy()
+    arr[...] = records(t, arr.dtype).reshape(arr.shape)
 
 
 class GpuBackend:
@@ -60,7 +49,7 @@ class GpuBackend:
         return torch.cuda.stream(self.stream) if self.stream is not None else torch.cuda.stream(torch.cuda.current_stream())
 
     def up_arenas(self, arenas):
-        return {k: _t(v, WIDTH[k]) for k, v in arenas.items()}
+        return {k: rows(v, DEV) for k, v in arenas.items()}
 
     def down_arenas(self, d, arenas):
         for k in arenas:
@@ -68,80 +57,80 @@ class GpuBackend:
 
     def frame_queue(self, infos, items, frame_first, sent, sent_first, queues, steps, log, ref_acked):
         with self.ctx():
-            q, lg, ra = _t(queues, 192), _t(log, 24), _t(ref_acked)
-            d = self.e.frame_queue(_t(infos, 32), _t(items, 24), _t(frame_first), _t(sent, 24), _t(sent_first), q,
-                                   _t(steps, 40), lg, ra, queues_out=q, stream=self.stream)
+            q, lg, ra = rows(queues, DEV), rows(log, DEV), rows(ref_acked, DEV)
+            d = self.e.frame_queue(rows(infos, DEV), rows(items, DEV), rows(frame_first, DEV), rows(sent, DEV), rows(sent_first, DEV), q,
+                                   rows(steps, DEV), lg, ra, queues_out=q, stream=self.stream)
             self.sync()
         _back(q, queues), _back(lg, log), _back(ra, ref_acked)
-        return _np(d["results"], fr.FRAME_QUEUE_RESULT_DTYPE)
+        return records(d["results"], fr.FRAME_QUEUE_RESULT_DTYPE)
 
     def resend_begin(self, infos, frame_first, queues, log, rate, flushes, states, senders, arenas, flags):
         with self.ctx():
-            A, s, sd = self.up_arenas(arenas), _t(states, 104), _t(senders, 304)
-            d = self.e.resend_begin(_t(infos, 32), _t(frame_first), _t(queues, 192), _t(log, 24), _t(rate, 56),
-                                    _t(flushes, 24), s, sd, A, flags=_t(flags), states_out=s, senders_out=sd,
+            A, s, sd = self.up_arenas(arenas), rows(states, DEV), rows(senders, DEV)
+            d = self.e.resend_begin(rows(infos, DEV), rows(frame_first, DEV), rows(queues, DEV), rows(log, DEV), rows(rate, DEV),
+                                    rows(flushes, DEV), s, sd, A, flags=rows(flags, DEV), states_out=s, senders_out=sd,
                                     stream=self.stream)
             self.sync()
         self.down_arenas(A, arenas)
         _back(s, states), _back(sd, senders)
-        return _np(d["results"], fr.RESEND_RESULT_DTYPE)
+        return records(d["results"], fr.RESEND_RESULT_DTYPE)
 
     def emit(self, packets, packet_first, senders, items):
         with self.ctx():
-            it = _t(items, 24)
-            out = self.e.emit_packets(_t(packets, 16), _t(packet_first), _t(senders, 304), items.size, items=it,
+            it = rows(items, DEV)
+            out = self.e.emit_packets(rows(packets, DEV), rows(packet_first, DEV), rows(senders, DEV), items.size, items=it,
                                       stream=self.stream)
             self.sync()
         _back(it, items)
-        return (items, _np(out[1], np.uint64), _np(out[2], fr.PACKET_RESULT_DTYPE), _np(out[3], fr.SENDER_RESULT_DTYPE),
-                _np(out[4], fr.SENDER_DTYPE), int(out[5].item()))
+        return (items, records(out[1], np.uint64), records(out[2], fr.PACKET_RESULT_DTYPE), records(out[3], fr.SENDER_RESULT_DTYPE),
+                records(out[4], fr.SENDER_DTYPE), int(out[5].item()))
 
     def emit_state(self, packets, packet_first, senders):
         with self.ctx():
-            out = self.e.emit_packets(_t(packets, 16), _t(packet_first), _t(senders, 304), 0, stream=self.stream)
+            out = self.e.emit_packets(rows(packets, DEV), rows(packet_first, DEV), rows(senders, DEV), 0, stream=self.stream)
             self.sync()
-        return _np(out[3], fr.SENDER_RESULT_DTYPE), _np(out[4], fr.SENDER_DTYPE)
+        return records(out[3], fr.SENDER_RESULT_DTYPE), records(out[4], fr.SENDER_DTYPE)
 
     def resend_place(self, states, begin_results, arenas, flush_first, items):
         with self.ctx():
-            it = _t(items, 24)
-            self.e.resend_place(_t(states, 104), _t(begin_results, 48), {"stage": _t(arenas["stage"], 24)}, _t(flush_first),
+            it = rows(items, DEV)
+            self.e.resend_place(rows(states, DEV), rows(begin_results, DEV), {"stage": rows(arenas["stage"], DEV)}, rows(flush_first, DEV),
                                 it, stream=self.stream)
             self.sync()
         _back(it, items)
 
     def pack(self, items, flush_first, flushes):
         with self.ctx():
-            infos, results, used = self.e.pack_flushes(_t(items, 24), _t(flush_first), _t(flushes, 24), stream=self.stream)
+            infos, results, used = self.e.pack_flushes(rows(items, DEV), rows(flush_first, DEV), rows(flushes, DEV), stream=self.stream)
             self.sync()
-        return _np(infos, fr.FRAME_INFO_DTYPE), _np(results, fr.FLUSH_RESULT_DTYPE), int(used.item())
+        return records(infos, fr.FRAME_INFO_DTYPE), records(results, fr.FLUSH_RESULT_DTYPE), int(used.item())
 
     def build_sizes(self, infos, items):
         if infos.size == 0:
             return np.zeros(1, dtype=np.uint64)
         with self.ctx():
-            offsets, _ = self.e.build_sizes_varlen(_t(infos, 32), _t(items, 24), 1 << 40, stream=self.stream)
+            offsets, _ = self.e.build_sizes_varlen(rows(infos, DEV), rows(items, DEV), 1 << 40, stream=self.stream)
             self.sync()
-        return _np(offsets, np.uint64)
+        return records(offsets, np.uint64)
 
     def resend_commit(self, flush_results, infos, out_offsets, frames_used, items, flush_first, packets, packet_first,
                       packet_results, sender_results, begin_results, rate, states, senders, arenas, next_extra_flags=None,
                       states_out=None):
         with self.ctx():
             A = self.up_arenas({k: v for k, v in arenas.items() if k not in ("ref_acked", "stage")})
-            s, extra = _t(states, 104), _t(next_extra_flags)
-            d = self.e.resend_commit(_t(flush_results, 24), _t(infos, 32), _t(out_offsets),
-                                     torch.tensor([frames_used], dtype=torch.int64, device=DEV), _t(items, 24),
-                                     _t(flush_first), _t(packets, 16), _t(packet_first), _t(packet_results, 16),
-                                     _t(sender_results, 32), _t(begin_results, 48), _t(rate, 56), s, _t(senders, 304), A,
+            s, extra = rows(states, DEV), rows(next_extra_flags, DEV)
+            d = self.e.resend_commit(rows(flush_results, DEV), rows(infos, DEV), rows(out_offsets, DEV),
+                                     torch.tensor([frames_used], dtype=torch.int64, device=DEV), rows(items, DEV),
+                                     rows(flush_first, DEV), rows(packets, DEV), rows(packet_first, DEV), rows(packet_results, DEV),
+                                     rows(sender_results, DEV), rows(begin_results, DEV), rows(rate, DEV), s, rows(senders, DEV), A,
                                      next_extra_flags=extra, states_out=s, stream=self.stream)
             self.sync()
         for k in A:
             _back(A[k], arenas[k])
         _back(s, states)
-        return {"results": _np(d["results"], fr.RESEND_COMMIT_RESULT_DTYPE), "retake": _np(d["retake"], fr.SENDER_DTYPE),
-                "sent": _np(d["sent"], fr.SENT_FRAME_DTYPE), "sent_first": _np(d["sent_first"], np.uint64),
-                "next_extra_flags": _np(extra, np.uint32)}
+        return {"results": records(d["results"], fr.RESEND_COMMIT_RESULT_DTYPE), "retake": records(d["retake"], fr.SENDER_DTYPE),
+                "sent": records(d["sent"], fr.SENT_FRAME_DTYPE), "sent_first": records(d["sent_first"], np.uint64),
+                "next_extra_flags": records(extra, np.uint32)}
 
 
 def _same(dev, host, what):
@@ -423,45 +412,46 @@ def test_end_to_end_on_the_device(engine):
     frags = int(np.maximum(1, (sizes + 1447) // 1448).sum())
     IC = frags + n * 320       # item slots: every fragment new, and a full stage per connection
     FC = IC                    # frames
-    d = {k: _t(v, w) for k, v, w in (("packets", packets, 16), ("senders", senders, 304), ("queues", queues, 192),
-                                     ("log", log, 24), ("states", states, 104), ("rstates", rstates, 112),
-                                     ("entries", entries, 16), ("windows", windows, 24), ("receivers", receivers, 560))}
-    A = {k: _t(v, WIDTH[k]) for k, v in arenas.items()}
-    pf = _t(np.arange(n + 1, dtype=np.uint64) * per)
+    d = {k: rows(v, DEV) for k, v in (("packets", packets), ("senders", senders), ("queues", queues), ("log", log),
+                                      ("states", states), ("rstates", rstates), ("entries", entries),
+                                      ("windows", windows), ("receivers", receivers))}
+    A = {k: rows(v, DEV) for k, v in arenas.items()}
+    pf = rows(np.arange(n + 1, dtype=np.uint64) * per, DEV)
     owner = torch.arange(n * per, device=DEV) // per
     local = torch.arange(n * per, device=DEV) % per
-    d_payload = _t(payload)
+    d_payload = rows(payload, DEV)
     z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device=DEV)  # noqa: E731
-    flushes = _t(np.zeros(n, dtype=fr.FLUSH_DTYPE), 24)
+    zrec = lambda count, dt: z(count, dt.itemsize)  # noqa: E731
+    flushes = rows(np.zeros(n, dtype=fr.FLUSH_DTYPE), DEV)
     ack_fl = np.zeros(n, dtype=fr.FLUSH_DTYPE)
     ack_fl["kind"], ack_fl["flush_alloc"] = fr.ACK, 1 << 40
-    ack_flushes = _t(ack_fl, 24)
+    ack_flushes = rows(ack_fl, DEV)
     data_fl = np.zeros(n, dtype=fr.FLUSH_DTYPE)
     data_fl["kind"], data_fl["flush_alloc"] = fr.DATA, 4000
-    flushes.copy_(_t(data_fl, 24))
+    flushes.copy_(rows(data_fl, DEV))
     budget = flushes[:, 0:8].clone()
     idx = torch.arange(n, dtype=torch.int32, device=DEV)
     extra = z(n, dtype=torch.int32)
-    slots, slot_first = z(n * W, 32), _t(np.arange(n + 1, dtype=np.uint64) * W)
+    slots, slot_first = zrec(n * W, fr.RX_SLOT_DTYPE), rows(np.arange(n + 1, dtype=np.uint64) * W, DEV)
     carry = [z(1 << 21), z(1 << 21)]
     GC = n + FC                # ack groups, and so ack frames
-    ack_infos, ack_items, ack_ff = z(GC, 32), z(GC, 24), z(n + 1, dtype=torch.int64)
-    sent, sent_first, fres = z(FC, 24), z(n + 1, dtype=torch.int64), z(n, 24)
+    ack_infos, ack_items, ack_ff = zrec(GC, fr.FRAME_INFO_DTYPE), zrec(GC, fr.ITEM_DTYPE), z(n + 1, dtype=torch.int64)
+    sent, sent_first, fres = zrec(FC, fr.SENT_FRAME_DTYPE), z(n + 1, dtype=torch.int64), zrec(n, fr.FLUSH_RESULT_DTYPE)
     nonce = torch.from_numpy(rng.integers(0, 1 << 31, (FC + 31) // 32 + 1).astype(np.int32)).to(DEV)
     keep_data = torch.from_numpy((rng.random((TICKS, FC)) >= 0.2).astype(U8)).to(DEV)
     keep_ack = torch.from_numpy((rng.random((TICKS, GC)) >= 0.1).astype(U8)).to(DEV)
     keep_data[TICKS - QUIET:], keep_ack[TICKS - QUIET:] = 1, 1        # (the link is clean at the end: the queues drain)
     ticks_np = np.zeros((TICKS, n), dtype=fr.RATE_TICK_DTYPE)
     ticks_np["now_ms"], ticks_np["delta_time_s"] = (1000 + 20 * np.arange(TICKS))[:, None], 0.02
-    d_ticks = _t(ticks_np.reshape(-1), 32).reshape(TICKS, n, 32)
+    d_ticks = rows(ticks_np.reshape(-1), DEV).reshape(TICKS, n, -1)
     d_now = torch.from_numpy(ticks_np["now_ms"].astype(np.int64)).to(DEV)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
-    def build(infos, items, pay, offsets, rows):
-        out = z(rows * 1472)
+    def build(infos, items, pay, offsets, count):
+        out = z(count * 1472)
         check(lib().ufc_build_batch_varlen(engine._ctx, P(infos), P(items), items.shape[0], None, P(pay) if pay.numel() else None,
-                                           pay.numel(), rows, P(offsets), P(out), out.numel(), 1, None, st), "build")
+                                           pay.numel(), count, P(offsets), P(out), out.numel(), 1, None, st), "build")
         return out
 
     delivered, trace = [], []
@@ -500,7 +490,7 @@ def test_end_to_end_on_the_device(engine):
         fw = engine.frame_window(infos2, sent_first, d["windows"], groups_cap=GC, windows_out=d["windows"])
         rx = engine.receive_packets(infos2, items2, wire, sent_first, d["receivers"], slots, slot_first, carry[t % 2],
                                     src_base=offsets[:FC].contiguous(), frame_accept=fw["frame_accept"],
-                                    carry_out=carry[1 - t % 2], out_bytes=z(1 << 18), packets=z(n * per + 8, 24),
+                                    carry_out=carry[1 - t % 2], out_bytes=z(1 << 18), packets=zrec(n * per + 8, fr.RX_PACKET_DTYPE),
                                     receivers_out=d["receivers"], want_item_status=False)
         delivered.append((rx["packets"], rx["packet_first"], rx["out_bytes"], rx["results"]))
         trace.append((br, cm["results"], fres, fq, d["senders"][:, 0:8].clone(), d["receivers"][:, 0:8].clone()))
@@ -521,11 +511,11 @@ def test_end_to_end_on_the_device(engine):
         """One line per tick of connection c, for a failure's message."""
         out = []
         for t, ((b, m, f, q, sd, rv), (pk, pfirst, _, res)) in enumerate(zip(trace, delivered)):
-            b, m = _np(b, fr.RESEND_RESULT_DTYPE)[c], _np(m, fr.RESEND_COMMIT_RESULT_DTYPE)[c]
-            f, q = _np(f, fr.FLUSH_RESULT_DTYPE)[c], _np(q, fr.FRAME_QUEUE_RESULT_DTYPE)[c]
+            b, m = records(b, fr.RESEND_RESULT_DTYPE)[c], records(m, fr.RESEND_COMMIT_RESULT_DTYPE)[c]
+            f, q = records(f, fr.FLUSH_RESULT_DTYPE)[c], records(q, fr.FRAME_QUEUE_RESULT_DTYPE)[c]
             sd, rv = sd.cpu().numpy().view(np.uint32)[c], rv.cpu().numpy().view(np.uint32)[c]
-            res = _np(res, fr.RECEIVER_RESULT_DTYPE)[c]
-            seqs = _np(pk, fr.RX_PACKET_DTYPE)["sequence_id"][int(pfirst[c]): int(pfirst[c + 1])]
+            res = records(res, fr.RECEIVER_RESULT_DTYPE)[c]
+            seqs = records(pk, fr.RX_PACKET_DTYPE)["sequence_id"][int(pfirst[c]): int(pfirst[c + 1])]
             out.append(f"t{t} begin stop {int(b['stop'])} resent {int(b['n_resent'])} pend {int(b['n_pending_staged'])} freed "
                        f"{int(b['packets_freed'])} dead {int(b['heap_popped_dead'])} acked {int(b['heap_popped_acked'])} | pack frames "
                        f"{int(f['frame_count'])} items {int(f['items_packed'])} stop {int(f['stop'])} | commit stop {int(m['stop'])} take "
@@ -539,9 +529,9 @@ def test_end_to_end_on_the_device(engine):
     got = {}
     order = {}
     for pk, pfirst, ob, res in delivered:
-        res = _np(res, fr.RECEIVER_RESULT_DTYPE)
+        res = records(res, fr.RECEIVER_RESULT_DTYPE)
         assert (res["stop"] == 0).all()
-        pk, pfirst, ob = _np(pk, fr.RX_PACKET_DTYPE), pfirst.cpu().numpy(), ob.cpu().numpy()
+        pk, pfirst, ob = records(pk, fr.RX_PACKET_DTYPE), pfirst.cpu().numpy(), ob.cpu().numpy()
         for c in range(n):
             for r in pk[int(pfirst[c]): int(pfirst[c + 1])]:
                 key = (c, int(r["sequence_id"]))
@@ -554,8 +544,8 @@ def test_end_to_end_on_the_device(engine):
             want = payload[int(p["data_offset"]): int(p["data_offset"]) + int(p["data_len"])].tobytes()
             assert got.get((c, (int(base[c]) + k) & E.ID_MASK)) == want, f"packet {k} of connection {c} {p}\n" + timeline(c)
     assert len(got) == n * per and all(v == sorted(v) for v in order.values())
-    s = _np(d["states"], fr.RESEND_DTYPE)
-    sd = _np(d["senders"], fr.SENDER_DTYPE)
+    s = records(d["states"], fr.RESEND_DTYPE)
+    sd = records(d["senders"], fr.SENDER_DTYPE)
     assert (s["heap_len"] == 0).all() and (s["pending_count"] == 0).all(), (s["heap_len"], s["pending_count"])
     assert (sd["base_id"] == sd["next_id"]).all() and (sd["alloc"] == 0).all()
     assert int(s["tx_head"].min()) > 20   # (frames went out, and fragments were resent: more refs than fragments)

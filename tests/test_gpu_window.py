@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from uflow_amd import frame as fr
+from uflow_amd.batch import records, rows
 from uflow_amd.frame import FLUSH_DTYPE, PACKET_DTYPE, SENDER_DTYPE
 
 import window_expect as E
@@ -22,30 +23,23 @@ DEV = "cuda:0"
 U8 = np.uint8
 
 
-def _t(a, width=None):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.astype(np.int64)
-    return torch.from_numpy(a.view(U8).reshape(-1, width) if width else a.copy()).to(DEV)
-
-
 def _host_out(d):
     return {"frame_accept": d["frame_accept"].cpu().numpy(),
-            "groups": d["groups"].cpu().numpy().view(fr.ITEM_DTYPE).reshape(-1),
+            "groups": records(d["groups"], fr.ITEM_DTYPE),
             "group_first": d["group_first"].cpu().numpy().astype(np.uint64),
             "groups_used": int(d["groups_used"].cpu()[0]),
-            "results": d["results"].cpu().numpy().view(fr.FRAME_WINDOW_RESULT_DTYPE).reshape(-1),
-            "windows_out": d["windows_out"].cpu().numpy().view(fr.FRAME_WINDOW_DTYPE).reshape(-1)}
+            "results": records(d["results"], fr.FRAME_WINDOW_RESULT_DTYPE),
+            "windows_out": records(d["windows_out"], fr.FRAME_WINDOW_DTYPE)}
 
 
 def gpu_call(engine, stream=None):
     """test_window_cpu.host's calling convention on the device form.  (group_first and results are the wrapper's
     own tensors: the call writes every entry of both.)"""
     def call(infos, frame_first, windows, groups_cap, nthreads, frame_accept, groups, group_first, results, windows_out):
-        d_w = _t(windows, 24)
-        d = engine.frame_window(_t(infos, 32), _t(frame_first), d_w, groups_cap=groups_cap,
-                                frame_accept=_t(frame_accept), groups=_t(groups, 24),
-                                windows_out=d_w if windows_out is windows else _t(windows_out, 24), stream=stream)
+        d_w = rows(windows, DEV)
+        d = engine.frame_window(rows(infos, DEV), rows(frame_first, DEV), d_w, groups_cap=groups_cap,
+                                frame_accept=rows(frame_accept, DEV), groups=rows(groups, DEV),
+                                windows_out=d_w if windows_out is windows else rows(windows_out, DEV), stream=stream)
         (stream.synchronize if stream is not None else torch.cuda.synchronize)()
         o = _host_out(d)
         if windows_out is windows:
@@ -89,7 +83,7 @@ def test_equals_the_host_call(engine):
     rng = np.random.default_rng(61)
     infos, ff, w = E.make_batch(rng, T.COUNTS * 3, hostile_every=3)
     h = fr.frame_window_host(infos, ff, w, nthreads=4)
-    d = engine.frame_window(_t(infos, 32), _t(ff), _t(w, 24))
+    d = engine.frame_window(rows(infos, DEV), rows(ff, DEV), rows(w, DEV))
     torch.cuda.synchronize()
     o = _host_out(d)
     assert o["groups_used"] == h["groups_used"] > 0
@@ -103,7 +97,7 @@ def test_two_streams_two_batches(engine):
     a = E.make_batch(rng, [130, 65, 0, 64] * 40, hostile_every=4)
     b = E.make_batch(rng, [1, 63, 130] * 7, hostile_every=2)
     s1, s2 = torch.cuda.Stream(device=DEV), torch.cuda.Stream(device=DEV)
-    args = [(_t(x[0], 32), _t(x[1]), _t(x[2], 24)) for x in (a, b)]
+    args = [(rows(x[0], DEV), rows(x[1], DEV), rows(x[2], DEV)) for x in (a, b)]
     torch.cuda.synchronize()
     outs = []
     for _ in range(3):
@@ -124,11 +118,11 @@ def test_two_streams_two_batches(engine):
 
 def test_argument_checks(engine):
     infos, ff, w = T.golden_batch(T.GOLDEN[1])
-    a = (_t(infos, 32), _t(ff), _t(w, 24))
+    a = (rows(infos, DEV), rows(ff, DEV), rows(w, DEV))
     with pytest.raises(ValueError):
         engine.frame_window(a[0], a[1][:1], a[2])
     with pytest.raises(ValueError):
-        engine.frame_window(a[0], a[1], a[2], groups=torch.zeros((1, 24), dtype=torch.uint8, device=DEV), groups_cap=2)
+        engine.frame_window(a[0], a[1], a[2], groups=torch.zeros((1, fr.ITEM_DTYPE.itemsize), dtype=torch.uint8, device=DEV), groups_cap=2)
     V = ctypes.c_void_p
     st = V(torch.cuda.current_stream().cuda_stream)
     buf = torch.zeros(4096, dtype=torch.uint8, device=DEV)
@@ -149,7 +143,7 @@ def test_argument_checks(engine):
     assert call(engine._ctx, None, 0, None, None, 0, None, None, 0, None, None, None, None, st) == 0
     torch.cuda.synchronize()
     assert int(buf[640:648].cpu().numpy().view(np.uint64)[0]) == 2
-    d = engine.frame_window(a[0][:0], _t(np.zeros(1, np.uint64)), a[2][:0])   # no connections: UFC_OK
+    d = engine.frame_window(a[0][:0], rows(np.zeros(1, np.uint64), DEV), a[2][:0])   # no connections: UFC_OK
     assert d["groups"].shape[0] == 0
 
 
@@ -172,17 +166,17 @@ def test_whole_path_on_the_device(engine):
     senders["window_size"], senders["max_alloc"], senders["take"] = 64, 1 << 30, per
     senders["window_parent_id"] = fr.NO_PARENT
     senders["channel_parent_id"] = fr.NO_PARENT
-    items, iff, _, _, _, _ = engine.emit_packets(_t(packets, 16), _t(np.arange(n + 1) * per), _t(senders, 304),
+    items, iff, _, _, _, _ = engine.emit_packets(rows(packets, DEV), rows(np.arange(n + 1) * per, DEV), rows(senders, DEV),
                                                  items_cap=int(np.maximum(1, (sizes + FRAG - 1) // FRAG).sum()))
     first_ids = np.array([0xFFFFFFF8, 5, 0x12345678], dtype=np.uint64)   # (the first sender's ids wrap)
     flushes = np.zeros(n, dtype=FLUSH_DTYPE)
     flushes["kind"], flushes["flush_alloc"], flushes["window_room"], flushes["id0"] = fr.DATA, 1 << 40, 1 << 20, first_ids
     nonce_words = rng.integers(0, 1 << 32, 64, dtype=np.uint64).astype(np.uint32)
-    infos, res, frames_used = engine.pack_flushes(items, iff, _t(flushes, 24), nonce_bits=_t(nonce_words.view(np.int32)))
-    wire, off, _ = engine.build_varlen(infos, items, _t(payload), seal=True)
+    infos, res, frames_used = engine.pack_flushes(items, iff, rows(flushes, DEV), nonce_bits=rows(nonce_words.view(np.int32), DEV))
+    wire, off, _ = engine.build_varlen(infos, items, rows(payload, DEV), seal=True)
     torch.cuda.synchronize()
     nfr = int(frames_used.cpu()[0])
-    fres = res.cpu().numpy().view(fr.FLUSH_RESULT_DTYPE).reshape(-1)
+    fres = records(res, fr.FLUSH_RESULT_DTYPE)
     assert (fres["frame_count"] >= 12).all()
     wire_h, off_h = wire.cpu().numpy(), off.cpu().numpy()[:nfr + 1]
     # what arrives: per sender every fifth frame lost, every third of the rest repeated at once, one older frame late
@@ -204,21 +198,21 @@ def test_whole_path_on_the_device(engine):
     off2 = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     wire2 = np.concatenate([wire_h[off_h[g]:off_h[g + 1]] for g in arrive])
     frame_first = np.searchsorted(np.array(owner), np.arange(n + 1)).astype(np.int64)
-    d_wire, d_off = _t(wire2), _t(off2)
+    d_wire, d_off = rows(wire2, DEV), rows(off2, DEV)
     _, valid = engine.crc_varlen(d_wire, d_off)
     infos2, items2, _ = engine.parse_varlen(d_wire, d_off, valid)
     windows = fr.new_frame_windows(n, 4096, first_ids.astype(np.uint32))
-    fw = engine.frame_window(infos2, _t(frame_first), _t(windows, 24))
+    fw = engine.frame_window(infos2, rows(frame_first, DEV), rows(windows, DEV))
     receivers = fr.new_receivers(n, 64, senders["base_id"])
-    slots = torch.zeros((n * 64, 32), dtype=torch.uint8, device=DEV)
-    rx = engine.receive_packets(infos2, items2, d_wire, _t(frame_first), _t(receivers, 560), slots,
-                                _t(np.arange(n + 1) * 64), torch.zeros(0, dtype=torch.uint8, device=DEV),
+    slots = torch.zeros((n * 64, fr.RX_SLOT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    rx = engine.receive_packets(infos2, items2, d_wire, rows(frame_first, DEV), rows(receivers, DEV), slots,
+                                rows(np.arange(n + 1) * 64, DEV), torch.zeros(0, dtype=torch.uint8, device=DEV),
                                 src_base=d_off[:-1].contiguous(), frame_accept=fw["frame_accept"])
     torch.cuda.synchronize()
     o = _host_out(fw)
     assert valid.cpu().numpy().all()
     assert np.array_equal(o["frame_accept"], 1 - np.array(repeated, dtype=U8))
-    h_infos = infos2.cpu().numpy().view(fr.FRAME_INFO_DTYPE).reshape(-1)
+    h_infos = records(infos2, fr.FRAME_INFO_DTYPE)
     status = rx["item_status"].cpu().numpy()
     for i, f in enumerate(h_infos):
         st = status[int(f["item_first"]): int(f["item_first"]) + int(f["item_count"])]
@@ -229,11 +223,11 @@ def test_whole_path_on_the_device(engine):
         assert o[k].tobytes() == h[k].tobytes(), k
     # the acks: one ack flush per connection over the window's groups
     used = o["groups_used"]
-    rx_base = rx["receivers_out"].cpu().numpy().view(fr.RECEIVER_DTYPE).reshape(-1)["base_id"]
+    rx_base = records(rx["receivers_out"], fr.RECEIVER_DTYPE)["base_id"]
     ack = np.zeros(n, dtype=FLUSH_DTYPE)
     ack["kind"], ack["flush_alloc"] = fr.ACK, 1 << 40
     ack["id0"], ack["id1"] = o["windows_out"]["base_id"], rx_base
-    a_infos, a_res, a_used = engine.pack_flushes(fw["groups"][:used].contiguous(), fw["group_first"], _t(ack, 24))
+    a_infos, a_res, a_used = engine.pack_flushes(fw["groups"][:used].contiguous(), fw["group_first"], rows(ack, DEV))
     a_wire, a_off, a_status = engine.build_varlen(a_infos, fw["groups"][:used].contiguous(),
                                                   torch.zeros(0, dtype=torch.uint8, device=DEV), seal=True)
     torch.cuda.synchronize()
@@ -243,8 +237,8 @@ def test_whole_path_on_the_device(engine):
     _, a_valid = engine.crc_varlen(a_wire, a_off)
     p_infos, p_items, p_used = engine.parse_varlen(a_wire, a_off, a_valid)
     torch.cuda.synchronize()
-    p_infos = p_infos.cpu().numpy().view(fr.FRAME_INFO_DTYPE).reshape(-1)
-    p_items = p_items.cpu().numpy().view(fr.ITEM_DTYPE).reshape(-1)
+    p_infos = records(p_infos, fr.FRAME_INFO_DTYPE)
+    p_items = records(p_items, fr.ITEM_DTYPE)
     assert int(p_used.cpu()[0]) == used and a_valid.cpu().numpy().all()
     for s in range(n):
         f = p_infos[s]

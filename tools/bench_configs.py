@@ -62,11 +62,16 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import oracle  # noqa: E402  (the checker and the CPU baseline only)
-from uflow_amd import synth  # noqa: E402
-from uflow_amd.batch import FrameCrcEngine  # noqa: E402
+from uflow_amd import frame as fr, synth  # noqa: E402
+from uflow_amd.batch import FrameCrcEngine, records, rows  # noqa: E402
 
 PEAK = 8e12
 CHECK = True  # --no-check: skip the oracle comparisons and CPU baselines
+
+
+def zrows(n, dtype, dev):
+    """n zeroed device rows of a record dtype (what the stage calls write their records into)."""
+    return torch.zeros((n, dtype.itemsize), dtype=torch.uint8, device=dev)
 
 
 def timed(fn, reps, group=10):
@@ -413,15 +418,15 @@ def pack(eng, dev, reps, n=1_000_000):
     infos0, items0, used0 = eng.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
     k0 = int(used0.cpu()[0])
-    h_infos0 = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-    h_items = items0[:k0].cpu().numpy().view(ITEM_DTYPE).reshape(-1).copy()
+    h_infos0 = records(infos0, FRAME_INFO_DTYPE)
+    h_items = records(items0[:k0], ITEM_DTYPE)
     del infos0, items0
     # payload offsets relative to the whole batch (one source base, 0, for every new frame), then the datagrams alone
     frame_of = np.repeat(np.arange(n), h_infos0["item_count"])
     h_items["data_offset"] = (h_items["data_offset"] + offsets[frame_of]).astype(np.uint32)
     h_items = np.ascontiguousarray(h_items[h_items["form"] != 3])
     k = h_items.size
-    d_items = torch.from_numpy(h_items.view(np.uint8).reshape(-1, 24)).to(dev)
+    d_items = rows(h_items, dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     lib, ctx = N.lib(), eng._ctx
@@ -433,9 +438,9 @@ def pack(eng, dev, reps, n=1_000_000):
         flushes["kind"], flushes["flush_alloc"], flushes["window_room"] = 10, 1 << 50, 0xFFFFFFFF
         flushes["id0"] = np.arange(nf, dtype=np.uint32) * 7
         d_first = torch.from_numpy(first.astype(np.int64)).to(dev)
-        d_flushes = torch.from_numpy(flushes.view(np.uint8).reshape(-1, 24)).to(dev)
-        infos = torch.zeros((k, 32), dtype=torch.uint8, device=dev)
-        res = torch.zeros((nf, 24), dtype=torch.uint8, device=dev)
+        d_flushes = rows(flushes, dev)
+        infos = zrows(k, fr.FRAME_INFO_DTYPE, dev)
+        res = zrows(nf, fr.FLUSH_RESULT_DTYPE, dev)
         used = torch.zeros(1, dtype=torch.int64, device=dev)
         f_pack = lambda: lib.ufc_pack_varlen(ctx, p(d_items), k, p(d_first), p(d_flushes), nf, None, p(infos), k,  # noqa: E731
                                              p(res), p(used), st)
@@ -455,8 +460,8 @@ def pack(eng, dev, reps, n=1_000_000):
             host_ms[T] = float(np.median(ts)) * 1e3
         extra = {}
         if CHECK:
-            g_infos = infos[:frames].cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1)
-            g_res = res.cpu().numpy().view(FLUSH_RESULT_DTYPE).reshape(-1)
+            g_infos = records(infos[:frames], FRAME_INFO_DTYPE)
+            g_res = records(res, FLUSH_RESULT_DTYPE)
             extra["equals_host_pack"] = bool(frames == h_used and np.array_equal(g_infos, h_infos[:frames]) and
                                              np.array_equal(g_res, h_res))
         # the build's write over these frames
@@ -532,14 +537,14 @@ def emit(eng, dev, reps):
                 assert h_call(h_items.ctypes.data, k, T) == 0
                 ts.append(time.perf_counter() - t0)
             host_ms[T] = float(np.median(ts)) * 1e3
-        d_packets = torch.from_numpy(packets.view(np.uint8).reshape(-1, 16)).to(dev)
+        d_packets = rows(packets, dev)
         d_first = torch.from_numpy(first.astype(np.int64)).to(dev)
-        d_senders = torch.from_numpy(senders.view(np.uint8).reshape(-1, 304)).to(dev)
-        items = torch.zeros((k, 24), dtype=torch.uint8, device=dev)
+        d_senders = rows(senders, dev)
+        items = zrows(k, fr.ITEM_DTYPE, dev)
         ff = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
-        pres = torch.zeros((npk, 16), dtype=torch.uint8, device=dev)
-        sres = torch.zeros((ns, 32), dtype=torch.uint8, device=dev)
-        sout = torch.zeros((ns, 304), dtype=torch.uint8, device=dev)
+        pres = zrows(npk, fr.PACKET_RESULT_DTYPE, dev)
+        sres = zrows(ns, fr.SENDER_RESULT_DTYPE, dev)
+        sout = zrows(ns, fr.SENDER_DTYPE, dev)
         used = torch.zeros(1, dtype=torch.int64, device=dev)
         f_emit = lambda: lib.ufc_emit_packets_varlen(ctx, p(d_packets), npk, p(d_first), p(d_senders), ns, p(items), k,  # noqa: E731
                                                      p(ff), p(pres), p(sres), p(sout), p(used), st)
@@ -556,9 +561,9 @@ def emit(eng, dev, reps):
         # the pack over these items
         flushes = np.zeros(ns, dtype=FLUSH_DTYPE)
         flushes["kind"], flushes["flush_alloc"], flushes["window_room"] = 10, 1 << 50, 0xFFFFFFFF
-        d_flushes = torch.from_numpy(flushes.view(np.uint8).reshape(-1, 24)).to(dev)
-        infos = torch.zeros((k, 32), dtype=torch.uint8, device=dev)
-        fres = torch.zeros((ns, 24), dtype=torch.uint8, device=dev)
+        d_flushes = rows(flushes, dev)
+        infos = zrows(k, fr.FRAME_INFO_DTYPE, dev)
+        fres = zrows(ns, fr.FLUSH_RESULT_DTYPE, dev)
         fused = torch.zeros(1, dtype=torch.int64, device=dev)
         f_pack = lambda: lib.ufc_pack_varlen(ctx, p(items), k, p(ff), p(d_flushes), ns, None, p(infos), k, p(fres),  # noqa: E731
                                              p(fused), st)
@@ -599,8 +604,8 @@ def receive(eng, dev, reps, n=1_000_000):
     infos0, items0, used0 = eng.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
     k = int(used0.cpu()[0])
-    h_infos = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1).copy()
-    h_items0 = items0[:k].cpu().numpy().view(ITEM_DTYPE).reshape(-1).copy()
+    h_infos = records(infos0, FRAME_INFO_DTYPE)
+    h_items0 = records(items0[:k], ITEM_DTYPE)
     h_valid = valid.cpu().numpy().copy()
     del infos0, items0
     counted = (h_infos["ok"] != 0) & (h_infos["kind"] == 10) & (h_valid != 0)
@@ -651,15 +656,14 @@ def receive(eng, dev, reps, n=1_000_000):
             host_ms[T] = float(np.median(ts)) * 1e3
         delivered, out_used = int(hu[1].value), int(hu[2].value)
         # device
-        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
-        g = {"infos": t(h_infos, 32), "accept": t(h_valid), "items": t(items, 24), "src": t(src_base.astype(np.int64)),
-             "ff": t(ff.astype(np.int64)), "recv": t(recv, 560), "slots": torch.zeros((ns, 32), dtype=torch.uint8, device=dev),
-             "sf": t(slot_first.astype(np.int64)), "carry_out": torch.zeros(caps["carry"], dtype=torch.uint8, device=dev),
+        g = {"infos": rows(h_infos, dev), "accept": rows(h_valid, dev), "items": rows(items, dev), "src": rows(src_base.astype(np.int64), dev),
+             "ff": rows(ff.astype(np.int64), dev), "recv": rows(recv, dev), "slots": zrows(ns, fr.RX_SLOT_DTYPE, dev),
+             "sf": rows(slot_first.astype(np.int64), dev), "carry_out": torch.zeros(caps["carry"], dtype=torch.uint8, device=dev),
              "cf": torch.zeros(nr + 1, dtype=torch.int64, device=dev), "used": torch.zeros(3, dtype=torch.int64, device=dev),
-             "packets": torch.zeros((k, 24), dtype=torch.uint8, device=dev),
+             "packets": zrows(k, fr.RX_PACKET_DTYPE, dev),
              "pf": torch.zeros(nr + 1, dtype=torch.int64, device=dev), "out": torch.zeros(pay, dtype=torch.uint8, device=dev),
-             "status": torch.zeros(k, dtype=torch.uint8, device=dev), "res": torch.zeros((nr, 80), dtype=torch.uint8, device=dev),
-             "rout": torch.zeros((nr, 560), dtype=torch.uint8, device=dev)}
+             "status": torch.zeros(k, dtype=torch.uint8, device=dev), "res": zrows(nr, fr.RECEIVER_RESULT_DTYPE, dev),
+             "rout": zrows(nr, fr.RECEIVER_DTYPE, dev)}
         u = g["used"].data_ptr()
         f_rx = lambda: lib.ufc_receive_packets_varlen(  # noqa: E731
             ctx, p(g["infos"]), n, p(g["accept"]), p(g["items"]), k, p(g["src"]), p(d), pay, p(g["ff"]), p(g["recv"]), nr,
@@ -717,7 +721,7 @@ def window(eng, dev, reps, n=1_000_000):
     _, valid = eng.crc_varlen(d, o)
     infos0, _, _ = eng.parse_varlen(d, o, valid)
     torch.cuda.synchronize()
-    h_infos0 = infos0.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1).copy()
+    h_infos0 = records(infos0, FRAME_INFO_DTYPE)
     del infos0, d, o
     torch.cuda.empty_cache()
     is_data = (h_infos0["ok"] != 0) & (h_infos0["kind"] == 10)
@@ -757,11 +761,10 @@ def window(eng, dev, reps, n=1_000_000):
                 assert h_call(T) == 0
                 ts.append(time.perf_counter() - t0)
             host_ms[T] = float(np.median(ts)) * 1e3
-        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
-        g = {"infos": t(infos, 32), "ff": t(ff.astype(np.int64)), "win": t(win, 24),
-             "accept": torch.zeros(n, dtype=torch.uint8, device=dev), "groups": torch.zeros((cap, 24), dtype=torch.uint8, device=dev),
+        g = {"infos": rows(infos, dev), "ff": rows(ff.astype(np.int64), dev), "win": rows(win, dev),
+             "accept": torch.zeros(n, dtype=torch.uint8, device=dev), "groups": zrows(cap, fr.ITEM_DTYPE, dev),
              "gf": torch.zeros(nw + 1, dtype=torch.int64, device=dev), "used": torch.zeros(1, dtype=torch.int64, device=dev),
-             "res": torch.zeros((nw, 40), dtype=torch.uint8, device=dev), "wout": torch.zeros((nw, 24), dtype=torch.uint8, device=dev)}
+             "res": zrows(nw, fr.FRAME_WINDOW_RESULT_DTYPE, dev), "wout": zrows(nw, fr.FRAME_WINDOW_DTYPE, dev)}
         f_fw = lambda: lib.ufc_frame_window_varlen(  # noqa: E731
             ctx, p(g["infos"]), n, p(g["ff"]), p(g["win"]), nw, p(g["accept"]), p(g["groups"]), cap, p(g["gf"]), p(g["used"]),
             p(g["res"]), p(g["wout"]), st)
@@ -865,11 +868,10 @@ def queue(eng, dev, reps, n=1_000_000):
                 assert h_call(T) == 0
                 ts.append(time.perf_counter() - t0)
             host_ms[T] = float(np.median(ts)) * 1e3
-        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a).to(dev)  # noqa: E731
-        g = {"infos": t(infos, 32), "items": t(items, 24), "ff": t(ff.astype(np.int64)), "none": t(none.astype(np.int64)),
-             "queues": t(queues, 192), "steps": t(steps, 40), "log0": t(log, 24), "log": t(log, 24),
+        g = {"infos": rows(infos, dev), "items": rows(items, dev), "ff": rows(ff.astype(np.int64), dev), "none": rows(none.astype(np.int64), dev),
+             "queues": rows(queues, dev), "steps": rows(steps, dev), "log0": rows(log, dev), "log": rows(log, dev),
              "refs": torch.zeros(nq * W, dtype=torch.uint8, device=dev),
-             "res": torch.zeros((nq, 80), dtype=torch.uint8, device=dev), "qout": torch.zeros((nq, 192), dtype=torch.uint8, device=dev)}
+             "res": zrows(nq, fr.FRAME_QUEUE_RESULT_DTYPE, dev), "qout": zrows(nq, fr.FRAME_QUEUE_DTYPE, dev)}
 
         def restore():
             g["log"].copy_(g["log0"])
@@ -1009,10 +1011,9 @@ def rate(eng, dev, reps, n=None):
         looked = fed | ((res["flags"] & N.UFC_RATE_NOFEEDBACK) != 0) & (mode == 2)
         read = nq * (112 + 32 + 80 + 4 + 24 + 4) + 16 * int(count[looked].sum())
         written = nq * (112 + 56 + 8) + 16 * int(fed.sum())
-        t = lambda a, w=None: torch.from_numpy(a.view(np.uint8).reshape(-1, w) if w else a.view(np.int32)).to(dev)  # noqa: E731
-        g = {"states": t(states, 112), "ticks": t(ticks, 32), "fq": t(fq, 80), "entries0": t(entries, 16),
-             "entries": t(entries, 16), "fres": t(fres, 24), "ri": t(ri), "flushes": t(flushes, 24), "fi": t(fi),
-             "res": torch.zeros((nq, 56), dtype=torch.uint8, device=dev), "out": torch.zeros((nq, 112), dtype=torch.uint8, device=dev),
+        g = {"states": rows(states, dev), "ticks": rows(ticks, dev), "fq": rows(fq, dev), "entries0": rows(entries, dev),
+             "entries": rows(entries, dev), "fres": rows(fres, dev), "ri": rows(ri, dev), "flushes": rows(flushes, dev), "fi": rows(fi, dev),
+             "res": zrows(nq, fr.RATE_RESULT_DTYPE, dev), "out": zrows(nq, fr.RATE_STATE_DTYPE, dev),
              "src": torch.zeros((read + written) // 2, dtype=torch.uint8, device=dev),
              "dst": torch.zeros((read + written) // 2, dtype=torch.uint8, device=dev)}
         restore = lambda: g["entries"].copy_(g["entries0"])  # noqa: E731
@@ -1164,29 +1165,27 @@ def resend(eng, dev, reps):
             n_items * 24 * 3 + nq * (104 + 304 + 48 + 24 + 32 + 56) + nq * NEW * 32 + frames_used * 40 + K * nq * 16
         written = nq * (104 + 304 + 48) + LIVE * nq + K * nq * 16 * 2 + n_items * 24 * 2 + nq * (104 + 304 + 40 + 8) + \
             nq * NEW * 25 + n_items * 8 + frames_used * 24
-        t = lambda a, w=None: torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a).view(np.uint8).reshape(-1, w) if w  # noqa: E731
-                                               else (a.view(np.int64) if a.dtype == np.uint64 else a).copy()).to(dev)
         host_final = {n_: A[n_].copy() for n_ in pristine}   # (what the host calls left, before the state goes up pristine)
         restore_host()
-        g = {"heap": t(A["heap"], 16), "pkts": t(A["pkts"], 24), "frag_acked": t(A["frag_acked"]), "tx": t(A["tx"], 8),
-             "ref_acked": t(A["ref_acked"]), "stage": t(A["stage"], 24)}
+        g = {"heap": rows(A["heap"], dev), "pkts": rows(A["pkts"], dev), "frag_acked": rows(A["frag_acked"], dev), "tx": rows(A["tx"], dev),
+             "ref_acked": rows(A["ref_acked"], dev), "stage": rows(A["stage"], dev)}
         g0 = {n_: g[n_].clone() for n_ in ("heap", "frag_acked", "ref_acked")}
-        d = {"infos": t(infos, 32), "ff": t(frame_first), "queues": t(queues, 192), "log": t(log, 24), "rate": t(rate_r, 56),
-             "flushes": t(flushes, 24), "states": t(states, 104), "senders": t(senders, 304), "packets": t(packets, 16),
-             "pf": t(packet_first), "pres": t(pres, 16), "sres": t(sres, 32), "fres": t(fres, 24), "frames": t(frames, 32),
-             "offs": t(offs), "used": torch.tensor([frames_used], dtype=torch.int64, device=dev), "flush_first": t(flush_first)}
+        d = {"infos": rows(infos, dev), "ff": rows(frame_first, dev), "queues": rows(queues, dev), "log": rows(log, dev), "rate": rows(rate_r, dev),
+             "flushes": rows(flushes, dev), "states": rows(states, dev), "senders": rows(senders, dev), "packets": rows(packets, dev),
+             "pf": rows(packet_first, dev), "pres": rows(pres, dev), "sres": rows(sres, dev), "fres": rows(fres, dev), "frames": rows(frames, dev),
+             "offs": rows(offs, dev), "used": torch.tensor([frames_used], dtype=torch.int64, device=dev), "flush_first": rows(flush_first, dev)}
         restore = lambda: [g[n_].copy_(v) for n_, v in g0.items()]  # noqa: E731
         rb = eng.resend_begin(d["infos"], d["ff"], d["queues"], d["log"], d["rate"], d["flushes"], d["states"], d["senders"], g)
-        items_d = t(E_fill(items, flush_first, br), 24)   # (the reserved slots empty, as the emit leaves them)
+        items_d = rows(E_fill(items, flush_first, br), dev)   # (the reserved slots empty, as the emit leaves them)
         f_begin = lambda: eng.resend_begin(d["infos"], d["ff"], d["queues"], d["log"], d["rate"], d["flushes"], d["states"],  # noqa: E731
                                            d["senders"], g, results=rb["results"], states_out=rb["states_out"],
                                            senders_out=rb["senders_out"])
         f_place = lambda: eng.resend_place(rb["states_out"], rb["results"], g, d["flush_first"], items_d)  # noqa: E731
         torch.cuda.synchronize()
         heap_mid_d = g["heap"].clone()
-        rc = eng.resend_commit(d["fres"], d["frames"], d["offs"], d["used"], t(items, 24), d["flush_first"], d["packets"], d["pf"],
+        rc = eng.resend_commit(d["fres"], d["frames"], d["offs"], d["used"], rows(items, dev), d["flush_first"], d["packets"], d["pf"],
                                d["pres"], d["sres"], rb["results"], d["rate"], rb["states_out"], rb["senders_out"], g)
-        items_full = t(items, 24)
+        items_full = rows(items, dev)
         f_commit = lambda: eng.resend_commit(d["fres"], d["frames"], d["offs"], d["used"], items_full, d["flush_first"],  # noqa: E731
                                              d["packets"], d["pf"], d["pres"], d["sres"], rb["results"], d["rate"],
                                              rb["states_out"], rb["senders_out"], g, sent=rc["sent"], results=rc["results"],

@@ -62,10 +62,26 @@ UFC_RATE_AWAIT_SEND, UFC_RATE_SLOW_START, UFC_RATE_THROUGHPUT_EQN = 0, 1, 2
 UFC_RATE_FRAME_SENT = 1
 UFC_RATE_DONE, UFC_RATE_BAD_STATE, UFC_RATE_REF_PANIC, UFC_RATE_RECV_FULL = 0, 1, 2, 3
 UFC_RATE_FEEDBACK, UFC_RATE_NOFEEDBACK, UFC_RATE_RESET_ISSUED, UFC_RATE_ENTERED_EQN, UFC_RATE_INV_STALLED = 1, 2, 4, 8, 16
+# the batched resend (include/uflow_frame_codec.h): a transmission record's flag, a connection's flag, why it stopped
+UFC_TX_RESEND = 1
+UFC_RS_NO_DATA_FLUSH = 1
+(UFC_RS_DONE, UFC_RS_SIZE_LIMITED, UFC_RS_WINDOW_LIMITED, UFC_RS_REF_HANG, UFC_RS_BAD_STATE, UFC_RS_STAGE_FULL,
+ UFC_RS_HEAP_FULL) = range(7)
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
-_V, _Z = ctypes.c_void_p, ctypes.c_size_t
+_V, _Z, _I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+# ufc_parse_batch_*: data, offsets, n, valid, infos, items, items_cap
+_PARSE_ARGS = [_V, _V, _Z, _V, _V, _V, _Z]
+# ufc_build_sizes_*: infos, items, n_items, src_base, payload_len, n, out_offsets, status
+_BUILD_SIZES_ARGS = [_V, _V, _Z, _V, _Z, _Z, _V, _V]
+# ufc_build_batch_*: infos, items, n_items, src_base, payload, payload_len, n, out_offsets, out, out_cap, seal, crc_out
+_BUILD_ARGS = [_V, _V, _Z, _V, _V, _Z, _Z, _V, _V, _Z, _I, _V]
+# ufc_pack_*: items, n_items, flush_first, flushes, n_flushes, nonce_bits, infos, frames_cap, results
+_PACK_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V]
+# ufc_emit_packets_*: packets, n_packets, packet_first, senders, n_senders, items, items_cap, flush_first,
+# packet_results, sender_results, senders_out
+_EMIT_ARGS = [_V, _Z, _V, _V, _Z, _V, _Z, _V, _V, _V, _V]
 _RX_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, _Z, _V, _V, _V, _Z, _V,
             _V, _V, _V]
 _FW_ARGS = [_V, _Z, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V]
@@ -155,40 +171,18 @@ _SIGNATURES = {
     "ufc_ack_frame_builder_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
     "ufc_builder_size": (ctypes.c_size_t, [ctypes.c_void_p]),
     "ufc_builder_build": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),
-    "ufc_parse_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                            ctypes.POINTER(ctypes.c_size_t), ctypes.c_int]),
-    "ufc_parse_batch_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_void_p]),
-    "ufc_build_sizes_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_int]),
-    "ufc_build_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
-                                            ctypes.c_int]),
-    "ufc_build_sizes_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p]),
-    "ufc_build_batch_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p]),
-    "ufc_pack_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                     ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
-    "ufc_pack_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ufc_emit_packets_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
-    "ufc_emit_packets_varlen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p]),
+    # each stage: the shared arguments, then its used count (where it has one), then nthreads (host) / ctx first and
+    # stream last (device)
+    "ufc_parse_batch_host": (_I, _PARSE_ARGS + [ctypes.POINTER(_Z), _I]),
+    "ufc_parse_batch_varlen": (_I, [_V] + _PARSE_ARGS + [_V, _V]),
+    "ufc_build_sizes_host": (_I, _BUILD_SIZES_ARGS + [_I]),
+    "ufc_build_batch_host": (_I, _BUILD_ARGS + [_I]),
+    "ufc_build_sizes_varlen": (_I, [_V] + _BUILD_SIZES_ARGS + [_V]),
+    "ufc_build_batch_varlen": (_I, [_V] + _BUILD_ARGS + [_V]),
+    "ufc_pack_host": (_I, _PACK_ARGS + [ctypes.POINTER(ctypes.c_uint64), _I]),
+    "ufc_pack_varlen": (_I, [_V] + _PACK_ARGS + [_V, _V]),
+    "ufc_emit_packets_host": (_I, _EMIT_ARGS + [ctypes.POINTER(ctypes.c_uint64), _I]),
+    "ufc_emit_packets_varlen": (_I, [_V] + _EMIT_ARGS + [_V, _V]),
     # infos, n_frames, frame_accept, items, n_items, src_base, payload, payload_len, frame_first, receivers,
     # n_receivers, slots, slot_first, n_slots, carry_in, carry_in_len, carry_out, carry_cap, carry_first, carry_used,
     # packets, packets_cap, packet_first, packets_used, out_bytes, out_cap, out_used, item_status, results,
@@ -221,7 +215,8 @@ _SIGNATURES = {
 SYMBOLS = tuple(_SIGNATURES)
 
 
-# Structs of include/uflow_frame_codec.h (layouts checked by tests/test_codec_cpu.py).
+# Structs of include/uflow_frame_codec.h the Python side instantiates (layouts checked against the
+# header by tests/test_records_cpu.py; every other record is a numpy dtype in records.py).
 class FrameInfo(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint8), ("ok", ctypes.c_uint8), ("aux", ctypes.c_uint8), ("crc_ok", ctypes.c_uint8),
                 ("f", ctypes.c_uint32 * 5), ("item_count", ctypes.c_uint32), ("item_first", ctypes.c_uint32)]
@@ -232,184 +227,6 @@ class Item(ctypes.Structure):
                 ("window_parent_lead", ctypes.c_uint16), ("channel_parent_lead", ctypes.c_uint16),
                 ("fragment_id", ctypes.c_uint16), ("fragment_id_last", ctypes.c_uint16), ("flags", ctypes.c_uint16),
                 ("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32)]
-
-
-class Flush(ctypes.Structure):
-    _fields_ = [("flush_alloc", ctypes.c_int64), ("kind", ctypes.c_uint32), ("window_room", ctypes.c_uint32),
-                ("id0", ctypes.c_uint32), ("id1", ctypes.c_uint32)]
-
-
-class FlushResult(ctypes.Structure):
-    _fields_ = [("frame_first", ctypes.c_uint32), ("frame_count", ctypes.c_uint32), ("items_packed", ctypes.c_uint32),
-                ("stop", ctypes.c_uint32), ("alloc_left", ctypes.c_int64)]
-
-
-class Packet(ctypes.Structure):
-    _fields_ = [("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32), ("flush_id", ctypes.c_uint32),
-                ("channel_id", ctypes.c_uint8), ("mode", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
-
-
-class Sender(ctypes.Structure):
-    _fields_ = [("base_id", ctypes.c_uint32), ("next_id", ctypes.c_uint32), ("window_size", ctypes.c_uint32),
-                ("flush_id", ctypes.c_uint32), ("alloc", ctypes.c_uint64), ("max_alloc", ctypes.c_uint64),
-                ("window_parent_id", ctypes.c_uint32), ("take", ctypes.c_uint32), ("reserve_items", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32), ("channel_parent_id", ctypes.c_uint32 * 64)]
-
-
-class PacketResult(ctypes.Structure):
-    _fields_ = [("sequence_id", ctypes.c_uint32), ("item_first", ctypes.c_uint32), ("item_count", ctypes.c_uint32),
-                ("status", ctypes.c_uint8), ("resend", ctypes.c_uint8), ("reserved", ctypes.c_uint16)]
-
-
-class SenderResult(ctypes.Structure):
-    _fields_ = [("item_first", ctypes.c_uint32), ("item_count", ctypes.c_uint32), ("packets_consumed", ctypes.c_uint32),
-                ("packets_emitted", ctypes.c_uint32), ("packets_dropped", ctypes.c_uint32), ("stop", ctypes.c_uint32),
-                ("bytes_dropped", ctypes.c_uint64)]
-
-
-class Receiver(ctypes.Structure):
-    _fields_ = [("base_id", ctypes.c_uint32), ("end_id", ctypes.c_uint32), ("window_size", ctypes.c_uint32),
-                ("window_ready", ctypes.c_uint8), ("deliver", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
-                ("resync_id", ctypes.c_uint32), ("reserved2", ctypes.c_uint32), ("alloc", ctypes.c_uint64),
-                ("max_alloc", ctypes.c_uint64), ("channel_ready_flags", ctypes.c_uint64),
-                ("channel_base_id", ctypes.c_uint32 * 64), ("channel_packet_count", ctypes.c_uint32 * 64)]
-
-
-class RxSlot(ctypes.Structure):
-    _fields_ = [("data_offset", ctypes.c_uint64), ("data_len", ctypes.c_uint32), ("asm_size", ctypes.c_uint32),
-                ("asm_window_parent_lead", ctypes.c_uint16), ("asm_channel_parent_lead", ctypes.c_uint16),
-                ("asm_last_fragment_id", ctypes.c_uint16), ("asm_received", ctypes.c_uint16),
-                ("rx_window_parent_lead", ctypes.c_uint16), ("rx_channel_parent_lead", ctypes.c_uint16),
-                ("asm_state", ctypes.c_uint8), ("asm_channel_id", ctypes.c_uint8), ("rx_channel_id", ctypes.c_uint8),
-                ("rx_flags", ctypes.c_uint8)]
-
-
-class RxPacket(ctypes.Structure):
-    _fields_ = [("out_offset", ctypes.c_uint64), ("sequence_id", ctypes.c_uint32), ("len", ctypes.c_uint32),
-                ("channel_id", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
-                ("reserved2", ctypes.c_uint32)]
-
-
-class ReceiverResult(ctypes.Structure):
-    _fields_ = [("packet_first", ctypes.c_uint32), ("packet_count", ctypes.c_uint32),
-                ("status_count", ctypes.c_uint32 * 11), ("packets_completed", ctypes.c_uint32),
-                ("packets_dud", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32), ("bytes_delivered", ctypes.c_uint64)]
-
-
-class FrameWindow(ctypes.Structure):
-    _fields_ = [("base_id", ctypes.c_uint32), ("size", ctypes.c_uint32), ("tail_base_id", ctypes.c_uint32),
-                ("tail_bitfield", ctypes.c_uint32), ("tail_nonce", ctypes.c_uint8), ("has_tail", ctypes.c_uint8),
-                ("sync_reply", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("reserved2", ctypes.c_uint32)]
-
-
-class FrameWindowResult(ctypes.Structure):
-    _fields_ = [("group_first", ctypes.c_uint32), ("group_count", ctypes.c_uint32), ("accepted", ctypes.c_uint32),
-                ("refused", ctypes.c_uint32), ("syncs", ctypes.c_uint32), ("packet_syncs", ctypes.c_uint32),
-                ("first_packet_sync", ctypes.c_uint32), ("advanced", ctypes.c_uint32), ("stop", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
-
-
-class SentFrame(ctypes.Structure):
-    _fields_ = [("send_time_ms", ctypes.c_uint64), ("size", ctypes.c_uint32), ("ref_first", ctypes.c_uint32),
-                ("ref_count", ctypes.c_uint32), ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
-
-
-class FrameQueue(ctypes.Structure):
-    _fields_ = [("log_base_id", ctypes.c_uint32), ("log_next_id", ctypes.c_uint32), ("window_base_id", ctypes.c_uint32),
-                ("window_size", ctypes.c_uint32), ("tail_size", ctypes.c_uint32), ("rb_base_id", ctypes.c_uint32),
-                ("rb_max_span", ctypes.c_uint32), ("rb_frames", ctypes.c_uint32 * 2), ("rb_count", ctypes.c_uint32),
-                ("rate_limited", ctypes.c_uint8), ("has_ack_data", ctypes.c_uint8), ("ack_rate_limited", ctypes.c_uint8),
-                ("has_last_feedback", ctypes.c_uint8), ("li_count", ctypes.c_uint32),
-                ("ack_last_send_time_ms", ctypes.c_uint64), ("ack_total_size", ctypes.c_uint64),
-                ("last_feedback_ms", ctypes.c_uint64), ("li_end_time_ms", ctypes.c_uint64 * 9),
-                ("li_length", ctypes.c_uint32 * 9), ("log_cap", ctypes.c_uint32), ("log_first", ctypes.c_uint64)]
-
-
-class FrameQueueStep(ctypes.Structure):
-    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("rtt_ms", ctypes.c_uint64),
-                ("thresh_ms", ctypes.c_uint64), ("now_ms", ctypes.c_uint64), ("reset_loss_rate", ctypes.c_double)]
-
-
-class FrameQueueResult(ctypes.Structure):
-    _fields_ = [("stop", ctypes.c_uint32), ("pushes_taken", ctypes.c_uint32), ("pushes_refused", ctypes.c_uint32),
-                ("ack_frames", ctypes.c_uint32), ("groups", ctypes.c_uint32), ("groups_dud", ctypes.c_uint32),
-                ("groups_unknown", ctypes.c_uint32), ("groups_bad_nonce", ctypes.c_uint32),
-                ("frames_acked", ctypes.c_uint32), ("li_acks", ctypes.c_uint32), ("li_nacks", ctypes.c_uint32),
-                ("window_advanced", ctypes.c_uint32), ("log_culled", ctypes.c_uint32), ("window_room", ctypes.c_uint32),
-                ("has_feedback", ctypes.c_uint8), ("rate_limited", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
-                ("receive_rate", ctypes.c_uint32), ("rtt_ms", ctypes.c_uint64), ("loss_rate", ctypes.c_double)]
-
-
-class RecvRateEntry(ctypes.Structure):
-    _fields_ = [("timestamp_ms", ctypes.c_uint64), ("value", ctypes.c_uint32), ("is_initial", ctypes.c_uint8),
-                ("reserved", ctypes.c_uint8 * 3)]
-
-
-class RateState(ctypes.Structure):
-    _fields_ = [("mode", ctypes.c_uint32), ("send_rate", ctypes.c_uint32), ("max_send_rate", ctypes.c_uint32),
-                ("send_rate_tcp", ctypes.c_uint32), ("has_time_last_doubled", ctypes.c_uint8),
-                ("has_nofeedback_exp", ctypes.c_uint8), ("nofeedback_idle", ctypes.c_uint8),
-                ("has_rtt_s", ctypes.c_uint8), ("has_rtt_ms", ctypes.c_uint8), ("has_rto_ms", ctypes.c_uint8),
-                ("has_last_flush", ctypes.c_uint8), ("has_reset", ctypes.c_uint8),
-                ("time_last_doubled_ms", ctypes.c_uint64), ("prev_loss_rate", ctypes.c_double),
-                ("nofeedback_exp_ms", ctypes.c_uint64), ("rtt_s", ctypes.c_double), ("rtt_ms", ctypes.c_uint64),
-                ("rto_ms", ctypes.c_uint64), ("now_ms", ctypes.c_uint64), ("flush_alloc", ctypes.c_int64),
-                ("reset_loss_rate", ctypes.c_double), ("recv_first", ctypes.c_uint64),
-                ("recv_count", ctypes.c_uint32), ("recv_cap", ctypes.c_uint32)]
-
-
-class RateTick(ctypes.Structure):
-    _fields_ = [("now_ms", ctypes.c_uint64), ("delta_time_s", ctypes.c_double), ("alloc_adjust", ctypes.c_int64),
-                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
-
-
-class RateResult(ctypes.Structure):
-    _fields_ = [("stop", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("now_ms", ctypes.c_uint64),
-                ("rtt_ms", ctypes.c_uint64), ("rto_ms", ctypes.c_uint64), ("flush_alloc", ctypes.c_int64),
-                ("send_rate", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("inv_iterations", ctypes.c_uint32),
-                ("recv_count", ctypes.c_uint32)]
-
-
-class ResendEntry(ctypes.Structure):
-    _fields_ = [("resend_time_ms", ctypes.c_uint64), ("sequence_id", ctypes.c_uint32), ("fragment_id", ctypes.c_uint16),
-                ("send_count", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
-
-
-class SentPacket(ctypes.Structure):
-    _fields_ = [("data_offset", ctypes.c_uint32), ("data_len", ctypes.c_uint32), ("frag_first", ctypes.c_uint32),
-                ("sequence_id", ctypes.c_uint32), ("window_parent_lead", ctypes.c_uint16),
-                ("channel_parent_lead", ctypes.c_uint16), ("channel_id", ctypes.c_uint8), ("resend", ctypes.c_uint8),
-                ("reserved", ctypes.c_uint16)]
-
-
-class TxRef(ctypes.Structure):
-    _fields_ = [("sequence_id", ctypes.c_uint32), ("fragment_id", ctypes.c_uint16), ("flags", ctypes.c_uint16)]
-
-
-class Resend(ctypes.Structure):
-    _fields_ = [("heap_first", ctypes.c_uint64), ("heap_cap", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
-                ("pkt_first", ctypes.c_uint64), ("pkt_cap", ctypes.c_uint32), ("frag_next", ctypes.c_uint32),
-                ("frag_first", ctypes.c_uint64), ("frag_cap", ctypes.c_uint32), ("tx_cap", ctypes.c_uint32),
-                ("tx_first", ctypes.c_uint64), ("tx_head", ctypes.c_uint32), ("tx_tail", ctypes.c_uint32),
-                ("stage_first", ctypes.c_uint64), ("stage_cap", ctypes.c_uint32), ("pending_seq", ctypes.c_uint32),
-                ("pending_next", ctypes.c_uint32), ("pending_count", ctypes.c_uint32),
-                ("pending_resend", ctypes.c_uint8), ("reserved0", ctypes.c_uint8), ("reserved1", ctypes.c_uint16),
-                ("reserved2", ctypes.c_uint32), ("window_bytes", ctypes.c_uint64)]
-
-
-class ResendResult(ctypes.Structure):
-    _fields_ = [("stop", ctypes.c_uint32), ("n_resent", ctypes.c_uint32), ("n_pending_staged", ctypes.c_uint32),
-                ("heap_popped_dead", ctypes.c_uint32), ("heap_popped_acked", ctypes.c_uint32),
-                ("packets_freed", ctypes.c_uint32), ("refs_acked", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
-                ("pending_count", ctypes.c_uint32), ("acks_ignored", ctypes.c_uint32), ("bytes_freed", ctypes.c_uint64)]
-
-
-class ResendCommitResult(ctypes.Structure):
-    _fields_ = [("stop", ctypes.c_uint32), ("pending_packed", ctypes.c_uint32), ("packets_entered", ctypes.c_uint32),
-                ("heap_pushed", ctypes.c_uint32), ("heap_dropped", ctypes.c_uint32), ("refs_written", ctypes.c_uint32),
-                ("frames", ctypes.c_uint32), ("take", ctypes.c_uint32), ("heap_len", ctypes.c_uint32),
-                ("pending_count", ctypes.c_uint32)]
 
 
 class Builder(ctypes.Structure):

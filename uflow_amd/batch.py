@@ -9,12 +9,20 @@ Per frame i:  crc[i] = compute(frame_i[:-4]),  valid[i] = len_i >= 5 and crc[i] 
 CRC words are returned as int32 tensors holding the uint32 bit patterns
 (`crc.cpu().numpy().view(numpy.uint32)`).
 """
+import contextlib
 import ctypes
 
 import numpy as np
 import torch
 
 from ._native import lib, check
+from .frame import _RS_ARENA_DTYPE
+from .records import (FLUSH_DTYPE, FLUSH_RESULT_DTYPE, FRAME_INFO_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_RESULT_DTYPE,
+                      FRAME_QUEUE_STEP_DTYPE, FRAME_WINDOW_DTYPE, FRAME_WINDOW_RESULT_DTYPE, ITEM_DTYPE, PACKET_DTYPE,
+                      PACKET_RESULT_DTYPE, RATE_RESULT_DTYPE, RATE_STATE_DTYPE, RATE_TICK_DTYPE, RECEIVER_DTYPE,
+                      RECEIVER_RESULT_DTYPE, RECV_RATE_ENTRY_DTYPE, RESEND_COMMIT_RESULT_DTYPE, RESEND_DTYPE,
+                      RESEND_RESULT_DTYPE, RX_PACKET_DTYPE, RX_SLOT_DTYPE, SENDER_DTYPE, SENDER_RESULT_DTYPE,
+                      SENT_FRAME_DTYPE)
 
 
 # Items of a flush whose frame chain one wave of the pack resolves in LDS at a time (kPackTile, csrc/frame_pack.hpp).
@@ -25,6 +33,35 @@ EMIT_TILE = 64
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _pn(t, count):
+    """The stage calls' pointer rule: NULL for no tensor and when the count that goes with it is 0."""
+    return _ptr(t) if count else None
+
+
+def rows(a, device):
+    """A numpy array as the device calls take it, on `device`: a structured (record) array becomes uint8[n, itemsize]
+    rows, uint64 goes up as int64 and uint32 as int32 (the same bits), any other plain array as it is.  Always a
+    fresh copy, never an alias of a's buffer (also on the CPU)."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.names is not None:
+        a = a.reshape(-1).view(np.uint8).reshape(a.size, a.dtype.itemsize)
+    elif a.dtype == np.uint64:
+        a = a.view(np.int64)
+    elif a.dtype == np.uint32:
+        a = a.view(np.int32)
+    device = torch.device(device)
+    if device.type == "cpu" or not a.flags.writeable:
+        a = a.copy()
+    return torch.from_numpy(a).to(device)
+
+
+def records(t, dtype):
+    """The tensor's bytes as a fresh, flat host array of `dtype` (a record dtype for rows, or a plain one: an int64
+    CSR reads back as numpy.uint64)."""
+    b = t.detach().contiguous().cpu().numpy().reshape(-1)
+    return b.view(np.uint8).view(dtype).copy()
 
 
 class FrameCrcEngine:
@@ -173,20 +210,46 @@ class FrameCrcEngine:
                                        self._stream(stream)), "ufc_hbm_read_probe")
         return nread.value
 
+    # ---- the stage calls' argument helpers ----
+    def _rec(self, name, t, dtype, count=None):
+        """A record argument: uint8 rows of dtype.itemsize bytes each (what rows() makes), at least `count` of them,
+        checked like _check before the C ABI sees the pointer.  Returns the number of records t holds (0 for None)."""
+        if t is None:
+            return 0
+        w = dtype.itemsize
+        self._check(name, t, (torch.uint8,), w * (count or 0))
+        if t.numel() % w or (t.dim() == 2 and t.shape[1] != w):
+            raise ValueError(f"{name} must hold rows of {w} bytes, got shape {tuple(t.shape)}")
+        return t.numel() // w
+
+    @contextlib.contextmanager
+    def _outputs(self, stream):
+        """Makes the stream a call is queued on torch's current one and yields z(given, count, kind): `given` when
+        the caller supplied it, else `count` zeroed entries, filled on that stream.  kind: a record dtype (uint8 rows
+        of its itemsize) or a torch dtype (1-D)."""
+        def z(given, count, kind=torch.uint8):
+            if given is not None:
+                return given
+            shape = (count, kind.itemsize) if isinstance(kind, np.dtype) else count
+            return torch.zeros(shape, dtype=torch.uint8 if isinstance(kind, np.dtype) else kind, device=self.device)
+
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            yield z
+
     # ---- Frame::read past the gate, on the device (uflow_frame_codec.h) ----
     def parse_varlen(self, data, offsets, valid, items_cap=None, stream=None):
         """Batched Frame::read of a CSR batch after the CRC gate (`valid`, from crc_varlen).
-        Returns (infos uint8[n, 32], items uint8[items_cap, 24], items_used int64[1]) device tensors;
-        the byte rows are ufc_frame_info / ufc_item records (numpy views: uflow_amd.frame
-        FRAME_INFO_DTYPE / ITEM_DTYPE).  items_cap defaults to a bound no batch can exceed."""
+        Returns (infos rows[n], items rows[items_cap], items_used int64[1]) device tensors; the byte rows are
+        ufc_frame_info / ufc_item records (records(infos, FRAME_INFO_DTYPE) reads them on the host).  items_cap
+        defaults to a bound no batch can exceed."""
         n = offsets.numel() - 1
         self._check("offsets", offsets, (torch.int64,), 1)
         self._check("data", data, (torch.uint8,), 0)
         self._check("valid", valid, (torch.uint8,), n)
         if items_cap is None:  # a datagram takes >= 6 bytes, an ack group 9
             items_cap = max(1, data.numel() // 6)
-        infos = torch.empty((max(n, 0), 32), dtype=torch.uint8, device=self.device)
-        items = torch.empty((items_cap, 24), dtype=torch.uint8, device=self.device)
+        infos = torch.empty((max(n, 0), FRAME_INFO_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        items = torch.empty((items_cap, ITEM_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
         used = torch.zeros(1, dtype=torch.int64, device=self.device)
         check(lib().ufc_parse_batch_varlen(self._ctx, self._bytes_ptr(data), _ptr(offsets), n, _ptr(valid), _ptr(infos),
                                            _ptr(items), items_cap, _ptr(used), self._stream(stream)),
@@ -196,19 +259,19 @@ class FrameCrcEngine:
     # ---- Frame::write of a batch, on the device (uflow_frame_codec.h) ----
     def build_sizes_varlen(self, infos, items, payload_len, src_base=None, n_items=None, stream=None):
         """ufc_build_sizes_varlen: (out_offsets int64[n + 1], status uint8[n]) of the frames the records
-        describe (infos uint8[n, 32], items uint8[*, 24]: what parse_varlen returns)."""
+        describe (infos rows[n] of ufc_frame_info, items rows of ufc_item: what parse_varlen returns)."""
         n = infos.shape[0]
         n_items = items.shape[0] if n_items is None else int(n_items)
-        self._check("infos", infos, (torch.uint8,), 32 * n)
-        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n)
+        self._rec("items", items, ITEM_DTYPE, n_items)
         self._check("src_base", src_base, (torch.int64,), n)
         # (no fill kernel on torch's current stream: the call writes all n + 1 offsets on `stream`)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device) if n else \
             torch.zeros(1, dtype=torch.int64, device=self.device)
         status = torch.empty(n, dtype=torch.uint8, device=self.device)
-        check(lib().ufc_build_sizes_varlen(self._ctx, _ptr(infos), _ptr(items) if n_items else None, n_items,
-                                           _ptr(src_base), int(payload_len), n, _ptr(offsets), _ptr(status),
-                                           self._stream(stream)), "ufc_build_sizes_varlen")
+        check(lib().ufc_build_sizes_varlen(self._ctx, _ptr(infos), _pn(items, n_items), n_items, _ptr(src_base),
+                                           int(payload_len), n, _ptr(offsets), _ptr(status), self._stream(stream)),
+              "ufc_build_sizes_varlen")
         return offsets, status
 
     def build_varlen(self, infos, items, payload, src_base=None, seal=True, out=None, stream=None, n_items=None,
@@ -234,41 +297,36 @@ class FrameCrcEngine:
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=self.device)
         self._check("out", out, (torch.uint8,), total)
-        check(lib().ufc_build_batch_varlen(self._ctx, _ptr(infos), _ptr(items) if n_items else None, n_items,
-                                           _ptr(src_base), _ptr(payload) if payload.numel() else None, payload.numel(),
-                                           n, _ptr(offsets), _ptr(out) if out.numel() else None, out.numel(),
-                                           1 if seal else 0, _ptr(crc_out), self._stream(stream)),
-              "ufc_build_batch_varlen")
+        check(lib().ufc_build_batch_varlen(self._ctx, _ptr(infos), _pn(items, n_items), n_items, _ptr(src_base),
+                                           _pn(payload, payload.numel()), payload.numel(), n, _ptr(offsets),
+                                           _pn(out, out.numel()), out.numel(), 1 if seal else 0, _ptr(crc_out),
+                                           self._stream(stream)), "ufc_build_batch_varlen")
         return out, offsets, status
 
     # ---- the emitters' push / finalize of many flushes, on the device (uflow_frame_codec.h) ----
     def pack_flushes(self, items, flush_first, flushes, frames_cap=None, nonce_bits=None, stream=None):
         """ufc_pack_varlen: cut every flush's items into frames as DataFrameEmitter / AckFrameEmitter do
-        (src/half_connection/emit.rs:47-125, 170-211).  items uint8[n_items, 24] (ufc_item records, what
-        parse_varlen returns), flush_first int64[n_flushes + 1] (CSR over the items), flushes uint8[n_flushes, 24]
-        (ufc_flush records, uflow_amd.frame.FLUSH_DTYPE), nonce_bits int32 words (bit g: the nonce of the batch's
-        g-th frame; default 0).  Returns (infos uint8[frames_cap, 32], results uint8[n_flushes, 24], frames_used
-        int64[1]) device tensors; frames_cap defaults to n_items, which is always enough.  infos is one that
-        build_varlen takes as is: the rows from frames_used on are zero, which the build skips (or pass
-        infos[:frames_used])."""
+        (src/half_connection/emit.rs:47-125, 170-211).  items rows[n_items] (ufc_item records, what parse_varlen
+        returns), flush_first int64[n_flushes + 1] (CSR over the items), flushes rows[n_flushes] (ufc_flush records,
+        FLUSH_DTYPE), nonce_bits int32 words (bit g: the nonce of the batch's g-th frame; default 0).  Returns (infos
+        rows[frames_cap] of ufc_frame_info, results rows[n_flushes] of ufc_flush_result, frames_used int64[1]) device
+        tensors; frames_cap defaults to n_items, which is always enough.  infos is one that build_varlen takes as is:
+        the rows from frames_used on are zero, which the build skips (or pass infos[:frames_used])."""
         n_items = items.shape[0]
         n = flushes.shape[0]
         if frames_cap is None:
             frames_cap = n_items
         frames_cap = int(frames_cap)
-        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._rec("items", items, ITEM_DTYPE, n_items)
         self._check("flush_first", flush_first, (torch.int64,), n + 1)
-        self._check("flushes", flushes, (torch.uint8,), 24 * n)
+        self._rec("flushes", flushes, FLUSH_DTYPE, n)
         self._check("nonce_bits", nonce_bits, (torch.int32, torch.uint32), (frames_cap + 31) // 32)
-        # (the outputs are zeroed on the stream the pack is queued on)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            infos = torch.zeros((frames_cap, 32), dtype=torch.uint8, device=self.device)
-            results = torch.zeros((n, 24), dtype=torch.uint8, device=self.device)
-            used = torch.zeros(1, dtype=torch.int64, device=self.device)
-        check(lib().ufc_pack_varlen(self._ctx, _ptr(items) if n_items else None, n_items, _ptr(flush_first),
-                                    _ptr(flushes) if n else None, n, _ptr(nonce_bits),
-                                    _ptr(infos) if frames_cap else None, frames_cap, _ptr(results) if n else None,
-                                    _ptr(used), self._stream(stream)), "ufc_pack_varlen")
+        with self._outputs(stream) as z:
+            infos, results = z(None, frames_cap, FRAME_INFO_DTYPE), z(None, n, FLUSH_RESULT_DTYPE)
+            used = z(None, 1, torch.int64)
+        check(lib().ufc_pack_varlen(self._ctx, _pn(items, n_items), n_items, _ptr(flush_first), _pn(flushes, n), n,
+                                    _ptr(nonce_bits), _pn(infos, frames_cap), frames_cap, _pn(results, n), _ptr(used),
+                                    self._stream(stream)), "ufc_pack_varlen")
         return infos, results, used
 
     # ---- PacketSender::emit_packet and fragmentation of many senders, on the device (uflow_frame_codec.h) ----
@@ -276,39 +334,32 @@ class FrameCrcEngine:
                      want_packet_results=True, stream=None):
         """ufc_emit_packets_varlen: turn every sender's queued packets into datagram items as
         PacketSender::emit_packet and PendingPacket do (src/half_connection/packet_sender.rs:149-238,
-        pending_packet.rs:23-42, 84-103).  packets uint8[n_packets, 16] (ufc_packet records,
-        uflow_amd.frame.PACKET_DTYPE), packet_first int64[n_senders + 1] (CSR over the packets), senders
-        uint8[n_senders, 304] (ufc_sender records, SENDER_DTYPE).  Returns (items uint8[items_cap, 24], flush_first
-        int64[n_senders + 1], packet_results uint8[n_packets, 16] or None, sender_results uint8[n_senders, 32],
-        senders_out uint8[n_senders, 304], items_used int64[1]) device tensors: items and flush_first are what
-        pack_flushes takes (items[:items_used] when items_cap is larger).  Items at an index >= items_cap are not
-        written (compare items_used); each sender's reserve_items slots stay as they were (zero in a tensor
-        allocated here).  `items`: a tensor to write into; senders_out: where the state after the consumed
-        packets goes (may be `senders`)."""
+        pending_packet.rs:23-42, 84-103).  packets rows[n_packets] (ufc_packet records, PACKET_DTYPE), packet_first
+        int64[n_senders + 1] (CSR over the packets), senders rows[n_senders] (ufc_sender records, SENDER_DTYPE).
+        Returns (items rows[items_cap] of ufc_item, flush_first int64[n_senders + 1], packet_results rows[n_packets]
+        of ufc_packet_result or None, sender_results rows[n_senders] of ufc_sender_result, senders_out
+        rows[n_senders], items_used int64[1]) device tensors: items and flush_first are what pack_flushes takes
+        (items[:items_used] when items_cap is larger).  Items at an index >= items_cap are not written (compare
+        items_used); each sender's reserve_items slots stay as they were (zero in a tensor allocated here).  `items`:
+        a tensor to write into; senders_out: where the state after the consumed packets goes (may be `senders`)."""
         n_packets = packets.shape[0]
         n = senders.shape[0]
         items_cap = int(items_cap)
-        self._check("packets", packets, (torch.uint8,), 16 * n_packets)
+        self._rec("packets", packets, PACKET_DTYPE, n_packets)
         self._check("packet_first", packet_first, (torch.int64,), n + 1)
-        self._check("senders", senders, (torch.uint8,), 304 * n)
-        self._check("items", items, (torch.uint8,), 24 * items_cap)
-        self._check("senders_out", senders_out, (torch.uint8,), 304 * n)
-        # (the outputs are zeroed on the stream the emit is queued on)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if items is None:
-                items = torch.zeros((items_cap, 24), dtype=torch.uint8, device=self.device)
-            flush_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-            packet_results = torch.zeros((n_packets, 16), dtype=torch.uint8, device=self.device) \
-                if want_packet_results else None
-            sender_results = torch.zeros((n, 32), dtype=torch.uint8, device=self.device)
-            if senders_out is None:
-                senders_out = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
-            used = torch.zeros(1, dtype=torch.int64, device=self.device)
-        check(lib().ufc_emit_packets_varlen(self._ctx, _ptr(packets) if n_packets else None, n_packets,
-                                            _ptr(packet_first), _ptr(senders) if n else None, n,
-                                            _ptr(items) if items_cap else None, items_cap, _ptr(flush_first),
-                                            _ptr(packet_results) if want_packet_results and n_packets else None,
-                                            _ptr(sender_results) if n else None, _ptr(senders_out) if n else None,
+        self._rec("senders", senders, SENDER_DTYPE, n)
+        self._rec("items", items, ITEM_DTYPE, items_cap)
+        self._rec("senders_out", senders_out, SENDER_DTYPE, n)
+        with self._outputs(stream) as z:
+            items = z(items, items_cap, ITEM_DTYPE)
+            flush_first = z(None, n + 1, torch.int64)
+            packet_results = z(None, n_packets, PACKET_RESULT_DTYPE) if want_packet_results else None
+            sender_results = z(None, n, SENDER_RESULT_DTYPE)
+            senders_out = z(senders_out, n, SENDER_DTYPE)
+            used = z(None, 1, torch.int64)
+        check(lib().ufc_emit_packets_varlen(self._ctx, _pn(packets, n_packets), n_packets, _ptr(packet_first),
+                                            _pn(senders, n), n, _pn(items, items_cap), items_cap, _ptr(flush_first),
+                                            _pn(packet_results, n_packets), _pn(sender_results, n), _pn(senders_out, n),
                                             _ptr(used), self._stream(stream)), "ufc_emit_packets_varlen")
         return items, flush_first, packet_results, sender_results, senders_out, used
 
@@ -318,36 +369,38 @@ class FrameCrcEngine:
                         carry_out=None, out_bytes=None, packets=None, receivers_out=None, want_item_status=True,
                         stream=None):
         """ufc_receive_packets_varlen: one step of PacketReceiver (handle_datagram, receive, resynchronize;
-        src/half_connection/packet_receiver/mod.rs:142-435) for every receiver.  infos uint8[n_frames, 32] and
-        items uint8[n_items, 24] (what parse_varlen returns), payload uint8 (the frames' bytes) with src_base
-        int64[n_frames] (the parse's offsets; None: zero), frame_first int64[n_receivers + 1] (CSR over the frames),
-        receivers uint8[n_receivers, 560] (ufc_receiver records, uflow_amd.frame.RECEIVER_DTYPE), slots
-        uint8[n_slots, 32] (ufc_rx_slot, updated in place), slot_first int64[n_receivers + 1], carry_in uint8 (the
-        carry arena the slots point into), frame_accept uint8[n_frames] or None.  Returns a dict of device tensors:
-        packets uint8[packets_cap, 24], packet_first int64[n + 1], packets_used, out_bytes, out_used, carry_out,
-        carry_first int64[n + 1], carry_used, item_status uint8[n_items] or None, results uint8[n, 80],
-        receivers_out uint8[n, 560] (may be given as `receivers`).  Caps that are not given are what the step needs,
+        src/half_connection/packet_receiver/mod.rs:142-435) for every receiver.  infos rows[n_frames] and items
+        rows[n_items] (what parse_varlen returns), payload uint8 (the frames' bytes) with src_base int64[n_frames]
+        (the parse's offsets; None: zero), frame_first int64[n_receivers + 1] (CSR over the frames), receivers
+        rows[n_receivers] (ufc_receiver records, RECEIVER_DTYPE), slots rows[n_slots] (ufc_rx_slot, updated in
+        place), slot_first int64[n_receivers + 1], carry_in uint8 (the carry arena the slots point into),
+        frame_accept uint8[n_frames] or None.  Returns a dict of device tensors: packets rows[packets_cap] of
+        ufc_rx_packet, packet_first int64[n + 1], packets_used, out_bytes, out_used, carry_out, carry_first
+        int64[n + 1], carry_used, item_status uint8[n_items] or None, results rows[n] of ufc_receiver_result,
+        receivers_out rows[n] (may be given as `receivers`).  Caps that are not given are what the step needs,
         found by a first pass on a copy of the state with caps of zero, whose counts are read back (this waits for
         the stream; give the caps or the tensors to stay asynchronous: an ACTIVE slot holds its whole fragment
         buffer, so the carry has no small bound from the batch's sizes alone, see the header); tensors given for
         carry_out, out_bytes and packets are written into.
         Pass carry_out[:carry_used] as the next step's carry_in (carry_out must not overlap carry_in)."""
         n_frames, n_items, n, n_slots = infos.shape[0], items.shape[0], receivers.shape[0], slots.shape[0]
-        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
-        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n_frames)
+        self._rec("items", items, ITEM_DTYPE, n_items)
         self._check("payload", payload, (torch.uint8,), 0)
         self._check("frame_first", frame_first, (torch.int64,), n + 1)
-        self._check("receivers", receivers, (torch.uint8,), 560 * n)
-        self._check("slots", slots, (torch.uint8,), 32 * n_slots)
+        self._rec("receivers", receivers, RECEIVER_DTYPE, n)
+        self._rec("slots", slots, RX_SLOT_DTYPE, n_slots)
         self._check("slot_first", slot_first, (torch.int64,), n + 1)
         self._check("carry_in", carry_in, (torch.uint8,), 0)
         self._check("src_base", src_base, (torch.int64,), n_frames)
         self._check("frame_accept", frame_accept, (torch.uint8,), n_frames)
-        self._check("receivers_out", receivers_out, (torch.uint8,), 560 * n)
-        for name, t in (("carry_out", carry_out), ("out_bytes", out_bytes), ("packets", packets)):
-            self._check(name, t, (torch.uint8,), 0)
+        self._rec("receivers_out", receivers_out, RECEIVER_DTYPE, n)
+        self._check("carry_out", carry_out, (torch.uint8,), 0)
+        self._check("out_bytes", out_bytes, (torch.uint8,), 0)
+        self._rec("packets", packets, RX_PACKET_DTYPE)
+
         def p(t):
-            return _ptr(t) if t is not None and t.numel() else None
+            return _pn(t, t is not None and t.numel())
 
         def size(t, width=1):
             return 0 if t is None else t.numel() // width
@@ -357,35 +410,29 @@ class FrameCrcEngine:
                 self._ctx, p(infos), n_frames, p(frame_accept), p(items), n_items, p(src_base), p(payload),
                 payload.numel(), _ptr(frame_first), p(receivers), n, p(slots_), _ptr(slot_first), n_slots, p(carry_in),
                 carry_in.numel(), p(carry_out_), size(carry_out_), _ptr(carry_first),
-                ctypes.c_void_p(used.data_ptr() + 16), p(packets_), size(packets_, 24), _ptr(packet_first),
-                ctypes.c_void_p(used.data_ptr()), p(out_bytes_), size(out_bytes_), ctypes.c_void_p(used.data_ptr() + 8),
-                p(status_), p(results), p(receivers_out_), self._stream(stream)), "ufc_receive_packets_varlen")
+                ctypes.c_void_p(used.data_ptr() + 16), p(packets_), size(packets_, RX_PACKET_DTYPE.itemsize),
+                _ptr(packet_first), ctypes.c_void_p(used.data_ptr()), p(out_bytes_), size(out_bytes_),
+                ctypes.c_void_p(used.data_ptr() + 8), p(status_), p(results), p(receivers_out_), self._stream(stream)),
+                "ufc_receive_packets_varlen")
 
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            def zeros(*shape, dtype=torch.uint8):
-                return torch.zeros(shape, dtype=dtype, device=self.device)
-            carry_first = zeros(n + 1, dtype=torch.int64)
-            packet_first = zeros(n + 1, dtype=torch.int64)
-            used = zeros(3, dtype=torch.int64)
-            results = zeros(n, 80)
+        with self._outputs(stream) as z:
+            carry_first, packet_first = z(None, n + 1, torch.int64), z(None, n + 1, torch.int64)
+            used = z(None, 3, torch.int64)
+            results = z(None, n, RECEIVER_RESULT_DTYPE)
             need = [(carry_out, carry_cap), (out_bytes, out_cap), (packets, packets_cap)]
             if n and any(t is None and cap is None for t, cap in need):
                 # The used counts are exact whatever the caps: a first pass on a copy of the state, with none.
                 # Reading them back waits for the stream: give the caps (or the tensors) to stay asynchronous.
-                call(slots.clone(), None, None, None, None, zeros(n, 560))
+                call(slots.clone(), None, None, None, None, z(None, n, RECEIVER_DTYPE))
                 u = used.cpu().tolist()
                 packets_cap = u[0] if packets_cap is None else packets_cap
                 out_cap = u[1] if out_cap is None else out_cap
                 carry_cap = u[2] if carry_cap is None else carry_cap
-            if carry_out is None:
-                carry_out = zeros(int(carry_cap or 0))
-            if out_bytes is None:
-                out_bytes = zeros(int(out_cap or 0))
-            if packets is None:
-                packets = zeros(int(packets_cap or 0), 24)
-            if receivers_out is None:
-                receivers_out = zeros(n, 560)
-            item_status = zeros(n_items) if want_item_status else None
+            carry_out = z(carry_out, int(carry_cap or 0))
+            out_bytes = z(out_bytes, int(out_cap or 0))
+            packets = z(packets, int(packets_cap or 0), RX_PACKET_DTYPE)
+            receivers_out = z(receivers_out, n, RECEIVER_DTYPE)
+            item_status = z(None, n_items) if want_item_status else None
         call(slots, carry_out, out_bytes, packets, item_status, receivers_out)
         return {"packets": packets, "packet_first": packet_first, "packets_used": used[0:1], "out_bytes": out_bytes,
                 "out_used": used[1:2], "carry_out": carry_out, "carry_first": carry_first, "carry_used": used[2:3],
@@ -396,44 +443,37 @@ class FrameCrcEngine:
                      windows_out=None, stream=None):
         """ufc_frame_window_varlen: one step of FrameAckQueue (window_contains, mark_seen, resynchronize;
         src/half_connection/frame_ack_queue.rs as half_connection/mod.rs:132-152 drives it) for every connection.
-        infos uint8[n_frames, 32] (what parse_varlen returns), frame_first int64[n + 1] (CSR over the frames, the one
-        receive_packets takes), windows uint8[n, 24] (ufc_frame_window records, uflow_amd.frame.FRAME_WINDOW_DTYPE).
-        Returns a dict of device tensors: frame_accept uint8[n_frames] (1 for the data frames inside the window:
-        pass it to receive_packets), groups uint8[groups_cap, 24] (ack groups as ufc_item records, each
-        connection's carried tail first), group_first int64[n + 1] (CSR over the groups: pack_flushes' flush_first),
-        groups_used int64[1], results uint8[n, 40], windows_out uint8[n, 24] (may be given as `windows`).  groups_cap
+        infos rows[n_frames] (what parse_varlen returns), frame_first int64[n + 1] (CSR over the frames, the one
+        receive_packets takes), windows rows[n] (ufc_frame_window records, FRAME_WINDOW_DTYPE).  Returns a dict of
+        device tensors: frame_accept uint8[n_frames] (1 for the data frames inside the window: pass it to
+        receive_packets), groups rows[groups_cap] (ack groups as ufc_item records, each connection's carried tail
+        first), group_first int64[n + 1] (CSR over the groups: pack_flushes' flush_first), groups_used int64[1],
+        results rows[n] of ufc_frame_window_result, windows_out rows[n] (may be given as `windows`).  groups_cap
         defaults to n + n_frames, which is always enough; groups at an index >= groups_cap are not written (compare
         groups_used).  Tensors given for frame_accept, groups and windows_out are written into."""
         n_frames, n = infos.shape[0], windows.shape[0]
         if groups_cap is None:
             groups_cap = groups.shape[0] if groups is not None else n + n_frames
         groups_cap = int(groups_cap)
-        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n_frames)
         self._check("frame_first", frame_first, (torch.int64,), n + 1)
-        self._check("windows", windows, (torch.uint8,), 24 * n)
+        self._rec("windows", windows, FRAME_WINDOW_DTYPE, n)
         self._check("frame_accept", frame_accept, (torch.uint8,), n_frames)
-        self._check("groups", groups, (torch.uint8,), 24 * groups_cap)
-        self._check("windows_out", windows_out, (torch.uint8,), 24 * n)
-        # (the outputs are zeroed on the stream the call is queued on)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if frame_accept is None:
-                frame_accept = torch.zeros(n_frames, dtype=torch.uint8, device=self.device)
+        self._rec("groups", groups, ITEM_DTYPE, groups_cap)
+        self._rec("windows_out", windows_out, FRAME_WINDOW_DTYPE, n)
+        with self._outputs(stream) as z:
+            frame_accept = z(frame_accept, n_frames)
             # (the pointer is required even when there are no frames, and an empty tensor has none)
-            accept_arg = frame_accept if n_frames else torch.zeros(1, dtype=torch.uint8, device=self.device)
-            if groups is None:
-                groups = torch.zeros((groups_cap, 24), dtype=torch.uint8, device=self.device)
-            if windows_out is None:
-                windows_out = torch.zeros((n, 24), dtype=torch.uint8, device=self.device)
-            group_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-            results = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
-            used = torch.zeros(1, dtype=torch.int64, device=self.device)
-        check(lib().ufc_frame_window_varlen(self._ctx, _ptr(infos) if n_frames else None, n_frames, _ptr(frame_first),
-                                            _ptr(windows) if n else None, n,
-                                            _ptr(accept_arg) if n else None,
-                                            _ptr(groups) if groups_cap else None, groups_cap, _ptr(group_first),
-                                            _ptr(used), _ptr(results) if n else None,
-                                            _ptr(windows_out) if n else None, self._stream(stream)),
-              "ufc_frame_window_varlen")
+            accept_arg = frame_accept if n_frames else z(None, 1)
+            groups = z(groups, groups_cap, ITEM_DTYPE)
+            windows_out = z(windows_out, n, FRAME_WINDOW_DTYPE)
+            group_first = z(None, n + 1, torch.int64)
+            results = z(None, n, FRAME_WINDOW_RESULT_DTYPE)
+            used = z(None, 1, torch.int64)
+        check(lib().ufc_frame_window_varlen(self._ctx, _pn(infos, n_frames), n_frames, _ptr(frame_first),
+                                            _pn(windows, n), n, _pn(accept_arg, n), _pn(groups, groups_cap), groups_cap,
+                                            _ptr(group_first), _ptr(used), _pn(results, n), _pn(windows_out, n),
+                                            self._stream(stream)), "ufc_frame_window_varlen")
         return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used,
                 "results": results, "windows_out": windows_out}
 
@@ -442,59 +482,51 @@ class FrameCrcEngine:
                     queues_out=None, stream=None):
         """ufc_frame_queue_varlen: one step of the sender's FrameQueue (push, acknowledge_group,
         advance_transfer_window, forget_frames, get_feedback; src/half_connection/frame_queue.rs with
-        reorder_buffer.rs and loss_rate.rs) for every connection.  infos uint8[n_frames, 32] and items uint8[n_items,
-        24] (what parse_varlen returns), frame_first int64[n + 1] (CSR over the frames), sent uint8[n_sent, 24]
-        (ufc_sent_frame records to push) with sent_first int64[n + 1], queues uint8[n, 192], steps uint8[n, 40], log
-        uint8[n_log, 24] (the log arena, updated in place), ref_acked uint8[refs_cap] or None (set to 1 for the
-        fragments of newly acked frames, in place).  Returns a dict of device tensors: results uint8[n, 80],
-        queues_out uint8[n, 192] (may be given as `queues`), log, ref_acked.  The record layouts are
-        uflow_amd.frame's FRAME_QUEUE_DTYPE, FRAME_QUEUE_STEP_DTYPE, SENT_FRAME_DTYPE and FRAME_QUEUE_RESULT_DTYPE."""
+        reorder_buffer.rs and loss_rate.rs) for every connection.  infos rows[n_frames] and items rows[n_items] (what
+        parse_varlen returns), frame_first int64[n + 1] (CSR over the frames), sent rows[n_sent] (ufc_sent_frame
+        records to push) with sent_first int64[n + 1], queues rows[n] (FRAME_QUEUE_DTYPE), steps rows[n]
+        (FRAME_QUEUE_STEP_DTYPE), log rows[n_log] (SENT_FRAME_DTYPE: the log arena, updated in place), ref_acked
+        uint8[refs_cap] or None (set to 1 for the fragments of newly acked frames, in place).  Returns a dict of
+        device tensors: results rows[n] (FRAME_QUEUE_RESULT_DTYPE), queues_out rows[n] (may be given as `queues`),
+        log, ref_acked."""
         n_frames, n_items, n_sent, n, n_log = infos.shape[0], items.shape[0], sent.shape[0], queues.shape[0], log.shape[0]
         refs_cap = ref_acked.shape[0] if ref_acked is not None else 0
-        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
-        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n_frames)
+        self._rec("items", items, ITEM_DTYPE, n_items)
         self._check("frame_first", frame_first, (torch.int64,), n + 1)
-        self._check("sent", sent, (torch.uint8,), 24 * n_sent)
+        self._rec("sent", sent, SENT_FRAME_DTYPE, n_sent)
         self._check("sent_first", sent_first, (torch.int64,), n + 1)
-        self._check("queues", queues, (torch.uint8,), 192 * n)
-        self._check("steps", steps, (torch.uint8,), 40 * n)
-        self._check("log", log, (torch.uint8,), 24 * n_log)
+        self._rec("queues", queues, FRAME_QUEUE_DTYPE, n)
+        self._rec("steps", steps, FRAME_QUEUE_STEP_DTYPE, n)
+        self._rec("log", log, SENT_FRAME_DTYPE, n_log)
         self._check("ref_acked", ref_acked, (torch.uint8,), refs_cap)
-        self._check("queues_out", queues_out, (torch.uint8,), 192 * n)
-        # (the outputs are zeroed on the stream the call is queued on)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if queues_out is None:
-                queues_out = torch.zeros((n, 192), dtype=torch.uint8, device=self.device)
-            results = torch.zeros((n, 80), dtype=torch.uint8, device=self.device)
-        check(lib().ufc_frame_queue_varlen(self._ctx, _ptr(infos) if n_frames else None, n_frames,
-                                           _ptr(items) if n_items else None, n_items, _ptr(frame_first),
-                                           _ptr(sent) if n_sent else None, n_sent, _ptr(sent_first),
-                                           _ptr(queues) if n else None, _ptr(steps) if n else None, n,
-                                           _ptr(log) if n_log else None, n_log,
-                                           _ptr(ref_acked) if refs_cap else None, refs_cap,
-                                           _ptr(results) if n else None, _ptr(queues_out) if n else None,
+        self._rec("queues_out", queues_out, FRAME_QUEUE_DTYPE, n)
+        with self._outputs(stream) as z:
+            queues_out = z(queues_out, n, FRAME_QUEUE_DTYPE)
+            results = z(None, n, FRAME_QUEUE_RESULT_DTYPE)
+        check(lib().ufc_frame_queue_varlen(self._ctx, _pn(infos, n_frames), n_frames, _pn(items, n_items), n_items,
+                                           _ptr(frame_first), _pn(sent, n_sent), n_sent, _ptr(sent_first),
+                                           _pn(queues, n), _pn(steps, n), n, _pn(log, n_log), n_log,
+                                           _pn(ref_acked, refs_cap), refs_cap, _pn(results, n), _pn(queues_out, n),
                                            self._stream(stream)), "ufc_frame_queue_varlen")
         return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
 
     # ---- the send rate control around the frame queue call, on the device (uflow_frame_codec.h) ----
     def rate_begin(self, states, now_ms, extra_flags=None, steps=None, states_out=None, stream=None):
-        """ufc_rate_begin_varlen: opens a tick.  states uint8[n, 112] (RATE_STATE_DTYPE records), now_ms int64[n],
+        """ufc_rate_begin_varlen: opens a tick.  states rows[n] (RATE_STATE_DTYPE records), now_ms int64[n],
         extra_flags int32[n] or None (OR-ed into the steps' flags: FQ_MARK_RATE_LIMITED).  Returns a dict of device
-        tensors: steps uint8[n, 40] (what frame_queue takes), states_out uint8[n, 112] (may be given as `states`)."""
+        tensors: steps rows[n] (FRAME_QUEUE_STEP_DTYPE: what frame_queue takes), states_out rows[n] (may be given as
+        `states`)."""
         n = states.shape[0]
-        self._check("states", states, (torch.uint8,), 112 * n)
+        self._rec("states", states, RATE_STATE_DTYPE, n)
         self._check("now_ms", now_ms, (torch.int64, torch.uint64), n)
         self._check("extra_flags", extra_flags, (torch.int32, torch.uint32), n)
-        self._check("steps", steps, (torch.uint8,), 40 * n)
-        self._check("states_out", states_out, (torch.uint8,), 112 * n)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if steps is None:
-                steps = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
-            if states_out is None:
-                states_out = torch.zeros((n, 112), dtype=torch.uint8, device=self.device)
-        check(lib().ufc_rate_begin_varlen(self._ctx, _ptr(states) if n else None, _ptr(now_ms) if n else None,
-                                          _ptr(extra_flags) if n else None, n, _ptr(steps) if n else None,
-                                          _ptr(states_out) if n else None, self._stream(stream)),
+        self._rec("steps", steps, FRAME_QUEUE_STEP_DTYPE, n)
+        self._rec("states_out", states_out, RATE_STATE_DTYPE, n)
+        with self._outputs(stream) as z:
+            steps, states_out = z(steps, n, FRAME_QUEUE_STEP_DTYPE), z(states_out, n, RATE_STATE_DTYPE)
+        check(lib().ufc_rate_begin_varlen(self._ctx, _pn(states, n), _pn(now_ms, n), _pn(extra_flags, n), n,
+                                          _pn(steps, n), _pn(states_out, n), self._stream(stream)),
               "ufc_rate_begin_varlen")
         return {"steps": steps, "states_out": states_out}
 
@@ -502,106 +534,90 @@ class FrameCrcEngine:
                   flush_index=None, results=None, states_out=None, stream=None):
         """ufc_rate_step_varlen: closes a tick behind frame_queue (notify_frame_sent, fill_flush_alloc and
         SendRateComp::step; src/half_connection/send_rate.rs, recv_rate_set.rs, mod.rs:165-215) for every connection.
-        states uint8[n, 112], ticks uint8[n, 32], fq_results uint8[n, 80] (frame_queue's results), entries
-        uint8[n_entries, 16] (the receive-rate sets, updated in place); flush_results uint8[m, 24] with result_index
-        int32[n] (the last data flush of each connection, -1 for none) and flushes uint8[k, 24] with flush_index
-        int32[n] (where the new flush_alloc goes, in place) are optional.  Returns a dict of device tensors: results
-        uint8[n, 56], states_out uint8[n, 112] (may be given as `states`), entries, flushes.  The record layouts are
-        uflow_amd.frame's RATE_STATE_DTYPE, RATE_TICK_DTYPE, RATE_RESULT_DTYPE and RECV_RATE_ENTRY_DTYPE."""
+        states rows[n] (RATE_STATE_DTYPE), ticks rows[n] (RATE_TICK_DTYPE), fq_results rows[n] (frame_queue's
+        results), entries rows[n_entries] (RECV_RATE_ENTRY_DTYPE: the receive-rate sets, updated in place);
+        flush_results rows[m] (FLUSH_RESULT_DTYPE) with result_index int32[n] (the last data flush of each
+        connection, -1 for none) and flushes rows[k] (FLUSH_DTYPE) with flush_index int32[n] (where the new
+        flush_alloc goes, in place) are optional.  Returns a dict of device tensors: results rows[n]
+        (RATE_RESULT_DTYPE), states_out rows[n] (may be given as `states`), entries, flushes."""
         n, n_entries = states.shape[0], entries.shape[0]
         n_fr = flush_results.shape[0] if flush_results is not None else 0
         n_fl = flushes.shape[0] if flushes is not None else 0
         if (n_fr and result_index is None) or (n_fl and flush_index is None):
             raise ValueError("flush_results needs result_index, flushes needs flush_index")
-        self._check("states", states, (torch.uint8,), 112 * n)
-        self._check("ticks", ticks, (torch.uint8,), 32 * n)
-        self._check("fq_results", fq_results, (torch.uint8,), 80 * n)
-        self._check("entries", entries, (torch.uint8,), 16 * n_entries)
-        self._check("flush_results", flush_results, (torch.uint8,), 24 * n_fr)
+        self._rec("states", states, RATE_STATE_DTYPE, n)
+        self._rec("ticks", ticks, RATE_TICK_DTYPE, n)
+        self._rec("fq_results", fq_results, FRAME_QUEUE_RESULT_DTYPE, n)
+        self._rec("entries", entries, RECV_RATE_ENTRY_DTYPE, n_entries)
+        self._rec("flush_results", flush_results, FLUSH_RESULT_DTYPE, n_fr)
         self._check("result_index", result_index, (torch.int32, torch.uint32), n)
-        self._check("flushes", flushes, (torch.uint8,), 24 * n_fl)
+        self._rec("flushes", flushes, FLUSH_DTYPE, n_fl)
         self._check("flush_index", flush_index, (torch.int32, torch.uint32), n)
-        self._check("results", results, (torch.uint8,), 56 * n)
-        self._check("states_out", states_out, (torch.uint8,), 112 * n)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if results is None:
-                results = torch.zeros((n, 56), dtype=torch.uint8, device=self.device)
-            if states_out is None:
-                states_out = torch.zeros((n, 112), dtype=torch.uint8, device=self.device)
-        check(lib().ufc_rate_step_varlen(self._ctx, _ptr(states) if n else None, _ptr(ticks) if n else None,
-                                         _ptr(fq_results) if n else None, n, _ptr(entries) if n_entries else None,
-                                         n_entries, _ptr(flush_results) if n_fr else None, n_fr,
-                                         _ptr(result_index) if n_fr else None, _ptr(flushes) if n_fl else None, n_fl,
-                                         _ptr(flush_index) if n_fl else None, _ptr(results) if n else None,
-                                         _ptr(states_out) if n else None, self._stream(stream)),
+        self._rec("results", results, RATE_RESULT_DTYPE, n)
+        self._rec("states_out", states_out, RATE_STATE_DTYPE, n)
+        with self._outputs(stream) as z:
+            results, states_out = z(results, n, RATE_RESULT_DTYPE), z(states_out, n, RATE_STATE_DTYPE)
+        check(lib().ufc_rate_step_varlen(self._ctx, _pn(states, n), _pn(ticks, n), _pn(fq_results, n), n,
+                                         _pn(entries, n_entries), n_entries, _pn(flush_results, n_fr), n_fr,
+                                         _pn(result_index, n_fr), _pn(flushes, n_fl), n_fl, _pn(flush_index, n_fl),
+                                         _pn(results, n), _pn(states_out, n), self._stream(stream)),
               "ufc_rate_step_varlen")
         return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
 
     # ---- the resend calls around the emit and the pack, on the device (uflow_frame_codec.h) ----
-    _RS_ARENA_WIDTH = (("heap", 16), ("pkts", 24), ("frag_acked", 1), ("tx", 8), ("ref_acked", 1), ("stage", 24))
-
-    def _rs_arenas(self, arenas):
-        """(pointer, record count) of every resend arena, uint8 device tensors, in the C calls' order."""
-        out = {}
-        for name, width in self._RS_ARENA_WIDTH:
+    def _rs_arenas(self, arenas, *names):
+        """(pointer, record count) of the named resend arenas, flat, in the order the C calls take them; the arenas
+        are device rows of frame.RESEND_ARENAS' dtypes."""
+        out = []
+        for name in names:
             t = arenas.get(name)
-            self._check(name, t, (torch.uint8,), 0)
-            count = 0 if t is None else t.numel() // width
-            out[name] = (_ptr(t) if count else None, count)
+            count = self._rec(name, t, _RS_ARENA_DTYPE[name])
+            out += [_pn(t, count), count]
         return out
 
     def resend_begin(self, infos, frame_first, queues, log, rate, flushes, states, senders, arenas, flags=None,
                      results=None, states_out=None, senders_out=None, stream=None):
         """ufc_resend_begin_varlen: behind rate_step, in front of emit_packets.  Ack propagation from ref_acked,
         PacketSender::acknowledge for the ack frames, the resend loop (the heap and the pack's rule) and the pending
-        fragments' staging for every connection.  infos uint8[n_frames, 32], frame_first int64[n + 1], queues
-        uint8[n, 192] and log uint8[n_log, 24] as frame_queue left them, rate uint8[n, 56] (rate_step's results),
-        flushes uint8[n, 24] (the data flushes the pack gets), states uint8[n, 104], senders uint8[n, 304], arenas a
-        dict of uint8 tensors heap [., 16], pkts [., 24], frag_acked, tx [., 8], ref_acked, stage [., 24] (updated in
-        place), flags int32[n] or None.  Returns a dict: results uint8[n, 48], states_out, senders_out (may be given
-        as `states`, `senders`).  Layouts: uflow_amd.frame's RESEND_DTYPE and RESEND_RESULT_DTYPE."""
+        fragments' staging for every connection.  infos rows[n_frames], frame_first int64[n + 1], queues rows[n] and
+        log rows[n_log] as frame_queue left them, rate rows[n] (rate_step's results), flushes rows[n] (the data
+        flushes the pack gets), states rows[n] (RESEND_DTYPE), senders rows[n] (SENDER_DTYPE), arenas a dict of
+        device rows heap, pkts, frag_acked, tx, ref_acked, stage (frame.RESEND_ARENAS names their records; updated in
+        place), flags int32[n] or None.  Returns a dict: results rows[n] (RESEND_RESULT_DTYPE), states_out,
+        senders_out (may be given as `states`, `senders`)."""
         n_frames, n, n_log = infos.shape[0], states.shape[0], log.shape[0]
-        self._check("infos", infos, (torch.uint8,), 32 * n_frames)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n_frames)
         self._check("frame_first", frame_first, (torch.int64,), n + 1)
-        self._check("queues", queues, (torch.uint8,), 192 * n)
-        self._check("log", log, (torch.uint8,), 24 * n_log)
-        self._check("rate", rate, (torch.uint8,), 56 * n)
-        self._check("flushes", flushes, (torch.uint8,), 24 * n)
-        self._check("states", states, (torch.uint8,), 104 * n)
-        self._check("senders", senders, (torch.uint8,), 304 * n)
+        self._rec("queues", queues, FRAME_QUEUE_DTYPE, n)
+        self._rec("log", log, SENT_FRAME_DTYPE, n_log)
+        self._rec("rate", rate, RATE_RESULT_DTYPE, n)
+        self._rec("flushes", flushes, FLUSH_DTYPE, n)
+        self._rec("states", states, RESEND_DTYPE, n)
+        self._rec("senders", senders, SENDER_DTYPE, n)
         self._check("flags", flags, (torch.int32, torch.uint32), n)
-        self._check("results", results, (torch.uint8,), 48 * n)
-        self._check("states_out", states_out, (torch.uint8,), 104 * n)
-        self._check("senders_out", senders_out, (torch.uint8,), 304 * n)
-        A = self._rs_arenas(arenas)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if results is None:
-                results = torch.zeros((n, 48), dtype=torch.uint8, device=self.device)
-            if states_out is None:
-                states_out = torch.zeros((n, 104), dtype=torch.uint8, device=self.device)
-            if senders_out is None:
-                senders_out = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
+        self._rec("results", results, RESEND_RESULT_DTYPE, n)
+        self._rec("states_out", states_out, RESEND_DTYPE, n)
+        self._rec("senders_out", senders_out, SENDER_DTYPE, n)
+        A = self._rs_arenas(arenas, "heap", "pkts", "frag_acked", "tx", "ref_acked", "stage")
+        with self._outputs(stream) as z:
+            results, states_out = z(results, n, RESEND_RESULT_DTYPE), z(states_out, n, RESEND_DTYPE)
+            senders_out = z(senders_out, n, SENDER_DTYPE)
         check(lib().ufc_resend_begin_varlen(
-            self._ctx, _ptr(infos) if n_frames else None, n_frames, _ptr(frame_first), _ptr(queues) if n else None,
-            _ptr(log) if n_log else None, n_log, _ptr(rate) if n else None, _ptr(flags) if n else None,
-            _ptr(flushes) if n else None, _ptr(states) if n else None, _ptr(senders) if n else None, n, *A["heap"],
-            *A["pkts"], *A["frag_acked"], *A["tx"], *A["ref_acked"], *A["stage"], _ptr(results) if n else None,
-            _ptr(states_out) if n else None, _ptr(senders_out) if n else None, self._stream(stream)),
-            "ufc_resend_begin_varlen")
+            self._ctx, _pn(infos, n_frames), n_frames, _ptr(frame_first), _pn(queues, n), _pn(log, n_log), n_log,
+            _pn(rate, n), _pn(flags, n), _pn(flushes, n), _pn(states, n), _pn(senders, n), n, *A, _pn(results, n),
+            _pn(states_out, n), _pn(senders_out, n), self._stream(stream)), "ufc_resend_begin_varlen")
         return {"results": results, "states_out": states_out, "senders_out": senders_out}
 
     def resend_place(self, states, begin_results, arenas, flush_first, items, stream=None):
         """ufc_resend_place_varlen: behind emit_packets.  Every connection's staged items into items[flush_first[c]
-        ..], the slots the emit reserved; items uint8[items_cap, 24] is written in place and returned."""
+        ..], the slots the emit reserved; items rows[items_cap] of ufc_item is written in place and returned."""
         n = states.shape[0]
-        self._check("states", states, (torch.uint8,), 104 * n)
-        self._check("begin_results", begin_results, (torch.uint8,), 48 * n)
+        self._rec("states", states, RESEND_DTYPE, n)
+        self._rec("begin_results", begin_results, RESEND_RESULT_DTYPE, n)
         self._check("flush_first", flush_first, (torch.int64,), n + 1)
-        self._check("items", items, (torch.uint8,), 0)
-        A = self._rs_arenas(arenas)
-        items_cap = items.numel() // 24
-        check(lib().ufc_resend_place_varlen(self._ctx, _ptr(states) if n else None, _ptr(begin_results) if n else None,
-                                            n, *A["stage"], _ptr(flush_first), _ptr(items) if items_cap else None,
+        items_cap = self._rec("items", items, ITEM_DTYPE)
+        check(lib().ufc_resend_place_varlen(self._ctx, _pn(states, n), _pn(begin_results, n), n,
+                                            *self._rs_arenas(arenas, "stage"), _ptr(flush_first), _pn(items, items_cap),
                                             items_cap, self._stream(stream)), "ufc_resend_place_varlen")
         return items
 
@@ -609,56 +625,45 @@ class FrameCrcEngine:
                       packet_results, sender_results, begin_results, rate, states, senders, arenas, sent=None,
                       next_extra_flags=None, results=None, states_out=None, retake=None, stream=None):
         """ufc_resend_commit_varlen: behind pack_flushes over the data flushes (flush c = connection c) and
-        build_sizes.  flush_results uint8[n, 24], infos uint8[n_infos, 32] (the pack's frames), out_offsets
-        int64[n_infos + 1] (the size pass), frames_used int64[1] (the pack's), items uint8[n_items, 24], flush_first
-        int64[n + 1], packets uint8[n_packets, 16], packet_first int64[n + 1], packet_results uint8[n_packets, 16] and
-        sender_results uint8[n, 32] (the first emit's), begin_results uint8[n, 48], rate uint8[n, 56], states
-        uint8[n, 104], senders uint8[n, 304] (as resend_begin wrote them), arenas as in resend_begin (updated in
-        place), next_extra_flags int32[n] or None (in place).  Returns a dict: results uint8[n, 40], states_out, retake
-        (the second emit's senders), sent uint8[n_infos, 24], sent_first int64[n + 1], next_extra_flags."""
+        build_sizes.  flush_results rows[n], infos rows[n_infos] (the pack's frames), out_offsets int64[n_infos + 1]
+        (the size pass), frames_used int64[1] (the pack's), items rows[n_items], flush_first int64[n + 1], packets
+        rows[n_packets], packet_first int64[n + 1], packet_results rows[n_packets] and sender_results rows[n] (the
+        first emit's), begin_results rows[n], rate rows[n], states rows[n], senders rows[n] (as resend_begin wrote
+        them), arenas as in resend_begin (updated in place), next_extra_flags int32[n] or None (in place).  Returns a
+        dict: results rows[n] (RESEND_COMMIT_RESULT_DTYPE), states_out, retake (the second emit's senders), sent
+        rows[n_infos] (SENT_FRAME_DTYPE), sent_first int64[n + 1], next_extra_flags."""
         n, n_infos, n_items, n_packets = states.shape[0], infos.shape[0], items.shape[0], packets.shape[0]
-        self._check("flush_results", flush_results, (torch.uint8,), 24 * n)
-        self._check("infos", infos, (torch.uint8,), 32 * n_infos)
+        self._rec("flush_results", flush_results, FLUSH_RESULT_DTYPE, n)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n_infos)
         self._check("out_offsets", out_offsets, (torch.int64,), n_infos + 1)
         self._check("frames_used", frames_used, (torch.int64,), 1)
-        self._check("items", items, (torch.uint8,), 24 * n_items)
+        self._rec("items", items, ITEM_DTYPE, n_items)
         self._check("flush_first", flush_first, (torch.int64,), n + 1)
-        self._check("packets", packets, (torch.uint8,), 16 * n_packets)
+        self._rec("packets", packets, PACKET_DTYPE, n_packets)
         self._check("packet_first", packet_first, (torch.int64,), n + 1)
-        self._check("packet_results", packet_results, (torch.uint8,), 16 * n_packets)
-        self._check("sender_results", sender_results, (torch.uint8,), 32 * n)
-        self._check("begin_results", begin_results, (torch.uint8,), 48 * n)
-        self._check("rate", rate, (torch.uint8,), 56 * n)
-        self._check("states", states, (torch.uint8,), 104 * n)
-        self._check("senders", senders, (torch.uint8,), 304 * n)
-        self._check("sent", sent, (torch.uint8,), 0)
+        self._rec("packet_results", packet_results, PACKET_RESULT_DTYPE, n_packets)
+        self._rec("sender_results", sender_results, SENDER_RESULT_DTYPE, n)
+        self._rec("begin_results", begin_results, RESEND_RESULT_DTYPE, n)
+        self._rec("rate", rate, RATE_RESULT_DTYPE, n)
+        self._rec("states", states, RESEND_DTYPE, n)
+        self._rec("senders", senders, SENDER_DTYPE, n)
+        sent_cap = self._rec("sent", sent, SENT_FRAME_DTYPE) if sent is not None else n_infos
         self._check("next_extra_flags", next_extra_flags, (torch.int32, torch.uint32), n)
-        self._check("results", results, (torch.uint8,), 40 * n)
-        self._check("states_out", states_out, (torch.uint8,), 104 * n)
-        self._check("retake", retake, (torch.uint8,), 304 * n)
-        A = self._rs_arenas(arenas)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
-            if sent is None:
-                sent = torch.zeros((n_infos, 24), dtype=torch.uint8, device=self.device)
-            if results is None:
-                results = torch.zeros((n, 40), dtype=torch.uint8, device=self.device)
-            if states_out is None:
-                states_out = torch.zeros((n, 104), dtype=torch.uint8, device=self.device)
-            if retake is None:
-                retake = torch.zeros((n, 304), dtype=torch.uint8, device=self.device)
-            sent_first = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        sent_cap = sent.numel() // 24
+        self._rec("results", results, RESEND_COMMIT_RESULT_DTYPE, n)
+        self._rec("states_out", states_out, RESEND_DTYPE, n)
+        self._rec("retake", retake, SENDER_DTYPE, n)
+        A = self._rs_arenas(arenas, "heap", "pkts", "frag_acked", "tx")
+        with self._outputs(stream) as z:
+            sent = z(sent, n_infos, SENT_FRAME_DTYPE)
+            results, states_out = z(results, n, RESEND_COMMIT_RESULT_DTYPE), z(states_out, n, RESEND_DTYPE)
+            retake = z(retake, n, SENDER_DTYPE)
+            sent_first = z(None, n + 1, torch.int64)
         check(lib().ufc_resend_commit_varlen(
-            self._ctx, _ptr(flush_results) if n else None, _ptr(infos) if n_infos else None, n_infos, _ptr(out_offsets),
-            _ptr(frames_used), _ptr(items) if n_items else None, n_items, _ptr(flush_first),
-            _ptr(packets) if n_packets else None, n_packets, _ptr(packet_first),
-            _ptr(packet_results) if n_packets else None, _ptr(sender_results) if n else None,
-            _ptr(begin_results) if n else None, _ptr(rate) if n else None, _ptr(states) if n else None,
-            _ptr(senders) if n else None, n, *A["heap"], *A["pkts"], *A["frag_acked"], *A["tx"],
-            _ptr(sent) if sent_cap else None, sent_cap, _ptr(sent_first),
-            _ptr(next_extra_flags) if next_extra_flags is not None and n else None, _ptr(results) if n else None,
-            _ptr(states_out) if n else None, _ptr(retake) if n else None, self._stream(stream)),
-            "ufc_resend_commit_varlen")
+            self._ctx, _pn(flush_results, n), _pn(infos, n_infos), n_infos, _ptr(out_offsets), _ptr(frames_used),
+            _pn(items, n_items), n_items, _ptr(flush_first), _pn(packets, n_packets), n_packets, _ptr(packet_first),
+            _pn(packet_results, n_packets), _pn(sender_results, n), _pn(begin_results, n), _pn(rate, n), _pn(states, n),
+            _pn(senders, n), n, *A, _pn(sent, sent_cap), sent_cap, _ptr(sent_first), _pn(next_extra_flags, n),
+            _pn(results, n), _pn(states_out, n), _pn(retake, n), self._stream(stream)), "ufc_resend_commit_varlen")
         return {"results": results, "states_out": states_out, "retake": retake, "sent": sent, "sent_first": sent_first,
                 "next_extra_flags": next_extra_flags}
 

@@ -42,10 +42,47 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._native import (Builder, DatagramRef, Flush, FlushResult, FrameInfo, FrameQueue, FrameQueueResult, FrameQueueStep,
-                      FrameWindow, FrameWindowResult, Item, Packet, PacketResult, RateResult, RateState, RateTick,
-                      Receiver, ReceiverResult, RecvRateEntry, Resend, ResendCommitResult, ResendEntry, ResendResult,
-                      RxPacket, RxSlot, SentFrame, SentPacket, Sender, SenderResult, TxRef, check, lib, UFC_ERR_NOMEM)
+from ._native import Builder, DatagramRef, FrameInfo, Item, check, lib, UFC_ERR_NOMEM
+# The stages' constants without their prefix: each value is written once, in _native.
+from ._native import (  # noqa: F401
+    UFC_PACK_DONE as PACK_DONE, UFC_PACK_SIZE_LIMITED as PACK_SIZE_LIMITED, UFC_PACK_WINDOW_LIMITED as PACK_WINDOW_LIMITED,
+    UFC_PACK_BAD_RANGE as PACK_BAD_RANGE,
+    UFC_SEND_TIME_SENSITIVE as SEND_TIME_SENSITIVE, UFC_SEND_UNRELIABLE as SEND_UNRELIABLE,
+    UFC_SEND_PERSISTENT as SEND_PERSISTENT, UFC_SEND_RELIABLE as SEND_RELIABLE, UFC_NO_PARENT as NO_PARENT,
+    UFC_EMIT_DONE as EMIT_DONE, UFC_EMIT_WINDOW_LIMITED as EMIT_WINDOW_LIMITED, UFC_EMIT_ALLOC_LIMITED as EMIT_ALLOC_LIMITED,
+    UFC_EMIT_BAD_PACKET as EMIT_BAD_PACKET, UFC_EMIT_BAD_RANGE as EMIT_BAD_RANGE,
+    UFC_PACKET_NOT_REACHED as PACKET_NOT_REACHED, UFC_PACKET_EMITTED as PACKET_EMITTED, UFC_PACKET_DROPPED as PACKET_DROPPED,
+    UFC_RX_ASM_OPEN as RX_ASM_OPEN, UFC_RX_ASM_CLOSED as RX_ASM_CLOSED, UFC_RX_ASM_ACTIVE as RX_ASM_ACTIVE,
+    UFC_RX_SLOT_ENTRY as RX_SLOT_ENTRY, UFC_RX_SLOT_DATA as RX_SLOT_DATA, UFC_RX_SLOT_DUD as RX_SLOT_DUD,
+    UFC_RX_PACKET_DUD as RX_PACKET_DUD,
+    UFC_RX_NOT_HANDLED as RX_NOT_HANDLED, UFC_RX_STORED as RX_STORED, UFC_RX_COMPLETED as RX_COMPLETED, UFC_RX_DUD as RX_DUD,
+    UFC_RX_DROPPED_INVALID as RX_DROPPED_INVALID, UFC_RX_DROPPED_WINDOW as RX_DROPPED_WINDOW,
+    UFC_RX_DROPPED_CHANNEL as RX_DROPPED_CHANNEL, UFC_RX_DROPPED_CLOSED as RX_DROPPED_CLOSED,
+    UFC_RX_DROPPED_MISMATCH as RX_DROPPED_MISMATCH, UFC_RX_DROPPED_DUPLICATE as RX_DROPPED_DUPLICATE,
+    UFC_RX_DROPPED_BAD_SRC as RX_DROPPED_BAD_SRC, UFC_RX_DONE as RX_DONE, UFC_RX_BAD_STATE as RX_BAD_STATE,
+    UFC_FW_DONE as FW_DONE, UFC_FW_BAD_STATE as FW_BAD_STATE,
+    UFC_SENT_NONCE as SENT_NONCE, UFC_SENT_RATE_LIMITED as SENT_RATE_LIMITED, UFC_SENT_ACKED as SENT_ACKED,
+    UFC_SENT_MARK as SENT_MARK,
+    UFC_FQ_HAS_RTT as FQ_HAS_RTT, UFC_FQ_RESET_LOSS as FQ_RESET_LOSS, UFC_FQ_MARK_RATE_LIMITED as FQ_MARK_RATE_LIMITED,
+    UFC_FQ_FORGET as FQ_FORGET, UFC_FQ_FEEDBACK as FQ_FEEDBACK, UFC_FQ_DONE as FQ_DONE, UFC_FQ_BAD_STATE as FQ_BAD_STATE,
+    UFC_RATE_AWAIT_SEND as RATE_AWAIT_SEND, UFC_RATE_SLOW_START as RATE_SLOW_START,
+    UFC_RATE_THROUGHPUT_EQN as RATE_THROUGHPUT_EQN, UFC_RATE_FRAME_SENT as RATE_FRAME_SENT,
+    UFC_RATE_DONE as RATE_DONE, UFC_RATE_BAD_STATE as RATE_BAD_STATE, UFC_RATE_REF_PANIC as RATE_REF_PANIC,
+    UFC_RATE_RECV_FULL as RATE_RECV_FULL,
+    UFC_RATE_FEEDBACK as RATE_FEEDBACK, UFC_RATE_NOFEEDBACK as RATE_NOFEEDBACK, UFC_RATE_RESET_ISSUED as RATE_RESET_ISSUED,
+    UFC_RATE_ENTERED_EQN as RATE_ENTERED_EQN, UFC_RATE_INV_STALLED as RATE_INV_STALLED,
+    UFC_NO_PARENT as NO_INDEX,  # in result_index / flush_index: no gather for this connection
+    UFC_TX_RESEND as TX_RESEND, UFC_RS_NO_DATA_FLUSH as RS_NO_DATA_FLUSH,
+    UFC_RS_DONE as RS_DONE, UFC_RS_SIZE_LIMITED as RS_SIZE_LIMITED, UFC_RS_WINDOW_LIMITED as RS_WINDOW_LIMITED,
+    UFC_RS_REF_HANG as RS_REF_HANG, UFC_RS_BAD_STATE as RS_BAD_STATE, UFC_RS_STAGE_FULL as RS_STAGE_FULL,
+    UFC_RS_HEAP_FULL as RS_HEAP_FULL)
+# The record layouts (numpy views of the header's structs) are declared in records.py.
+from .records import (  # noqa: F401
+    FRAME_INFO_DTYPE, ITEM_DTYPE, FLUSH_DTYPE, FLUSH_RESULT_DTYPE, PACKET_DTYPE, SENDER_DTYPE, PACKET_RESULT_DTYPE,
+    SENDER_RESULT_DTYPE, RECEIVER_DTYPE, RX_SLOT_DTYPE, RX_PACKET_DTYPE, RECEIVER_RESULT_DTYPE, FRAME_WINDOW_DTYPE,
+    FRAME_WINDOW_RESULT_DTYPE, SENT_FRAME_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_STEP_DTYPE, FRAME_QUEUE_RESULT_DTYPE,
+    RECV_RATE_ENTRY_DTYPE, RATE_STATE_DTYPE, RATE_TICK_DTYPE, RATE_RESULT_DTYPE, RESEND_ENTRY_DTYPE, SENT_PACKET_DTYPE,
+    TX_REF_DTYPE, RESEND_DTYPE, RESEND_RESULT_DTYPE, RESEND_COMMIT_RESULT_DTYPE)
 
 MAX_FRAME_SIZE = 1472  # src/lib.rs:286-294
 DATA_FRAME_MAX_DATAGRAM_COUNT = 127  # serial/mod.rs:42
@@ -53,158 +90,10 @@ HANDSHAKE_SYN, HANDSHAKE_SYN_ACK, HANDSHAKE_ACK, HANDSHAKE_ERROR = 0, 1, 2, 3
 DISCONNECT, DISCONNECT_ACK, DATA, SYNC, ACK = 4, 5, 10, 11, 12
 HANDSHAKE_ERRORS = ("Version", "Config", "ServerFull")  # HandshakeErrorType, src/frame/mod.rs:30-35
 
-# numpy views of ufc_frame_info / ufc_item (batched outputs)
-FRAME_INFO_DTYPE = np.dtype([("kind", "u1"), ("ok", "u1"), ("aux", "u1"), ("crc_ok", "u1"), ("f", "<u4", (5,)),
-                             ("item_count", "<u4"), ("item_first", "<u4")])
-ITEM_DTYPE = np.dtype([("id", "<u4"), ("channel_id", "u1"), ("form", "u1"), ("window_parent_lead", "<u2"),
-                       ("channel_parent_lead", "<u2"), ("fragment_id", "<u2"), ("fragment_id_last", "<u2"),
-                       ("flags", "<u2"), ("data_offset", "<u4"), ("data_len", "<u4")])
-assert FRAME_INFO_DTYPE.itemsize == ctypes.sizeof(FrameInfo) == 32
-assert ITEM_DTYPE.itemsize == ctypes.sizeof(Item) == 24
-# ufc_flush / ufc_flush_result (batched packs)
-FLUSH_DTYPE = np.dtype([("flush_alloc", "<i8"), ("kind", "<u4"), ("window_room", "<u4"), ("id0", "<u4"), ("id1", "<u4")])
-FLUSH_RESULT_DTYPE = np.dtype([("frame_first", "<u4"), ("frame_count", "<u4"), ("items_packed", "<u4"), ("stop", "<u4"),
-                               ("alloc_left", "<i8")])
-assert FLUSH_DTYPE.itemsize == ctypes.sizeof(Flush) == 24
-assert FLUSH_RESULT_DTYPE.itemsize == ctypes.sizeof(FlushResult) == 24
-PACK_DONE, PACK_SIZE_LIMITED, PACK_WINDOW_LIMITED, PACK_BAD_RANGE = 0, 1, 2, 3
-# ufc_packet / ufc_sender / ufc_packet_result / ufc_sender_result (batched packet emits)
-PACKET_DTYPE = np.dtype([("data_offset", "<u4"), ("data_len", "<u4"), ("flush_id", "<u4"), ("channel_id", "u1"),
-                         ("mode", "u1"), ("reserved", "<u2")])
-SENDER_DTYPE = np.dtype([("base_id", "<u4"), ("next_id", "<u4"), ("window_size", "<u4"), ("flush_id", "<u4"),
-                         ("alloc", "<u8"), ("max_alloc", "<u8"), ("window_parent_id", "<u4"), ("take", "<u4"),
-                         ("reserve_items", "<u4"), ("reserved", "<u4"), ("channel_parent_id", "<u4", (64,))])
-PACKET_RESULT_DTYPE = np.dtype([("sequence_id", "<u4"), ("item_first", "<u4"), ("item_count", "<u4"), ("status", "u1"),
-                                ("resend", "u1"), ("reserved", "<u2")])
-SENDER_RESULT_DTYPE = np.dtype([("item_first", "<u4"), ("item_count", "<u4"), ("packets_consumed", "<u4"),
-                                ("packets_emitted", "<u4"), ("packets_dropped", "<u4"), ("stop", "<u4"),
-                                ("bytes_dropped", "<u8")])
-assert PACKET_DTYPE.itemsize == ctypes.sizeof(Packet) == 16
-assert SENDER_DTYPE.itemsize == ctypes.sizeof(Sender) == 304
-assert PACKET_RESULT_DTYPE.itemsize == ctypes.sizeof(PacketResult) == 16
-assert SENDER_RESULT_DTYPE.itemsize == ctypes.sizeof(SenderResult) == 32
-SEND_TIME_SENSITIVE, SEND_UNRELIABLE, SEND_PERSISTENT, SEND_RELIABLE = 0, 1, 2, 3
-NO_PARENT = 0xFFFFFFFF
-EMIT_DONE, EMIT_WINDOW_LIMITED, EMIT_ALLOC_LIMITED, EMIT_BAD_PACKET, EMIT_BAD_RANGE = 0, 1, 2, 3, 4
-PACKET_NOT_REACHED, PACKET_EMITTED, PACKET_DROPPED = 0, 1, 2
-# ufc_receiver / ufc_rx_slot / ufc_rx_packet / ufc_receiver_result (batched packet receives)
-RECEIVER_DTYPE = np.dtype([("base_id", "<u4"), ("end_id", "<u4"), ("window_size", "<u4"), ("window_ready", "u1"),
-                           ("deliver", "u1"), ("reserved", "<u2"), ("resync_id", "<u4"), ("reserved2", "<u4"),
-                           ("alloc", "<u8"), ("max_alloc", "<u8"), ("channel_ready_flags", "<u8"),
-                           ("channel_base_id", "<u4", (64,)), ("channel_packet_count", "<u4", (64,))])
-RX_SLOT_DTYPE = np.dtype([("data_offset", "<u8"), ("data_len", "<u4"), ("asm_size", "<u4"),
-                          ("asm_window_parent_lead", "<u2"), ("asm_channel_parent_lead", "<u2"),
-                          ("asm_last_fragment_id", "<u2"), ("asm_received", "<u2"), ("rx_window_parent_lead", "<u2"),
-                          ("rx_channel_parent_lead", "<u2"), ("asm_state", "u1"), ("asm_channel_id", "u1"),
-                          ("rx_channel_id", "u1"), ("rx_flags", "u1")])
-RX_PACKET_DTYPE = np.dtype([("out_offset", "<u8"), ("sequence_id", "<u4"), ("len", "<u4"), ("channel_id", "u1"),
-                            ("flags", "u1"), ("reserved", "<u2"), ("reserved2", "<u4")])
-RECEIVER_RESULT_DTYPE = np.dtype([("packet_first", "<u4"), ("packet_count", "<u4"), ("status_count", "<u4", (11,)),
-                                  ("packets_completed", "<u4"), ("packets_dud", "<u4"), ("advanced", "<u4"),
-                                  ("stop", "<u4"), ("reserved", "<u4"), ("bytes_delivered", "<u8")])
-assert RECEIVER_DTYPE.itemsize == ctypes.sizeof(Receiver) == 560
-assert RX_SLOT_DTYPE.itemsize == ctypes.sizeof(RxSlot) == 32
-assert RX_PACKET_DTYPE.itemsize == ctypes.sizeof(RxPacket) == 24
-assert RECEIVER_RESULT_DTYPE.itemsize == ctypes.sizeof(ReceiverResult) == 80
-RX_ASM_OPEN, RX_ASM_CLOSED, RX_ASM_ACTIVE = 0, 1, 2
-RX_SLOT_ENTRY, RX_SLOT_DATA, RX_SLOT_DUD = 1, 2, 4
-RX_PACKET_DUD = 1
-(RX_NOT_HANDLED, RX_STORED, RX_COMPLETED, RX_DUD, RX_DROPPED_INVALID, RX_DROPPED_WINDOW, RX_DROPPED_CHANNEL,
- RX_DROPPED_CLOSED, RX_DROPPED_MISMATCH, RX_DROPPED_DUPLICATE, RX_DROPPED_BAD_SRC) = range(11)
-RX_DONE, RX_BAD_STATE = 0, 1
-# ufc_frame_window / ufc_frame_window_result (batched frame windows)
-FRAME_WINDOW_DTYPE = np.dtype([("base_id", "<u4"), ("size", "<u4"), ("tail_base_id", "<u4"), ("tail_bitfield", "<u4"),
-                               ("tail_nonce", "u1"), ("has_tail", "u1"), ("sync_reply", "u1"), ("reserved", "u1"),
-                               ("reserved2", "<u4")])
-FRAME_WINDOW_RESULT_DTYPE = np.dtype([("group_first", "<u4"), ("group_count", "<u4"), ("accepted", "<u4"),
-                                      ("refused", "<u4"), ("syncs", "<u4"), ("packet_syncs", "<u4"),
-                                      ("first_packet_sync", "<u4"), ("advanced", "<u4"), ("stop", "<u4"),
-                                      ("reserved", "<u4")])
-assert FRAME_WINDOW_DTYPE.itemsize == ctypes.sizeof(FrameWindow) == 24
-assert FRAME_WINDOW_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameWindowResult) == 40
-FW_DONE, FW_BAD_STATE = 0, 1
-# ufc_sent_frame / ufc_frame_queue / ufc_frame_queue_step / ufc_frame_queue_result (batched sender frame queues)
-SENT_FRAME_DTYPE = np.dtype([("send_time_ms", "<u8"), ("size", "<u4"), ("ref_first", "<u4"), ("ref_count", "<u4"),
-                             ("flags", "u1"), ("reserved", "u1", (3,))])
-FRAME_QUEUE_DTYPE = np.dtype([("log_base_id", "<u4"), ("log_next_id", "<u4"), ("window_base_id", "<u4"),
-                              ("window_size", "<u4"), ("tail_size", "<u4"), ("rb_base_id", "<u4"), ("rb_max_span", "<u4"),
-                              ("rb_frames", "<u4", (2,)), ("rb_count", "<u4"), ("rate_limited", "u1"),
-                              ("has_ack_data", "u1"), ("ack_rate_limited", "u1"), ("has_last_feedback", "u1"),
-                              ("li_count", "<u4"), ("ack_last_send_time_ms", "<u8"), ("ack_total_size", "<u8"),
-                              ("last_feedback_ms", "<u8"), ("li_end_time_ms", "<u8", (9,)), ("li_length", "<u4", (9,)),
-                              ("log_cap", "<u4"), ("log_first", "<u8")])
-FRAME_QUEUE_STEP_DTYPE = np.dtype([("flags", "<u4"), ("reserved", "<u4"), ("rtt_ms", "<u8"), ("thresh_ms", "<u8"),
-                                   ("now_ms", "<u8"), ("reset_loss_rate", "<f8")])
-FRAME_QUEUE_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("pushes_taken", "<u4"), ("pushes_refused", "<u4"),
-                                     ("ack_frames", "<u4"), ("groups", "<u4"), ("groups_dud", "<u4"),
-                                     ("groups_unknown", "<u4"), ("groups_bad_nonce", "<u4"), ("frames_acked", "<u4"),
-                                     ("li_acks", "<u4"), ("li_nacks", "<u4"), ("window_advanced", "<u4"),
-                                     ("log_culled", "<u4"), ("window_room", "<u4"), ("has_feedback", "u1"),
-                                     ("rate_limited", "u1"), ("reserved", "<u2"), ("receive_rate", "<u4"),
-                                     ("rtt_ms", "<u8"), ("loss_rate", "<f8")])
-assert SENT_FRAME_DTYPE.itemsize == ctypes.sizeof(SentFrame) == 24
-assert FRAME_QUEUE_DTYPE.itemsize == ctypes.sizeof(FrameQueue) == 192
-assert FRAME_QUEUE_STEP_DTYPE.itemsize == ctypes.sizeof(FrameQueueStep) == 40
-assert FRAME_QUEUE_RESULT_DTYPE.itemsize == ctypes.sizeof(FrameQueueResult) == 80
-SENT_NONCE, SENT_RATE_LIMITED, SENT_ACKED, SENT_MARK = 1, 2, 4, 8
-FQ_HAS_RTT, FQ_RESET_LOSS, FQ_MARK_RATE_LIMITED, FQ_FORGET, FQ_FEEDBACK = 1, 2, 4, 8, 16
-FQ_DONE, FQ_BAD_STATE = 0, 1
-# ufc_recv_rate_entry / ufc_rate_state / ufc_rate_tick / ufc_rate_result (batched send rate control)
-RECV_RATE_ENTRY_DTYPE = np.dtype([("timestamp_ms", "<u8"), ("value", "<u4"), ("is_initial", "u1"),
-                                  ("reserved", "u1", (3,))])
-RATE_STATE_DTYPE = np.dtype([("mode", "<u4"), ("send_rate", "<u4"), ("max_send_rate", "<u4"), ("send_rate_tcp", "<u4"),
-                             ("has_time_last_doubled", "u1"), ("has_nofeedback_exp", "u1"), ("nofeedback_idle", "u1"),
-                             ("has_rtt_s", "u1"), ("has_rtt_ms", "u1"), ("has_rto_ms", "u1"), ("has_last_flush", "u1"),
-                             ("has_reset", "u1"), ("time_last_doubled_ms", "<u8"), ("prev_loss_rate", "<f8"),
-                             ("nofeedback_exp_ms", "<u8"), ("rtt_s", "<f8"), ("rtt_ms", "<u8"), ("rto_ms", "<u8"),
-                             ("now_ms", "<u8"), ("flush_alloc", "<i8"), ("reset_loss_rate", "<f8"),
-                             ("recv_first", "<u8"), ("recv_count", "<u4"), ("recv_cap", "<u4")])
-RATE_TICK_DTYPE = np.dtype([("now_ms", "<u8"), ("delta_time_s", "<f8"), ("alloc_adjust", "<i8"), ("flags", "<u4"),
-                            ("reserved", "<u4")])
-RATE_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("mode", "<u4"), ("now_ms", "<u8"), ("rtt_ms", "<u8"), ("rto_ms", "<u8"),
-                              ("flush_alloc", "<i8"), ("send_rate", "<u4"), ("flags", "<u4"), ("inv_iterations", "<u4"),
-                              ("recv_count", "<u4")])
-assert RECV_RATE_ENTRY_DTYPE.itemsize == ctypes.sizeof(RecvRateEntry) == 16
-assert RATE_STATE_DTYPE.itemsize == ctypes.sizeof(RateState) == 112
-assert RATE_TICK_DTYPE.itemsize == ctypes.sizeof(RateTick) == 32
-assert RATE_RESULT_DTYPE.itemsize == ctypes.sizeof(RateResult) == 56
-RATE_AWAIT_SEND, RATE_SLOW_START, RATE_THROUGHPUT_EQN = 0, 1, 2
-RATE_FRAME_SENT = 1
-RATE_DONE, RATE_BAD_STATE, RATE_REF_PANIC, RATE_RECV_FULL = 0, 1, 2, 3
-RATE_FEEDBACK, RATE_NOFEEDBACK, RATE_RESET_ISSUED, RATE_ENTERED_EQN, RATE_INV_STALLED = 1, 2, 4, 8, 16
-NO_INDEX = 0xFFFFFFFF  # UFC_NO_PARENT in result_index / flush_index: no gather for this connection
-# ufc_resend_entry / ufc_sent_packet / ufc_tx_ref / ufc_resend / ufc_resend_result / ufc_resend_commit_result
-RESEND_ENTRY_DTYPE = np.dtype([("resend_time_ms", "<u8"), ("sequence_id", "<u4"), ("fragment_id", "<u2"),
-                               ("send_count", "u1"), ("reserved", "u1")])
-SENT_PACKET_DTYPE = np.dtype([("data_offset", "<u4"), ("data_len", "<u4"), ("frag_first", "<u4"), ("sequence_id", "<u4"),
-                              ("window_parent_lead", "<u2"), ("channel_parent_lead", "<u2"), ("channel_id", "u1"),
-                              ("resend", "u1"), ("reserved", "<u2")])
-TX_REF_DTYPE = np.dtype([("sequence_id", "<u4"), ("fragment_id", "<u2"), ("flags", "<u2")])
-RESEND_DTYPE = np.dtype([("heap_first", "<u8"), ("heap_cap", "<u4"), ("heap_len", "<u4"), ("pkt_first", "<u8"),
-                         ("pkt_cap", "<u4"), ("frag_next", "<u4"), ("frag_first", "<u8"), ("frag_cap", "<u4"),
-                         ("tx_cap", "<u4"), ("tx_first", "<u8"), ("tx_head", "<u4"), ("tx_tail", "<u4"),
-                         ("stage_first", "<u8"), ("stage_cap", "<u4"), ("pending_seq", "<u4"), ("pending_next", "<u4"),
-                         ("pending_count", "<u4"), ("pending_resend", "u1"), ("reserved0", "u1"), ("reserved1", "<u2"),
-                         ("reserved2", "<u4"), ("window_bytes", "<u8")])
-RESEND_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("n_resent", "<u4"), ("n_pending_staged", "<u4"),
-                                ("heap_popped_dead", "<u4"), ("heap_popped_acked", "<u4"), ("packets_freed", "<u4"),
-                                ("refs_acked", "<u4"), ("heap_len", "<u4"), ("pending_count", "<u4"),
-                                ("acks_ignored", "<u4"), ("bytes_freed", "<u8")])
-RESEND_COMMIT_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("pending_packed", "<u4"), ("packets_entered", "<u4"),
-                                       ("heap_pushed", "<u4"), ("heap_dropped", "<u4"), ("refs_written", "<u4"),
-                                       ("frames", "<u4"), ("take", "<u4"), ("heap_len", "<u4"), ("pending_count", "<u4")])
-assert RESEND_ENTRY_DTYPE.itemsize == ctypes.sizeof(ResendEntry) == 16
-assert SENT_PACKET_DTYPE.itemsize == ctypes.sizeof(SentPacket) == 24
-assert TX_REF_DTYPE.itemsize == ctypes.sizeof(TxRef) == 8
-assert RESEND_DTYPE.itemsize == ctypes.sizeof(Resend) == 104
-assert RESEND_RESULT_DTYPE.itemsize == ctypes.sizeof(ResendResult) == 48
-assert RESEND_COMMIT_RESULT_DTYPE.itemsize == ctypes.sizeof(ResendCommitResult) == 40
-TX_RESEND = 1
-RS_NO_DATA_FLUSH = 1
-RS_DONE, RS_SIZE_LIMITED, RS_WINDOW_LIMITED, RS_REF_HANG, RS_BAD_STATE, RS_STAGE_FULL, RS_HEAP_FULL = range(7)
 # The arenas of the resend state, in the order the C calls take them: name, record dtype.
 RESEND_ARENAS = (("heap", RESEND_ENTRY_DTYPE), ("pkts", SENT_PACKET_DTYPE), ("frag_acked", np.dtype(np.uint8)),
                  ("tx", TX_REF_DTYPE), ("ref_acked", np.dtype(np.uint8)), ("stage", ITEM_DTYPE))
+_RS_ARENA_DTYPE = dict(RESEND_ARENAS)
 
 
 def _pow2_at_least(v: int) -> int:
@@ -550,18 +439,43 @@ class AckFrameBuilder:
         return self._buf.raw[:n]
 
 
+_U8, _U32, _U64 = np.dtype(np.uint8), np.dtype(np.uint32), np.dtype(np.uint64)
+
+
+def _in(name, arr, dt, count=0):
+    """An input argument: a C-contiguous array of dt (the array itself when it is one, else a coerced copy) holding
+    at least count entries."""
+    arr = np.ascontiguousarray(arr, dtype=dt)
+    if arr.size < count:
+        raise ValueError(f"{name} must hold at least {count} entries, holds {arr.size}")
+    return arr
+
+
+def _inout(name, arr, dt, size=0):
+    """An argument the C call writes: allocated (zeroed, size entries) when None, else it must be exactly dt,
+    C-contiguous, writable and hold at least size entries (nothing is coerced: a copy would take the writes)."""
+    if arr is None:
+        return np.zeros(size, dtype=dt)
+    if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
+        raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
+    return arr
+
+
+def _p(a):
+    """The array's address for the C ABI; None (NULL) for no array and for an empty one."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
 def parse_batch_host(data: np.ndarray, offsets: np.ndarray, valid: Optional[np.ndarray] = None, nthreads: int = 1):
     """Frame::read of every frame of a CSR batch in host memory, after the batched CRC gate
     (`valid`, from the GPU; None = gate on the host).  Returns (infos[n], items) as numpy
     structured arrays (FRAME_INFO_DTYPE, ITEM_DTYPE); infos['item_first'] indexes items."""
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    data = _in("data", data, _U8)
+    offsets = _in("offsets", offsets, _U64)
     n = offsets.size - 1
     infos = np.zeros(max(n, 0), dtype=FRAME_INFO_DTYPE)
-    if valid is not None:
-        valid = np.ascontiguousarray(valid, dtype=np.uint8)
     used = ctypes.c_size_t(0)
-    vp = valid.ctypes.data if valid is not None else None
+    vp = _in("valid", valid, _U8).ctypes.data if valid is not None else None
     rc = lib().ufc_parse_batch_host(data.ctypes.data, offsets.ctypes.data, n, vp, infos.ctypes.data, None, 0,
                                     ctypes.byref(used), nthreads)
     check(rc, "ufc_parse_batch_host")
@@ -579,25 +493,20 @@ def build_batch_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarray, 
     src_base[i] + data_offset (src_base uint64[n], default zeros; a parsed batch's own offsets and bytes
     re-emit it).  Returns (out_bytes uint8, out_offsets uint64[n + 1], status uint8[n], crc uint32[n]);
     frames whose status is not UFC_BUILD_OK have length 0; seal=False leaves 4 zero bytes as trailers."""
-    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
-    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    items = _in("items", items, ITEM_DTYPE)
+    payload = _in("payload", payload, _U8)
     n = infos.size
-    sb = None
-    if src_base is not None:
-        src_base = np.ascontiguousarray(src_base, dtype=np.uint64)
-        if src_base.size < n:
-            raise ValueError("src_base must hold one offset per frame")
-        sb = src_base.ctypes.data
+    sb = _in("src_base", src_base, _U64, n).ctypes.data if src_base is not None else None
     offsets = np.zeros(n + 1, dtype=np.uint64)
     status = np.zeros(n, dtype=np.uint8)
     crc = np.zeros(n, dtype=np.uint32)
-    ip = items.ctypes.data if items.size else None
+    ip = _p(items)
     check(lib().ufc_build_sizes_host(infos.ctypes.data, ip, items.size, sb, payload.size, n, offsets.ctypes.data,
                                      status.ctypes.data, nthreads), "ufc_build_sizes_host")
     out = np.zeros(int(offsets[n]), dtype=np.uint8)
-    check(lib().ufc_build_batch_host(infos.ctypes.data, ip, items.size, sb, payload.ctypes.data if payload.size else None,
-                                     payload.size, n, offsets.ctypes.data, out.ctypes.data if out.size else None, out.size,
+    check(lib().ufc_build_batch_host(infos.ctypes.data, ip, items.size, sb, _p(payload), payload.size, n,
+                                     offsets.ctypes.data, _p(out), out.size,
                                      1 if seal else 0, crc.ctypes.data, nthreads), "ufc_build_batch_host")
     return out, offsets, status, crc
 
@@ -611,30 +520,21 @@ def pack_host(items: np.ndarray, flush_first: np.ndarray, flushes: np.ndarray, f
     which the builds skip), one FLUSH_RESULT_DTYPE record per flush, and the number of frames.  frames_cap
     (default: the number of items, always enough) bounds the records written; nonce_bits: uint32 words, bit g
     the nonce of the batch's g-th frame (default 0); infos: an array to write into."""
-    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-    flush_first = np.ascontiguousarray(flush_first, dtype=np.uint64)
-    flushes = np.ascontiguousarray(flushes, dtype=FLUSH_DTYPE)
+    items = _in("items", items, ITEM_DTYPE)
+    flushes = _in("flushes", flushes, FLUSH_DTYPE)
     n = flushes.size
-    if flush_first.size < n + 1:
-        raise ValueError("flush_first must hold one more entry than there are flushes")
+    flush_first = _in("flush_first", flush_first, _U64, n + 1)
     if frames_cap is None:
         frames_cap = items.size if infos is None else infos.size
-    if infos is None:
-        infos = np.zeros(frames_cap, dtype=FRAME_INFO_DTYPE)
-    elif infos.dtype != FRAME_INFO_DTYPE or not infos.flags.c_contiguous or infos.size < frames_cap:
-        raise ValueError("infos must be a contiguous FRAME_INFO_DTYPE array of at least frames_cap records")
+    infos = _inout("infos", infos, FRAME_INFO_DTYPE, frames_cap)
     nb = None
-    if nonce_bits is not None:
-        nonce_bits = np.ascontiguousarray(nonce_bits, dtype=np.uint32)
-        if nonce_bits.size * 32 < frames_cap:
-            raise ValueError("nonce_bits must hold one bit per frame below frames_cap")
-        nb = nonce_bits.ctypes.data
+    if nonce_bits is not None:  # one bit per frame below frames_cap
+        nb = _in("nonce_bits", nonce_bits, _U32, (frames_cap + 31) // 32).ctypes.data
     results = np.zeros(n, dtype=FLUSH_RESULT_DTYPE)
     used = ctypes.c_uint64(0)
-    check(lib().ufc_pack_host(items.ctypes.data if items.size else None, items.size, flush_first.ctypes.data,
-                              flushes.ctypes.data if n else None, n, nb, infos.ctypes.data if frames_cap else None,
-                              frames_cap, results.ctypes.data if n else None, ctypes.byref(used), nthreads),
-          "ufc_pack_host")
+    check(lib().ufc_pack_host(_p(items), items.size, flush_first.ctypes.data, _p(flushes), n, nb,
+                              infos.ctypes.data if frames_cap else None, frames_cap, _p(results), ctypes.byref(used),
+                              nthreads), "ufc_pack_host")
     return infos, results, used.value
 
 
@@ -650,29 +550,20 @@ def emit_packets_host(packets: np.ndarray, packet_first: np.ndarray, senders: np
     want_packet_results), one SENDER_RESULT_DTYPE record per sender, and the senders' state after the packets they
     consumed.  items_cap bounds the items written (default: what the call needs, found by a first call with
     none); items: an array to write into; senders_out: where the state goes (may be `senders` itself)."""
-    packets = np.ascontiguousarray(packets, dtype=PACKET_DTYPE)
-    packet_first = np.ascontiguousarray(packet_first, dtype=np.uint64)
-    if senders.dtype != SENDER_DTYPE or not senders.flags.c_contiguous:
-        senders = np.ascontiguousarray(senders, dtype=SENDER_DTYPE)
+    packets = _in("packets", packets, PACKET_DTYPE)
+    senders = _in("senders", senders, SENDER_DTYPE)
     n = senders.size
-    if packet_first.size < n + 1:
-        raise ValueError("packet_first must hold one more entry than there are senders")
-    if senders_out is None:
-        senders_out = np.zeros(n, dtype=SENDER_DTYPE)
-    elif senders_out.dtype != SENDER_DTYPE or not senders_out.flags.c_contiguous or senders_out.size < n:
-        raise ValueError("senders_out must be a contiguous SENDER_DTYPE array of one record per sender")
+    packet_first = _in("packet_first", packet_first, _U64, n + 1)
+    senders_out = _inout("senders_out", senders_out, SENDER_DTYPE, n)
     flush_first = np.zeros(n + 1, dtype=np.uint64)
     packet_results = np.zeros(packets.size, dtype=PACKET_RESULT_DTYPE) if want_packet_results else None
     sender_results = np.zeros(n, dtype=SENDER_RESULT_DTYPE)
     used = ctypes.c_uint64(0)
 
     def call(items_p, cap):
-        check(lib().ufc_emit_packets_host(packets.ctypes.data if packets.size else None, packets.size,
-                                          packet_first.ctypes.data, senders.ctypes.data if n else None, n, items_p, cap,
-                                          flush_first.ctypes.data, packet_results.ctypes.data
-                                          if want_packet_results and packets.size else None,
-                                          sender_results.ctypes.data if n else None,
-                                          senders_out.ctypes.data if n else None, ctypes.byref(used), nthreads),
+        check(lib().ufc_emit_packets_host(_p(packets), packets.size, packet_first.ctypes.data, _p(senders), n, items_p, cap,
+                                          flush_first.ctypes.data, _p(packet_results), _p(sender_results),
+                                          _p(senders_out) if n else None, ctypes.byref(used), nthreads),
               "ufc_emit_packets_host")
 
     if items_cap is None:
@@ -683,10 +574,7 @@ def emit_packets_host(packets: np.ndarray, packet_first: np.ndarray, senders: np
         else:
             call(None, 0)
             items_cap = used.value
-    if items is None:
-        items = np.zeros(items_cap, dtype=ITEM_DTYPE)
-    elif items.dtype != ITEM_DTYPE or not items.flags.c_contiguous or items.size < items_cap:
-        raise ValueError("items must be a contiguous ITEM_DTYPE array of at least items_cap records")
+    items = _inout("items", items, ITEM_DTYPE, items_cap)
     call(items.ctypes.data if items_cap else None, items_cap)
     return items, flush_first, packet_results, sender_results, senders_out, used.value
 
@@ -708,38 +596,26 @@ def receive_packets_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarr
     pass on a copy of the state with caps of zero (an ACTIVE slot holds its whole fragment buffer, so the carry
     has no small bound from the batch's sizes alone); arrays given for carry_out, out_bytes and packets are written
     into (their sizes are then the caps).  Pass carry_out as the next step's carry_in."""
-    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
-    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-    payload = np.ascontiguousarray(payload, dtype=np.uint8)
-    carry_in = np.ascontiguousarray(carry_in, dtype=np.uint8)
-    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
-    slot_first = np.ascontiguousarray(slot_first, dtype=np.uint64)
-    if receivers.dtype != RECEIVER_DTYPE or not receivers.flags.c_contiguous:
-        receivers = np.ascontiguousarray(receivers, dtype=RECEIVER_DTYPE)
-    if slots.dtype != RX_SLOT_DTYPE or not slots.flags.c_contiguous or not slots.flags.writeable:
-        raise ValueError("slots must be a writable contiguous RX_SLOT_DTYPE array (it is updated in place)")
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    items = _in("items", items, ITEM_DTYPE)
+    payload = _in("payload", payload, _U8)
+    carry_in = _in("carry_in", carry_in, _U8)
+    receivers = _in("receivers", receivers, RECEIVER_DTYPE)
     n = receivers.size
-    if frame_first.size < n + 1 or slot_first.size < n + 1:
-        raise ValueError("frame_first and slot_first must hold one more entry than there are receivers")
+    frame_first = _in("frame_first", frame_first, _U64, n + 1)
+    slot_first = _in("slot_first", slot_first, _U64, n + 1)
+    slots = _inout("slots", slots, RX_SLOT_DTYPE)
     if src_base is not None:
-        src_base = np.ascontiguousarray(src_base, dtype=np.uint64)
-        if src_base.size < infos.size:
-            raise ValueError("src_base must hold one entry per frame")
+        src_base = _in("src_base", src_base, _U64, infos.size)
     if frame_accept is not None:
-        frame_accept = np.ascontiguousarray(frame_accept, dtype=np.uint8)
-        if frame_accept.size < infos.size:
-            raise ValueError("frame_accept must hold one entry per frame")
-    if receivers_out is None:
-        receivers_out = np.zeros(n, dtype=RECEIVER_DTYPE)
-    elif receivers_out.dtype != RECEIVER_DTYPE or not receivers_out.flags.c_contiguous or receivers_out.size < n:
-        raise ValueError("receivers_out must be a contiguous RECEIVER_DTYPE array of one record per receiver")
+        frame_accept = _in("frame_accept", frame_accept, _U8, infos.size)
+    receivers_out = _inout("receivers_out", receivers_out, RECEIVER_DTYPE, n)
     carry_first = np.zeros(n + 1, dtype=np.uint64)
     packet_first = np.zeros(n + 1, dtype=np.uint64)
     results = np.zeros(n, dtype=RECEIVER_RESULT_DTYPE)
     carry_used, packets_used, out_used = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
 
-    def p(a):
-        return a.ctypes.data if a is not None and a.size else None
+    p = _p
 
     def call(slots_, carry_out_, out_bytes_, packets_, status_, receivers_out_):
         size = lambda a: 0 if a is None else a.size  # noqa: E731
@@ -758,16 +634,10 @@ def receive_packets_host(infos: np.ndarray, items: np.ndarray, payload: np.ndarr
         carry_cap = carry_used.value if carry_cap is None else carry_cap
         out_cap = out_used.value if out_cap is None else out_cap
         packets_cap = packets_used.value if packets_cap is None else packets_cap
-    if carry_out is None:
-        carry_out = np.zeros(int(carry_cap), dtype=np.uint8)
-    if out_bytes is None:
-        out_bytes = np.zeros(int(out_cap), dtype=np.uint8)
-    if packets is None:
-        packets = np.zeros(int(packets_cap), dtype=RX_PACKET_DTYPE)
-    for name, arr, dt in (("carry_out", carry_out, np.uint8), ("out_bytes", out_bytes, np.uint8),
-                          ("packets", packets, RX_PACKET_DTYPE)):
-        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable:
-            raise ValueError(f"{name} must be a writable contiguous {dt} array")
+    # (arrays that are given set the caps by their sizes)
+    carry_out = _inout("carry_out", carry_out, _U8, 0 if carry_out is not None else int(carry_cap))
+    out_bytes = _inout("out_bytes", out_bytes, _U8, 0 if out_bytes is not None else int(out_cap))
+    packets = _inout("packets", packets, RX_PACKET_DTYPE, 0 if packets is not None else int(packets_cap))
     if np.shares_memory(carry_out, carry_in):
         raise ValueError("carry_out must not overlap carry_in")
     item_status = np.zeros(items.size, dtype=np.uint8) if want_item_status else None
@@ -790,37 +660,25 @@ def frame_window_host(infos: np.ndarray, frame_first: np.ndarray, windows: np.nd
     pack_host's flush_first), groups_used, results (FRAME_WINDOW_RESULT_DTYPE), windows_out.  groups_cap bounds
     the groups written (default n_windows + n_frames, always enough); arrays given for frame_accept, groups,
     group_first, results and windows_out (which may be `windows`) are written into."""
-    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
-    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
-    if windows.dtype != FRAME_WINDOW_DTYPE or not windows.flags.c_contiguous:
-        windows = np.ascontiguousarray(windows, dtype=FRAME_WINDOW_DTYPE)
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    windows = _in("windows", windows, FRAME_WINDOW_DTYPE)
     n = windows.size
-    if frame_first.size < n + 1:
-        raise ValueError("frame_first must hold one more entry than there are windows")
+    frame_first = _in("frame_first", frame_first, _U64, n + 1)
     if groups_cap is None:
         groups_cap = groups.size if groups is not None else n + infos.size
     groups_cap = int(groups_cap)
-
-    def out(name, arr, size, dt):
-        if arr is None:
-            return np.zeros(size, dtype=dt)
-        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
-            raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
-        return arr
-
-    frame_accept = out("frame_accept", frame_accept, infos.size, np.dtype(np.uint8))
-    groups = out("groups", groups, groups_cap, ITEM_DTYPE)
-    group_first = out("group_first", group_first, n + 1, np.dtype(np.uint64))
-    results = out("results", results, n, FRAME_WINDOW_RESULT_DTYPE)
-    windows_out = out("windows_out", windows_out, n, FRAME_WINDOW_DTYPE)
+    frame_accept = _inout("frame_accept", frame_accept, _U8, infos.size)
+    groups = _inout("groups", groups, ITEM_DTYPE, groups_cap)
+    group_first = _inout("group_first", group_first, _U64, n + 1)
+    results = _inout("results", results, FRAME_WINDOW_RESULT_DTYPE, n)
+    windows_out = _inout("windows_out", windows_out, FRAME_WINDOW_DTYPE, n)
     used = ctypes.c_uint64(0)
     one = np.zeros(1, dtype=np.uint8)  # (frame_accept is required even when there are no frames)
-    check(lib().ufc_frame_window_host(infos.ctypes.data if infos.size else None, infos.size, frame_first.ctypes.data,
-                                      windows.ctypes.data if n else None, n,
-                                      frame_accept.ctypes.data if frame_accept.size else one.ctypes.data,
-                                      groups.ctypes.data if groups_cap else None, groups_cap, group_first.ctypes.data,
-                                      ctypes.addressof(used), results.ctypes.data if n else None,
-                                      windows_out.ctypes.data if n else None, nthreads), "ufc_frame_window_host")
+    check(lib().ufc_frame_window_host(_p(infos), infos.size, frame_first.ctypes.data, _p(windows), n,
+                                      _p(frame_accept) or one.ctypes.data, groups.ctypes.data if groups_cap else None,
+                                      groups_cap, group_first.ctypes.data, ctypes.addressof(used),
+                                      results.ctypes.data if n else None, windows_out.ctypes.data if n else None,
+                                      nthreads), "ufc_frame_window_host")
     return {"frame_accept": frame_accept, "groups": groups, "group_first": group_first, "groups_used": used.value,
             "results": results, "windows_out": windows_out}
 
@@ -836,48 +694,25 @@ def frame_queue_host(infos: np.ndarray, items: np.ndarray, frame_first: np.ndarr
     the arena new_frame_queues returns) and ref_acked (uint8, optional: set to 1 for every fragment of a newly
     acked frame) are updated in place.  Returns a dict: results (FRAME_QUEUE_RESULT_DTYPE), queues_out (may be
     given as `queues`), log, ref_acked."""
-    infos = np.ascontiguousarray(infos, dtype=FRAME_INFO_DTYPE)
-    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-    sent = np.ascontiguousarray(sent, dtype=SENT_FRAME_DTYPE)
-    frame_first = np.ascontiguousarray(frame_first, dtype=np.uint64)
-    sent_first = np.ascontiguousarray(sent_first, dtype=np.uint64)
-    steps = np.ascontiguousarray(steps, dtype=FRAME_QUEUE_STEP_DTYPE)
-    if queues.dtype != FRAME_QUEUE_DTYPE or not queues.flags.c_contiguous:
-        queues = np.ascontiguousarray(queues, dtype=FRAME_QUEUE_DTYPE)
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    items = _in("items", items, ITEM_DTYPE)
+    sent = _in("sent", sent, SENT_FRAME_DTYPE)
+    queues = _in("queues", queues, FRAME_QUEUE_DTYPE)
     n = queues.size
-    if frame_first.size < n + 1 or sent_first.size < n + 1 or steps.size < n:
-        raise ValueError("frame_first and sent_first must hold one more entry than there are queues, steps one each")
-
-    def inout(name, arr, size, dt):
-        if arr is None:
-            return np.zeros(size, dtype=dt)
-        if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
-            raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
-        return arr
-
-    log = inout("log", log, 0, SENT_FRAME_DTYPE)
+    frame_first = _in("frame_first", frame_first, _U64, n + 1)
+    sent_first = _in("sent_first", sent_first, _U64, n + 1)
+    steps = _in("steps", steps, FRAME_QUEUE_STEP_DTYPE, n)
+    log = _inout("log", log, SENT_FRAME_DTYPE)
     if ref_acked is not None:
-        ref_acked = inout("ref_acked", ref_acked, 0, np.dtype(np.uint8))
-    results = inout("results", results, n, FRAME_QUEUE_RESULT_DTYPE)
-    queues_out = inout("queues_out", queues_out, n, FRAME_QUEUE_DTYPE)
+        ref_acked = _inout("ref_acked", ref_acked, _U8)
+    results = _inout("results", results, FRAME_QUEUE_RESULT_DTYPE, n)
+    queues_out = _inout("queues_out", queues_out, FRAME_QUEUE_DTYPE, n)
     refs_cap = ref_acked.size if ref_acked is not None else 0
-    check(lib().ufc_frame_queue_host(infos.ctypes.data if infos.size else None, infos.size,
-                                     items.ctypes.data if items.size else None, items.size, frame_first.ctypes.data,
-                                     sent.ctypes.data if sent.size else None, sent.size, sent_first.ctypes.data,
-                                     queues.ctypes.data if n else None, steps.ctypes.data if n else None, n,
-                                     log.ctypes.data if log.size else None, log.size,
-                                     ref_acked.ctypes.data if refs_cap else None, refs_cap,
-                                     results.ctypes.data if n else None, queues_out.ctypes.data if n else None, nthreads),
-          "ufc_frame_queue_host")
+    check(lib().ufc_frame_queue_host(_p(infos), infos.size, _p(items), items.size, frame_first.ctypes.data, _p(sent),
+                                     sent.size, sent_first.ctypes.data, _p(queues), _p(steps) if n else None, n, _p(log),
+                                     log.size, _p(ref_acked), refs_cap, results.ctypes.data if n else None,
+                                     queues_out.ctypes.data if n else None, nthreads), "ufc_frame_queue_host")
     return {"results": results, "queues_out": queues_out, "log": log, "ref_acked": ref_acked}
-
-
-def _rate_inout(name, arr, size, dt):
-    if arr is None:
-        return np.zeros(size, dtype=dt)
-    if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.size < size:
-        raise ValueError(f"{name} must be a writable contiguous {dt} array of at least {size} entries")
-    return arr
 
 
 def rate_begin_host(states: np.ndarray, now_ms: np.ndarray, extra_flags: Optional[np.ndarray] = None,
@@ -886,19 +721,15 @@ def rate_begin_host(states: np.ndarray, now_ms: np.ndarray, extra_flags: Optiona
     its now_ms, the FRAME_QUEUE_STEP_DTYPE record the frame queue call of this tick takes (forget, feedback, the rtt
     and a pending reset_loss_rate, OR-ed with extra_flags: the caller's FQ_MARK_RATE_LIMITED).  Returns a dict:
     steps, states_out (the pending reset taken; may be given as `states`)."""
-    if states.dtype != RATE_STATE_DTYPE or not states.flags.c_contiguous:
-        states = np.ascontiguousarray(states, dtype=RATE_STATE_DTYPE)
+    states = _in("states", states, RATE_STATE_DTYPE)
     n = states.size
-    now_ms = np.ascontiguousarray(now_ms, dtype=np.uint64)
+    now_ms = _in("now_ms", now_ms, _U64, n)
     if extra_flags is not None:
-        extra_flags = np.ascontiguousarray(extra_flags, dtype=np.uint32)
-    if now_ms.size < n or (extra_flags is not None and extra_flags.size < n):
-        raise ValueError("now_ms and extra_flags must hold one entry per state")
-    steps = _rate_inout("steps", steps, n, FRAME_QUEUE_STEP_DTYPE)
-    states_out = _rate_inout("states_out", states_out, n, RATE_STATE_DTYPE)
-    check(lib().ufc_rate_begin_host(states.ctypes.data if n else None, now_ms.ctypes.data if n else None,
-                                    extra_flags.ctypes.data if extra_flags is not None and n else None, n,
-                                    steps.ctypes.data if n else None, states_out.ctypes.data if n else None, nthreads),
+        extra_flags = _in("extra_flags", extra_flags, _U32, n)
+    steps = _inout("steps", steps, FRAME_QUEUE_STEP_DTYPE, n)
+    states_out = _inout("states_out", states_out, RATE_STATE_DTYPE, n)
+    check(lib().ufc_rate_begin_host(_p(states), _p(now_ms) if n else None, _p(extra_flags) if n else None, n,
+                                    _p(steps) if n else None, _p(states_out) if n else None, nthreads),
           "ufc_rate_begin_host")
     return {"steps": steps, "states_out": states_out}
 
@@ -915,63 +746,40 @@ def rate_step_host(states: np.ndarray, ticks: np.ndarray, fq_results: np.ndarray
     alloc_left and frame_count; flushes (FLUSH_DTYPE, updated in place) with flush_index receives the new
     flush_alloc.  Returns a dict: results (RATE_RESULT_DTYPE), states_out (may be given as `states`), entries,
     flushes."""
-    if states.dtype != RATE_STATE_DTYPE or not states.flags.c_contiguous:
-        states = np.ascontiguousarray(states, dtype=RATE_STATE_DTYPE)
+    states = _in("states", states, RATE_STATE_DTYPE)
     n = states.size
-    ticks = np.ascontiguousarray(ticks, dtype=RATE_TICK_DTYPE)
-    fq_results = np.ascontiguousarray(fq_results, dtype=FRAME_QUEUE_RESULT_DTYPE)
-    if ticks.size < n or fq_results.size < n:
-        raise ValueError("ticks and fq_results must hold one record per state")
-    entries = _rate_inout("entries", entries, 0, RECV_RATE_ENTRY_DTYPE)
+    ticks = _in("ticks", ticks, RATE_TICK_DTYPE, n)
+    fq_results = _in("fq_results", fq_results, FRAME_QUEUE_RESULT_DTYPE, n)
+    entries = _inout("entries", entries, RECV_RATE_ENTRY_DTYPE)
     n_fr = n_fl = 0
     if (flush_results is not None and result_index is None) or (flushes is not None and flush_index is None):
         raise ValueError("flush_results needs result_index, flushes needs flush_index")
     if flush_results is not None:
-        flush_results = np.ascontiguousarray(flush_results, dtype=FLUSH_RESULT_DTYPE)
-        result_index = np.ascontiguousarray(result_index, dtype=np.uint32)
+        flush_results = _in("flush_results", flush_results, FLUSH_RESULT_DTYPE)
+        result_index = _in("result_index", result_index, _U32, n)
         n_fr = flush_results.size
-        if result_index.size < n:
-            raise ValueError("result_index must hold one entry per state")
     if flushes is not None:
-        flushes = _rate_inout("flushes", flushes, 0, FLUSH_DTYPE)
-        flush_index = np.ascontiguousarray(flush_index, dtype=np.uint32)
+        flushes = _inout("flushes", flushes, FLUSH_DTYPE)
+        flush_index = _in("flush_index", flush_index, _U32, n)
         n_fl = flushes.size
-        if flush_index.size < n:
-            raise ValueError("flush_index must hold one entry per state")
-    results = _rate_inout("results", results, n, RATE_RESULT_DTYPE)
-    states_out = _rate_inout("states_out", states_out, n, RATE_STATE_DTYPE)
-    check(lib().ufc_rate_step_host(states.ctypes.data if n else None, ticks.ctypes.data if n else None,
-                                   fq_results.ctypes.data if n else None, n,
-                                   entries.ctypes.data if entries.size else None, entries.size,
-                                   flush_results.ctypes.data if n_fr else None, n_fr,
-                                   result_index.ctypes.data if n_fr else None,
-                                   flushes.ctypes.data if n_fl else None, n_fl,
-                                   flush_index.ctypes.data if n_fl else None,
-                                   results.ctypes.data if n else None, states_out.ctypes.data if n else None, nthreads),
+    results = _inout("results", results, RATE_RESULT_DTYPE, n)
+    states_out = _inout("states_out", states_out, RATE_STATE_DTYPE, n)
+    check(lib().ufc_rate_step_host(_p(states), _p(ticks) if n else None, _p(fq_results) if n else None, n, _p(entries),
+                                   entries.size, _p(flush_results), n_fr, _p(result_index) if n_fr else None,
+                                   _p(flushes), n_fl, _p(flush_index) if n_fl else None,
+                                   _p(results) if n else None, _p(states_out) if n else None, nthreads),
           "ufc_rate_step_host")
     return {"results": results, "states_out": states_out, "entries": entries, "flushes": flushes}
 
 
-def _rs_arenas(arenas):
-    out = {}
-    for name, dt in RESEND_ARENAS:
-        a = arenas.get(name)
-        if a is None:
-            a = np.zeros(0, dtype=dt)
-        if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
-            raise ValueError(f"arena {name} must be a writable contiguous {dt} array")
-        out[name] = a
+def _rs_arenas(arenas, *names):
+    """(pointer, count) of the named resend arenas, flat, as the C calls take them: each a writable array of its
+    RESEND_ARENAS dtype (none: empty)."""
+    out = []
+    for name in names:
+        a = _inout(f"arena {name}", arenas.get(name), _RS_ARENA_DTYPE[name])
+        out += [_p(a), a.size]
     return out
-
-
-def _rs_ptr(a):
-    return a.ctypes.data if a is not None and a.size else None
-
-
-def _rs_in(arr, dt):
-    if arr.dtype != dt or not arr.flags.c_contiguous:
-        arr = np.ascontiguousarray(arr, dtype=dt)
-    return arr
 
 
 def resend_begin_host(infos: np.ndarray, frame_first: np.ndarray, queues: np.ndarray, log: np.ndarray,
@@ -984,32 +792,25 @@ def resend_begin_host(infos: np.ndarray, frame_first: np.ndarray, queues: np.nda
     the RATE_RESULT_DTYPE records of rate_step_host; flushes the data FLUSH_DTYPE records the pack will get).  The
     arenas (the dict new_resend_states returns) are updated in place.  Returns a dict: results (RESEND_RESULT_DTYPE),
     states_out and senders_out (may be given as `states` and `senders`)."""
-    infos = _rs_in(infos, FRAME_INFO_DTYPE)
-    frame_first = _rs_in(frame_first, np.dtype(np.uint64))
-    queues = _rs_in(queues, FRAME_QUEUE_DTYPE)
-    log = _rs_in(log, SENT_FRAME_DTYPE)
-    rate = _rs_in(rate, RATE_RESULT_DTYPE)
-    flushes = _rs_in(flushes, FLUSH_DTYPE)
-    states = _rs_in(states, RESEND_DTYPE)
-    senders = _rs_in(senders, SENDER_DTYPE)
+    states = _in("states", states, RESEND_DTYPE)
     n = states.size
-    if min(queues.size, rate.size, flushes.size, senders.size) < n or frame_first.size < n + 1:
-        raise ValueError("queues, rate, flushes and senders must hold one record per state, frame_first one more")
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    frame_first = _in("frame_first", frame_first, _U64, n + 1)
+    queues = _in("queues", queues, FRAME_QUEUE_DTYPE, n)
+    log = _in("log", log, SENT_FRAME_DTYPE)
+    rate = _in("rate", rate, RATE_RESULT_DTYPE, n)
+    flushes = _in("flushes", flushes, FLUSH_DTYPE, n)
+    senders = _in("senders", senders, SENDER_DTYPE, n)
     if flags is not None:
-        flags = _rs_in(flags, np.dtype(np.uint32))
-        if flags.size < n:
-            raise ValueError("flags must hold one entry per state")
-    A = _rs_arenas(arenas)
-    results = _rate_inout("results", results, n, RESEND_RESULT_DTYPE)
-    states_out = _rate_inout("states_out", states_out, n, RESEND_DTYPE)
-    senders_out = _rate_inout("senders_out", senders_out, n, SENDER_DTYPE)
-    check(lib().ufc_resend_begin_host(_rs_ptr(infos), infos.size, frame_first.ctypes.data, _rs_ptr(queues), _rs_ptr(log),
-                                      log.size, _rs_ptr(rate), _rs_ptr(flags), _rs_ptr(flushes), _rs_ptr(states),
-                                      _rs_ptr(senders), n, _rs_ptr(A["heap"]), A["heap"].size, _rs_ptr(A["pkts"]),
-                                      A["pkts"].size, _rs_ptr(A["frag_acked"]), A["frag_acked"].size, _rs_ptr(A["tx"]),
-                                      A["tx"].size, _rs_ptr(A["ref_acked"]), A["ref_acked"].size, _rs_ptr(A["stage"]),
-                                      A["stage"].size, _rs_ptr(results), _rs_ptr(states_out), _rs_ptr(senders_out),
-                                      nthreads), "ufc_resend_begin_host")
+        flags = _in("flags", flags, _U32, n)
+    A = _rs_arenas(arenas, "heap", "pkts", "frag_acked", "tx", "ref_acked", "stage")
+    results = _inout("results", results, RESEND_RESULT_DTYPE, n)
+    states_out = _inout("states_out", states_out, RESEND_DTYPE, n)
+    senders_out = _inout("senders_out", senders_out, SENDER_DTYPE, n)
+    check(lib().ufc_resend_begin_host(_p(infos), infos.size, frame_first.ctypes.data, _p(queues), _p(log), log.size,
+                                      _p(rate), _p(flags), _p(flushes), _p(states), _p(senders), n,
+                                      *A, _p(results), _p(states_out), _p(senders_out), nthreads),
+          "ufc_resend_begin_host")
     return {"results": results, "states_out": states_out, "senders_out": senders_out}
 
 
@@ -1017,18 +818,13 @@ def resend_place_host(states: np.ndarray, begin_results: np.ndarray, arenas: dic
                       items: np.ndarray, nthreads: int = 1):
     """ufc_resend_place_host: every connection's staged items into items[flush_first[c] ..], the slots the emit
     reserved; items (ITEM_DTYPE) is written in place and returned."""
-    states = _rs_in(states, RESEND_DTYPE)
-    begin_results = _rs_in(begin_results, RESEND_RESULT_DTYPE)
-    flush_first = _rs_in(flush_first, np.dtype(np.uint64))
+    states = _in("states", states, RESEND_DTYPE)
     n = states.size
-    if begin_results.size < n or flush_first.size < n + 1:
-        raise ValueError("begin_results must hold one record per state, flush_first one more")
-    if items.dtype != ITEM_DTYPE or not items.flags.c_contiguous or not items.flags.writeable:
-        raise ValueError("items must be a writable contiguous ITEM_DTYPE array")
-    stage = _rs_arenas(arenas)["stage"]
-    check(lib().ufc_resend_place_host(_rs_ptr(states), _rs_ptr(begin_results), n, _rs_ptr(stage), stage.size,
-                                      flush_first.ctypes.data, _rs_ptr(items), items.size, nthreads),
-          "ufc_resend_place_host")
+    begin_results = _in("begin_results", begin_results, RESEND_RESULT_DTYPE, n)
+    flush_first = _in("flush_first", flush_first, _U64, n + 1)
+    items = _inout("items", items, ITEM_DTYPE)
+    check(lib().ufc_resend_place_host(_p(states), _p(begin_results), n, *_rs_arenas(arenas, "stage"),
+                                      flush_first.ctypes.data, _p(items), items.size, nthreads), "ufc_resend_place_host")
     return items
 
 
@@ -1044,41 +840,34 @@ def resend_commit_host(flush_results: np.ndarray, infos: np.ndarray, out_offsets
     the frames' SENT_FRAME_DTYPE records for the next frame_queue_host call, and the second emit's senders.  Returns a
     dict: results (RESEND_COMMIT_RESULT_DTYPE), states_out (may be given as `states`), retake (SENDER_DTYPE, may be
     given as `senders`), sent (one record per frame of infos unless given), sent_first, next_extra_flags."""
-    flush_results = _rs_in(flush_results, FLUSH_RESULT_DTYPE)
-    infos = _rs_in(infos, FRAME_INFO_DTYPE)
-    out_offsets = _rs_in(out_offsets, np.dtype(np.uint64))
-    items = _rs_in(items, ITEM_DTYPE)
-    flush_first = _rs_in(flush_first, np.dtype(np.uint64))
-    packets = _rs_in(packets, PACKET_DTYPE)
-    packet_first = _rs_in(packet_first, np.dtype(np.uint64))
-    packet_results = _rs_in(packet_results, PACKET_RESULT_DTYPE)
-    sender_results = _rs_in(sender_results, SENDER_RESULT_DTYPE)
-    begin_results = _rs_in(begin_results, RESEND_RESULT_DTYPE)
-    rate = _rs_in(rate, RATE_RESULT_DTYPE)
-    states = _rs_in(states, RESEND_DTYPE)
-    senders = _rs_in(senders, SENDER_DTYPE)
+    states = _in("states", states, RESEND_DTYPE)
     n = states.size
-    if min(flush_results.size, sender_results.size, begin_results.size, rate.size, senders.size) < n or \
-            min(flush_first.size, packet_first.size) < n + 1 or out_offsets.size < infos.size + 1 or \
-            packet_results.size < packets.size:
-        raise ValueError("one record per state (one more in the CSRs), out_offsets one more than infos")
-    A = _rs_arenas(arenas)
+    flush_results = _in("flush_results", flush_results, FLUSH_RESULT_DTYPE, n)
+    infos = _in("infos", infos, FRAME_INFO_DTYPE)
+    out_offsets = _in("out_offsets", out_offsets, _U64, infos.size + 1)
+    items = _in("items", items, ITEM_DTYPE)
+    flush_first = _in("flush_first", flush_first, _U64, n + 1)
+    packets = _in("packets", packets, PACKET_DTYPE)
+    packet_first = _in("packet_first", packet_first, _U64, n + 1)
+    packet_results = _in("packet_results", packet_results, PACKET_RESULT_DTYPE, packets.size)
+    sender_results = _in("sender_results", sender_results, SENDER_RESULT_DTYPE, n)
+    begin_results = _in("begin_results", begin_results, RESEND_RESULT_DTYPE, n)
+    rate = _in("rate", rate, RATE_RESULT_DTYPE, n)
+    senders = _in("senders", senders, SENDER_DTYPE, n)
+    A = _rs_arenas(arenas, "heap", "pkts", "frag_acked", "tx")
     used = np.array([frames_used], dtype=np.uint64)
-    sent = _rate_inout("sent", sent, infos.size, SENT_FRAME_DTYPE)
+    sent = _inout("sent", sent, SENT_FRAME_DTYPE, infos.size)
     sent_first = np.zeros(n + 1, dtype=np.uint64)
     if next_extra_flags is not None:
-        next_extra_flags = _rate_inout("next_extra_flags", next_extra_flags, n, np.dtype(np.uint32))
-    results = _rate_inout("results", results, n, RESEND_COMMIT_RESULT_DTYPE)
-    states_out = _rate_inout("states_out", states_out, n, RESEND_DTYPE)
-    retake = _rate_inout("retake", retake, n, SENDER_DTYPE)
-    check(lib().ufc_resend_commit_host(_rs_ptr(flush_results), _rs_ptr(infos), infos.size, out_offsets.ctypes.data,
-                                       used.ctypes.data, _rs_ptr(items), items.size, flush_first.ctypes.data,
-                                       _rs_ptr(packets), packets.size, packet_first.ctypes.data, _rs_ptr(packet_results),
-                                       _rs_ptr(sender_results), _rs_ptr(begin_results), _rs_ptr(rate), _rs_ptr(states),
-                                       _rs_ptr(senders), n, _rs_ptr(A["heap"]), A["heap"].size, _rs_ptr(A["pkts"]),
-                                       A["pkts"].size, _rs_ptr(A["frag_acked"]), A["frag_acked"].size, _rs_ptr(A["tx"]),
-                                       A["tx"].size, _rs_ptr(sent), sent.size, sent_first.ctypes.data,
-                                       _rs_ptr(next_extra_flags), _rs_ptr(results), _rs_ptr(states_out), _rs_ptr(retake),
-                                       nthreads), "ufc_resend_commit_host")
+        next_extra_flags = _inout("next_extra_flags", next_extra_flags, _U32, n)
+    results = _inout("results", results, RESEND_COMMIT_RESULT_DTYPE, n)
+    states_out = _inout("states_out", states_out, RESEND_DTYPE, n)
+    retake = _inout("retake", retake, SENDER_DTYPE, n)
+    check(lib().ufc_resend_commit_host(_p(flush_results), _p(infos), infos.size, out_offsets.ctypes.data, used.ctypes.data,
+                                       _p(items), items.size, flush_first.ctypes.data, _p(packets), packets.size,
+                                       packet_first.ctypes.data, _p(packet_results), _p(sender_results), _p(begin_results),
+                                       _p(rate), _p(states), _p(senders), n, *A,
+                                       _p(sent), sent.size, sent_first.ctypes.data, _p(next_extra_flags), _p(results),
+                                       _p(states_out), _p(retake), nthreads), "ufc_resend_commit_host")
     return {"results": results, "states_out": states_out, "retake": retake, "sent": sent, "sent_first": sent_first,
             "next_extra_flags": next_extra_flags}
