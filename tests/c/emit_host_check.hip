@@ -7,7 +7,12 @@
 // stop by find-first, the window parent from the reliable lanes below, the channel parent from 64 per-channel
 // lane masks and a 64-entry table carried across tiles, then the item search (the sender in flush_first, the
 // packet among the sender's first items) for every item slot.  All buffers have their exact sizes.  Both must
-// agree in every item, result and state field.
+// agree in every item, result and state field.  The tile form keeps the kernel's shape where a lane reads
+// another's value: the three carries are lane 63's inclusive sums, the item search is narrowed to the senders
+// of a workgroup's 256 slots first, and the finish pass runs in both of its lane widths.
+// directed_cases() places stops, parents and carried sums on lane 63 and on lane 0 of the next tile, and
+// senders on the seams of the item search (tests/emit_expect.py lane_cases, the same numbers), and compares
+// with literals as well.
 // Prints "ok: <checks>" and exits 0; any difference or sanitizer report stops the program.
 #include <cstdint>
 #include <cstdio>
@@ -137,7 +142,7 @@ void tile_form(const ufc_packet* q, uint64_t n_range, const ufc_sender& sd, uint
     const uint32_t nv = (uint32_t)(n - t0 < 64 ? n - t0 : 64);
     ufc_packet pk[64];
     uint32_t cls[64], rank[64], y[64], fc[64];
-    uint64_t a_sz[64], A_ex[64], f_ex[64];
+    uint64_t a_sz[64], A_incl[64], A_ex[64], f_incl[64], f_ex[64], d_incl[64];
     uint64_t live_mask = 0;
     for (uint32_t l = 0; l < 64; l++) {
       pk[l] = ufc_packet{};
@@ -153,8 +158,9 @@ void tile_form(const ufc_packet* q, uint64_t n_range, const ufc_sender& sd, uint
       const bool live = (live_mask >> l) & 1;
       rank[l] = rank_base + (uint32_t)popc(live_mask & ((1ull << l) - 1));
       a_sz[l] = live ? ufc_codec::emit_alloc_size(pk[l].data_len) : 0;
-      A_ex[l] = A_base + run;
       run += a_sz[l];
+      A_incl[l] = run;
+      A_ex[l] = A_base + A_incl[l] - a_sz[l];
       y[l] = UFC_EMIT_DONE;
       if (l < nv) {
         if (cls[l] == ufc_codec::kEmitBad)
@@ -175,16 +181,19 @@ void tile_form(const ufc_packet* q, uint64_t n_range, const ufc_sender& sd, uint
       A_base = A_ex[l];
       stopped = true;
     } else {
-      A_base += run;
+      A_base += A_incl[63];
     }
-    uint64_t emit_mask = 0, drop_mask = 0, rel_mask = 0, frun = 0;
+    uint64_t emit_mask = 0, drop_mask = 0, rel_mask = 0, frun = 0, drun = 0;
     for (uint32_t l = 0; l < 64; l++) {
       const bool in_prefix = l < limit;
       if (in_prefix && ((live_mask >> l) & 1)) emit_mask |= 1ull << l;
       if (in_prefix && cls[l] == ufc_codec::kEmitStale) drop_mask |= 1ull << l;
       fc[l] = (emit_mask >> l) & 1 ? ufc_codec::emit_fragment_count(pk[l].data_len) : 0;
-      f_ex[l] = made + frun;
       frun += fc[l];
+      f_incl[l] = frun;
+      f_ex[l] = made + (f_incl[l] - fc[l]);
+      drun += (drop_mask >> l) & 1 ? (uint64_t)pk[l].data_len : 0;
+      d_incl[l] = drun;
       if (((emit_mask >> l) & 1) && pk[l].mode == UFC_SEND_RELIABLE) rel_mask |= 1ull << l;
     }
     auto seq_of = [&](uint32_t h) -> uint32_t {
@@ -210,15 +219,17 @@ void tile_form(const ufc_packet* q, uint64_t n_range, const ufc_sender& sd, uint
         pres[t0 + l].resend = pk[l].mode >= UFC_SEND_PERSISTENT ? 1 : 0;
       } else if ((drop_mask >> l) & 1) {
         pres[t0 + l].status = UFC_PACKET_DROPPED;
-        dropped_bytes += pk[l].data_len;
       }
     }
     for (int c = 0; c < 64; c++)
       if (mask[c]) parent[c] = seq_of(high_bit(mask[c])), mask[c] = 0;
     if (rel_mask) wparent = seq_of(high_bit(rel_mask));
     rank_base += (uint32_t)popc(emit_mask);
-    made += frun;
-    dropped += (uint32_t)popc(drop_mask);
+    made += f_incl[63];
+    if (drop_mask != 0) {
+      dropped += (uint32_t)popc(drop_mask);
+      dropped_bytes += d_incl[63];
+    }
     done = t0 + nv;
   }
   for (uint64_t k = done; k < n_range; k++) pres[k] = ufc_packet_result{};
@@ -256,13 +267,15 @@ ufc_packet random_packet(uint32_t flush_id, uint32_t& arena, bool allow_bad) {
   return p;
 }
 
-void check_batch(uint32_t n_senders, uint32_t max_queue) {
-  std::vector<uint64_t> first(n_senders + 1, 0);
-  for (uint32_t s = 0; s < n_senders; s++) first[s + 1] = first[s] + (rnd() % 4 == 0 ? 0 : rnd() % (max_queue + 1));
+// The emit's launches over one batch in exactly-sized arrays (a read or write past an end is a sanitizer
+// report), checked against the serial walk, whose outputs are returned.
+std::vector<Out> run_batch(const std::vector<uint64_t>& first, const ufc_packet* packets_in, const ufc_sender* senders_in) {
+  const uint32_t n_senders = (uint32_t)first.size() - 1;
   const uint64_t n_packets = first[n_senders];
-  // exactly-sized arrays: a read or write past the end is a sanitizer report
   ufc_packet* packets = new ufc_packet[n_packets ? n_packets : 1];
   ufc_sender* senders = new ufc_sender[n_senders];
+  for (uint64_t i = 0; i < n_packets; i++) packets[i] = packets_in[i];
+  for (uint32_t s = 0; s < n_senders; s++) senders[s] = senders_in[s];
   uint32_t* rel_first = new uint32_t[n_packets ? n_packets : 1];
   uint64_t* meta = new uint64_t[n_packets ? n_packets : 1];
   ufc_packet_result* pres = new ufc_packet_result[n_packets ? n_packets : 1];
@@ -270,28 +283,7 @@ void check_batch(uint32_t n_senders, uint32_t max_queue) {
   ufc_sender* sout = new ufc_sender[n_senders];
   uint64_t* flush_first = new uint64_t[n_senders + 1];
   std::vector<Out> ref(n_senders);
-  uint32_t arena = 0;
-  for (uint32_t s = 0; s < n_senders; s++) {
-    ufc_sender sd{};
-    const uint64_t n = first[s + 1] - first[s];
-    sd.base_id = rnd() & kMask;
-    sd.next_id = (sd.base_id + rnd() % 50) & kMask;
-    sd.flush_id = rnd() % 4;
-    const uint32_t kind = rnd() % 3;
-    sd.window_size = kind == 1 ? 1u << (rnd() % 9) : 4096;
-    sd.alloc = rnd() % 100000;
-    sd.max_alloc = kind == 2 ? sd.alloc + rnd() % 80000 : (uint64_t)1 << 40;
-    if (rnd() % 16 == 0) sd.max_alloc = sd.alloc / 2;
-    sd.window_parent_id = rnd() % 2 ? (sd.next_id - 1 - rnd() % 50) & kMask : UFC_NO_PARENT;
-    for (int c = 0; c < 64; c++)
-      sd.channel_parent_id[c] = rnd() % 4 == 0 ? (sd.next_id - 1 - rnd() % 70) & kMask : UFC_NO_PARENT;
-    sd.take = rnd() % 5 ? 0xFFFFFFFFu : rnd() % (uint32_t)(n + 2);
-    sd.reserve_items = rnd() % 3 ? 0 : rnd() % 5;
-    sd.reserved = rnd();
-    senders[s] = sd;
-    for (uint64_t i = 0; i < n; i++) packets[first[s] + i] = random_packet(sd.flush_id, arena, true);
-    ref[s] = serial_walk(packets + first[s], n, sd);
-  }
+  for (uint32_t s = 0; s < n_senders; s++) ref[s] = serial_walk(packets + first[s], first[s + 1] - first[s], senders[s]);
   // launch 1, per sender; the scan
   flush_first[0] = 0;
   for (uint32_t s = 0; s < n_senders; s++) {
@@ -304,13 +296,18 @@ void check_batch(uint32_t n_senders, uint32_t max_queue) {
   ufc_item* items = new ufc_item[total ? total : 1];
   for (uint64_t g = 0; g < total; g++) items[g] = untouched();
   // launch 4: every item slot on its own
-  for (uint64_t g = 0; g < total; g++) {
-    uint64_t lo = 0, hi = n_senders - 1;
+  auto sender_of = [&](uint64_t g, uint64_t lo, uint64_t hi) -> uint64_t {
     while (lo < hi) {
       const uint64_t mid = lo + (hi - lo + 1) / 2;
       if (flush_first[mid] <= g) lo = mid; else hi = mid - 1;
     }
-    const uint64_t s = lo;
+    return lo;
+  };
+  for (uint64_t g = 0; g < total; g++) {
+    const uint64_t g0 = g / 256 * 256;  // the workgroup's slots: its senders first, then the slot's among them
+    const uint64_t s_lo = sender_of(g0, 0, n_senders - 1);
+    const uint64_t s_hi = sender_of((g0 + 256 < total ? g0 + 256 : total) - 1, s_lo, n_senders - 1);
+    const uint64_t s = sender_of(g, s_lo, s_hi);
     if (!(flush_first[s] <= g && g < flush_first[s + 1])) fail("sender search", (long)g, (long)s, 0);
     const uint32_t consumed = sres[s].packets_consumed;
     if (consumed == 0) continue;
@@ -327,6 +324,26 @@ void check_batch(uint32_t n_senders, uint32_t max_queue) {
     if (f > last) fail("fragment past the packet", (long)g, (long)f, (long)last);
     const uint64_t m = meta[first[s] + a];
     items[g] = ufc_codec::emit_item(pk, (uint32_t)m, (uint16_t)(m >> 32), (uint16_t)(m >> 48), f, last);
+  }
+  // launch 3 in both widths, on copies: the emitted packets' first items made absolute
+  for (uint32_t lanes : {8u, 64u}) {
+    ufc_packet_result* abs_pres = new ufc_packet_result[n_packets ? n_packets : 1];
+    for (uint64_t i = 0; i < n_packets; i++) abs_pres[i] = pres[i];
+    for (uint32_t s = 0; s < n_senders; s++)
+      for (uint32_t lane = 0; lane < lanes; lane++)
+        for (uint32_t q = lane; q < sres[s].packets_consumed; q += lanes) {
+          ufc_packet_result* pr = abs_pres + first[s] + q;
+          if (pr->status == UFC_PACKET_EMITTED) pr->item_first += (uint32_t)flush_first[s];
+        }
+    for (uint32_t s = 0; s < n_senders; s++)
+      for (uint64_t i = 0; i < first[s + 1] - first[s]; i++) {
+        const ufc_packet_result& a = ref[s].pres[i];
+        const ufc_packet_result& b = abs_pres[first[s] + i];
+        if (b.status != a.status || b.item_first != a.item_first + (a.status == UFC_PACKET_EMITTED ? (uint32_t)flush_first[s] : 0u))
+          fail("finish", (long)lanes, (long)s, (long)i);
+      }
+    checks++;
+    delete[] abs_pres;
   }
   // against the serial walk
   for (uint32_t s = 0; s < n_senders; s++) {
@@ -359,6 +376,37 @@ void check_batch(uint32_t n_senders, uint32_t max_queue) {
   delete[] sout;
   delete[] flush_first;
   delete[] items;
+  return ref;
+}
+
+void check_batch(uint32_t n_senders, uint32_t max_queue) {
+  std::vector<uint64_t> first(n_senders + 1, 0);
+  for (uint32_t s = 0; s < n_senders; s++) first[s + 1] = first[s] + (rnd() % 4 == 0 ? 0 : rnd() % (max_queue + 1));
+  const uint64_t n_packets = first[n_senders];
+  std::vector<ufc_packet> packets(n_packets ? n_packets : 1);
+  std::vector<ufc_sender> senders(n_senders);
+  uint32_t arena = 0;
+  for (uint32_t s = 0; s < n_senders; s++) {
+    ufc_sender sd{};
+    const uint64_t n = first[s + 1] - first[s];
+    sd.base_id = rnd() & kMask;
+    sd.next_id = (sd.base_id + rnd() % 50) & kMask;
+    sd.flush_id = rnd() % 4;
+    const uint32_t kind = rnd() % 3;
+    sd.window_size = kind == 1 ? 1u << (rnd() % 9) : 4096;
+    sd.alloc = rnd() % 100000;
+    sd.max_alloc = kind == 2 ? sd.alloc + rnd() % 80000 : (uint64_t)1 << 40;
+    if (rnd() % 16 == 0) sd.max_alloc = sd.alloc / 2;
+    sd.window_parent_id = rnd() % 2 ? (sd.next_id - 1 - rnd() % 50) & kMask : UFC_NO_PARENT;
+    for (int c = 0; c < 64; c++)
+      sd.channel_parent_id[c] = rnd() % 4 == 0 ? (sd.next_id - 1 - rnd() % 70) & kMask : UFC_NO_PARENT;
+    sd.take = rnd() % 5 ? 0xFFFFFFFFu : rnd() % (uint32_t)(n + 2);
+    sd.reserve_items = rnd() % 3 ? 0 : rnd() % 5;
+    sd.reserved = rnd();
+    senders[s] = sd;
+    for (uint64_t i = 0; i < n; i++) packets[first[s] + i] = random_packet(sd.flush_id, arena, true);
+  }
+  run_batch(first, packets.data(), senders.data());
 }
 
 void check_arithmetic() {
@@ -390,10 +438,213 @@ void check_arithmetic() {
     }
 }
 
+// ---- directed cases (tests/emit_expect.py lane_cases, the same numbers) ----
+
+constexpr uint8_t kT = 0, kU = 1, kR = 3;  // SendMode: time-sensitive, unreliable, reliable
+
+ufc_packet pkt(uint32_t len, uint8_t channel = 0, uint8_t mode = kU, uint32_t flush_id = 0) {
+  ufc_packet p{};
+  p.data_len = len;
+  p.channel_id = channel;
+  p.mode = mode;
+  p.flush_id = flush_id;
+  return p;
+}
+ufc_packet stale(uint32_t len = 7, uint8_t channel = 2) { return pkt(len, channel, kT, 1); }  // under flush_id 0
+std::vector<ufc_packet> rep(const ufc_packet& p, size_t n) { return std::vector<ufc_packet>(n, p); }
+std::vector<ufc_packet> operator+(std::vector<ufc_packet> a, const std::vector<ufc_packet>& b) {
+  a.insert(a.end(), b.begin(), b.end());
+  return a;
+}
+
+struct Directed {
+  std::vector<ufc_packet> packets;
+  std::vector<uint64_t> first{0};
+  std::vector<ufc_sender> senders;
+  uint32_t arena = 0;
+  // A sender with nothing in flight, no parents and no limits; the caller sets what the case needs.
+  ufc_sender& add(const std::vector<ufc_packet>& q) {
+    for (ufc_packet p : q) {
+      p.data_offset = arena;
+      if (p.data_len <= kFrag * 65536u) arena += p.data_len;
+      packets.push_back(p);
+    }
+    first.push_back(packets.size());
+    ufc_sender sd{};
+    sd.window_size = 4096;
+    sd.max_alloc = (uint64_t)1 << 40;
+    sd.window_parent_id = UFC_NO_PARENT;
+    for (int c = 0; c < 64; c++) sd.channel_parent_id[c] = UFC_NO_PARENT;
+    sd.take = 0xFFFFFFFFu;
+    senders.push_back(sd);
+    return senders.back();
+  }
+};
+
+void want(const char* what, long tag, uint64_t got, uint64_t lit) {
+  if (got != lit) fail(what, tag, (long)got, (long)lit);
+  checks++;
+}
+// The leads of emitted packet i, from its first item.
+uint32_t wlead(const Out& o, uint32_t i) { return o.items[o.pres[i].item_first].window_parent_lead; }
+uint32_t clead(const Out& o, uint32_t i) { return o.items[o.pres[i].item_first].channel_parent_lead; }
+
+void directed_cases() {
+  Directed d;
+  // the item search: a packet on slots 254, 255 | 256; reserved slots 510, 511 | 512; a range that starts at
+  // slot 768 behind two empty senders; a range that starts at slot 1023
+  const size_t seams = d.senders.size();
+  d.add(rep(pkt(1), 254) + rep(pkt(3000), 1) + rep(pkt(1), 253));
+  d.add(rep(pkt(1, 1, kR), 255)).reserve_items = 3;
+  d.add({});
+  d.add({});
+  d.add(rep(pkt(3000, 2, kR), 1) + rep(pkt(1, 2), 252));
+  d.add(rep(pkt(1, 4, kR), 2));  // starts on the last slot of a workgroup, 1023
+  // stop_at[p] x {window, alloc, bad} x {all live, the even packets but p stale}
+  const uint32_t ps[] = {63, 64, 65, 127, 128}, rank_lit[2][5] = {{63, 64, 65, 127, 128}, {31, 32, 32, 63, 64}},
+                 frags_lit[2][5] = {{84, 86, 87, 170, 171}, {41, 43, 43, 84, 85}};  // alloc sizes before p, in fragments
+  const uint32_t base = 0xFFFC0;
+  const size_t stops = d.senders.size();
+  for (int pi = 0; pi < 5; pi++)
+    for (int form = 0; form < 2; form++) {
+      const uint32_t p = ps[pi], rank = rank_lit[form][pi];
+      std::vector<ufc_packet> q;
+      for (uint32_t k = 0; k < p + 10; k++) {
+        const bool live = form == 0 || k % 2 == 1 || k == p;
+        q.push_back(live ? pkt(kFrag * (1 + (k % 3 == 0)), (uint8_t)(k % 5), k % 7 == 3 ? kR : kU) : stale(9, (uint8_t)(k % 5)));
+      }
+      for (int why = 0; why < 3; why++) {
+        std::vector<ufc_packet> qq = q;
+        if (why == 2) qq[p] = pkt(1, 70);
+        ufc_sender& sd = d.add(qq);
+        sd.base_id = base;
+        sd.next_id = why == 0 ? (base + 256 - rank) & kMask : base;
+        sd.window_size = why == 0 ? 256 : 4096;
+        sd.alloc = 500 * kFrag;
+        if (why == 1) sd.max_alloc = (500 + (uint64_t)frags_lit[form][pi]) * kFrag;
+      }
+    }
+  // the window parent on lane 63, on lanes 62 and 63, on lane 0 of tile 2
+  const size_t wp = d.senders.size();
+  for (int v = 0; v < 3; v++) {
+    std::vector<ufc_packet> q = rep(pkt(2, 1), 130);
+    if (v == 0) q[63].mode = kR;
+    if (v == 1) q[62].mode = q[63].mode = kR;
+    if (v == 2) q[64].mode = kR;
+    ufc_sender& sd = d.add(q);
+    sd.next_id = 100, sd.window_parent_id = 90, sd.channel_parent_id[1] = 80;
+  }
+  // the channel parent through parent[5], two tiles on; lane 63 moves mask[63] into parent[63]
+  const size_t cp = d.senders.size();
+  {
+    std::vector<ufc_packet> q = rep(pkt(2, 1), 130);
+    q[63] = pkt(2, 5, kR), q[64] = pkt(2, 5), q[128] = pkt(2, 5);
+    ufc_sender& sd = d.add(q);
+    sd.next_id = 100, sd.channel_parent_id[5] = 70;
+    q = rep(pkt(2, 1), 70);
+    q[0] = pkt(2, 63, kR), q[63] = pkt(2, 63), q[64] = pkt(2, 63);
+    d.add(q).next_id = 100;
+  }
+  // what only lane 63 carries: the fragment count, the alloc size, the dropped bytes
+  const size_t only = d.senders.size();
+  d.add(rep(stale(), 63) + rep(pkt(3000), 1) + rep(pkt(kFrag), 10)).next_id = 500;
+  d.add(rep(stale(), 63) + rep(pkt(3000), 1) + rep(pkt(kFrag), 10)).max_alloc = 3 * kFrag;
+  d.add(rep(stale(), 63) + rep(pkt(3000), 1) + rep(pkt(kFrag), 10)).max_alloc = 4 * kFrag;
+  d.add(rep(pkt(5), 63) + rep(stale(777), 1) + rep(pkt(5), 10));
+  d.add(rep(pkt(5, 3, kR), 63) + rep(stale(11), 1) + rep(pkt(1, 70), 1) + rep(pkt(5), 5));  // stale_63_then_stop_64
+  // take at 63, 64, 65, 128 of 200
+  const size_t takes = d.senders.size();
+  const uint32_t take_lit[] = {63, 64, 65, 128};
+  {
+    std::vector<ufc_packet> q;
+    const uint32_t lens[] = {0, 5, 300, 1448, 1449, 4000};
+    for (int k = 0; k < 200; k++) q.push_back(pkt(lens[rnd() % 6], (uint8_t)(rnd() % 4), (uint8_t)(rnd() % 4), rnd() % 3 == 0));
+    for (uint32_t t : take_lit) d.add(q).take = t;
+  }
+  d.add(rep(pkt(3000, 1, kR), 8)).reserve_items = 1;  // the finish's 8 lanes: one pass, and a second for the 9th
+  d.add(rep(pkt(3000, 1, kR), 9)).reserve_items = 1;
+
+  const std::vector<Out> o = run_batch(d.first, d.packets.data(), d.senders.data());
+  std::vector<uint64_t> ff(o.size() + 1, 0);
+  for (size_t s = 0; s < o.size(); s++) ff[s + 1] = ff[s] + o[s].items.size();
+
+  want("seams: straddle", 0, ff[seams] + o[seams].pres[254].item_first, 254);
+  want("seams: straddle", 1, o[seams].pres[254].item_count, 3);
+  want("seams: straddle", 2, ff[seams] + o[seams].pres[255].item_first, 257);
+  want("seams: reserved", 0, ff[seams + 1], 510);
+  want("seams: reserved", 1, ff[seams + 1] + o[seams + 1].pres[0].item_first, 513);
+  want("seams: empty", 0, ff[seams + 2], 768);
+  want("seams: empty", 1, ff[seams + 3], 768);
+  want("seams: range start", 0, ff[seams + 4], 768);
+  want("seams: range start", 1, ff[seams + 4] + o[seams + 4].pres[1].item_first, 771);
+  want("seams: range start", 2, clead(o[seams + 4], 5), 5);
+  want("seams: last slot", 0, ff[seams + 5], 1023);
+  want("seams: last slot", 1, ff[seams + 5] + o[seams + 5].pres[1].item_first, 1024);
+  for (int pi = 0; pi < 5; pi++)
+    for (int form = 0; form < 2; form++)
+      for (int why = 0; why < 3; why++) {
+        const Out& x = o[stops + (pi * 2 + form) * 3 + why];
+        const uint32_t p = ps[pi], rank = rank_lit[form][pi];
+        const uint32_t why_lit[] = {UFC_EMIT_WINDOW_LIMITED, UFC_EMIT_ALLOC_LIMITED, UFC_EMIT_BAD_PACKET};
+        want("stop_at: consumed", p, x.res.packets_consumed, p);
+        want("stop_at: stop", p, x.res.stop, why_lit[why]);
+        want("stop_at: emitted", p, x.res.packets_emitted, rank);
+        want("stop_at: dropped", p, x.res.packets_dropped, p - rank);
+        want("stop_at: bytes dropped", p, x.res.bytes_dropped, 9 * (uint64_t)(p - rank));
+        want("stop_at: alloc", p, x.state.alloc, (500 + (uint64_t)frags_lit[form][pi]) * kFrag);
+        want("stop_at: next_id", p, x.state.next_id, why == 0 ? 192 : (base + rank) & kMask);
+      }
+  want("window parent at 63", 0, wlead(o[wp], 0), 10);
+  want("window parent at 63", 62, wlead(o[wp], 62), 72);
+  want("window parent at 63", 63, wlead(o[wp], 63), 73);
+  want("window parent at 63", 64, wlead(o[wp], 64), 1);
+  want("window parent at 63", 129, wlead(o[wp], 129), 66);
+  want("window parent at 63", 1, clead(o[wp], 63), 83);
+  want("window parent at 63", 2, o[wp].state.window_parent_id, 163);
+  want("window parents at 62 and 63", 63, wlead(o[wp + 1], 63), 1);
+  want("window parents at 62 and 63", 64, wlead(o[wp + 1], 64), 1);
+  want("window parents at 62 and 63", 0, o[wp + 1].state.window_parent_id, 163);
+  want("window parent at 64", 63, wlead(o[wp + 2], 63), 73);
+  want("window parent at 64", 64, wlead(o[wp + 2], 64), 74);
+  want("window parent at 64", 65, wlead(o[wp + 2], 65), 1);
+  want("window parent at 64", 129, wlead(o[wp + 2], 129), 65);
+  want("window parent at 64", 0, o[wp + 2].state.window_parent_id, 164);
+  want("channel parent at 63", 63, clead(o[cp], 63), 93);
+  want("channel parent at 63", 64, clead(o[cp], 64), 1);
+  want("channel parent at 63", 128, clead(o[cp], 128), 65);
+  want("channel parent at 63", 0, o[cp].state.channel_parent_id[5], 163);
+  want("channel 63", 63, clead(o[cp + 1], 63), 63);
+  want("channel 63", 64, clead(o[cp + 1], 64), 64);
+  want("channel 63", 0, o[cp + 1].state.channel_parent_id[63], 100);
+  want("only lane 63: fragments", 64, o[only].pres[64].item_first, 3);
+  want("only lane 63: fragments", 0, o[only].res.item_count, 13);
+  want("only lane 63: fragments", 1, o[only].res.packets_emitted, 11);
+  want("only lane 63: fragments", 2, o[only].pres[64].sequence_id, 501);
+  want("only lane 63: alloc", 0, o[only + 1].res.packets_consumed, 64);
+  want("only lane 63: alloc", 1, o[only + 1].res.stop, UFC_EMIT_ALLOC_LIMITED);
+  want("only lane 63: alloc", 2, o[only + 2].res.packets_consumed, 65);
+  want("only lane 63: alloc", 3, o[only + 2].state.alloc, 4 * kFrag);
+  want("only lane 63: dropped", 0, o[only + 3].res.packets_dropped, 1);
+  want("only lane 63: dropped", 1, o[only + 3].res.bytes_dropped, 777);
+  want("stale 63 then stop 64", 0, o[only + 4].res.packets_consumed, 64);
+  want("stale 63 then stop 64", 1, o[only + 4].res.stop, UFC_EMIT_BAD_PACKET);
+  want("stale 63 then stop 64", 2, o[only + 4].res.packets_dropped, 1);
+  want("stale 63 then stop 64", 3, o[only + 4].pres[63].status, UFC_PACKET_DROPPED);
+  want("stale 63 then stop 64", 4, o[only + 4].pres[64].status, 0);
+  for (int k = 0; k < 4; k++) {
+    const Out& x = o[takes + k];
+    want("take_at", take_lit[k], x.res.packets_consumed, take_lit[k]);
+    for (uint32_t i = take_lit[k]; i < 200; i++) want("take_at: zero past", i, x.pres[i].status | x.pres[i].item_count | x.pres[i].sequence_id, 0);
+  }
+  want("finish 8", 0, o[takes + 4].res.packets_consumed, 8);
+  want("finish 9", 0, o[takes + 5].res.packets_consumed, 9);
+}
+
 }  // namespace
 
 int main() {
   check_arithmetic();
+  directed_cases();
   check_batch(1, 0);
   check_batch(3, 1);
   for (int r = 0; r < 40; r++) check_batch(1 + rnd() % 60, rnd() % 4 ? 1 + rnd() % 300 : 1 + rnd() % 8);

@@ -231,10 +231,15 @@ class Senders:
     def __init__(self):
         self.packets, self.first, self.senders, self.names = [], [0], [], []
         self.arena = 0
+        self.facts = {}
 
-    def add(self, packets, name="", tx=None, flush_id=0, take=0xFFFFFFFF, reserve_items=0, **state):
+    def add(self, packets, name="", tx=None, flush_id=0, take=0xFFFFFFFF, reserve_items=0, facts=None, **state):
         """tx: a Tx to take the state from; else Tx(window_size, base_id, max_alloc) with next_id, alloc,
-        window_parent_id, channel_parents={channel: id} set as given."""
+        window_parent_id, channel_parents={channel: id} set as given.  facts: what check_facts asserts of the
+        model's output for this sender."""
+        if facts is not None:
+            assert name and name not in self.facts, name
+            self.facts[name] = facts
         if tx is None:
             tx = Tx(state.pop("window_size", MAX_PACKET_WINDOW_SIZE), state.pop("base_id", 0),
                     state.pop("max_alloc", 1 << 40))
@@ -456,3 +461,157 @@ def check_max_packets(items, flush_first, packets, packet_first, senders, big):
                           ("data_len", MAX_FRAGMENT_SIZE)):
             assert np.array_equal(got[fld], np.broadcast_to(want, n)), (s, fld)
         assert (got["form"][:-1] == got["form"][0]).all() and (got["flags"][:-1] == got["flags"][0]).all(), s
+
+
+# ---- lane 63 and the tile seam of the sender kernel, the seams of the item kernel, the finish kernel's widths ----
+
+SENDER_FACTS = ("packets_consumed", "stop", "packets_emitted", "packets_dropped", "bytes_dropped", "item_count", "item_first")
+
+
+def check_facts(b, exp):
+    """Every named sender's facts against exp = expect(...), the model's output.  Keys: a sender result's field; a
+    field of senders_out (alloc, next_id, window_parent_id); channel_parents {channel: id} of senders_out;
+    window_leads, channel_leads, seq, status, slot {packet: value} (slot: the packet's absolute first item);
+    first_item {packet: its first item relative to the sender's}; zero_past: the packet results from that packet
+    on are zero records."""
+    for name, f in b.facts.items():
+        s = b.index(name)
+        a, z = b.first[s], b.first[s + 1]
+        r, out = exp.sender_results[s], exp.senders_out[s]
+        pr = exp.packet_results[a:z]
+        for key, want in f.items():
+            if key in SENDER_FACTS:
+                got = int(r[key])
+            elif key in ("alloc", "next_id", "window_parent_id"):
+                got = int(out[key])
+            elif key == "channel_parents":
+                got = {ch: int(out["channel_parent_id"][ch]) for ch in want}
+            elif key in ("window_leads", "channel_leads"):
+                fld = "window_parent_lead" if key == "window_leads" else "channel_parent_lead"
+                assert all(pr["status"][k] == EMITTED for k in want), (name, key)
+                got = {k: int(exp.items[int(pr["item_first"][k])][fld]) for k in want}
+            elif key == "seq":
+                got = {k: int(pr["sequence_id"][k]) for k in want}
+            elif key == "status":
+                got = {k: int(pr["status"][k]) for k in want}
+            elif key == "slot":
+                got = {k: int(pr["item_first"][k]) for k in want}
+            elif key == "first_item":
+                got = {k: int(pr["item_first"][k]) - int(r["item_first"]) for k in want}
+            elif key == "zero_past":
+                assert want < z - a, (name, key)
+                got = want if not pr[want:].view(np.uint8).any() else None
+            else:
+                raise KeyError(key)
+            assert got == want, (name, key, got, want)
+
+
+def lane_cases(tile=64):
+    """Senders whose deciding packet sits on lane 63 of a tile of `tile` packets or on lane 0 of the next one,
+    for every read of the sender kernel that crosses lanes or tiles; senders laid out so that the item kernel's
+    workgroups of 256 slots meet a range start, a packet and reserved slots at their seams.  One batch, the item
+    kernel's senders first (their slot numbers are absolute).  The packet count is a multiple of 16 (padded)."""
+    U, R, T = UNRELIABLE, RELIABLE, TIME_SENSITIVE
+    F = MAX_FRAGMENT_SIZE
+    assert tile == 64
+    b = Senders()
+    stale = lambda n=7, ch=2: pkt(n, ch, T, flush_id=1)  # noqa: E731  (under the senders' flush_id 0)
+
+    # The item kernel.  One seam cannot hold all three events, so they sit on three: a packet of three
+    # fragments on slots 254, 255 | 256; reserved slots 510, 511 | 512; a range that starts at slot 768 behind
+    # two empty senders whose flush_first is 768 as well; and one that starts at slot 1023.
+    b.add([pkt(1)] * 254 + [pkt(3000)] + [pkt(1)] * 253, "items_kernel_seams[straddle]",
+          facts={"item_first": 0, "item_count": 510, "slot": {253: 253, 254: 254, 255: 257}})
+    b.add([pkt(1, 1, R)] * 255, "items_kernel_seams[reserved]", reserve_items=3,
+          facts={"item_first": 510, "item_count": 258, "slot": {0: 513}})
+    b.add([], "items_kernel_seams[empty_a]", facts={"item_first": 768, "item_count": 0})
+    b.add([], "items_kernel_seams[empty_b]", facts={"item_first": 768, "item_count": 0})
+    b.add([pkt(3000, 2, R)] + [pkt(1, 2)] * 252, "items_kernel_seams[starts_at_seam]",
+          facts={"item_first": 768, "item_count": 255, "slot": {0: 768, 1: 771}, "channel_leads": {1: 1, 5: 5}})
+    # (own) a range that starts on the last slot of a workgroup: the narrowed search's upper end is its sender
+    b.add([pkt(1, 4, R)] * 2, "items_kernel_seams[starts_at_last_slot]",
+          facts={"item_first": 1023, "item_count": 2, "slot": {0: 1023, 1: 1024}})
+
+    # stop_at[p]: a stop of each kind on lane 63, on lane 0 and lane 1 of tile 2, on lane 63 of tile 2 and on
+    # lane 0 of tile 3; over an all-live queue, and over one whose even packets (but p) are stale: rank != lane
+    for p in (63, 64, 65, 127, 128):
+        for form in ("live", "stale_even"):
+            is_live = [form == "live" or k % 2 == 1 or k == p for k in range(p + 10)]
+            q = [pkt(F * (1 + (k % 3 == 0)), k % 5, R if k % 7 == 3 else U) if is_live[k] else stale(9, k % 5)
+                 for k in range(p + 10)]
+            rank = sum(is_live[:p])
+            before = sum(alloc_size(int(q[k][0]["data_len"])) for k in range(p) if is_live[k])
+            dropped = p - rank
+            common = {"packets_consumed": p, "packets_emitted": rank, "packets_dropped": dropped, "bytes_dropped": 9 * dropped,
+                      "alloc": 500 * F + before}
+            base = 0xFFFC0  # (the ids wrap inside the queue)
+            # room for `rank` packets: the window stops the live packet with that rank, packet p
+            b.add(q, f"stop_at[{p}][window][{form}]", window_size=256, base_id=base, next_id=(base + 256 - rank) & ID_MASK,
+                  alloc=500 * F, facts=dict(common, stop=WINDOW_LIMITED, next_id=(base + 256) & ID_MASK))
+            assert before % F == 0
+            b.add(q, f"stop_at[{p}][alloc][{form}]", base_id=base, next_id=base, alloc=500 * F, max_alloc=500 * F + before,
+                  facts=dict(common, stop=ALLOC_LIMITED, next_id=(base + rank) & ID_MASK))
+            bad = list(q)
+            bad[p] = pkt(1, channel=70)
+            b.add(bad, f"stop_at[{p}][bad][{form}]", base_id=base, next_id=base, alloc=500 * F,
+                  facts=dict(common, stop=BAD_PACKET, next_id=(base + rank) & ID_MASK))
+
+    # the window parent: the only reliable packet on lane 63; reliable packets on lanes 62 and 63; the reliable
+    # packet on lane 0 of tile 2, read by lane 1.  next_id 100, the carried parent 90.
+    def on_channel_1(n, reliable):
+        return [pkt(2, 1, R if k in reliable else U) for k in range(n)]
+
+    state = dict(next_id=100, window_parent_id=90, channel_parents={1: 80})
+    b.add(on_channel_1(130, (63,)), "window_parent_at_63", **state,
+          facts={"window_leads": {0: 10, 62: 72, 63: 73, 64: 1, 129: 66}, "channel_leads": {63: 83, 64: 1, 129: 66},
+                 "window_parent_id": 163, "channel_parents": {1: 163}})
+    b.add(on_channel_1(130, (62, 63)), "window_parent_at_63[62_and_63]", **state,
+          facts={"window_leads": {62: 72, 63: 1, 64: 1, 129: 66}, "window_parent_id": 163})
+    b.add(on_channel_1(130, (64,)), "window_parent_at_63[64]", **state,
+          facts={"window_leads": {63: 73, 64: 74, 65: 1, 129: 65}, "window_parent_id": 164})
+
+    # the channel parent: through parent[5] two tiles on; and lane 63 as the lane that moves mask[63] into parent[63]
+    q = on_channel_1(130, ())
+    q[63], q[64], q[128] = pkt(2, 5, R), pkt(2, 5, U), pkt(2, 5, U)
+    b.add(q, "channel_parent_at_63", next_id=100, channel_parents={5: 70},
+          facts={"channel_leads": {63: 93, 64: 1, 128: 65}, "channel_parents": {5: 163, 63: NO_PARENT}})
+    q = on_channel_1(70, ())
+    q[0], q[63], q[64] = pkt(2, 63, R), pkt(2, 63, U), pkt(2, 63, U)
+    b.add(q, "channel_parent_at_63[channel_63]", next_id=100,
+          facts={"channel_leads": {0: 0, 63: 63, 64: 64}, "channel_parents": {63: 100, 5: NO_PARENT}})
+
+    # values that only lane 63 carries into the next tile: the fragment count, the alloc size, the dropped bytes
+    b.add([stale()] * 63 + [pkt(3000)] + [pkt(F)] * 10, "only_lane_63[fragments]", next_id=500,
+          facts={"first_item": {63: 0, 64: 3, 65: 4}, "item_count": 13, "packets_emitted": 11, "seq": {63: 500, 64: 501},
+                 "packets_dropped": 63, "alloc": 3 * F + 10 * F})
+    b.add([stale()] * 63 + [pkt(3000)] + [pkt(F)] * 10, "only_lane_63[alloc]", max_alloc=3 * F,
+          facts={"stop": ALLOC_LIMITED, "packets_consumed": 64, "packets_emitted": 1, "alloc": 3 * F})
+    b.add([stale()] * 63 + [pkt(3000)] + [pkt(F)] * 10, "only_lane_63[alloc][one_more]", max_alloc=4 * F,
+          facts={"stop": ALLOC_LIMITED, "packets_consumed": 65, "packets_emitted": 2, "alloc": 4 * F})
+    b.add([pkt(5)] * 63 + [stale(777)] + [pkt(5)] * 10, "only_lane_63[dropped]",
+          facts={"packets_dropped": 1, "bytes_dropped": 777, "packets_emitted": 73, "status": {63: DROPPED, 64: EMITTED}})
+
+    b.add([pkt(5, 3, R)] * 63 + [stale(11)] + [pkt(1, channel=70)] + [pkt(5)] * 5, "stale_63_then_stop_64",
+          facts={"packets_consumed": 64, "stop": BAD_PACKET, "packets_dropped": 1, "bytes_dropped": 11, "packets_emitted": 63,
+                 "status": {62: EMITTED, 63: DROPPED, 64: NOT_REACHED}})
+
+    rng = random.Random(63)
+    q200 = [pkt(rng.choice((0, 5, 300, F, F + 1, 4000)), rng.randrange(4), rng.choice((T, U, U, PERSISTENT, R)),
+                flush_id=rng.choice((0, 0, 1))) for _ in range(200)]
+    for t in (63, 64, 65, 128):
+        b.add(q200, f"take_at[{t}]", take=t, facts={"packets_consumed": t, "stop": DONE, "zero_past": t})
+
+    # the finish kernel's widths: 8 lanes serve 8 packets in one pass and the 9th in a second one
+    b.add([pkt(3000, 1, R)] * 8, "finish_form_switch[8]", reserve_items=1, facts={"packets_consumed": 8})
+    b.add([pkt(3000, 1, R)] * 9, "finish_form_switch[9]", reserve_items=1, facts={"packets_consumed": 9})
+    b.add([pkt(1)] * (-len(b.packets) % 16), "pad_to_16")
+    assert len(b.packets) % 16 == 0 and len(b.packets) // 16 > len(b.senders)
+    return b
+
+
+def with_empty_senders(packets, first, senders, n_senders):
+    """The batch with empty senders behind it, n_senders in all."""
+    extra = n_senders - senders.size
+    assert extra >= 0
+    empty = np.array([Senders().add([]).senders[0]] * extra, dtype=SENDER_DTYPE)
+    return (packets, np.concatenate([first, np.full(extra, first[-1], dtype=np.uint64)]), np.concatenate([senders, empty]))

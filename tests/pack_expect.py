@@ -23,6 +23,7 @@ MAX_FRAGMENT_SIZE = MAX_FRAME_SIZE - DATA_FRAME_OVERHEAD - MAX_DATAGRAM_OVERHEAD
 MAX_PACKET_COUNT = min(0x100000 // (4096 * 2), 127)  # emit.rs:61-62
 DATA, ACK = 10, 12
 DONE, SIZE_LIMITED, WINDOW_LIMITED, BAD_RANGE = 0, 1, 2, 3
+PACK_GRID = 256  # items per workgroup of the hops kernel (batch-relative) and per tile of the chain (flush-relative)
 
 _size_cache = {}
 
@@ -139,14 +140,29 @@ class Flushes:
 
     def __init__(self):
         self.items, self.first, self.flushes = [], [0], []
+        self.names, self.facts = [], {}
 
-    def add(self, kind, items, flush_alloc=1 << 40, window_room=1 << 20, id0=0, id1=0):
+    def add(self, kind, items, flush_alloc=1 << 40, window_room=1 << 20, id0=0, id1=0, name="", at=None, facts=None):
+        """at: the batch index modulo PACK_GRID the flush has to start at; a filler DATA flush of dgram(800)
+        items goes in front of it where it would not.  facts: what check_facts asserts of the model's output."""
+        if at is not None:
+            pad = (at - len(self.items)) % PACK_GRID
+            if pad:
+                self.add(DATA, [dgram(800)] * pad)
+            assert len(self.items) % PACK_GRID == at
+        if name:
+            assert name not in self.facts and name not in self.names, name
+            self.facts[name] = dict(facts or {})
+        self.names.append(name)
         self.items.extend(items)
         self.first.append(len(self.items))
         fl = np.zeros((), dtype=FLUSH_DTYPE)
         fl["kind"], fl["flush_alloc"], fl["window_room"], fl["id0"], fl["id1"] = kind, flush_alloc, window_room, id0, id1
         self.flushes.append(fl)
         return self
+
+    def index(self, name):
+        return self.names.index(name)
 
     def arrays(self):
         items = np.array(self.items, dtype=ITEM_DTYPE) if self.items else np.zeros(0, ITEM_DTYPE)
@@ -260,3 +276,117 @@ def random_batch(seed, n_flushes, max_items):
 def nonce_words(seed, frames):
     rng = random.Random(seed)
     return np.array([rng.getrandbits(32) for _ in range((frames + 31) // 32 + 1)], dtype=np.uint32)
+
+
+# ---- lane 63, the slot seams and the tile seams of the chain kernel; the hop window's seams ----
+
+def check_facts(b, exp):
+    """Every named flush's facts against exp = expect(...), the model's output: `starts` and `counts` (the
+    frames' first items relative to the flush, and their item counts), `stop`, `items_packed`, `frame_count`."""
+    infos, results, _ = exp
+    for name, f in b.facts.items():
+        j = b.index(name)
+        r = results[j]
+        fr = infos[int(r["frame_first"]): int(r["frame_first"]) + int(r["frame_count"])]
+        got = {"starts": [int(x) - b.first[j] for x in fr["item_first"]], "counts": [int(x) for x in fr["item_count"]],
+               "stop": int(r["stop"]), "items_packed": int(r["items_packed"]), "frame_count": int(r["frame_count"])}
+        for key, want in f.items():
+            assert got[key] == want, (name, key, got[key], want)
+
+
+def _size_stops(b, prefix, kind, items, unit, overhead, starts, stops, at):
+    """Per i of stops two flushes of `items`: flush_alloc = F(i) - 1 stops at i, flush_alloc = F(i) at i + 1, with
+    F(i) = overhead * (starts before i) + unit * i over the unlimited chain's starts."""
+    for i in stops:
+        before = sum(1 for s in starts if s < i)
+        upto = sum(1 for s in starts if s <= i)
+        F = overhead * before + unit * i
+        for alloc, tag, packed, n in ((F - 1, "", i, before), (F, "+1", i + 1, upto)):
+            b.add(kind, items, flush_alloc=alloc, id0=i, id1=n, name=f"{prefix}[{i}]{tag}@{at}", at=at,
+                  facts={"stop": SIZE_LIMITED, "items_packed": packed, "frame_count": n, "starts": starts[:n],
+                         "counts": [q - p for p, q in zip(starts, starts[1:n] + [packed])]})
+
+
+def lane_cases():
+    """Flushes whose deciding item sits on lane 63, on lane 0 of the next slot of 64 or on item 0 of the next
+    tile of PACK_GRID items, for the reads of the chain kernel that cross lanes; and flushes placed in the batch
+    so that the hops kernel's window of prefix sums ends where they need it.  Every named flush carries the
+    facts check_facts asserts of the model's output.  One batch: `short_beside_long` first (its four flushes are
+    one workgroup's), the hop window's flushes last (one of them has to end the batch)."""
+    T = PACK_GRID
+    big, five = dgram(800), dgram(5)
+    assert [encoded_size(d) for d in (big, five, dgram(16), dgram(67), dgram(0))] == [814, 11, 22, 76, 6]
+    sixty_four = ([dgram(16)] * 63 + [dgram(67)]) * 9  # every frame 1472 bytes and 64 items
+    assert DATA_FRAME_OVERHEAD + 63 * 22 + 76 == MAX_FRAME_SIZE
+    b = Flushes()
+
+    # four flushes of one workgroup: a wave's LDS rows and loop count beside its neighbours'
+    b.add(DATA, [five] * 3, id0=1, name="short_beside_long[0]", facts={"starts": [0], "counts": [3], "stop": DONE})
+    b.add(DATA, [big] * 513, id0=2, name="short_beside_long[1]",
+          facts={"starts": list(range(513)), "counts": [1] * 513, "stop": DONE})
+    b.add(DATA, [], id0=3, name="short_beside_long[2]", facts={"starts": [], "frame_count": 0, "stop": DONE})
+    b.add(DATA, sixty_four[:257], id0=4, name="short_beside_long[3]",
+          facts={"starts": [0, 64, 128, 192, 256], "counts": [64] * 4 + [1], "stop": DONE})
+    assert [b.index(f"short_beside_long[{k}]") for k in range(4)] == [0, 1, 2, 3]
+
+    small = [five] * 600
+    frames, _, _, _ = pack_flush([encoded_size(d) for d in small], DATA, 1 << 40, 1 << 20)
+    data_starts = [s for s, _ in frames]
+    assert data_starts == [0, 127, 254, 381, 508]
+    groups = rand_groups(random.Random(63), 600)
+    frames, _, _, _ = pack_flush([ACK_GROUP_SIZE] * 600, ACK, 1 << 40, 1 << 20)
+    ack_starts = [s for s, _ in frames]
+    assert ack_starts == [0, 161, 322, 483]
+
+    for at in (0, 7):
+        for n in (64, 128, 255, 256, 257, 512, 513):  # the doubling's last round, lane 63's rank in every slot
+            b.add(DATA, [big] * n, id0=n, name=f"every_item_a_start[{n}]@{at}", at=at,
+                  facts={"starts": list(range(n)), "counts": [1] * n, "stop": DONE, "items_packed": n})
+        for r in (63, 64, 65, 127, 128, 191, 192, 255, 256, 257, 511, 512):
+            b.add(DATA, [big] * 600, window_room=r, id0=r, name=f"window_stop_at[{r}]@{at}", at=at,
+                  facts={"stop": WINDOW_LIMITED, "items_packed": r, "frame_count": r, "starts": list(range(r))})
+        _size_stops(b, "size_stop_at", DATA, small, 11, DATA_FRAME_OVERHEAD, data_starts,
+                    (63, 64, 127, 128, 191, 192, 254, 255, 256, 257, 381, 511, 512), at)
+        for n, name in ((576, "frames_of_64_exact"), (256, "frames_of_64_exact[256]"), (257, "frames_of_64_exact[257]")):
+            starts = list(range(0, n, 64))
+            b.add(DATA, sixty_four[:n], id0=n, name=f"{name}@{at}", at=at,
+                  facts={"starts": starts, "counts": [min(64, n - s) for s in starts], "stop": DONE})
+        # a frame that starts on the tile's last item and goes on in the next tile; a frame that starts before
+        # the tile's end and covers the whole part-tile behind it
+        # (a datagram of 700 bytes does not fit behind one of 800, and takes the small ones behind it)
+        b.add(DATA, [big] * 255 + [dgram(700)] + [five] * 39 + [big] * 5, name=f"start_at_255_straddles@{at}", at=at,
+              facts={"starts": list(range(256)) + list(range(295, 300)), "counts": [1] * 255 + [40] + [1] * 5, "stop": DONE})
+        b.add(DATA, [big] * 230 + [dgram(700)] + [five] * 65, name=f"start_at_255_straddles[covers]@{at}", at=at,
+              facts={"starts": list(range(231)), "counts": [1] * 230 + [66], "stop": DONE, "items_packed": T + 40})
+        _size_stops(b, "ack_stops", ACK, groups, ACK_GROUP_SIZE, ACK_FRAME_OVERHEAD, ack_starts,
+                    (63, 64, 161, 255, 256, 322), at)
+        b.add(ACK, groups[:322], id0=5, id1=6, name=f"ack_stops[2x161]@{at}", at=at,
+              facts={"starts": [0, 161], "counts": [161, 161], "stop": DONE})
+
+    # the hops kernel's window: zero-length datagrams, hop 127 by count
+    zeros = [dgram(0, seq=k) for k in range(300)]
+    assert DATA_FRAME_OVERHEAD + 127 * 6 < MAX_FRAME_SIZE
+    for at in (129, 255):  # the items at batch index 129 and 255 (mod 256) read P up to base + 256 and base + 382
+        b.add(DATA, zeros, name=f"hop_window_seams[at{at}]", at=at,
+              facts={"starts": [0, 127, 254], "counts": [127, 127, 46], "stop": DONE})
+    # hops near the flush's end are computed across the flush boundary (100 zero-length datagrams and one of 800
+    # bytes fit a frame): the emit pass cuts them at the flush's end
+    assert DATA_FRAME_OVERHEAD + 100 * 6 + 814 <= MAX_FRAME_SIZE
+    b.add(DATA, zeros[:100], name="hop_window_seams[followed]", at=156,
+          facts={"starts": [0], "counts": [100], "stop": DONE})
+    b.add(DATA, [big] * 5, name="hop_window_seams[follower]", facts={"starts": [0, 1, 2, 3, 4], "counts": [1] * 5})
+    assert b.first[b.index("hop_window_seams[follower]")] % T == 0
+    # the last hops workgroup holds one item, and the last 126 hops are cut by n_items
+    b.add(DATA, zeros[:130], name="hop_window_seams[last]", at=127,
+          facts={"starts": [0, 127], "counts": [127, 3], "stop": DONE})
+    assert len(b.items) % T == 1 and b.names[-1] == "hop_window_seams[last]"
+    return b
+
+
+def batch_end_case():
+    """(own) A batch that ends on two 800-byte datagrams, the first on the last thread of a hops workgroup: its
+    hop is 1 only by P[n_items], the one prefix sum the staged window's cap at n_items reaches."""
+    b = Flushes().add(DATA, [dgram(800)] * 2, name="batch_ends_on_size", at=PACK_GRID - 1,
+                      facts={"starts": [0, 1], "counts": [1, 1], "stop": DONE})
+    assert len(b.items) == PACK_GRID + 1
+    return b

@@ -150,6 +150,39 @@ def test_tile_cases(nthreads):
     assert r("take_mid_tile")["packets_consumed"] == 73
 
 
+def _finish_forms(packets, first, senders):
+    """emit_expect.lane_cases padded with empty senders to the two sides of the finish kernel's width switch:
+    n_packets == 16 * n_senders (8 lanes per sender), and one sender fewer (64)."""
+    m = packets.size
+    assert m % 16 == 0 and m // 16 - 1 >= senders.size
+    return [EE.with_empty_senders(packets, first, senders, n) for n in (m // 16, m // 16 - 1)]
+
+
+@pytest.mark.parametrize("nthreads", [1, 4])
+def test_lane_cases(nthreads):
+    """emit_expect.lane_cases: stops, parents and carried sums on lane 63 and on lane 0 of the next tile of the
+    sender kernel, the item kernel's seams, the finish kernel's two widths.  The host call runs the serial
+    walk; the facts hold the generator to what it claims (asserted on the model's output)."""
+    b = EE.lane_cases()
+    packets, first, senders = b.arrays()
+    (items, ff, pres, sres, sout, used), exp = _emit(packets, first, senders, nthreads=nthreads)
+    EE.check_facts(b, exp)
+    for name in ("stop_at[64][window][stale_even]", "stop_at[128][alloc][live]", "stop_at[63][bad][live]", "window_parent_at_63",
+                 "channel_parent_at_63", "only_lane_63[fragments]", "only_lane_63[alloc]", "only_lane_63[dropped]",
+                 "stale_63_then_stop_64", "take_at[64]", "items_kernel_seams[straddle]", "finish_form_switch[9]"):
+        assert b.facts[name], name  # the named cases exist and carry facts
+    consumed = exp.sender_results["packets_consumed"]
+    assert (consumed > 64).any() and (consumed == 8).any() and (consumed == 9).any()
+    assert (exp.packet_results["status"] == EE.EMITTED).sum() > 1000 and exp.packet_results["item_first"].max() > 4000
+    for p2, f2, s2 in _finish_forms(packets, first, senders):
+        assert (p2.size <= 16 * s2.size) == (s2.size == packets.size // 16)
+        _emit(p2, f2, s2, nthreads=nthreads)
+    _emit(packets, first, senders, nthreads=nthreads, want_packet_results=False)
+    state = senders.copy()  # senders_out == senders
+    got = emit_packets_host(packets, first, state, items=EE.filled_items(exp.items_used), senders_out=state)
+    EE.check(got, exp)
+
+
 def test_max_packet():
     b = EE.big_case()
     (items, ff, pres, sres, *_), exp = _run(b)
@@ -347,8 +380,8 @@ def test_emit_pack_emit_equals_the_interleaved_loop():
 def test_emit_core_under_sanitizers():
     """tests/c/emit_host_check.hip: the emit core and the GPU emit's tile form (ballots as 64-bit masks, the
     per-channel masks, the carries, the stop search, the item search) as host code under AddressSanitizer and
-    UBSan against the serial walk, over exact-size buffers; a stand-alone program (nothing is loaded into Python
-    under a sanitizer)."""
+    UBSan against the serial walk, over exact-size buffers, seeded senders and emit_expect.lane_cases' numbers
+    with literals; a stand-alone program (nothing is loaded into Python under a sanitizer)."""
     src = os.path.join(REPO_DIR, "tests", "c", "emit_host_check.hip")
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "emit_host_check")

@@ -94,6 +94,41 @@ def test_tile_cases(engine):
         EE.check(_host(out), exp, items_cap=cap)
 
 
+def test_lane_63_and_tile_seam(engine):
+    """emit_expect.lane_cases on the device into items pre-filled with EE.FILL (reserved slots stay untouched):
+    as it is, in place (senders_out == senders), and without packet results."""
+    b = EE.lane_cases(EMIT_TILE)
+    packets, first, senders = b.arrays()
+    (_, _, _, sres, _, _), exp = _emit(engine, packets, first, senders)
+    EE.check_facts(b, exp)
+    d = _dev(packets, first, senders)
+    state = d[2].clone()
+    items = torch.full((exp.items_used + 8, ITEM_DTYPE.itemsize), EE.FILL, dtype=torch.uint8, device=DEV)
+    out = engine.emit_packets(d[0], d[1], state, items_cap=exp.items_used, items=items, senders_out=state)
+    torch.cuda.synchronize()
+    assert out[4] is state
+    EE.check(_host(out), exp)
+    _emit(engine, packets, first, senders, exp=exp, want_packet_results=False)
+
+
+def test_finish_form_switch(engine):
+    """The lane cases padded with empty senders until n_packets == 16 * n_senders (emit_finish_kernel<8>), and
+    with one empty sender fewer (<64>): both the model's, every EMITTED record's absolute item_first included."""
+    b = EE.lane_cases(EMIT_TILE)
+    packets, first, senders = b.arrays()
+    m = packets.size
+    assert m % 16 == 0 and m // 16 - 1 >= senders.size
+    exp = EE.expect(packets, first, senders)
+    consumed = exp.sender_results["packets_consumed"]
+    assert (consumed > 64).any() and (consumed == 8).any() and (consumed == 9).any()
+    assert (exp.packet_results["status"] == EE.EMITTED).sum() > 1000 and exp.packet_results["item_first"].max() > 4000
+    for n in (m // 16, m // 16 - 1):
+        p2, f2, s2 = EE.with_empty_senders(packets, first, senders, n)
+        assert (p2.size <= 16 * s2.size) == (n == m // 16)  # the switch's condition (packet_emit.hip, emit_batch)
+        _emit(engine, p2, f2, s2)
+        _emit(engine, p2, f2, s2, want_packet_results=False)
+
+
 def test_max_packet(engine):
     """A MAX_PACKET_SIZE packet: 65 536 items of one packet, written by many workgroups."""
     b = EE.big_case()

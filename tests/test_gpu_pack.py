@@ -97,6 +97,28 @@ def test_flushes_longer_than_a_tile(engine):
     assert res["stop"][6] == PE.SIZE_LIMITED and T < res["items_packed"][6] < 2 * T
 
 
+def test_lane_63_slot_and_tile_seams(engine):
+    """pack_expect.lane_cases on the device, without and with nonce bits: against the model, and record for
+    record against what ufc_pack_host gave for the same batch."""
+    from uflow_amd.frame import pack_host
+    b = PE.lane_cases()
+    items, first, flushes = b.arrays()
+    for nb in (None, PE.nonce_words(63, items.size)):
+        exp = PE.expect(items, first, flushes, nb)
+        PE.check_facts(b, exp)
+        got = _pack(engine, items, first, flushes, nb)
+        PE.check(got, exp)
+        h_infos, h_res, h_used = pack_host(items, first, flushes, nonce_bits=nb)
+        assert got[2] == h_used == exp[2]
+        assert got[1].view(FLUSH_RESULT_DTYPE).reshape(-1).tobytes() == h_res.tobytes()
+        g_infos = got[0].view(FRAME_INFO_DTYPE).reshape(-1)[:h_used]
+        for fld in FRAME_INFO_DTYPE.names:
+            assert np.array_equal(g_infos[fld], h_infos[fld][:h_used]), fld
+    b = PE.batch_end_case()  # the last prefix sum decides the hop of the hops workgroup's last thread
+    _, exp, _ = _run(engine, b)
+    PE.check_facts(b, exp)
+
+
 def test_empty_ends_one_item_and_no_flushes(engine):
     rng = random.Random(8)
     b = PE.Flushes()

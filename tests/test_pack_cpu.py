@@ -165,9 +165,30 @@ def test_random_batches(nthreads):
     assert {PE.DONE, PE.SIZE_LIMITED, PE.WINDOW_LIMITED} == set(res["stop"])
 
 
+@pytest.mark.parametrize("nthreads", [1, 16])
+def test_lane_cases(nthreads):
+    """pack_expect.lane_cases: starts, stops and frame ends on lane 63, on lane 0 of the next slot and on item 0
+    of the next tile of the chain kernel, and flushes at the seams of the hops kernel's window.  The host call
+    runs the serial loop; the facts hold the generator to what it claims (asserted on the model's output)."""
+    b = PE.lane_cases()
+    items, first, flushes = b.arrays()
+    exp = PE.expect(items, first, flushes)
+    PE.check_facts(b, exp)
+    for name in ("every_item_a_start[513]@7", "window_stop_at[256]@0", "size_stop_at[255]+1@7", "frames_of_64_exact@0",
+                 "start_at_255_straddles[covers]@7", "ack_stops[322]@0", "hop_window_seams[last]", "short_beside_long[3]"):
+        assert b.facts[name], name  # the named cases exist and carry facts
+    nb = PE.nonce_words(63, items.size)
+    PE.check(pack_host(items, first, flushes, nthreads=nthreads), exp)
+    PE.check(pack_host(items, first, flushes, nthreads=nthreads, nonce_bits=nb), PE.expect(items, first, flushes, nb))
+    b = PE.batch_end_case()
+    (_, res, _), (items, first, flushes) = _run(b, nthreads=nthreads)
+    PE.check_facts(b, PE.expect(items, first, flushes))
+
+
 def test_pack_core_under_sanitizers():
     """tests/c/pack_host_check.hip: the pack core and the GPU pack's parallel form (prefix sums, hops, chain,
-    ranks, stop predicate) as host code under AddressSanitizer and UBSan against the emitters' loop, a
+    ranks, stop predicate) as host code under AddressSanitizer and UBSan against the emitters' loop, and the
+    kernels' tiling lane by lane over seeded flushes and over pack_expect.lane_cases' numbers with literals; a
     stand-alone program (nothing is loaded into Python under a sanitizer)."""
     src = os.path.join(REPO_DIR, "tests", "c", "pack_host_check.hip")
     with tempfile.TemporaryDirectory() as d:
