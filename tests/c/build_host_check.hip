@@ -184,8 +184,16 @@ void ref_write_frame(const HostBatch& b, size_t i, std::vector<uint8_t>& out) {
   out.insert(out.end(), 4, 0);  // the write leaves the trailer zero
 }
 
+// What a write call's workgroups did with their tables.
+struct WriteStats {
+  long spans = 0, frames_staged = 0, items_staged = 0, max_nf = 0, max_window = 0;
+};
+WriteStats last_write;
+
 // One write call as the kernels run it: item destinations, flags and span owners, then every piece of
-// every workgroup span.  out_bytes = buf + lead with exactly out_len bytes behind it.
+// every workgroup span, each workgroup with its LDS tables where the kernel stages them (arrays of the kernel's
+// sizes on the heap, poisoned where no thread stored: a read of an entry that was not staged shows as a wrong
+// byte, an index past a table as a sanitizer report).  out_bytes = buf + lead with exactly out_len bytes behind it.
 void emulate_write(const HostBatch& b, const std::vector<uint64_t>& off, uint8_t* out_bytes, uint64_t out_len,
                    const uint8_t* payload, uint64_t payload_len) {
   using namespace ufc_dev;
@@ -205,6 +213,7 @@ void emulate_write(const HostBatch& b, const std::vector<uint64_t>& off, uint8_t
     note_span_owner(base, off[0], off[i], off[i + 1], (uint32_t)i, owner.data(), spans);
   }
   const uint64_t lo = off[0], hi = off[n] < out_len ? off[n] : out_len;
+  last_write = WriteStats{};
   if (hi <= lo) return;
   const uint64_t addr_lo = base + lo, addr_hi = base + hi;
   for (uint64_t blk = 0; blk < spans; blk++) {
@@ -219,13 +228,46 @@ void emulate_write(const HostBatch& b, const std::vector<uint64_t>& off, uint8_t
       f_b = owner[blk + 1] < n - 1 ? owner[blk + 1] : (uint32_t)n - 1;
       if (f_b < f_a) f_b = f_a;
     }
+    // the workgroup's tables (frame_build.hip build_write_kernel)
+    const uint32_t nf = f_b - f_a + 1;
+    const bool staged = UFC_BUILD_FRAMES_STAGED(nf);
+    uint64_t* tab = (uint64_t*)std::malloc((kTabFrames + 1) * sizeof(uint64_t));
+    ufc_frame_info* sinfo = (ufc_frame_info*)std::malloc(kTabFrames * sizeof(ufc_frame_info));
+    uint8_t* sflag = (uint8_t*)std::malloc(kTabFrames);
+    uint64_t* sdst = (uint64_t*)std::malloc((kTabItems + 1) * sizeof(uint64_t));
+    std::memset(tab, 0xEE, (kTabFrames + 1) * sizeof(uint64_t));
+    std::memset(sinfo, 0xEE, kTabFrames * sizeof(ufc_frame_info));
+    std::memset(sflag, 0xEE, kTabFrames);
+    std::memset(sdst, 0xEE, (kTabItems + 1) * sizeof(uint64_t));
+    uint32_t item_lo = 0xFFFFFFFFu, item_hi = 0;
+    if (staged) {
+      for (uint32_t j = 0; j <= nf; j++) tab[j] = off[f_a + j];
+      for (uint32_t j = 0; j < nf; j++) {
+        const ufc_frame_info info = b.infos[f_a + j];
+        const uint8_t fl = flags[f_a + j];
+        sinfo[j] = info;
+        sflag[j] = fl;
+        if (fl && info.kind == UFC_FRAME_DATA && info.item_count) {
+          if (info.item_first < item_lo) item_lo = info.item_first;
+          if (info.item_first + info.item_count > item_hi) item_hi = info.item_first + info.item_count;
+        }
+      }
+    }
+    const bool items_staged = UFC_BUILD_ITEMS_STAGED(staged, item_lo, item_hi);
+    if (items_staged)
+      for (uint32_t j = 0; j <= item_hi - item_lo; j++) sdst[j] = dst[item_lo + j];
+    const SpanTables tb{tab, sinfo, sflag, sdst, GlobalTables{off.data(), flags.data(), b.infos.data(), dst.data()},
+                        f_a, item_lo, staged, items_staged};
+    last_write.spans++, last_write.frames_staged += staged, last_write.items_staged += items_staged;
+    if ((long)nf > last_write.max_nf) last_write.max_nf = nf;
+    if (item_lo < item_hi && (long)(item_hi - item_lo) > last_write.max_window) last_write.max_window = item_hi - item_lo;
     for (int r = 0; r < kPiecesPerLane; r++)
       for (uint32_t t = 0; t < (uint32_t)kBuildThreads; t++) {
         const uint64_t addr = span0 + ((uint64_t)r * kBuildThreads + t) * kPiece;
         const uint64_t pa = addr > addr_lo ? addr : addr_lo, pb = addr + kPiece < addr_hi ? addr + kPiece : addr_hi;
         if (pa >= pb) continue;
         Piece pc;
-        assemble_piece(a, GlobalTables{off.data(), flags.data(), b.infos.data(), dst.data()}, f_a, f_b, addr, pa, pb, pc);
+        assemble_piece(a, tb, f_a, f_b, addr, pa, pb, pc);
         for (uint32_t j = 0; j < kPiece; j++)
           if (pc.set & (1u << j)) {
             if (addr + j < pa || addr + j >= pb) fail("byte outside the piece's range", (long)blk, t, j);
@@ -233,6 +275,7 @@ void emulate_write(const HostBatch& b, const std::vector<uint64_t>& off, uint8_t
           }
         checks++;
       }
+    std::free(tab), std::free(sinfo), std::free(sflag), std::free(sdst);
   }
 }
 
@@ -279,6 +322,173 @@ void check_write(uint32_t seed, uint32_t nframes, uint32_t lead, uint32_t shift,
   }
   std::free(buf);
   std::free(pay);
+}
+
+// ---- table limits and caller-made layouts (tests/build_expect.py table_cases, the same numbers) ----
+ufc_item poison_item() {
+  ufc_item p{};
+  p.id = 0xFFFFFFFFu, p.channel_id = 255, p.form = 9, p.flags = 0xFFFF, p.data_offset = 0xFFFFFF00u, p.data_len = 60000;
+  return p;
+}
+HostBatch layout_batch(uint32_t n_items) {
+  HostBatch b;
+  b.items.assign(n_items, poison_item());
+  return b;
+}
+// A frame whose items go to item_first: a data frame of cnt datagrams of dl + k bytes (form by k % 3), or an ack
+// frame of cnt groups.  src >= 0: the frame takes its payload from that source base (a frame that names another's items).
+size_t add_frame(HostBatch& b, Lcg& r, uint8_t kind, uint32_t item_first, uint32_t cnt, uint32_t dl, long src = -1) {
+  ufc_frame_info in{};
+  in.kind = kind, in.ok = 1, in.aux = (uint8_t)r.below(2), in.item_first = item_first, in.item_count = cnt;
+  for (int k = 0; k < 5; k++) in.f[k] = r.next() * 2654435761u;
+  b.src_base.push_back(src >= 0 ? (uint64_t)src : b.payload.size());
+  if (src < 0) {
+    uint32_t off = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      ufc_item d{};
+      if (kind == UFC_FRAME_DATA) {
+        const uint32_t t = k % 3;
+        d.id = r.below(1u << 20), d.channel_id = (uint8_t)r.below(64);
+        d.window_parent_lead = (uint16_t)(t == 0 ? r.below(128) : r.below(65536));
+        d.channel_parent_lead = (uint16_t)(t == 0 ? r.below(256) : r.below(65536));
+        d.fragment_id_last = (uint16_t)(t == 2 ? 1 + r.below(65535) : 0);
+        d.fragment_id = (uint16_t)(t == 2 ? r.below(65536) : 0);
+        d.data_len = dl + (dl ? k : 0), d.data_offset = off;
+        off += d.data_len;
+      } else {
+        d.id = r.next() * 2654435761u, d.data_offset = r.next() * 40503u, d.channel_id = (uint8_t)r.below(2), d.form = 3;
+      }
+      b.items[item_first + k] = d;
+    }
+    for (uint32_t k = 0; k < off; k++) b.payload.push_back((uint8_t)r.next());
+  }
+  b.infos.push_back(in);
+  return b.infos.size() - 1;
+}
+
+struct LayoutFacts {
+  long spans = -1, frames_staged = -1, items_staged = -1, max_nf = -1, max_window = -1;
+};
+
+// The write over b at the given offsets (empty: the sizes' running sum from first_off).  In-order offsets: every
+// frame's bytes where its span is, guard bytes everywhere else.  backward: the rule for offsets that go backwards.
+void check_layout(const char* name, const HostBatch& b, std::vector<uint64_t> off, uint32_t lead, uint64_t first_off,
+                  const LayoutFacts& facts, bool backward) {
+  const uint64_t n = b.infos.size();
+  std::vector<std::vector<uint8_t>> frames(n);
+  std::vector<uint64_t> sizes(n + 1, first_off);
+  for (uint64_t i = 0; i < n; i++) {
+    uint64_t size;
+    if (ufc_codec::check_frame(b.infos[i], b.items.data(), b.items.size(), b.src_base[i], b.payload.size(), size) != UFC_BUILD_OK)
+      fail(name, (long)i, -1, 0);
+    ref_write_frame(b, i, frames[i]);
+    if (frames[i].size() != size) fail("frame size", (long)i, (long)size, (long)frames[i].size());
+    sizes[i + 1] = sizes[i] + size;
+  }
+  if (off.empty()) off = sizes;
+  uint64_t out_len = 0;
+  for (uint64_t o : off) out_len = o > out_len ? o : out_len;
+  uint8_t* buf = (uint8_t*)std::malloc(lead + out_len + 1);
+  std::memset(buf, 0xA5, lead + out_len + 1);
+  uint8_t* pay = (uint8_t*)std::malloc(b.payload.size() + 1);
+  std::memcpy(pay, b.payload.data(), b.payload.size());
+  emulate_write(b, off, buf + lead, out_len, pay, b.payload.size());
+  const WriteStats& w = last_write;
+  if ((facts.spans >= 0 && w.spans != facts.spans) || (facts.frames_staged >= 0 && w.frames_staged != facts.frames_staged) ||
+      (facts.items_staged >= 0 && w.items_staged != facts.items_staged))
+    fail(name, w.spans, w.frames_staged, w.items_staged);
+  if ((facts.max_nf >= 0 && w.max_nf != facts.max_nf) || (facts.max_window >= 0 && w.max_window != facts.max_window))
+    fail(name, w.max_nf, w.max_window, -2);
+  const uint8_t* out = buf + lead;
+  std::vector<uint8_t> allowed(out_len, 0);
+  for (uint64_t p = 0; p < lead; p++)
+    if (buf[p] != 0xA5) fail("write before the buffer", (long)p, 0, 0);
+  for (uint64_t p = 0; p < out_len; p++)
+    if ((p < off[0] || p >= off[n]) && out[p] != 0xA5) fail("write outside the batch", (long)p, 0, 0);
+  for (uint64_t p = 0; p < out_len; p++) allowed[p] = out[p] == 0xA5;
+  for (uint64_t i = 0; i < n; i++) {
+    if (off[i + 1] < off[i] || off[i + 1] - off[i] != frames[i].size()) continue;
+    bool whole = true;
+    for (uint64_t k = 0; k < frames[i].size(); k++) {
+      const bool same = out[off[i] + k] == frames[i][k];
+      allowed[off[i] + k] |= same;
+      whole &= same;
+    }
+    uint64_t floor = ~0ull;  // the lowest offset from the first backward step on
+    for (uint64_t j = 0; j < n; j++)
+      if (off[j + 1] < off[j])
+        for (uint64_t q = j + 1; q <= n; q++) floor = off[q] < floor ? off[q] : floor;
+    if (!whole && (!backward || off[i + 1] <= floor)) fail("frame bytes", (long)i, (long)off[i], backward);
+    checks++;
+  }
+  for (uint64_t p = 0; p < out_len; p++)
+    if (!allowed[p]) fail("a byte that is neither guard nor its span's frame's", (long)p, 0, 0);
+  std::free(buf);
+  std::free(pay);
+}
+
+void table_cases() {
+  Lcg r{515};
+  {  // frames of 32 bytes: the kernel counts 512 frames for span 0 one byte past a 16-byte boundary, 513 at it
+    for (uint32_t lead : {1u, 0u}) {
+      HostBatch b = layout_batch(1100);
+      for (uint32_t i = 0; i < 1100; i++) add_frame(b, r, UFC_FRAME_DATA, i, 1, 16);
+      LayoutFacts f;
+      f.spans = 3, f.max_nf = 513, f.frames_staged = lead == 1 ? 2 : 1, f.items_staged = f.frames_staged;
+      check_layout(lead ? "frames_per_span[512]" : "frames_per_span[513]", b, {}, lead, 0, f, false);
+    }
+  }
+  for (uint32_t window : {1024u, 1025u}) {  // two frames whose items lie a window apart, poison between
+    HostBatch b = layout_batch(window);
+    add_frame(b, r, UFC_FRAME_DATA, 0, 3, 40);
+    add_frame(b, r, UFC_FRAME_DATA, window - 3, 3, 30);
+    LayoutFacts f;
+    f.spans = 1, f.frames_staged = 1, f.items_staged = window <= 1024, f.max_window = window, f.max_nf = 2;
+    check_layout(window == 1024 ? "item_window[1024]" : "item_window[1025]", b, {}, 0, 0, f, false);
+  }
+  {  // a resent frame: the same records named twice in one span and once in the next
+    HostBatch b = layout_batch(400);
+    const size_t a = add_frame(b, r, UFC_FRAME_DATA, 7, 5, 50);
+    add_frame(b, r, UFC_FRAME_DATA, 7, 5, 50, (long)b.src_base[a]);
+    for (uint32_t k = 0; k < 50; k++) add_frame(b, r, UFC_FRAME_DATA, 20 + 4 * k, 4, 90);
+    add_frame(b, r, UFC_FRAME_DATA, 7, 5, 50, (long)b.src_base[a]);
+    LayoutFacts f;
+    f.spans = 2, f.frames_staged = 2, f.items_staged = 2;
+    check_layout("shared_items", b, {}, 0, 0, f, false);
+  }
+  {  // frame i's items lie behind frame i + 1's
+    HostBatch b = layout_batch(200);
+    uint32_t at = 200;
+    for (uint32_t k = 0; k < 60; k++) {
+      const uint32_t cnt = 1 + k % 4;
+      at -= cnt;
+      add_frame(b, r, k % 7 == 3 ? UFC_FRAME_ACK : UFC_FRAME_DATA, at, cnt, 100 + k);
+    }
+    LayoutFacts f;
+    f.spans = 2, f.frames_staged = 2, f.items_staged = 2;
+    check_layout("items_reversed", b, {}, 0, 0, f, false);
+  }
+  for (uint32_t lead = 0; lead < 4; lead++) {  // the batch starts 37 bytes into the buffer
+    HostBatch b = layout_batch(240);
+    for (uint32_t k = 0; k < 60; k++) add_frame(b, r, UFC_FRAME_DATA, 4 * k, 4, 60 + k);
+    LayoutFacts f;
+    f.spans = 2;
+    check_layout("lo_nonzero", b, {}, lead, 37, f, false);
+  }
+  {  // one backward step in the middle of 40 frames: frame 20 starts 500 bytes before frame 19 does
+    HostBatch b = layout_batch(160);
+    for (uint32_t k = 0; k < 40; k++) add_frame(b, r, UFC_FRAME_DATA, 4 * k, 4, 30 + k);
+    std::vector<uint64_t> off(41, 0);
+    for (uint32_t i = 0; i < 40; i++) {
+      uint64_t size;
+      ufc_codec::check_frame(b.infos[i], b.items.data(), b.items.size(), b.src_base[i], b.payload.size(), size);
+      off[i + 1] = off[i] + size;
+    }
+    const uint64_t back = off[20] - off[19] + 500;
+    for (uint32_t i = 20; i <= 40; i++) off[i] -= back;
+    if (!(off[20] < off[19])) fail("offsets_backwards", 0, 0, 0);
+    check_layout("offsets_backwards", b, off, 3, 0, LayoutFacts{}, true);
+  }
 }
 
 }  // namespace
@@ -438,6 +648,7 @@ int main() {
   for (uint32_t lead = 0; lead < 16; lead++) check_write(100 + lead, 160, lead, lead % 5, lead % 3 ? 0 : 5, lead == 7);
   check_write(7, 900, 3, 1, 0, false);
   check_write(8, 900, 11, 0, 7, true);
+  table_cases();
   std::printf("ok: %ld checks\n", checks);
   return 0;
 }

@@ -109,6 +109,40 @@ def test_host_write_skip_rule_and_arguments():
                                     out.ctypes.data, out.size, 1, None, 1) == _native.UFC_ERR_INVALID_ARG
 
 
+def _host_write(case, seal=0):
+    infos, items, payload, src = case.arrays()
+    off = case.given_offsets().astype(np.uint64)
+    total = int(off.max())
+    out = np.full(total + 64, BE.GUARD, dtype=np.uint8)
+    rc = _native.lib().ufc_build_batch_host(infos.ctypes.data, items.ctypes.data, items.size, src.ctypes.data,
+                                            payload.ctypes.data, payload.size, infos.size, off.ctypes.data,
+                                            out.ctypes.data, total, seal, None, 1)
+    assert rc == 0
+    return out
+
+
+@pytest.mark.parametrize("case", BE.table_cases(), ids=lambda c: c.name)
+def test_table_cases(case):
+    """The table-limit and caller-made-layout cases of build_expect.table_cases: the facts hold
+    on the case's own records, the sizes call gives the oracle's sizes, and the host write gives the oracle's bytes
+    at the caller's offsets with the guard bytes around them untouched.  With offsets that go backwards the host
+    write keeps the documented bounds too (it writes every frame whose span has the frame's size, so where two
+    spans overlap the later frame's bytes win)."""
+    BE.check_table_facts(case)
+    infos, items, payload, src = case.arrays()
+    sizes = np.zeros(infos.size + 1, dtype=np.uint64)
+    status = np.zeros(infos.size, dtype=np.uint8)
+    assert _native.lib().ufc_build_sizes_host(infos.ctypes.data, items.ctypes.data, items.size, src.ctypes.data,
+                                              payload.size, infos.size, sizes.ctypes.data, status.ctypes.data, 1) == 0
+    assert (status == BE.OK).all()
+    assert np.array_equal(sizes.astype(np.int64) + case.first_off, case.sizes())
+    out = _host_write(case)
+    if case.name == "offsets_backwards":
+        BE.check_backward_output(case, out)
+    else:
+        assert np.array_equal(out, BE.expected_region(case, out.size))
+
+
 def test_encode_core_under_sanitizers():
     """tests/c/build_host_check.hip: the encode core as host code under AddressSanitizer and UBSan, a
     stand-alone program (nothing is loaded into Python under a sanitizer)."""

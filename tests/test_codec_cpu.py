@@ -316,3 +316,79 @@ def test_parse_expect_records_vs_host_parse():
     infos, items = F.parse_batch_host(big, offs, None, nthreads=4)
     parse_expect.compare(infos, items, t_infos, t_items)
     assert items.size == t_items.size
+
+
+_LANE_BATCHES = []
+
+
+def _lane_batches():
+    import parse_expect
+    if not _LANE_BATCHES:  # built once, shared by the cases
+        _LANE_BATCHES.extend(parse_expect.lane_cases())
+    return _LANE_BATCHES
+
+
+@pytest.mark.parametrize("which", range(5))
+def test_lane_cases(which):
+    """The named seam and limit cases of tests/parse_expect.lane_cases: every group's facts
+    hold on the oracle's records, and the host parse returns those records (one thread and four)."""
+    import parse_expect
+    batch = _lane_batches()[which]
+    exp_infos, exp_items = batch.records()
+    parse_expect.check_facts(batch, exp_infos)
+    data, offsets = batch.arrays()
+    for threads in (1, 4):
+        infos, items = F.parse_batch_host(data, offsets.astype(np.uint64), None, nthreads=threads)
+        parse_expect.compare(infos, items, exp_infos, exp_items)
+        assert items.size == exp_items.size
+
+
+def test_lane_cases_caller_made_offsets():
+    """The two byte-load cases: their facts hold on the oracle's records.  The host call does not take them:
+    ufc_parse_batch_host refuses offsets that go backwards (UFC_ERR_INVALID_ARG, nothing parsed), so
+    fallback_backward_offsets runs on the device and in tests/c/parse_host_check.hip only; in the order the
+    buffer holds them the same frames parse to the same records.  fallback_span_4gib needs a buffer over 4 GiB."""
+    import parse_expect
+    from uflow_amd import _native
+    batch, data, offsets, valid = parse_expect.backward_offsets_case()
+    parse_expect.check_facts(batch)
+    n = len(batch.frames)
+    infos = np.zeros(n, dtype=F.FRAME_INFO_DTYPE)
+    off = offsets.astype(np.uint64)
+    rc = _native.lib().ufc_parse_batch_host(data.ctypes.data, off.ctypes.data, n, valid.ctypes.data, infos.ctypes.data,
+                                            None, 0, None, 1)
+    assert rc == _native.UFC_ERR_INVALID_ARG
+    # the same bytes in buffer order (workgroup 1's frames, then frames 0..254): the host parse agrees with the oracle
+    order = list(range(256, n)) + list(range(255))
+    frames = [batch.frames[i] for i in order]
+    d2, o2 = _batch(frames)
+    assert np.array_equal(d2, data)
+    infos, items = F.parse_batch_host(d2, o2, valid[order], nthreads=1)
+    e_infos, e_items = parse_expect.oracle_records(frames)
+    parse_expect.compare(infos, items, e_infos, e_items)
+    case = parse_expect.span_4gib_case(2 ** 32 + 8192)
+    parse_expect.check_facts(case[0])
+    assert case[4][101] - case[4][0] >= 2 ** 32 - 65536 and case[4][-1] - case[4][0] >= 2 ** 32
+
+
+def test_parse_plan_under_sanitizers():
+    """tests/c/parse_host_check.hip: the device parse thread by thread on the host (walk, scan and emit per
+    workgroup with the arithmetic of frame_parse_plan.hpp) over the lane cases' shapes, in three thread orders, on
+    frame buffers of exactly the bytes the call may read, under AddressSanitizer and UBSan: a stand-alone program
+    (nothing is loaded into Python under a sanitizer)."""
+    import subprocess
+    import tempfile
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    src = os.path.join(repo, "tests", "c", "parse_host_check.hip")
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "parse_host_check")
+        san = "-fsanitize=address,undefined"
+        cmd = [hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-Xarch_host", san,
+               "-Xarch_host", "-fno-sanitize-recover=all", san, "-fno-gpu-sanitize", src, "-o", exe]
+        b = subprocess.run(cmd, capture_output=True, text=True)
+        assert b.returncode == 0, b.stderr[-3000:]
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        assert r.stdout.startswith("ok:"), r.stdout
+        assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]

@@ -211,6 +211,44 @@ def test_skip_rule(engine):
     assert np.array_equal(got[off[38]:off[39]], exp[int(eoff[38]):int(eoff[39])])
 
 
+@pytest.mark.parametrize("case", BE.table_cases(), ids=lambda c: c.name)
+def test_table_cases(engine, case):
+    """The write call alone on build_expect.table_cases: 512 and 513 frames counted for a span
+    (the LDS tables' switch), item windows of 1024 and 1025 records with poison between the frames' items, frames
+    that name the same records, items in reverse frame order, a batch that starts 37 bytes into the buffer at
+    output alignments 0..3, and offsets with one backward step.  Expected bytes are frame_write's; 64 guard bytes
+    before the output and everything behind the batch stay as they were.  The output pointer sits `lead` bytes past
+    a 16-byte boundary."""
+    BE.check_table_facts(case)
+    infos, items, payload, src = case.arrays()
+    off = case.given_offsets()
+    total = int(off.max())
+    d_infos, d_items, d_payload = rows(infos, DEV), rows(items, DEV), rows(payload, DEV)
+    d_src, d_off = rows(src.astype(np.int64), DEV), torch.from_numpy(off.astype(np.int64)).to(DEV)
+    big = torch.full((64 + case.lead + total + 64,), BE.GUARD, dtype=torch.uint8, device=DEV)
+    assert big.data_ptr() % 16 == 0
+    out = big[64 + case.lead:]
+    assert _raw_write(engine, d_infos, d_items, items.size, d_src, d_payload, d_off, out, total, 0) == 0
+    torch.cuda.synchronize()
+    got = big.cpu().numpy()
+    assert (got[:64 + case.lead] == BE.GUARD).all()
+    got = got[64 + case.lead:]
+    if case.name == "offsets_backwards":
+        BE.check_backward_output(case, got)
+        # the host write, for the record: both keep the documented bounds; where spans overlap the host writes every
+        # frame whose span matches, the device only the bytes whose frame its search finds
+        h = np.full(got.size, BE.GUARD, dtype=np.uint8)
+        o64 = off.astype(np.uint64)
+        assert _native.lib().ufc_build_batch_host(infos.ctypes.data, items.ctypes.data, items.size, src.ctypes.data,
+                                                  payload.ctypes.data, payload.size, infos.size, o64.ctypes.data,
+                                                  h.ctypes.data, total, 0, None, 1) == 0
+        BE.check_backward_output(case, h)
+        print(f"offsets_backwards: device and host writes {'agree' if np.array_equal(h, got) else 'differ'}; "
+              f"{int((h != got).sum())} bytes differ, {int((got == BE.GUARD).sum())} device bytes left as guard")
+    else:
+        assert np.array_equal(got, BE.expected_region(case, got.size))
+
+
 def test_seal_and_status(engine):
     """seal=False leaves zero trailers; seal=True with crc_out gives oracle.compute of each body; the
     statuses of the bad-input records equal the host build's (and the oracle's expectations)."""

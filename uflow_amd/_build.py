@@ -13,7 +13,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libuflowcrc.so")
 SOURCES = ["frame_crc.hip", "frame_crc_varlen8.hip", "frame_parse.hip", "frame_build.hip", "frame_pack.hip",
            "packet_emit.hip", "packet_receive.hip", "frame_window.hip", "frame_queue.hip", "send_rate.hip", "resend.hip", "hbm_probe.hip", "ufc_api.cpp", "ufc_shard.cpp", "crc_math.cpp", "frame_codec.cpp"]
-HEADERS = ["frame_crc_dev.hpp", "frame_crc_kernels.hpp", "crc_math.hpp", "frame_codec_core.hpp", "frame_parse.hpp",
+HEADERS = ["frame_crc_dev.hpp", "frame_crc_kernels.hpp", "crc_math.hpp", "frame_codec_core.hpp", "frame_parse.hpp", "frame_parse_plan.hpp",
            "frame_build.hpp", "frame_build_piece.hpp", "frame_pack.hpp", "packet_emit.hpp", "packet_receive.hpp",
            "frame_window.hpp", "frame_queue.hpp", "send_rate.hpp", "resend.hpp", "ufc_internal.hpp", "wave.hpp",
            "wave_dev.hpp", "scratch.hpp", "scan.hpp"]

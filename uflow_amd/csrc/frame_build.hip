@@ -41,9 +41,6 @@ namespace ufc_dev {
 
 namespace {
 
-constexpr uint32_t kTabFrames = 512;   // frames whose offsets, flags and infos a workgroup stages in LDS
-constexpr uint32_t kTabItems = 1024;   // item destinations it stages
-
 __global__ __launch_bounds__(kBuildThreads) void build_item_sizes_kernel(const ufc_item* items, uint64_t n_items,
                                                                           uint64_t* dst) {
   const uint64_t g = (uint64_t)blockIdx.x * kBuildThreads + threadIdx.x;
@@ -80,25 +77,6 @@ __global__ __launch_bounds__(kBuildThreads) void build_check_kernel(BuildArgs a,
   }
 }
 
-// The write kernel's tables for one workgroup span, in LDS when they fit: the offsets, flags and infos of
-// the frames that touch the span, and the destinations of the items of its written data frames (the
-// window from the lowest first item to the highest last one, wherever the frames keep their items).
-// What does not fit is read from global memory: more than kTabFrames frames (tiny or empty frames), or
-// an item window over kTabItems.
-struct SpanTables {
-  const uint64_t* tab;          // LDS: out_offsets[f_a ..]
-  const ufc_frame_info* sinfo;  // LDS: infos[f_a ..]
-  const uint8_t* sflag;         // LDS: flags[f_a ..]
-  const uint64_t* sdst;         // LDS: dst[item_lo ..]
-  GlobalTables g;
-  uint32_t f_a, item_lo;
-  bool frames_staged, items_staged;
-  __device__ __forceinline__ uint64_t off(uint32_t k) const { return frames_staged ? tab[k - f_a] : g.off(k); }
-  __device__ __forceinline__ bool flag(uint32_t f) const { return frames_staged ? sflag[f - f_a] != 0 : g.flag(f); }
-  __device__ __forceinline__ ufc_frame_info info(uint32_t f) const { return frames_staged ? sinfo[f - f_a] : g.info(f); }
-  __device__ __forceinline__ uint64_t dst(uint32_t k) const { return items_staged ? sdst[k - item_lo] : g.dst(k); }
-};
-
 __global__ __launch_bounds__(kBuildThreads) void build_write_kernel(BuildArgs a, const uint64_t* dst,
                                                                     const uint8_t* flags, const uint32_t* span_owner) {
   __shared__ uint64_t tab[kTabFrames + 1];
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(kBuildThreads) void build_write_kernel(BuildArgs a,
   const uint32_t f_a = min(span_owner[blockIdx.x], n - 1);
   const uint32_t f_b = span1 < addr_hi ? max(f_a, min(span_owner[blockIdx.x + 1], n - 1)) : n - 1;
   const uint32_t nf = f_b - f_a + 1;
-  const bool staged = nf <= kTabFrames;
+  const bool staged = UFC_BUILD_FRAMES_STAGED(nf);
   if (t == 0) {
     s_item_lo = 0xFFFFFFFFu;
     s_item_hi = 0;
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(kBuildThreads) void build_write_kernel(BuildArgs a,
   }
   __syncthreads();
   const uint32_t item_lo = s_item_lo, item_hi = s_item_hi;
-  const bool items_staged = staged && item_lo < item_hi && item_hi - item_lo <= kTabItems;
+  const bool items_staged = UFC_BUILD_ITEMS_STAGED(staged, item_lo, item_hi);
   if (items_staged)
     for (uint32_t j = t; j <= item_hi - item_lo; j += kBuildThreads) sdst[j] = dst[item_lo + j];
   __syncthreads();

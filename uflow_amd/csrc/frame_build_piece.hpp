@@ -133,6 +133,32 @@ struct GlobalTables {
   UFC_BHD uint64_t dst(uint32_t k) const { return dsts[k]; }
 };
 
+constexpr uint32_t kTabFrames = 512;   // frames whose offsets, flags and infos a workgroup stages in LDS
+constexpr uint32_t kTabItems = 1024;   // item destinations it stages
+// Whether a span's nf frames, and the item window [lo, hi) of its written data frames, are staged (the kernel
+// and tests/c/build_host_check.hip take both switches from here).
+#define UFC_BUILD_FRAMES_STAGED(nf) ((nf) <= kTabFrames)
+#define UFC_BUILD_ITEMS_STAGED(staged, lo, hi) ((staged) && (lo) < (hi) && (hi) - (lo) <= kTabItems)
+
+// The write kernel's tables for one workgroup span, in LDS when they fit: the offsets, flags and infos of
+// the frames that touch the span, and the destinations of the items of its written data frames (the
+// window from the lowest first item to the highest last one, wherever the frames keep their items).
+// What does not fit is read from global memory: more than kTabFrames frames (tiny or empty frames), or
+// an item window over kTabItems.
+struct SpanTables {
+  const uint64_t* tab;          // LDS: out_offsets[f_a ..]
+  const ufc_frame_info* sinfo;  // LDS: infos[f_a ..]
+  const uint8_t* sflag;         // LDS: flags[f_a ..]
+  const uint64_t* sdst;         // LDS: dst[item_lo ..]
+  GlobalTables g;
+  uint32_t f_a, item_lo;
+  bool frames_staged, items_staged;
+  UFC_BHD uint64_t off(uint32_t k) const { return frames_staged ? tab[k - f_a] : g.off(k); }
+  UFC_BHD bool flag(uint32_t f) const { return frames_staged ? sflag[f - f_a] != 0 : g.flag(f); }
+  UFC_BHD ufc_frame_info info(uint32_t f) const { return frames_staged ? sinfo[f - f_a] : g.info(f); }
+  UFC_BHD uint64_t dst(uint32_t k) const { return items_staged ? sdst[k - item_lo] : g.dst(k); }
+};
+
 template <class Tables>
 UFC_BHD void assemble_piece(const BuildArgs& a, const Tables& tb, uint32_t f_a, uint32_t f_b, uint64_t addr, uint64_t pa,
                             uint64_t pb, Piece& pc) {

@@ -28,19 +28,14 @@
 
 #include "frame_codec_core.hpp"
 #include "frame_parse.hpp"
+#include "frame_parse_plan.hpp"
 #include "scan.hpp"
 
 namespace ufc_dev {
 
 namespace {
 
-constexpr int kParseThreads = 256;
-#ifndef UFC_POS_SLOTS
-#define UFC_POS_SLOTS 64
-#endif
-constexpr uint32_t kPosSlots = UFC_POS_SLOTS;  // datagram headers recorded per frame (a data frame holds <= 127)
-constexpr uint64_t kSegWords = (uint64_t)kPosSlots * kParseThreads;  // u16 per workgroup segment
-enum : uint8_t { kItemsNone = 0, kItemsPos = 1, kItemsAck = 2, kItemsWalk = 3 };
+using namespace ufc_parse_plan;  // the index arithmetic the host check shares (frame_parse_plan.hpp)
 
 // Two per-frame counts scanned at once (each workgroup sum < 2^32: 256 frames x < 2^24), low and high halves.
 typedef hipcub::BlockScan<uint64_t, kParseThreads> BlockScan2;
@@ -125,51 +120,9 @@ struct PackedSink {
   __device__ void header(uint32_t, uint32_t) const {}
 };
 
-__device__ __forceinline__ uint32_t frame_len32(const uint64_t* offsets, uint64_t i, uint64_t& a) {
-  a = offsets[i];
-  const uint64_t b = offsets[i + 1];
-  const uint64_t len64 = b >= a ? b - a : 0;
-  return len64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len64;
-}
-
-// The walk with pooled header slots (round 3): kInlineSlots slots per frame in LDS, and the headers
-// past them in a per-workgroup pool of linked LDS entries (offset | next << 16) taken one at a time
-// with ds_add_rtn.  A frame averages ~15 datagrams, so 16 + a shared pool hold what 64 fixed slots per
-// frame held, in a third of the LDS: more workgroups per CU and more frames walking at once (the walk
-// is a dependent load chain per frame, bound by how many chains are in flight).  A frame that finds
-// the pool full is walked again by the emit step, as one with more than kPosSlots datagrams.
-constexpr uint32_t kInlineSlots = 16;
-constexpr uint32_t kPoolSlots = 2048;
-constexpr uint32_t kPoolNil = 0xFFFFu;
-
-struct PoolSink {
-  static constexpr bool kDecode = false;
-  uint16_t* slot;     // this thread's inline slots (slot k at k * kParseThreads)
-  uint32_t* pool;     // the workgroup's pool
-  uint32_t* ctr;      // its allocation counter
-  uint32_t* head;     // this thread's list (registers, through pointers: the sink is const)
-  uint32_t* tail;
-  bool* full;
-  __device__ bool on() const { return true; }
-  __device__ void operator()(uint32_t, const ufc_item&) const {}
-  __device__ void header(uint32_t k, uint32_t off) const {
-    if (k < kInlineSlots) {
-      slot[k * kParseThreads] = (uint16_t)off;
-      return;
-    }
-    if (*full) return;
-    const uint32_t idx = atomicAdd(ctr, 1u);  // (LDS atomic)
-    if (idx >= kPoolSlots) {
-      *full = true;
-      return;
-    }
-    pool[idx] = off | (kPoolNil << 16);
-    if (k == kInlineSlots)
-      *head = idx;
-    else
-      pool[*tail] = (pool[*tail] & 0xFFFFu) | (idx << 16);
-    *tail = idx;
-  }
+// The pool's one LDS add (ds_add_rtn) behind the sink of frame_parse_plan.hpp.
+struct LdsAdd {
+  __device__ static uint32_t add(uint32_t* ctr) { return atomicAdd(ctr, 1u); }
 };
 
 __global__ __launch_bounds__(kParseThreads) void parse_walk_pool_kernel(const uint8_t* bytes, const uint64_t* offsets,
@@ -196,12 +149,12 @@ __global__ __launch_bounds__(kParseThreads) void parse_walk_pool_kernel(const ui
     ufc_frame_info info;
     const DevBytesHead rd = DevBytesHead::load(bytes + a, len);
     const bool ok = ufc_codec::read_frame_to(rd, len, valid[i] != 0, info,
-                                             PoolSink{slots + t, pool, &pool_ctr, &head, &tail, &full}, kPosSlots);
+                                             PoolSink<LdsAdd>{slots + t, pool, &pool_ctr, &head, &tail, &full}, kPosSlots);
     const uint32_t cnt = ok ? info.item_count : 0u;
     if (cnt) {
       if (info.kind == UFC_FRAME_ACK) {
         mode = kItemsAck;
-      } else if (cnt <= kPosSlots && len <= 0xFFFFu && !full) {
+      } else if (UFC_PARSE_SLOTS_HOLD(cnt, len, full)) {
         mode = kItemsPos;
         npos = cnt;
       } else {
@@ -221,7 +174,7 @@ __global__ __launch_bounds__(kParseThreads) void parse_walk_pool_kernel(const ui
   if (t == 0) {
     // (64-bit cursor: the sum of every workgroup's total may pass 2^32 long after the cap is reached)
     const unsigned long long b64 = total ? atomicAdd(seg_cursor, (unsigned long long)total) : 0ull;
-    const uint32_t b = (total && b64 + total > seg_cap) ? 0xFFFFFFFFu : (uint32_t)b64;
+    const uint32_t b = UFC_PARSE_SEG_NO_ROOM(b64, total, seg_cap) ? kNoSegment : (uint32_t)b64;
     base_lds = b;
     seg_base[blockIdx.x] = b;
   }
@@ -288,9 +241,10 @@ __global__ __launch_bounds__(kParseThreads) void parse_emit_kernel(
   const uint64_t span_lo = lstart[0];
   const uint64_t span_hi = offsets[i0 + nb];
   const uintptr_t base_addr = (uintptr_t)(bytes + span_lo);
-  const uint32_t delta = (uint32_t)(base_addr & 3u);
-  const uint64_t range = (span_hi - span_lo + delta + 3) & ~(uint64_t)3;
-  const bool buf_ok = span_hi >= span_lo && range < 0xFFFFFFF0ull;
+  const SpanRange sr = span_range(span_lo, span_hi, (uint64_t)base_addr);
+  const uint32_t delta = sr.delta;
+  const uint64_t range = sr.range;
+  const bool buf_ok = sr.ok;
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)(base_addr - delta), 0, buf_ok ? (int)(uint32_t)range : 0, 0x00020000);
 
@@ -313,21 +267,13 @@ __global__ __launch_bounds__(kParseThreads) void parse_emit_kernel(
         mm[u] = kItemsNone;
         hoff[u] = fo[u] = 0;
         if (g < g_end) {
-          uint32_t lo_f = 0, hi_f = nb - 1;  // owner: the last frame whose first item is <= g
-          while (lo_f < hi_f) {
-            const uint32_t mid = (lo_f + hi_f + 1) >> 1;
-            if (lfirst[mid] <= (uint32_t)g)
-              lo_f = mid;
-            else
-              hi_f = mid - 1;
-          }
-          const uint32_t f = lo_f, k = (uint32_t)g - lfirst[f];
+          const uint32_t f = owner_of([&](uint32_t m) -> uint32_t { return lfirst[m]; }, nb, (uint32_t)g);
+          const uint32_t k = (uint32_t)g - lfirst[f];
           const uint8_t m = lmode[f];
           if (m == kItemsPos || m == kItemsAck) {
             mm[u] = m;
             fo[u] = f;
-            hoff[u] = m == kItemsPos ? (uint32_t)seg[lseg[f] + k]
-                                     : 1u + ufc_codec::kAckPayloadHeader + UFC_ACK_GROUP_SIZE * k;
+            hoff[u] = m == kItemsPos ? (uint32_t)seg[lseg[f] + k] : ack_hoff(k);
           }
         }
       }
@@ -335,9 +281,9 @@ __global__ __launch_bounds__(kParseThreads) void parse_emit_kernel(
 #pragma unroll
         for (int u = 0; u < U; u++) {
           if (mm[u] == kItemsNone) continue;
-          const uint32_t ex = (uint32_t)(lstart[fo[u]] - span_lo) + delta + hoff[u];
+          const uint32_t ex = fetch_ex(lstart[fo[u]], span_lo, delta, hoff[u]);
           const uint32_t al = ex & ~3u;
-          if (X4 == 2 && ex + 16 <= (uint32_t)range) {  // one unaligned 16-byte load at the header
+          if (X4 == 2 && fetch_exact(ex, range)) {  // one unaligned 16-byte load at the header
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)ex, 0, AUX);
             x[u][0] = v.x, x[u][1] = v.y, x[u][2] = v.z, x[u][3] = v.w;
@@ -360,17 +306,19 @@ __global__ __launch_bounds__(kParseThreads) void parse_emit_kernel(
         const uint32_t f = fo[u];
         uint32_t w[4];
         if (buf_ok) {
-          const uint32_t ex = (uint32_t)(lstart[f] - span_lo) + delta + hoff[u];
-          const uint32_t sh = (X4 == 2 && ex + 16 <= (uint32_t)range) ? 0u : ex & 3u;
+          const uint32_t ex = fetch_ex(lstart[f], span_lo, delta, hoff[u]);
+          const uint32_t sh = (X4 == 2 && fetch_exact(ex, range)) ? 0u : ex & 3u;
 #pragma unroll
           for (int q = 0; q < 4; q++) w[q] = __builtin_amdgcn_alignbyte(x[u][q + 1], x[u][q], sh);
         } else {
           const DevBytes rd{bytes + lstart[f] + hoff[u]};
 #pragma unroll
           for (int q = 0; q < 4; q++) w[q] = 0;
-          // (only the bytes the header occupies: a datagram's hs <= 14, an ack group 9)
-          const uint32_t nbytes = m == kItemsAck ? UFC_ACK_GROUP_SIZE : 14u;
-          for (uint32_t c = 0; c < nbytes; c++) w[c >> 2] |= rd(c) << (8 * (c & 3));
+          // (only the bytes the header occupies, sized by its first byte: a micro header with no payload
+          // ends 4 bytes before its frame, and the batch's last frame may end the caller's buffer)
+          w[0] = rd(0);
+          const uint32_t nbytes = fallback_bytes(m == kItemsAck, w[0]);
+          for (uint32_t c = 1; c < nbytes; c++) w[c >> 2] |= rd(c) << (8 * (c & 3));
         }
         auto h = [&](uint32_t c) -> uint32_t { return (w[c >> 2] >> (8 * (c & 3))) & 0xFFu; };
         ufc_item it{};
@@ -405,8 +353,7 @@ hipError_t parse_batch(const ParseArgs& a, const ScratchSource& scratch, hipStre
   // counter, and a workgroup that finds no room left leaves its frames to the emit step's re-walk); below 2^32 - 1
   // so that every segment fits 32-bit offsets and no segment base can equal the overflow sentinel 0xFFFFFFFF
   // (frames past the cap are walked again, kItemsWalk)
-  const uint64_t seg_cap = std::min<uint64_t>(std::min<uint64_t>(n * kPosSlots, std::max<uint64_t>(a.items_cap, 1)),
-                                              0xFFFFFFFEull - kSegWords);
+  const uint64_t seg_cap = ufc_parse_plan::seg_cap(n, a.items_cap);
   const size_t temp_bytes = scan_temp_bytes<uint32_t>(blocks);  // the scan over the workgroups' item counts
   ScratchPlan plan;
   const uint64_t at_counts = plan.take(n * 4);
