@@ -1,8 +1,11 @@
 // rate_host_check.hip -- the send rate control's core (frame_codec_core.hpp: rate_step, rate_begin) as host code
 // under AddressSanitizer and UBSan: the shapes of tests/golden/send_rate_cases.json with their hand-traced numbers,
-// then a random batch over buffers of exactly the sizes the states name, so that an entry written outside a
+// the named cases of tests/rate_expect.py's set_cases() (sets longer than the kRateHeld entries a step holds in
+// registers) against literals over a heap arena of exactly the rooms' bytes, with the same numbers as there,
+// then a random batch over buffers of exactly the sizes the states name (rooms of up to 24 entries), so that an entry written outside a
 // connection's room, a gather past its array or a float cast with undefined behaviour stops the run.
 // A stand-alone program; tests/test_rate_cpu.py builds and runs it.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -77,6 +80,194 @@ struct One {
     rate_step(a, 0, s, t, f, r);
   }
 };
+
+
+// ---- rate_expect.set_cases(): sets past the held entries ----
+struct Ent {
+  uint64_t t;
+  uint32_t v;
+  bool initial;
+};
+static bool operator==(const ufc_recv_rate_entry& e, const Ent& w) {
+  return e.timestamp_ms == w.t && e.value == w.v && e.is_initial == (w.initial ? 1 : 0) && e.reserved[0] == 0 &&
+         e.reserved[1] == 0 && e.reserved[2] == 0;
+}
+struct SetCase {
+  const char* name;
+  uint32_t cap;
+  std::vector<Ent> in;
+  uint32_t stop;
+  std::vector<Ent> want;  // the set afterwards (DONE)
+  uint32_t send_rate;
+  bool limited = true, feedback = true, arena_last = false;
+  double prev_loss = 1e-9;
+  uint64_t now = 10000;
+};
+static const uint64_t kNow = 10000, kF = 9950, kX = 9000;  // with rtt_ms 50: ages 50 (kept) and 1000 (dropped)
+static const uint32_t kFed = 50000;
+static uint32_t val(uint32_t k) { return 100000 + 1000 * k; }
+static std::vector<Ent> set_of(const std::vector<uint64_t>& stamps, const std::vector<uint32_t>& values = {}) {
+  std::vector<Ent> e;
+  for (size_t k = 0; k < stamps.size(); k++) e.push_back({stamps[k], values.empty() ? val((uint32_t)k) : values[k], false});
+  return e;
+}
+static std::vector<Ent> kept(const std::vector<Ent>& e, const std::vector<int>& idx, uint64_t now = kNow) {
+  std::vector<Ent> w;
+  for (int k : idx) w.push_back(e[k]);
+  w.push_back({now, kFed, false});
+  return w;
+}
+static std::vector<uint64_t> stamps(std::initializer_list<std::pair<int, uint64_t>> runs) {
+  std::vector<uint64_t> s;
+  for (auto& r : runs) s.insert(s.end(), r.first, r.second);
+  return s;
+}
+static std::vector<int> upto(int n) {
+  std::vector<int> v(n);
+  for (int k = 0; k < n; k++) v[k] = k;
+  return v;
+}
+static std::vector<SetCase> set_cases() {
+  std::vector<SetCase> c;
+  auto add = [&](const char* name, uint32_t cap, std::vector<Ent> in, uint32_t stop, std::vector<Ent> want, uint32_t rate) {
+    SetCase s;
+    s.name = name, s.cap = cap, s.in = in, s.stop = stop, s.want = want, s.send_rate = rate;
+    c.push_back(s);
+    return &c.back();
+  };
+  const uint32_t DONE = UFC_RATE_DONE, FULL = UFC_RATE_RECV_FULL;
+  std::vector<Ent> e = set_of(stamps({{5, kF}}));
+  add("five_all_kept", 8, e, DONE, kept(e, upto(5)), 2 * val(4));
+  e = set_of(stamps({{4, kX}, {4, kF}}));
+  add("tail_only_kept", 8, e, DONE, kept(e, {4, 5, 6, 7}), 2 * val(7));
+  e = set_of(stamps({{4, kF}, {4, kX}}));
+  add("head_only_kept", 8, e, DONE, kept(e, {0, 1, 2, 3}), 2 * val(3));
+  e = set_of({kF, kX, kF, kX, kF, kX, kF, kX});
+  add("alternate_kept", 8, e, DONE, kept(e, {0, 2, 4, 6}), 2 * val(6));
+  e = set_of(stamps({{8, kX}}));
+  add("none_kept", 8, e, DONE, kept(e, {}), 2 * kFed);
+  e = set_of(stamps({{5, kF}}));
+  add("full_by_the_tail", 5, e, FULL, {}, 0);
+  e = set_of(stamps({{4, kF}, {1, kX}}));
+  add("room_by_the_tail", 5, e, DONE, kept(e, upto(4)), 2 * val(3));
+  e = set_of(stamps({{23, kF}}));
+  add("cap24_fills", 24, e, DONE, kept(e, upto(23)), 2 * val(22));
+  e = set_of(stamps({{24, kF}}));
+  add("cap24_full", 24, e, FULL, {}, 0);
+  const std::vector<uint32_t> desc = {val(5), val(4), val(3), val(2), val(1), 900000};
+  e = set_of(stamps({{6, kF}}), desc);
+  add("max_in_tail", 8, e, DONE, kept(e, upto(6)), 1800000);
+  e = set_of(stamps({{5, kF}, {1, kX}}), desc);
+  add("max_in_tail_expired", 8, e, DONE, kept(e, upto(5)), 2 * val(5));
+  // now 40: ~0 - 10 and ~0 wrap to the ages 51 and 41 (kept); 45 and 1000 lie ahead of now (ages near 2^64)
+  e = set_of({10, 10, 10, 10, ~0ull - 10, 45, ~0ull, 1000});
+  add("wrapped_ages_in_tail", 8, e, DONE, kept(e, {0, 1, 2, 3, 4, 6}, 40), 2 * val(6))->now = 40;
+  e = set_of(stamps({{8, kF}}), {val(0), val(1), val(2), val(3), val(4), val(5), 900000, val(7)});
+  add("replace_max_tail", 8, e, DONE, {{kNow, 900000, false}}, 1800000)->limited = false;
+  SetCase* li = add("replace_max_tail_loss_increase", 8, e, DONE, {{kNow, 450000, false}}, 450000);
+  li->limited = false, li->prev_loss = 0.0;
+  e = set_of(stamps({{6, kF}}), {0xFFFFFFFFu, val(1), val(2), val(3), val(4), 900000});
+  e[0].initial = true;
+  add("initial_skipped_with_tail", 8, e, DONE, {{kNow, 900000, false}}, 1800000)->limited = false;
+  e = set_of(stamps({{8, kF}}), {val(0), val(1), val(2), val(3), val(4), val(5), val(6), 900000});
+  add("nofeedback_max_in_tail", 8, e, DONE, {{kNow, 450000, false}}, 900000)->feedback = false;
+  e = set_of(stamps({{5, kF}}));
+  add("room_at_arena_end", 6, e, DONE, kept(e, upto(5)), 2 * val(4))->arena_last = true;
+  return c;
+}
+// Every case between two neighbours of one entry, the rooms adjoining in a heap arena of exactly the rooms' bytes
+// (room_at_arena_end's room last, the last neighbour's first): an entry written outside a room is a changed
+// neighbour or, past the arena, AddressSanitizer's.
+static void run_set_cases() {
+  const std::vector<SetCase> cases = set_cases();
+  const size_t n = 2 * cases.size() + 1;
+  std::vector<const SetCase*> conn(n, nullptr);
+  for (size_t k = 0; k < cases.size(); k++) conn[2 * k + 1] = &cases[k];
+  CHECK(cases.size() == 17 && cases.back().arena_last);
+  std::vector<uint32_t> cap(n), first(n);
+  size_t total = 0;
+  for (size_t c = 0; c < n; c++) total += cap[c] = conn[c] ? conn[c]->cap : 1;
+  first[n - 1] = 0;  // the neighbour behind the last case
+  uint32_t at = 1;
+  for (size_t c = 0; c + 1 < n; c++) {
+    first[c] = at;
+    at += cap[c];
+  }
+  CHECK(at == total && first[n - 2] + cap[n - 2] == total);
+  ufc_recv_rate_entry* arena = (ufc_recv_rate_entry*)std::malloc(total * sizeof(ufc_recv_rate_entry));
+  std::vector<ufc_rate_state> states(n);
+  std::vector<ufc_rate_tick> ticks(n);
+  std::vector<ufc_frame_queue_result> fq(n);
+  std::vector<ufc_flush> flushes(n);
+  std::vector<uint32_t> fi(n);
+  std::memset(flushes.data(), 0, n * sizeof(ufc_flush));
+  for (size_t c = 0; c < n; c++) {
+    const SetCase* k = conn[c];
+    const uint64_t now = k ? k->now : kNow;
+    ufc_rate_state s = new_state(0xFFFFFFFFu, cap[c]);
+    s.mode = UFC_RATE_THROUGHPUT_EQN;
+    s.send_rate = s.send_rate_tcp = 100000;
+    s.has_rtt_s = s.has_rtt_ms = s.has_rto_ms = s.nofeedback_idle = s.has_nofeedback_exp = 1;
+    s.rtt_s = 0.05;
+    s.rtt_ms = 50;
+    s.rto_ms = 200;
+    s.nofeedback_exp_ms = now + 5000;
+    s.prev_loss_rate = k ? k->prev_loss : 1e-9;
+    s.now_ms = now - 10;
+    s.recv_first = first[c];
+    if (k && !k->feedback) {
+      s.nofeedback_exp_ms = now;
+      s.nofeedback_idle = 0;
+      s.send_rate_tcp = 1000000000;
+    }
+    const std::vector<Ent> one = {{kF, 30000 + (uint32_t)(c / 2), false}};
+    const std::vector<Ent>& in = k ? k->in : one;
+    s.recv_count = (uint32_t)in.size();
+    for (uint32_t j = 0; j < cap[c]; j++) {
+      ufc_recv_rate_entry& e = arena[first[c] + j];
+      std::memset(&e, 0x5A, sizeof e);  // (behind the count: rubbish)
+      if (j < in.size()) e = rate_entry(in[j].t, in[j].v, in[j].initial);
+    }
+    states[c] = s;
+    ticks[c] = tick(now, 0.01, 0, 0);
+    fq[c] = (!k || k->feedback) ? feedback(50, kFed, 1e-9, k ? k->limited : false) : ufc_frame_queue_result{};
+    flushes[c].flush_alloc = -7;
+    fi[c] = (uint32_t)c;
+  }
+  std::vector<ufc_recv_rate_entry> before(arena, arena + total);
+  RateArgs a{};
+  a.n = n;
+  a.entries = arena;
+  a.n_entries = total;
+  a.flushes = flushes.data();
+  a.n_flushes = n;
+  a.flush_index = fi.data();
+  for (size_t c = 0; c < n; c++) {
+    const SetCase* k = conn[c];
+    ufc_rate_state S = states[c];
+    ufc_rate_result R;
+    rate_step(a, c, S, ticks[c], fq[c], R);
+    const ufc_recv_rate_entry* room = arena + first[c];
+    if (!k) {  // a neighbour: its one entry replaced by the maximum of itself and the feedback
+      CHECK(R.stop == UFC_RATE_DONE && S.recv_count == 1 && (room[0] == Ent{kNow, kFed, false}));
+      continue;
+    }
+    if (R.stop != k->stop) std::printf("FAIL %s: stop %u\n", k->name, R.stop), failures++;
+    if (k->stop != UFC_RATE_DONE) {
+      CHECK(std::memcmp(&S, &states[c], sizeof S) == 0 && flushes[c].flush_alloc == -7);
+      CHECK(std::memcmp(room, &before[first[c]], cap[c] * sizeof *room) == 0);
+      continue;
+    }
+    bool ok = S.rtt_ms == 50 && S.recv_count == k->want.size() && R.recv_count == S.recv_count && R.send_rate == k->send_rate &&
+              S.send_rate == k->send_rate && flushes[c].flush_alloc == R.flush_alloc;
+    for (size_t j = 0; ok && j < k->want.size(); j++) ok = room[j] == k->want[j];
+    const size_t behind = std::max<size_t>(k->want.size(), k->in.size());  // what no entry reached is what it was
+    ok = ok && std::memcmp(room + behind, &before[first[c] + behind], (cap[c] - behind) * sizeof *room) == 0;
+    if (k->arena_last) ok = ok && first[c] + cap[c] == total && (arena[total - 1] == Ent{kNow, kFed, false});
+    if (!ok) std::printf("FAIL %s: count %u, send_rate %u\n", k->name, S.recv_count, R.send_rate), failures++;
+  }
+  std::free(arena);
+}
 
 int main() {
   // ---- the goldens' shapes, numbers traced by hand ----
@@ -180,6 +371,8 @@ int main() {
     CHECK(q.rtt_ms == 20 && q.now_ms == 500 && q.reset_loss_rate == 0.25 && !s.has_reset && s.reset_loss_rate == 0.0);
   }
 
+  run_set_cases();
+
   // ---- a random batch over exact-size buffers ----
   const double edge_f[] = {0.0, -0.0, 1.0, 1e-9, 5e-324, 1e-310, INFINITY, -INFINITY, NAN, -1.0, 1e300, 0.5};
   const uint64_t edge_u[] = {0, 1, 150, 1ull << 32, (1ull << 63) - 1, 1ull << 63, ~0ull - 2000, ~0ull};
@@ -190,7 +383,7 @@ int main() {
   size_t stops[4] = {0, 0, 0, 0}, stalled = 0;
   for (int round = 0; round < 40; round++) {
     const size_t n = 1 + rnd_below(300);
-    const uint32_t cap = 1 + (uint32_t)rnd_below(5);
+    const uint32_t cap = 1 + (uint32_t)(round % 3 == 2 ? rnd_below(24) : rnd_below(5));
     std::vector<ufc_rate_state> states(n), out(n);
     std::vector<ufc_rate_tick> ticks(n);
     std::vector<ufc_frame_queue_result> fq(n);

@@ -33,7 +33,7 @@ class ReferenceHang(Exception):
 def f64_round(v):          # f64::round: half away from zero, either sign
     if v != v or math.isinf(v):
         return v
-    t = float(math.trunc(v))
+    t = math.copysign(float(math.trunc(v)), v)   # (trunc keeps the sign of a zero)
     d = v - t
     return t + 1.0 if d >= 0.5 else t - 1.0 if d <= -0.5 else t
 
@@ -85,11 +85,17 @@ def ms_to_s(v_ms):
     return float(v_ms) / 1000.0
 
 
-def eval_tcp_throughput(rtt, p):
+def eval_tcp_throughput_f64(rtt, p):
+    """The value eval_tcp_throughput casts (not a function of the reference: tests/test_float_paths.py compares it
+    as 64 bits)."""
     s = float(MSS)
     f_p = f64_sqrt(f64_mul(p, 2.0) / 3.0) + f64_mul(f64_mul(f64_mul(12.0, f64_sqrt(f64_mul(p, 3.0) / 8.0)), p),
                                                     1.0 + f64_mul(f64_mul(32.0, p), p))
-    return as_u32(f64_div(s, f64_mul(rtt, f_p)))
+    return f64_div(s, f64_mul(rtt, f_p))
+
+
+def eval_tcp_throughput(rtt, p):
+    return as_u32(eval_tcp_throughput_f64(rtt, p))
 
 
 def eval_tcp_throughput_inv(rtt, target_rate_bps, stall_rule=False):
@@ -524,6 +530,24 @@ def make_feedback(rtt_ms, receive_rate, loss_rate, rate_limited=False):
     return f
 
 
+# ---- the square root sweep (tests/test_gpu_rate.py, tests/test_float_paths.py) ----
+def sweep_values():
+    """4096 (rtt_ms, loss_rate) pairs: loss rates over the decades with their neighbours in the last bit, 0, 1,
+    denormals, infinity and NaN; RTTs over the decades."""
+    rng = np.random.default_rng(42)
+    decades = 10.0 ** rng.uniform(-12, 0.5, 1200)
+    near = np.concatenate([np.nextafter(decades[:400], 0.0), np.nextafter(decades[:400], 2.0)])
+    third = np.array([2.0 / 3.0, 1.5, 8.0 / 3.0, 0.375, 0.25, 1.0, 0.0, -0.0, np.inf, np.nan, -1.0, 5e-324, 1e-310,
+                      2.2250738585072014e-308, 2.225073858507201e-308, 1e-300, 4.0, 1e300])
+    edges = np.concatenate([third, np.nextafter(third, 0.0), np.nextafter(third, np.inf)])
+    squares = (rng.integers(1, 1 << 26, 600).astype(np.float64) ** 2) * 1.5 / 2.0 ** 60   # p*2/3 a perfect square
+    loss = np.concatenate([decades, near, edges, squares, np.nextafter(squares, 0.0), np.nextafter(squares, 1.0)])
+    loss = np.resize(loss, 4096)
+    rtt = np.resize(np.concatenate([[0, 1, 2, 3, 10, 50, 100, 1000, 60000, 1 << 40],
+                                    (10.0 ** rng.uniform(0, 4.5, 500)).astype(np.uint64)]), 4096).astype(np.uint64)
+    return rtt, rng.permutation(loss)
+
+
 # ---- generated batches ----
 EDGE_U64 = [0, 1, 2, 999, 150, 1 << 31, (1 << 32) - 1, 1 << 32, (1 << 63) - 1, 1 << 63, M64 - 2000, M64 - 1, M64]
 EDGE_F64 = [0.0, -0.0, 1.0, 0.5, 1e-3, 1e-9, 5e-324, 2.2250738585072014e-308, 1e-310, float("inf"), float("-inf"),
@@ -554,12 +578,14 @@ def _f64(rng, lo=-6.0, hi=0.0):
     return float(10 ** rng.uniform(lo, hi))
 
 
-def random_batch(rng, n, recv_cap=4, spoil=0.05):
+def random_batch(rng, n, recv_cap=4, spoil=0.05, fill=0.0):
     """n random connections for one ufc_rate_step call: states over all three modes that pass the state check (but
     for a fraction `spoil`, broken in one rule each), their sets, ticks, frame queue results with and without
     feedback, timers expired or not, and both gathers.  The inputs include rtt 0 (REF_PANIC with a rate-limited
     feedback), sets at their capacity (RECV_FULL), times near the u64 wrap, NaN, infinite and denormal loss rates,
-    receive rates 0 and u32::MAX.  Returns a dict of arrays."""
+    receive rates 0 and u32::MAX.  A fraction `fill` of the connections has its set at capacity, every stamp younger
+    than two RTTs, and a rate-limited feedback (RECV_FULL whatever recv_cap is); at fill = 0 nothing more is drawn, so
+    a seed gives the batch it always gave.  Returns a dict of arrays."""
     states, entries = fr.new_rate_states(n, 0, recv_cap)
     slack = int(rng.integers(0, 5))
     entries = np.zeros(len(entries) + slack, dtype=fr.RECV_RATE_ENTRY_DTYPE)
@@ -606,6 +632,15 @@ def random_batch(rng, n, recv_cap=4, spoil=0.05):
         else:   # (everything but has_feedback must be ignored)
             f["rtt_ms"], f["receive_rate"], f["loss_rate"], f["rate_limited"] = 5, 5, 0.5, 1
         f["stop"], f["window_room"] = int(rng.integers(0, 2)), int(rng.integers(0, 100))
+        if fill and rng.random() < fill:   # a full room: rtt_ms stays 50, every entry younger than 100 ms
+            s["mode"] = int(rng.integers(1, 3))
+            s["has_rtt_s"], s["rtt_s"], s["recv_count"] = 1, 0.05, recv_cap
+            t["now_ms"] = (base + 100) & M64
+            t["flags"] = 0
+            for k in range(recv_cap):
+                entries[first + k] = ((base + 1 + int(rng.integers(0, 100))) & M64, _u32(rng), 0, (0, 0, 0))
+            f["has_feedback"], f["rtt_ms"], f["rate_limited"] = 1, 50, 1
+            f["receive_rate"], f["loss_rate"] = _u32(rng), _f64(rng)
         if rng.random() < spoil:
             rule = int(rng.integers(0, 6))
             if rule == 0:
@@ -634,3 +669,218 @@ def random_batch(rng, n, recv_cap=4, spoil=0.05):
     flush_index[rng.random(n) < 0.05] = n + 3
     return {"states": states, "entries": entries, "ticks": ticks, "fq": fq, "flush_results": flush_results,
             "result_index": result_index, "flushes": flushes, "flush_index": flush_index}
+
+
+# ---- sets longer than the entries a step holds in registers (kRateHeld = 4) ----
+HELD = 4
+NOW, FRESH, EXPIRED = 10000, 9950, 9000          # with rtt_ms 50: ages 50 (< 100, kept) and 1000 (dropped)
+TINY_LOSS = 1e-9                                 # send_rate_tcp about 1.1e9: the receive limit decides send_rate
+FED = 50000                                      # the feedback's receive rate, below every value of the sets
+RUBBISH = (0x5A5A5A5A5A5A5A5A, 0xA5A5A5A5, 0, (7, 7, 7))
+
+
+def _val(k):
+    return 100000 + 1000 * k
+
+
+def _set(stamps, values=None):
+    return [(t, _val(k) if values is None else values[k], 0) for k, t in enumerate(stamps)]
+
+
+def set_cases():
+    """One connection per case, as dicts: name, cap, entries [(timestamp_ms, value, is_initial)], what differs from
+    the common state (THROUGHPUT_EQN, rtt_s 0.05, rtt_ms 50, max_send_rate u32::MAX), tick and feedback (now 10,000,
+    rtt 50 ms, receive rate 50,000, loss 1e-9, rate limited), and `facts`, which check_set_facts asserts on the
+    restatement's output: `stop`; `entries`, the set afterwards ("new" is the entry the feedback appends);
+    `send_rate`; `unchanged` for a stopped connection; `arena_last` for the room that ends the arena."""
+    F, X = FRESH, EXPIRED
+    new = (NOW, FED, 0)
+    cases = []
+
+    def case(name, cap, entries, facts, **kw):
+        cases.append(dict(name=name, cap=cap, entries=entries, facts=facts, **kw))
+
+    def kept(entries, idx):
+        return [entries[k] for k in idx] + [new]
+
+    e = _set([F] * 5)
+    case("five_all_kept", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(5)), "send_rate": 2 * _val(4)})
+    e = _set([X] * 4 + [F] * 4)
+    case("tail_only_kept", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, (4, 5, 6, 7)), "send_rate": 2 * _val(7)})
+    e = _set([F] * 4 + [X] * 4)
+    case("head_only_kept", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, (0, 1, 2, 3)), "send_rate": 2 * _val(3)})
+    e = _set([F, X] * 4)
+    case("alternate_kept", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, (0, 2, 4, 6)), "send_rate": 2 * _val(6)})
+    e = _set([X] * 8)
+    case("none_kept", 8, e, {"stop": fr.RATE_DONE, "entries": [new], "send_rate": 2 * FED})
+    e = _set([F] * 5)
+    case("full_by_the_tail", 5, e, {"stop": fr.RATE_RECV_FULL, "unchanged": True})
+    e = _set([F] * 4 + [X])
+    case("room_by_the_tail", 5, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(4)), "send_rate": 2 * _val(3)})
+    e = _set([F] * 23)
+    case("cap24_fills", 24, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(23)), "send_rate": 2 * _val(22)})
+    e = _set([F] * 24)
+    case("cap24_full", 24, e, {"stop": fr.RATE_RECV_FULL, "unchanged": True})
+    values = [_val(5), _val(4), _val(3), _val(2), _val(1), 900000]
+    e = _set([F] * 6, values)
+    case("max_in_tail", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(6)), "send_rate": 2 * 900000})
+    e = _set([F] * 5 + [X], values)
+    case("max_in_tail_expired", 8, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(5)), "send_rate": 2 * _val(5)})
+    # now 40: M64 - 10 and M64 wrap to the ages 51 and 41 (kept); 45 and 1000 lie ahead of now (ages near 2^64)
+    e = _set([10, 10, 10, 10, M64 - 10, 45, M64, 1000])
+    case("wrapped_ages_in_tail", 8, e, {"stop": fr.RATE_DONE, "send_rate": 2 * _val(6),
+                                        "entries": [e[k] for k in (0, 1, 2, 3, 4, 6)] + [(40, FED, 0)]}, now=40)
+
+    values = [_val(k) for k in range(6)] + [900000, _val(7)]
+    e = _set([F] * 8, values)
+    case("replace_max_tail", 8, e, {"stop": fr.RATE_DONE, "entries": [(NOW, 900000, 0)], "send_rate": 2 * 900000},
+         limited=False)
+    case("replace_max_tail_loss_increase", 8, e, {"stop": fr.RATE_DONE, "entries": [(NOW, 450000, 0)],
+                                                  "send_rate": 450000}, limited=False, prev_loss=0.0)
+    e = [(F, M32, 1)] + _set([F] * 5, [_val(1), _val(2), _val(3), _val(4), 900000])
+    case("initial_skipped_with_tail", 8, e, {"stop": fr.RATE_DONE, "entries": [(NOW, 900000, 0)],
+                                             "send_rate": 2 * 900000}, limited=False)
+
+    values = [_val(k) for k in range(7)] + [900000]
+    e = _set([F] * 8, values)
+    # current_limit = min(send_rate_tcp, 2 * 900000), new_limit = 900000: the set becomes one entry of new_limit / 2
+    case("nofeedback_max_in_tail", 8, e, {"stop": fr.RATE_DONE, "entries": [(NOW, 450000, 0)], "send_rate": 900000},
+         feedback=False, state={"nofeedback_exp_ms": NOW, "nofeedback_idle": 0, "send_rate_tcp": 1000000000})
+
+    e = _set([F] * 5)
+    case("room_at_arena_end", 6, e, {"stop": fr.RATE_DONE, "entries": kept(e, range(5)), "send_rate": 2 * _val(4),
+                                     "arena_last": True}, arena_last=True)
+    return cases
+
+
+def set_neighbour(k=0, count=1):
+    """A connection with `count` entries in a room of as many: what stands beside the cases (count 1), and the
+    fillers of the device batch (1..3)."""
+    e = [(FRESH, 30000 + k % 1000 + j, 0) for j in range(count)]
+    return dict(name=None, cap=count, entries=e, facts=None, limited=False)
+
+
+def set_batch(conns):
+    """The connections `conns` (dicts of set_cases or set_neighbour) as one batch in their order.  The rooms lie in
+    the arena in the connections' order and adjoin each other, but for the last connection with `arena_last`, whose
+    room ends the arena, and the connection behind it, whose room then begins it.  Behind a set's count the room is
+    rubbish.  Every connection has a flush of its own; no flush result is gathered.  The dict of random_batch, and
+    "index": the connections of each name."""
+    n = len(conns)
+    last = max((c for c in range(n) if conns[c].get("arena_last")), default=None)
+    order = list(range(n))
+    if last is not None:
+        tail = order[last + 1:]
+        order = tail + order[:last] + [last]
+    total = sum(c["cap"] for c in conns)
+    states, _ = fr.new_rate_states(n, M32, 1)
+    entries = np.zeros(total, dtype=fr.RECV_RATE_ENTRY_DTYPE)
+    first = 0
+    for c in order:
+        states[c]["recv_first"], states[c]["recv_cap"] = first, conns[c]["cap"]
+        first += conns[c]["cap"]
+    ticks = np.zeros(n, dtype=fr.RATE_TICK_DTYPE)
+    fq = np.zeros(n, dtype=fr.FRAME_QUEUE_RESULT_DTYPE)
+    index = {}
+    for c, conn in enumerate(conns):
+        s = states[c]
+        now = conn.get("now", NOW)
+        s["mode"], s["send_rate"], s["send_rate_tcp"] = THROUGHPUT_EQN, 100000, 100000
+        s["has_rtt_s"], s["rtt_s"], s["has_rtt_ms"], s["rtt_ms"] = 1, 0.05, 1, 50
+        s["has_rto_ms"], s["rto_ms"], s["nofeedback_idle"] = 1, 200, 1
+        s["has_nofeedback_exp"], s["nofeedback_exp_ms"] = 1, now + 5000
+        s["prev_loss_rate"] = conn.get("prev_loss", TINY_LOSS)
+        s["now_ms"] = max(now - 10, 0)
+        for k, v in conn.get("state", {}).items():
+            s[k] = v
+        s["recv_count"] = len(conn["entries"])
+        r0 = int(s["recv_first"])
+        for k in range(conn["cap"]):
+            entries[r0 + k] = conn["entries"][k] + ((0, 0, 0),) if k < len(conn["entries"]) else RUBBISH
+        ticks[c] = make_tick(now, 0.01)
+        if conn.get("feedback", True):
+            fq[c] = make_feedback(50, FED, TINY_LOSS, conn.get("limited", True))
+        if conn["name"] is not None:
+            index.setdefault(conn["name"], []).append(c)
+    flushes = np.zeros(n, dtype=fr.FLUSH_DTYPE)
+    flushes["flush_alloc"], flushes["kind"] = -7, 1
+    return {"states": states, "entries": entries, "ticks": ticks, "fq": fq, "flush_results": None, "result_index": None,
+            "flushes": flushes, "flush_index": np.arange(n, dtype=np.uint32), "index": index, "conns": conns}
+
+
+def set_cases_between_neighbours():
+    """Every case between two connections of one entry: neighbour, case, neighbour, case, ..., neighbour."""
+    conns = [set_neighbour(0)]
+    for k, case in enumerate(set_cases()):
+        conns += [case, set_neighbour(k + 1)]
+    return set_batch(conns)
+
+
+def set_cases_at_tile_seams():
+    """Case i at the connections 64 i + 63 and 64 i + 64 (lane 63 of one tile of the kernel and lane 0 of the next),
+    connections of 1 to 3 entries everywhere else."""
+    cases = set_cases()
+    conns = [set_neighbour(c, 1 + c % 3) for c in range(64 * len(cases) + 1)]
+    for i, case in enumerate(cases):
+        conns[64 * i + 63] = case
+        conns[64 * i + 64] = case
+    return set_batch(conns)
+
+
+def check_set_facts(b, exp):
+    """Every named connection's facts against exp = expect_step(...), the restatement's output; and for every
+    connection that the room behind its set is what it was."""
+    arena, ends = len(b["entries"]), 0
+    for c, conn in enumerate(b["conns"]):
+        s, out, res = b["states"][c], exp["states_out"][c], exp["results"][c]
+        r0, cap = int(s["recv_first"]), int(s["recv_cap"])
+        room_in, room = b["entries"][r0:r0 + cap], exp["entries"][r0:r0 + cap]
+        behind = max(int(out["recv_count"]), int(s["recv_count"]))
+        assert room[behind:].tobytes() == room_in[behind:].tobytes(), (conn["name"], c)
+        f = conn["facts"]
+        if f is None:
+            assert int(res["stop"]) == fr.RATE_DONE and int(out["recv_count"]) == 1 and cap <= 3, c
+            continue
+        assert int(res["stop"]) == f["stop"], (conn["name"], int(res["stop"]))
+        assert cap > HELD and int(s["recv_count"]) >= HELD + 1, conn["name"]
+        if f.get("unchanged"):
+            assert out.tobytes() == s.tobytes() and room.tobytes() == room_in.tobytes(), conn["name"]
+            assert int(exp["flushes"][c]["flush_alloc"]) == -7, conn["name"]
+            continue
+        assert int(out["rtt_ms"]) == 50, (conn["name"], int(out["rtt_ms"]))
+        count = int(out["recv_count"])
+        have = [(int(e["timestamp_ms"]), int(e["value"]), int(e["is_initial"])) for e in room[:count]]
+        assert have == list(f["entries"]) and int(res["recv_count"]) == count, (conn["name"], have)
+        assert all(bytes(e["reserved"]) == b"\0\0\0" for e in room[:count]), conn["name"]
+        assert int(res["send_rate"]) == f["send_rate"] == int(out["send_rate"]), (conn["name"], int(res["send_rate"]))
+        assert int(exp["flushes"][c]["flush_alloc"]) == int(res["flush_alloc"]), conn["name"]
+        if f.get("arena_last") and r0 + cap == arena:   # (of two copies of the case only one can end the arena)
+            assert count == cap and have[-1] == f["entries"][-1], conn["name"]
+            assert exp["entries"][arena - 1].tobytes() != b["entries"][arena - 1].tobytes(), conn["name"]
+            ends += 1
+    assert ends == 1
+
+
+def set_coverage(b, exp):
+    """What a batch does past the held entries, counted on exp = expect_step(...): DONE connections that came in with
+    more than HELD entries (`large_done`), RECV_FULL in a room of more than HELD (`full_large`), and rate-limited
+    updates that carry a survivor from an index >= HELD to one below (`moved`)."""
+    seen = {"large_done": 0, "full_large": 0, "moved": 0, "largest": 0}
+    for c in range(len(b["states"])):
+        s, out, res, f = b["states"][c], exp["states_out"][c], exp["results"][c], b["fq"][c]
+        stop, count = int(res["stop"]), int(s["recv_count"])
+        if stop == fr.RATE_RECV_FULL and int(s["recv_cap"]) > HELD:
+            seen["full_large"] += 1
+        if stop != fr.RATE_DONE or count <= HELD:
+            continue
+        seen["large_done"] += 1
+        seen["largest"] = max(seen["largest"], count)
+        if int(s["mode"]) == AWAIT_SEND or not f["has_feedback"] or not f["rate_limited"]:
+            continue
+        r0, now, two_rtt = int(s["recv_first"]), int(b["ticks"][c]["now_ms"]), (2 * int(out["rtt_ms"])) & M64
+        room_in, room = b["entries"][r0:r0 + count], exp["entries"][r0:r0 + count]
+        kept = [k for k in range(count) if ((now - int(room_in[k]["timestamp_ms"])) & M64) < two_rtt]
+        assert len(kept) + 1 == int(out["recv_count"]), c
+        assert all(room[j].tobytes()[:13] == room_in[k].tobytes()[:13] for j, k in enumerate(kept)), c
+        seen["moved"] += any(k >= HELD and j < HELD for j, k in enumerate(kept))
+    return seen

@@ -1,8 +1,9 @@
 """GPU: the batched send rate control (ufc_rate_begin_varlen, ufc_rate_step_varlen; FrameCrcEngine.rate_begin and
 rate_step) against the host calls, byte for byte on states (every double as its 64 bits), results, the entry arena,
 the frame queue steps and the gathered flushes: generated batches at the tile edges of the LDS staging and past the
-launch grid, the square root's exactness through the public call, and 200 ticks of begin -> frame_queue -> step queued
-on device tensors with nothing read back before the end.  tests/test_rate_cpu.py holds the host calls against the
+launch grid, rate_expect's set cases (sets longer than the four held entries) on lane 63 and on lane 0 of the next tile,
+rooms of 5, 8 and 24 entries, the square root's exactness through the public call, and two closed loops of begin ->
+frame_queue -> step queued on device tensors with nothing read back before the end.  tests/test_rate_cpu.py holds the host calls against the
 restatement of the reference."""
 import ctypes
 
@@ -95,6 +96,41 @@ def test_equals_the_host_calls(engine, n):
         assert rounds < 400, seen
 
 
+def test_set_cases(engine):
+    """rate_expect.set_cases() on lane 63 of a tile and on lane 0 of the next: case i at the connections 64 i + 63
+    and 64 i + 64, connections of 1 to 3 entries on every other lane, so that lanes that go on from memory sit beside
+    lanes that have nothing there.  The facts are asserted on the restatement, the host call against it, and the
+    device against the host call byte for byte, states_out separate and aliased."""
+    b = E.set_cases_at_tile_seams()
+    for i, name in enumerate(c["name"] for c in E.set_cases()):
+        assert b["index"][name] == [64 * i + 63, 64 * i + 64], name
+    want = E.expect_step(b["states"], b["ticks"], b["fq"], b["entries"], None, None, b["flushes"], b["flush_index"])
+    E.check_set_facts(b, want)
+    host = compare_step(engine, b, gather_in=False)
+    for k in ("results", "states_out", "entries", "flushes"):
+        same(host[k], want[k], k)
+    compare_step(engine, b, gather_in=False, in_place=True)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 130])
+def test_equals_the_host_calls_large_sets(engine, n):
+    """Rooms of 5, 8 and 24 entries in turn, a fifth of the connections full: batches are drawn until the host side
+    has seen, past the 4 held entries, DONE connections (100 in 1,600 connections, as on the CPU), a RECV_FULL and a
+    survivor carried from memory into a held slot; separate and aliased states_out, with and without each gather."""
+    rng = np.random.default_rng(2000 + n)
+    seen = {"large_done": 0, "full_large": 0, "moved": 0}
+    rounds = 0
+    while rounds < 3 or min(seen.values()) == 0 or seen["large_done"] * 16 < rounds * n:
+        b = E.random_batch(rng, n, recv_cap=(5, 8, 24)[rounds % 3], spoil=0.1, fill=0.2)
+        variant = rounds % 4
+        want = compare_step(engine, b, in_place=variant in (1, 3), gather_in=variant != 2, gather_out=variant != 3)
+        for key, v in E.set_coverage(b, want).items():
+            if key in seen:
+                seen[key] += v
+        rounds += 1
+        assert rounds < 600, seen
+
+
 def tiled_batch(rng, n, unit=2000, recv_cap=3):
     """n connections made of a generated batch of `unit`, repeated: every copy with its own room in the arena and
     its own flush."""
@@ -129,21 +165,7 @@ def test_many_connections_equal_the_host_calls(engine, n):
 
 
 # ---- the square root ----
-def sweep_values():
-    """4096 (rtt_ms, loss_rate) pairs: loss rates over the decades with their neighbours in the last bit, 0, 1,
-    denormals, infinity and NaN; RTTs over the decades."""
-    rng = np.random.default_rng(42)
-    decades = 10.0 ** rng.uniform(-12, 0.5, 1200)
-    near = np.concatenate([np.nextafter(decades[:400], 0.0), np.nextafter(decades[:400], 2.0)])
-    third = np.array([2.0 / 3.0, 1.5, 8.0 / 3.0, 0.375, 0.25, 1.0, 0.0, -0.0, np.inf, np.nan, -1.0, 5e-324, 1e-310,
-                      2.2250738585072014e-308, 2.225073858507201e-308, 1e-300, 4.0, 1e300])
-    edges = np.concatenate([third, np.nextafter(third, 0.0), np.nextafter(third, np.inf)])
-    squares = (rng.integers(1, 1 << 26, 600).astype(np.float64) ** 2) * 1.5 / 2.0 ** 60   # p*2/3 a perfect square
-    loss = np.concatenate([decades, near, edges, squares, np.nextafter(squares, 0.0), np.nextafter(squares, 1.0)])
-    loss = np.resize(loss, 4096)
-    rtt = np.resize(np.concatenate([[0, 1, 2, 3, 10, 50, 100, 1000, 60000, 1 << 40],
-                                    (10.0 ** rng.uniform(0, 4.5, 500)).astype(np.uint64)]), 4096).astype(np.uint64)
-    return rtt, rng.permutation(loss)
+sweep_values = E.sweep_values
 
 
 def sweep_batch(mode):
@@ -203,9 +225,10 @@ def test_square_root_exactness_first_loss(engine):
 
 
 # ---- the closed loop ----
-def loop_traffic(n, ticks, seed):
+def loop_traffic(n, ticks, seed, dt_ms=(5, 60), mark=0.1):
     """Per tick and connection, generated up front: the sent frames of the last flush, the acks that arrived, the
-    rate tick.  Returns (queues, log, states, entries, [per-tick dict])."""
+    rate tick.  A tick lasts dt_ms[0] .. dt_ms[1] - 1 ms, and a share `mark` of the connection-ticks asks for
+    MARK_RATE_LIMITED.  Returns (queues, log, states, entries, [per-tick dict])."""
     rng = np.random.default_rng(seed)
     window = 16
     queues, log = fr.new_frame_queues(n, window, window, 0)
@@ -217,7 +240,7 @@ def loop_traffic(n, ticks, seed):
     out = []
     arr = lambda xs, dt: np.array(xs, dtype=dt) if xs else np.zeros(0, dtype=dt)
     for t in range(ticks):
-        dt = rng.integers(5, 60, n)
+        dt = rng.integers(dt_ms[0], dt_ms[1], n)
         quiet = rng.random(n) < 0.02
         dt[quiet] += rng.integers(500, 5000, int(quiet.sum()))
         now = now + dt.astype(np.uint64)
@@ -243,7 +266,7 @@ def loop_traffic(n, ticks, seed):
         out.append({"infos": arr(infos, fr.FRAME_INFO_DTYPE), "items": arr(items, fr.ITEM_DTYPE),
                     "frame_first": np.array(ff, dtype=np.uint64), "sent": arr(sent, fr.SENT_FRAME_DTYPE),
                     "sent_first": np.array(sf, dtype=np.uint64), "now": now.copy(), "ticks": rate_ticks,
-                    "extra": (rng.random(n) < 0.1).astype(np.uint32) * np.uint32(fr.FQ_MARK_RATE_LIMITED)})
+                    "extra": (rng.random(n) < mark).astype(np.uint32) * np.uint32(fr.FQ_MARK_RATE_LIMITED)})
     return queues, log, states, entries, out
 
 
@@ -295,6 +318,69 @@ def test_closed_loop_on_the_device(engine):
     same(records(d_fl, fr.FLUSH_DTYPE), h_fl, "flushes")
     same(records(d_fq, fr.FRAME_QUEUE_RESULT_DTYPE), np.concatenate(h_fq), "frame queue results")
     same(records(d_rate, fr.RATE_RESULT_DTYPE), np.concatenate(h_rate), "rate results")
+
+
+def run_closed_loop(engine, n, ticks, traffic_args):
+    """`ticks` ticks of begin -> frame_queue -> step for n connections, on the host calls and then on device tensors
+    only, nothing read back before the end; everything compared.  Returns what the host run saw: the rate results
+    of every tick and the set sizes every tick came in with."""
+    queues, log, states, entries, traffic = loop_traffic(n, ticks, *traffic_args)
+    flush_index = np.arange(n, dtype=np.uint32)[::-1].copy()
+    flushes = np.zeros(n, dtype=fr.FLUSH_DTYPE)
+    flushes["kind"], flushes["id1"] = 1, 77
+    # the host calls
+    h_q, h_log, h_s, h_e, h_fl = queues.copy(), log.copy(), states.copy(), entries.copy(), flushes.copy()
+    h_fq, h_rate, h_counts = [], [], []
+    for tr in traffic:
+        opened = fr.rate_begin_host(h_s, tr["now"], tr["extra"], nthreads=16)
+        fq = fr.frame_queue_host(tr["infos"], tr["items"], tr["frame_first"], tr["sent"], tr["sent_first"], h_q,
+                                 opened["steps"], h_log, nthreads=16)
+        h_counts.append(opened["states_out"]["recv_count"].copy())
+        closed = fr.rate_step_host(opened["states_out"], tr["ticks"], fq["results"], h_e, flushes=h_fl,
+                                   flush_index=flush_index, nthreads=16)
+        h_q, h_s = fq["queues_out"], closed["states_out"]
+        h_fq.append(fq["results"])
+        h_rate.append(closed["results"])
+    flags = np.bitwise_or.reduce(np.concatenate(h_rate)["flags"])
+    assert flags & 15 == 15 and (np.concatenate(h_rate)["stop"] == fr.RATE_DONE).all()
+    assert (np.concatenate(h_fq)["stop"] == fr.FQ_DONE).all()
+    # the device: everything uploaded first, then 3 calls per tick queued, then one synchronize
+    up = [{"infos": rows(tr["infos"], DEV), "items": rows(tr["items"], DEV), "frame_first": rows(tr["frame_first"], DEV),
+           "sent": rows(tr["sent"], DEV), "sent_first": rows(tr["sent_first"], DEV), "now": rows(tr["now"], DEV),
+           "ticks": rows(tr["ticks"], DEV), "extra": rows(tr["extra"], DEV)} for tr in traffic]
+    d_q, d_log, d_s, d_e = rows(queues, DEV), rows(log, DEV), rows(states, DEV), rows(entries, DEV)
+    d_fl, d_fi = rows(flushes, DEV), rows(flush_index, DEV)
+    d_steps = torch.zeros((n, fr.FRAME_QUEUE_STEP_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    d_fq = torch.zeros((ticks, n, fr.FRAME_QUEUE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    d_rate = torch.zeros((ticks, n, fr.RATE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=DEV)
+    torch.cuda.synchronize()
+    for t, u in enumerate(up):
+        engine.rate_begin(d_s, u["now"], u["extra"], steps=d_steps, states_out=d_s)
+        fq = engine.frame_queue(u["infos"], u["items"], u["frame_first"], u["sent"], u["sent_first"], d_q, d_steps, d_log,
+                                queues_out=d_q)
+        d_fq[t].copy_(fq["results"])
+        engine.rate_step(d_s, u["ticks"], d_fq[t], d_e, flushes=d_fl, flush_index=d_fi, results=d_rate[t], states_out=d_s)
+    torch.cuda.synchronize()
+    same(records(d_s, fr.RATE_STATE_DTYPE), h_s, "states")
+    same(records(d_q, fr.FRAME_QUEUE_DTYPE), h_q, "queues")
+    same(records(d_log, fr.SENT_FRAME_DTYPE), h_log, "log")
+    same(records(d_e, fr.RECV_RATE_ENTRY_DTYPE), h_e, "entries")
+    same(records(d_fl, fr.FLUSH_DTYPE), h_fl, "flushes")
+    same(records(d_fq, fr.FRAME_QUEUE_RESULT_DTYPE), np.concatenate(h_fq), "frame queue results")
+    same(records(d_rate, fr.RATE_RESULT_DTYPE), np.concatenate(h_rate), "rate results")
+    return np.concatenate(h_rate), np.concatenate(h_counts)
+
+
+def test_closed_loop_large_sets(engine):
+    """A second loop, 130 connections over 120 ticks of 2 to 9 ms with MARK_RATE_LIMITED on 80 % of the
+    connection-ticks: rate-limited feedback arrives faster than two RTTs pass, and the sets grow into their rooms of
+    24.  On the host run at least 5 % of the connection-ticks come in with more than 4 entries and the largest set
+    has at least 12 (measured with the host calls: 10.6 % and 21); nothing stops."""
+    rate, counts = run_closed_loop(engine, 130, 120, (9, (2, 10), 0.8))
+    assert (rate["stop"] == fr.RATE_DONE).all()
+    share, largest = float((counts > E.HELD).mean()), int(counts.max())
+    print(f"connection-ticks that come in with more than {E.HELD} entries: {share:.3f}; the largest set: {largest}")
+    assert share >= 0.05 and largest >= 12, (share, largest)
 
 
 def test_argument_checks(engine):

@@ -1,6 +1,7 @@
 """CPU: the batched send rate control on the host (ufc_rate_begin_host, ufc_rate_step_host; uflow_amd.frame's
 rate_begin_host and rate_step_host) against tests/rate_expect.py, SendRateComp and RecvRateSet restated from the
-reference, and the hand-traced cases of tests/golden/send_rate_cases.json.  Results, states (every double as its 64
+reference, the hand-traced cases of tests/golden/send_rate_cases.json, and rate_expect.set_cases(), the sets longer
+than the four entries a step holds in registers.  Results, states (every double as its 64
 bits), every entry of the arena and the gathered flushes are compared as bytes.  tests/test_gpu_rate.py runs the
 same comparisons with the device calls in the host calls' place."""
 import json
@@ -167,6 +168,55 @@ def test_random_batches_cover_every_outcome():
         stops += np.bincount(got["results"]["stop"], minlength=4)
         flags |= int(np.bitwise_or.reduce(got["results"]["flags"]))
     assert (stops > 0).all() and flags == 31, (stops, flags)
+
+
+# ---- sets past the entries a step holds in registers ----
+def test_set_cases():
+    """rate_expect.set_cases(): sets of more than kRateHeld = 4 entries, every case between two connections of one
+    entry whose rooms adjoin its own.  The facts are asserted on the restatement's output first; then the host calls
+    against it, bit for bit, serial and threaded, separate and in place."""
+    b = E.set_cases_between_neighbours()
+    assert len(b["index"]) == 17 and all(len(v) == 1 for v in b["index"].values())
+    for (c,) in b["index"].values():   # a neighbour's room on either side, but at the arena's ends
+        lo, cap = int(b["states"][c]["recv_first"]), int(b["states"][c]["recv_cap"])
+        beside = [k for k in (c - 1, c + 1) if int(b["states"][k]["recv_first"]) in (lo - 1, lo + cap)]
+        assert all(int(b["states"][k]["recv_cap"]) == 1 for k in (c - 1, c + 1)), c
+        assert len(beside) == (1 if lo + cap == len(b["entries"]) else 2), c
+    want = E.expect_step(b["states"], b["ticks"], b["fq"], b["entries"], None, None, b["flushes"], b["flush_index"])
+    E.check_set_facts(b, want)
+    seen = E.set_coverage(b, want)
+    assert seen["large_done"] == 15 and seen["full_large"] == 2 and seen["moved"] == 2 and seen["largest"] == 23, seen
+    one = check_step(b, gather_in=False)
+    many = check_step(b, gather_in=False, nthreads=16, in_place=True)
+    same(many["entries"], one["entries"], "entries")
+
+
+@pytest.mark.parametrize("recv_cap", [5, 8, 24])
+def test_random_states_large_sets(recv_cap):
+    """4 x 400 generated connections in rooms of 5, 8 and 24 entries, a fifth of them full: on the restatement's
+    side at least 100 DONE connections that came in with more than 4 entries, a RECV_FULL in such a room, and a
+    survivor carried from the part of the set read from memory into a held slot."""
+    rng = np.random.default_rng(200 + recv_cap)
+    seen = {}
+    for k in range(4):
+        b = E.random_batch(rng, 400, recv_cap=recv_cap, spoil=0.0, fill=0.2)
+        want = E.expect_step(b["states"], b["ticks"], b["fq"], b["entries"], b["flush_results"], b["result_index"],
+                             b["flushes"], b["flush_index"])
+        for key, v in E.set_coverage(b, want).items():
+            seen[key] = max(seen.get(key, 0), v) if key == "largest" else seen.get(key, 0) + v
+        check_step(b, in_place=bool(k & 1), nthreads=1 + 15 * (k >> 1))
+    assert seen["large_done"] >= 100 and seen["full_large"] >= 1 and seen["moved"] >= 1, seen
+    assert seen["largest"] == recv_cap, seen
+
+
+def test_fill_leaves_the_seeds_alone():
+    """fill = 0 draws nothing more: a seed's batch is what it was; and the filled connections are RECV_FULL."""
+    a = E.random_batch(np.random.default_rng(5), 50, recv_cap=3)
+    b = E.random_batch(np.random.default_rng(5), 50, recv_cap=3, fill=0.0)
+    assert all(a[k].tobytes() == b[k].tobytes() for k in a)
+    c = E.random_batch(np.random.default_rng(5), 50, recv_cap=3, spoil=0.0, fill=1.0)
+    want = E.expect_step(c["states"], c["ticks"], c["fq"], c["entries"])
+    assert (want["results"]["stop"] == fr.RATE_RECV_FULL).all()
 
 
 def bad_state_rules():

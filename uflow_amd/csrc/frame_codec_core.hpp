@@ -2254,7 +2254,8 @@ UFC_HD uint32_t rate_initial_send_rate(double rtt_s) {  // :110-112
   const double v = (double)kRateInitialWindow / rtt_s;
   return rate_f64_u32(v);
 }
-UFC_HD uint32_t rate_tcp_throughput(double rtt, double p) {  // :24-28
+// The equation's value before its cast (tests/c/float_paths_gpu.hip compares it as 64 bits).
+UFC_HD double rate_tcp_throughput_f64(double rtt, double p) {  // :24-28
 #pragma clang fp contract(off)
   const double s = (double)UFC_MAX_FRAME_SIZE;
   const double p2 = p * 2.0;
@@ -2272,8 +2273,9 @@ UFC_HD uint32_t rate_tcp_throughput(double rtt, double p) {  // :24-28
   const double f_p = r0 + t2;
   const double den = rtt * f_p;
   const double v = s / den;
-  return rate_f64_u32(v);
+  return v;
 }
+UFC_HD uint32_t rate_tcp_throughput(double rtt, double p) { return rate_f64_u32(rate_tcp_throughput_f64(rtt, p)); }
 // eval_tcp_throughput_inv (:30-59) with the stall rule of the header: a midpoint equal to an end of the interval
 // is returned where the reference would go round for ever.
 UFC_HD double rate_tcp_throughput_inv(double rtt, uint32_t target, uint32_t& iterations, bool& stalled) {
