@@ -48,6 +48,11 @@
  *                                 (resend_queue.rs), the pending queue (pending_queue.rs) and emit_data_frames
  *                                 (half_connection/mod.rs:335-432) around the emit and the pack, many connections per
  *                                 call, on the host and on the GPU
+ *   ufc_flush_acks_*, ufc_flush_sync_* (declared in uflow_flush_ctl.h, included at the end of this header)
+ *                              <- emit_ack_frames with push_dud and the FrameAckQueue deque's carry
+ *                                 (half_connection/mod.rs:296-333 over emit.rs:137-211), emit_sync_frame
+ *                                 (mod.rs:234-294) and the early returns of emit_frames (:217-232), many
+ *                                 connections per call, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -270,7 +275,7 @@ int ufc_build_batch_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const uf
  *   4. start a frame with this item (no size check: a datagram larger than a frame gets a frame of its own).
  * After the last item, finalize.  Finalize: emit the frame, frames += 1, alloc -= s.
  * The pack judges no field value (that stays UFC_BUILD_BAD_FIELD in the build); an ack flush with no groups
- * yields no frame (push_dud stays with the caller); a kind other than UFC_FRAME_ACK packs as data. */
+ * yields no frame (push_dud is ufc_flush_acks_*, uflow_flush_ctl.h); a kind other than UFC_FRAME_ACK packs as data. */
 typedef struct ufc_flush {        /* 24 bytes */
   int64_t  flush_alloc;           /* the emitter's flush_alloc in bytes; may be negative */
   uint32_t kind;                  /* UFC_FRAME_DATA or UFC_FRAME_ACK */
@@ -654,11 +659,12 @@ typedef struct ufc_frame_window_result { /* 40 bytes */
  *                      last output group, with has_tail = 1 if any group came out (else has_tail = 0 and the tail
  *                      fields as they came); sync_reply = the input OR'd with 1 if the range holds an ok sync frame;
  *                      size and the reserved fields copied.  tail_nonce is read as tail_nonce & 1.
- * A caller that flushed every group clears has_tail: the reference's empty deque then opens a new group even
- * within 32 ids of the old one.  After a SIZE_LIMITED ack flush the caller keeps the unpacked groups and leaves the
- * tail as it is.  Any 24 bytes are a state, and every input has one answer (size <= 2^31 is what makes the ids of one
- * group strictly increasing, so that the answer does not depend on the order in which a tile's lanes meet).  Ranges
- * of different connections must not overlap; where they do, the frame_accept of the shared frames is unspecified.
+ * A flush that sent every group clears has_tail: the reference's empty deque then opens a new group even
+ * within 32 ids of the old one.  After a SIZE_LIMITED ack flush the unpacked groups are kept and the tail is left
+ * as it is.  ufc_flush_acks_* (uflow_flush_ctl.h) does both, and clears sync_reply.  Any 24 bytes are a state, and
+ * every input has one answer (size <= 2^31 is what makes the ids of one group strictly increasing, so that the
+ * answer does not depend on the order in which a tile's lanes meet).  Ranges of different connections must not
+ * overlap; where they do, the frame_accept of the shared frames is unspecified.
  * n_frames and n_windows < 2^31 - 1; n_windows == 0 returns UFC_OK whatever the pointers; a NULL infos with
  * n_frames != 0, groups with groups_cap != 0, or a NULL frame_first, windows, windows_out, frame_accept, group_first,
  * groups_used or results is UFC_ERR_INVALID_ARG. */
@@ -833,7 +839,8 @@ int ufc_frame_queue_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, size_t n
  * writes them, `as u32` / `as u64` / `as isize` on a float saturate with NaN giving 0, f64::round is half away from
  * zero, f64::max returns the other operand for a NaN, and debug_assert!s do not exist.  MSS = UFC_MAX_FRAME_SIZE,
  * MINIMUM_RATE = MSS / 64 = 23, INITIAL_TCP_WINDOW = 4380.  PacketSender::acknowledge and the resend and pending
- * queues are ufc_resend_* below; the sync frame's decision (and push_dud) stay with the caller.
+ * queues are ufc_resend_* below; the sync frame's decision and push_dud are ufc_flush_sync_* and ufc_flush_acks_*
+ * (uflow_flush_ctl.h).
  *
  * A tick of a device-resident sender is queued calls with no host code between them:
  *   ufc_rate_begin_varlen -> ufc_frame_queue_varlen -> ufc_rate_step_varlen -> (emit) -> ufc_pack_varlen,
@@ -1243,5 +1250,9 @@ int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_resul
 #ifdef __cplusplus
 }
 #endif
+
+/* The batched flush control (ufc_flush_acks_*, ufc_flush_sync_*: the ack flush with dud and carry, the sync frame)
+ * is declared in its own header, which this one brings along. */
+#include "uflow_flush_ctl.h"
 
 #endif /* UFLOW_FRAME_CODEC_H */

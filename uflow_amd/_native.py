@@ -67,6 +67,10 @@ UFC_TX_RESEND = 1
 UFC_RS_NO_DATA_FLUSH = 1
 (UFC_RS_DONE, UFC_RS_SIZE_LIMITED, UFC_RS_WINDOW_LIMITED, UFC_RS_REF_HANG, UFC_RS_BAD_STATE, UFC_RS_STAGE_FULL,
  UFC_RS_HEAP_FULL) = range(7)
+# the batched flush control (include/uflow_flush_ctl.h): why an ack flush stopped, why no sync frame went out
+UFC_FA_DONE, UFC_FA_BAD_STATE, UFC_FA_CARRY_FULL = 0, 1, 2
+(UFC_FS_SENT, UFC_FS_ACK_LIMITED, UFC_FS_DATA_LIMITED, UFC_FS_UPSTREAM, UFC_FS_NOT_DUE, UFC_FS_IDLE,
+ UFC_FS_NO_ALLOC) = range(7)
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -100,6 +104,12 @@ _RS_PLACE_ARGS = [_V, _V, _Z, _V, _Z, _V, _V, _Z]
 _RS_COMMIT_ARGS = [_V, _V, _Z, _V, _V, _V, _Z, _V, _V, _Z, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _Z, _V, _Z,
                    _V, _Z, _V, _V, _V, _V, _V]
 _RATE_STEP_ARGS = [_V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _Z, _V, _V, _V]
+# ufc_flush_acks_*: ctl, windows, groups, n_groups, group_first, receivers, rate, n, carry, n_carry, merged, merged_cap,
+# merged_first, merged_used, infos, frames_cap, frames_used, results, ack_results, windows_out, ctl_out, flushes, flags
+_FLUSH_ACKS_ARGS = [_V, _V, _V, _Z, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, _Z, _V, _V, _V, _V, _V, _V, _V]
+# ufc_flush_sync_*: ctl, rate, ack_results, begin_results, pack_results, commit_results, queues, senders, n, infos,
+# syncs_cap, sync_index, syncs_used, results, ctl_out, ticks_next
+_FLUSH_SYNC_ARGS = [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _Z, _V, _V, _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -213,6 +223,14 @@ _SIGNATURES = {
     "ufc_resend_commit_varlen": (ctypes.c_int, [ctypes.c_void_p] + _RS_COMMIT_ARGS + [ctypes.c_void_p]),
 }
 SYMBOLS = tuple(_SIGNATURES)
+# include/uflow_flush_ctl.h: the batched flush control's symbols, bound with the others in lib().
+_FLUSH_SIGNATURES = {
+    "ufc_flush_acks_host": (_I, _FLUSH_ACKS_ARGS + [_I]),
+    "ufc_flush_acks_varlen": (_I, [_V] + _FLUSH_ACKS_ARGS + [_V]),
+    "ufc_flush_sync_host": (_I, _FLUSH_SYNC_ARGS + [_I]),
+    "ufc_flush_sync_varlen": (_I, [_V] + _FLUSH_SYNC_ARGS + [_V]),
+}
+FLUSH_SYMBOLS = tuple(_FLUSH_SIGNATURES)
 
 
 # Structs of include/uflow_frame_codec.h the Python side instantiates (layouts checked against the
@@ -264,7 +282,7 @@ def lib():
             raise ImportError(f"libuflowcrc.so not found at {LIB_PATH}: run `python -m uflow_amd._build` "
                               "(the native library is required; there is no CPU fallback)")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_FLUSH_SIGNATURES.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

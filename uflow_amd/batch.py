@@ -17,7 +17,8 @@ import torch
 
 from ._native import lib, check
 from .frame import _RS_ARENA_DTYPE
-from .records import (FLUSH_DTYPE, FLUSH_RESULT_DTYPE, FRAME_INFO_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_RESULT_DTYPE,
+from .records import (FLUSH_ACKS_RESULT_DTYPE, FLUSH_CTL_DTYPE, FLUSH_DTYPE, FLUSH_RESULT_DTYPE,
+                      FLUSH_SYNC_RESULT_DTYPE, FRAME_INFO_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_RESULT_DTYPE,
                       FRAME_QUEUE_STEP_DTYPE, FRAME_WINDOW_DTYPE, FRAME_WINDOW_RESULT_DTYPE, ITEM_DTYPE, PACKET_DTYPE,
                       PACKET_RESULT_DTYPE, RATE_RESULT_DTYPE, RATE_STATE_DTYPE, RATE_TICK_DTYPE, RECEIVER_DTYPE,
                       RECEIVER_RESULT_DTYPE, RECV_RATE_ENTRY_DTYPE, RESEND_COMMIT_RESULT_DTYPE, RESEND_DTYPE,
@@ -666,6 +667,93 @@ class FrameCrcEngine:
             _pn(results, n), _pn(states_out, n), _pn(retake, n), self._stream(stream)), "ufc_resend_commit_varlen")
         return {"results": results, "states_out": states_out, "retake": retake, "sent": sent, "sent_first": sent_first,
                 "next_extra_flags": next_extra_flags}
+
+    # ---- the flush control around the data flush, on the device (uflow_flush_ctl.h) ----
+    def flush_acks(self, ctl, windows, groups, group_first, receivers, rate, carry, merged_cap=None, frames_cap=None,
+                   flushes=None, flags=None, merged=None, infos=None, windows_out=None, ctl_out=None, stream=None):
+        """ufc_flush_acks_varlen: emit_ack_frames with push_dud and the deque carry (half_connection/mod.rs:296-333
+        over emit.rs:137-211) for every connection, behind frame_window and rate_step, in front of resend_begin.  ctl
+        rows[n] (FLUSH_CTL_DTYPE), windows rows[n], groups rows[n_groups] and group_first int64[n + 1] as frame_window
+        left them, receivers rows[n], rate rows[n] (rate_step's results), carry rows[n_carry] (ufc_item: the carry
+        arena, updated in place), flushes rows[n] (the data flushes) and flags int32[n] optional, in place.  Returns a
+        dict of device tensors: merged rows[merged_cap], merged_first int64[n + 1] (the ack flushes' flush_first),
+        merged_used int64[1], infos rows[frames_cap] (the ack frames: build_varlen takes them over merged),
+        frames_used int64[1], results rows[n] (FLUSH_RESULT_DTYPE), ack_results rows[n] (FLUSH_ACKS_RESULT_DTYPE),
+        windows_out, ctl_out (may be given as `windows`, `ctl`), carry, flushes, flags.  merged_cap defaults to n_carry
+        + n_groups and frames_cap to n + merged_cap, which are always enough."""
+        n, n_groups = ctl.shape[0], groups.shape[0]
+        self._rec("ctl", ctl, FLUSH_CTL_DTYPE, n)
+        self._rec("windows", windows, FRAME_WINDOW_DTYPE, n)
+        self._rec("groups", groups, ITEM_DTYPE, n_groups)
+        self._check("group_first", group_first, (torch.int64,), n + 1)
+        self._rec("receivers", receivers, RECEIVER_DTYPE, n)
+        self._rec("rate", rate, RATE_RESULT_DTYPE, n)
+        n_carry = self._rec("carry", carry, ITEM_DTYPE)
+        if merged_cap is None:
+            merged_cap = merged.shape[0] if merged is not None else n_carry + n_groups
+        merged_cap = int(merged_cap)
+        if frames_cap is None:
+            frames_cap = infos.shape[0] if infos is not None else n + merged_cap
+        frames_cap = int(frames_cap)
+        self._rec("merged", merged, ITEM_DTYPE, merged_cap)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, frames_cap)
+        self._rec("flushes", flushes, FLUSH_DTYPE, n)
+        self._check("flags", flags, (torch.int32, torch.uint32), n)
+        self._rec("windows_out", windows_out, FRAME_WINDOW_DTYPE, n)
+        self._rec("ctl_out", ctl_out, FLUSH_CTL_DTYPE, n)
+        with self._outputs(stream) as z:
+            merged, infos = z(merged, merged_cap, ITEM_DTYPE), z(infos, frames_cap, FRAME_INFO_DTYPE)
+            windows_out, ctl_out = z(windows_out, n, FRAME_WINDOW_DTYPE), z(ctl_out, n, FLUSH_CTL_DTYPE)
+            merged_first = z(None, n + 1, torch.int64)
+            results, ack_results = z(None, n, FLUSH_RESULT_DTYPE), z(None, n, FLUSH_ACKS_RESULT_DTYPE)
+            merged_used, frames_used = z(None, 1, torch.int64), z(None, 1, torch.int64)
+        check(lib().ufc_flush_acks_varlen(
+            self._ctx, _pn(ctl, n), _pn(windows, n), _pn(groups, n_groups), n_groups, _ptr(group_first),
+            _pn(receivers, n), _pn(rate, n), n, _pn(carry, n_carry), n_carry, _pn(merged, merged_cap), merged_cap,
+            _ptr(merged_first), _ptr(merged_used), _pn(infos, frames_cap), frames_cap, _ptr(frames_used),
+            _pn(results, n), _pn(ack_results, n), _pn(windows_out, n), _pn(ctl_out, n), _pn(flushes, n), _pn(flags, n),
+            self._stream(stream)), "ufc_flush_acks_varlen")
+        return {"merged": merged, "merged_first": merged_first, "merged_used": merged_used, "infos": infos,
+                "frames_used": frames_used, "results": results, "ack_results": ack_results, "windows_out": windows_out,
+                "ctl_out": ctl_out, "carry": carry, "flushes": flushes, "flags": flags}
+
+    def flush_sync(self, ctl, rate, ack_results, begin_results, pack_results, commit_results, queues, senders,
+                   syncs_cap=None, ticks_next=None, infos=None, ctl_out=None, stream=None):
+        """ufc_flush_sync_varlen: emit_sync_frame and emit_frames' early returns (half_connection/mod.rs:217-294) for
+        every connection, behind the data flush's last call.  ctl rows[n] (FLUSH_CTL_DTYPE), rate rows[n] (rate_step's
+        results), ack_results rows[n] (flush_acks' results, FLUSH_RESULT_DTYPE), begin_results rows[n], pack_results
+        rows[n] (the data pack's), commit_results rows[n], queues rows[n] (after this tick's frame_queue), senders
+        rows[n] (as the second emit left them), ticks_next rows[n] (RATE_TICK_DTYPE, optional: alloc_adjust = -14 or 0,
+        in place).  Returns a dict of device tensors: infos rows[syncs_cap] (the sync frames in connection order:
+        build_varlen takes them), sync_index int32[n] (-1: none), syncs_used int64[1], results rows[n]
+        (FLUSH_SYNC_RESULT_DTYPE), ctl_out (may be given as `ctl`), ticks_next.  syncs_cap defaults to n."""
+        n = ctl.shape[0]
+        self._rec("ctl", ctl, FLUSH_CTL_DTYPE, n)
+        self._rec("rate", rate, RATE_RESULT_DTYPE, n)
+        self._rec("ack_results", ack_results, FLUSH_RESULT_DTYPE, n)
+        self._rec("begin_results", begin_results, RESEND_RESULT_DTYPE, n)
+        self._rec("pack_results", pack_results, FLUSH_RESULT_DTYPE, n)
+        self._rec("commit_results", commit_results, RESEND_COMMIT_RESULT_DTYPE, n)
+        self._rec("queues", queues, FRAME_QUEUE_DTYPE, n)
+        self._rec("senders", senders, SENDER_DTYPE, n)
+        if syncs_cap is None:
+            syncs_cap = infos.shape[0] if infos is not None else n
+        syncs_cap = int(syncs_cap)
+        self._rec("infos", infos, FRAME_INFO_DTYPE, syncs_cap)
+        self._rec("ticks_next", ticks_next, RATE_TICK_DTYPE, n)
+        self._rec("ctl_out", ctl_out, FLUSH_CTL_DTYPE, n)
+        with self._outputs(stream) as z:
+            infos, ctl_out = z(infos, syncs_cap, FRAME_INFO_DTYPE), z(ctl_out, n, FLUSH_CTL_DTYPE)
+            sync_index = z(None, n, torch.int32)
+            results = z(None, n, FLUSH_SYNC_RESULT_DTYPE)
+            used = z(None, 1, torch.int64)
+        check(lib().ufc_flush_sync_varlen(
+            self._ctx, _pn(ctl, n), _pn(rate, n), _pn(ack_results, n), _pn(begin_results, n), _pn(pack_results, n),
+            _pn(commit_results, n), _pn(queues, n), _pn(senders, n), n, _pn(infos, syncs_cap), syncs_cap,
+            _pn(sync_index, n), _ptr(used), _pn(results, n), _pn(ctl_out, n), _pn(ticks_next, n),
+            self._stream(stream)), "ufc_flush_sync_varlen")
+        return {"infos": infos, "sync_index": sync_index, "syncs_used": used, "results": results, "ctl_out": ctl_out,
+                "ticks_next": ticks_next}
 
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):

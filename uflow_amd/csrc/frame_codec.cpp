@@ -774,4 +774,58 @@ int ufc_resend_commit_host(const ufc_flush_result* flush_results, const ufc_fram
   return UFC_OK;
 }
 
+// ---- batched host flush control ----
+int ufc_flush_acks_host(const ufc_flush_ctl* ctl, const ufc_frame_window* windows, const ufc_item* groups,
+                        size_t n_groups, const uint64_t* group_first, const ufc_receiver* receivers,
+                        const ufc_rate_result* rate, size_t n, ufc_item* carry, size_t n_carry, ufc_item* merged,
+                        size_t merged_cap, uint64_t* merged_first, uint64_t* merged_used, ufc_frame_info* infos,
+                        size_t frames_cap, uint64_t* frames_used, ufc_flush_result* results,
+                        ufc_flush_acks_result* ack_results, ufc_frame_window* windows_out, ufc_flush_ctl* ctl_out,
+                        ufc_flush* flushes, uint32_t* flags, int nthreads) {
+  if (n == 0) return UFC_OK;
+  const ufc_codec::FaArgs a{ctl, windows, groups, n_groups, group_first, receivers, rate, n, carry, n_carry, merged,
+                            merged_cap, merged_first, merged_used, infos, frames_cap, frames_used, results, ack_results,
+                            windows_out, ctl_out, flushes, flags};
+  if (!ufc_codec::fa_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  // Pass 1: every connection's merged and frame counts; then their exclusive sums; pass 2: the outputs.
+  std::vector<uint64_t> frame_first(n + 1);
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
+    for (size_t c = lo; c < hi; c++) {
+      const ufc_codec::FaPlan p = ufc_codec::fa_plan(a, c);
+      merged_first[c + 1] = p.merged;
+      frame_first[c + 1] = p.frames;
+    }
+  });
+  *merged_used = counts_to_firsts(merged_first, n);
+  *frames_used = counts_to_firsts(frame_first.data(), n);
+  for_ranges(n, nthreads, kStepGrain, [&](size_t lo, size_t hi) {
+    ufc_codec::FaWaveShared sh;
+    for (size_t c = lo; c < hi; c++) ufc_codec::fa_write(ufc_codec::SerialWave{}, sh, a, c, frame_first[c]);
+  });
+  return UFC_OK;
+}
+
+int ufc_flush_sync_host(const ufc_flush_ctl* ctl, const ufc_rate_result* rate, const ufc_flush_result* ack_results,
+                        const ufc_resend_result* begin_results, const ufc_flush_result* pack_results,
+                        const ufc_resend_commit_result* commit_results, const ufc_frame_queue* queues,
+                        const ufc_sender* senders, size_t n, ufc_frame_info* infos, size_t syncs_cap,
+                        uint32_t* sync_index, uint64_t* syncs_used, ufc_flush_sync_result* results,
+                        ufc_flush_ctl* ctl_out, ufc_rate_tick* ticks_next, int nthreads) {
+  if (n == 0) return UFC_OK;
+  const ufc_codec::FsArgs a{ctl, rate, ack_results, begin_results, pack_results, commit_results, queues, senders, n,
+                            infos, syncs_cap, sync_index, syncs_used, results, ctl_out, ticks_next};
+  if (!ufc_codec::fs_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  // The tiles the device gives a wave each: the decisions, the exclusive sum of their counts, the frames.
+  const size_t n_tiles = (n + 63) / 64;
+  std::vector<uint64_t> tile_first(n_tiles + 1);
+  for_ranges(n_tiles, nthreads, kRecordGrain / 64, [&](size_t lo, size_t hi) {
+    for (size_t t = lo; t < hi; t++) tile_first[t + 1] = ufc_codec::fs_decide_tile(ufc_codec::SerialWave{}, a, t);
+  });
+  *syncs_used = counts_to_firsts(tile_first.data(), n_tiles);
+  for_ranges(n_tiles, nthreads, kRecordGrain / 64, [&](size_t lo, size_t hi) {
+    for (size_t t = lo; t < hi; t++) ufc_codec::fs_write_tile(ufc_codec::SerialWave{}, a, t, tile_first[t]);
+  });
+  return UFC_OK;
+}
+
 }  // extern "C"

@@ -3,7 +3,8 @@
 // encode for the batched builds (frame_build.hip), the emitters' arithmetic for the batched packs
 // (frame_pack.hip), the packet sender's for the batched packet emits (packet_emit.hip), the packet receiver's
 // step for the batched packet receives (packet_receive.hip), the frame window's for the batched frame windows
-// (frame_window.hip) and the sender's frame queue's for the batched frame queues (frame_queue.hip).
+// (frame_window.hip), the sender's frame queue's for the batched frame queues (frame_queue.hip), the send rate
+// control's (send_rate.hip), the resend's (resend.hip) and the flush control's (flush_ctl.hip).
 //
 // Restates src/frame/serial/mod.rs:694-705 (dispatch on the frame id) and read_*_payload :54-434,
 // read_datagram :183-309.  A byte reader abstracts the frame: rd(i) = frame byte i (i < len).
@@ -3309,6 +3310,329 @@ inline __host__ __device__ void rs_commit(const Wv& wv, RsWaveShared& sh, const 
     if (a.next_extra_flags)
       a.next_extra_flags[c] = (a.next_extra_flags[c] & ~(uint32_t)UFC_FQ_MARK_RATE_LIMITED) |
                               (limited ? (uint32_t)UFC_FQ_MARK_RATE_LIMITED : 0u);
+  });
+}
+
+// ---- batched flush control (ufc_flush_acks_*, ufc_flush_sync_*) ----
+// The glue of HalfConnection::flush around the data flush: emit_ack_frames (half_connection/mod.rs:296-333 over
+// AckFrameEmitter, emit.rs:137-211, push_dud :149-166) with the deque carry of FrameAckQueue, and emit_sync_frame
+// (mod.rs:234-294) with the early returns of emit_frames (:217-232); the rules are in include/uflow_flush_ctl.h.
+// The ack flush is counted by a lane per connection (fa_plan: a loop over frames), and after the exclusive sums of
+// the group and frame counts written by a wave per connection with a lane per group (fa_write).  The sync decision
+// takes a lane per connection in tiles of 64 (fs_decide_tile), and after a scan over the tiles' ballot counts the
+// same tiles write the frames' records in connection order (fs_write_tile).
+struct FaArgs {
+  const ufc_flush_ctl* ctl;
+  const ufc_frame_window* windows;
+  const ufc_item* groups;
+  uint64_t n_groups;
+  const uint64_t* group_first;
+  const ufc_receiver* receivers;
+  const ufc_rate_result* rate;
+  uint64_t n;
+  ufc_item* carry;
+  uint64_t n_carry;
+  ufc_item* merged;
+  uint64_t merged_cap;
+  uint64_t* merged_first;
+  uint64_t* merged_used;
+  ufc_frame_info* infos;
+  uint64_t frames_cap;
+  uint64_t* frames_used;
+  ufc_flush_result* results;
+  ufc_flush_acks_result* ack_results;
+  ufc_frame_window* windows_out;
+  ufc_flush_ctl* ctl_out;
+  ufc_flush* flushes;
+  uint32_t* flags;
+};
+// (The n + 1 group and frame counts are scanned with a 32-bit count; n_groups + n_carry < 2^32 keeps every merged
+// count and every index into `merged` inside 32 bits.)
+inline bool fa_args_ok(const FaArgs& a) {
+  const bool bad = !a.ctl || !a.windows || !a.group_first || !a.receivers || !a.rate || !a.merged_first ||
+                   !a.merged_used || !a.frames_used || !a.results || !a.ack_results || !a.windows_out || !a.ctl_out ||
+                   (!a.groups && a.n_groups) || (!a.carry && a.n_carry) || (!a.merged && a.merged_cap) ||
+                   (!a.infos && a.frames_cap) || a.n >= kCountLim || a.n_groups >= kCountLim || a.n_carry >= kCountLim;
+  return !bad;
+}
+
+// What one connection's ack flush comes to: the merged list's length, and the emitter's run over it.
+struct FaPlan {
+  bool ok;           // false: BAD_STATE
+  bool dud;          // push_dud opened the first frame
+  uint32_t skip;     // carry groups in front of the window's (carry_count - 1, or 0)
+  uint64_t g0;       // the window's first group
+  uint32_t merged;   // groups in the merged list
+  uint32_t frames, packed, stop;
+  int64_t alloc_left;
+};
+// AckFrameEmitter over n groups of 9 bytes, frame by frame (emit.rs:170-211; steps 1, 2 and 4 of the ufc_flush
+// comment with H = 15, e = 9, no count limit), behind an optional push_dud.  While a frame is in progress alloc
+// stands still and its size grows by 9 a group, so the groups it takes are the least of what is left, what fits the
+// frame, and the pushes that pass `alloc - size >= 0`.
+UFC_HD void fa_pack(FaPlan& p, int64_t alloc, bool sync_reply, uint64_t n) {
+  uint64_t s = 0, i = 0;
+  p.frames = 0;
+  p.stop = UFC_PACK_DONE;
+  p.dud = false;
+  if (sync_reply) {  // push_dud, emit.rs:149-166
+    if (alloc < 0) {
+      p.packed = 0;
+      p.stop = UFC_PACK_SIZE_LIMITED;
+      p.alloc_left = alloc;
+      return;
+    }
+    p.dud = true;
+    s = kAckFrameOverhead;
+  }
+  while (i < n) {
+    if (s == 0) {  // :190-202
+      if (alloc < 0) {
+        p.stop = UFC_PACK_SIZE_LIMITED;
+        break;
+      }
+      s = kAckFrameOverhead + UFC_ACK_GROUP_SIZE;
+      i++;
+    }
+    const uint64_t k_size = (kMaxFrameSize - s) / UFC_ACK_GROUP_SIZE;
+    const uint64_t k_alloc = alloc >= (int64_t)s ? (uint64_t)(alloc - (int64_t)s) / UFC_ACK_GROUP_SIZE + 1 : 0;
+    uint64_t k = n - i;
+    if (k > k_size) k = k_size;
+    if (k > k_alloc) k = k_alloc;
+    i += k;
+    s += k * UFC_ACK_GROUP_SIZE;
+    if (i == n) break;
+    // the push of group i does not go into this frame: finalize (:176-182)
+    p.frames++;
+    alloc = (int64_t)((uint64_t)alloc - s);
+    s = 0;
+    if (k == k_alloc) {  // it was the allocation that refused it
+      p.stop = UFC_PACK_SIZE_LIMITED;
+      break;
+    }
+  }
+  if (s) {  // finalize (:205-211)
+    p.frames++;
+    alloc = (int64_t)((uint64_t)alloc - s);
+  }
+  p.packed = (uint32_t)i;
+  p.alloc_left = alloc;
+}
+UFC_HD FaPlan fa_plan(const FaArgs& a, uint64_t c) {
+  const ufc_flush_ctl& C = a.ctl[c];
+  const uint64_t g0 = a.group_first[c], g1 = a.group_first[c + 1];
+  const uint32_t cc = C.carry_count;
+  FaPlan p{};
+  p.g0 = g0;
+  p.alloc_left = a.rate[c].flush_alloc;
+  p.stop = UFC_PACK_BAD_RANGE;
+  p.ok = g0 <= g1 && g1 <= a.n_groups && cc <= C.carry_cap && rs_region_ok(C.carry_first, C.carry_cap, a.n_carry);
+  // The window writes the carried tail first, as updated: the carry's own copy of it is dropped.
+  if (p.ok && cc) p.ok = g1 > g0 && a.groups[g0].id == a.carry[C.carry_first + cc - 1].id;
+  if (!p.ok) return p;
+  p.skip = cc ? cc - 1 : 0;
+  p.merged = p.skip + (uint32_t)(g1 - g0);
+  fa_pack(p, a.rate[c].flush_alloc, a.windows[c].sync_reply != 0, p.merged);
+  return p;
+}
+
+struct FaWaveShared {
+  ufc_item tile[64];
+};
+// Frame k of a flush holds the groups [k * kAckFrameMaxGroups ..) of its merged list: every frame but the last is
+// full, with or without a dud in front (a dud frame that takes no group is the flush's only one).
+template <class Wv>
+inline __host__ __device__ void fa_write(const Wv& wv, FaWaveShared& sh, const FaArgs& a, uint64_t c, uint64_t ffirst) {
+  // (read in place: the outputs, which may be the inputs, are written last, behind every read)
+  const ufc_flush_ctl C = a.ctl[c];
+  const ufc_frame_window W = a.windows[c];
+  const FaPlan p = fa_plan(a, c);
+  const uint64_t mfirst = a.merged_first[c];
+  const uint32_t id0 = W.base_id, id1 = a.receivers[c].base_id;
+  const uint32_t left = p.merged - p.packed;                    // the groups no frame took
+  const uint32_t kept = left < C.carry_cap ? left : C.carry_cap;  // the newest of them stay
+  const uint32_t from = p.merged - kept;
+  for (uint64_t t = 0; t < p.merged; t += 64) {
+    wv.lanes([&](uint32_t lane) {
+      const uint64_t j = t + lane;
+      if (j < p.merged) sh.tile[lane] = j < p.skip ? a.carry[C.carry_first + j] : a.groups[p.g0 + (j - p.skip)];
+    });
+    wv.lanes([&](uint32_t lane) {
+      const uint64_t j = t + lane;
+      if (j >= p.merged) return;
+      if (mfirst + j < a.merged_cap) a.merged[mfirst + j] = sh.tile[lane];
+      if (j >= from) a.carry[C.carry_first + (j - from)] = sh.tile[lane];  // (j - from <= j: no later tile reads it)
+    });
+  }
+  for (uint64_t t = 0; t < p.frames; t += 64)
+    wv.lanes([&](uint32_t lane) {
+      const uint64_t k = t + lane;
+      if (k >= p.frames || ffirst + k >= a.frames_cap) return;
+      const uint64_t first = k * kAckFrameMaxGroups;
+      const uint64_t cnt = p.packed > first ? p.packed - first : 0;
+      ufc_frame_info info{};
+      info.kind = UFC_FRAME_ACK;
+      info.ok = 1;
+      info.f[0] = id0;
+      info.f[1] = id1;
+      info.item_count = cnt < kAckFrameMaxGroups ? (uint32_t)cnt : kAckFrameMaxGroups;
+      info.item_first = (uint32_t)(mfirst + first);
+      a.infos[ffirst + k] = info;
+    });
+  wv.one([&] {
+    ufc_flush_result res{};
+    res.frame_first = (uint32_t)ffirst;
+    res.frame_count = p.frames;
+    res.items_packed = p.packed;
+    res.stop = p.stop;
+    res.alloc_left = p.alloc_left;
+    a.results[c] = res;
+    ufc_flush_acks_result ar{};
+    ar.stop = !p.ok ? UFC_FA_BAD_STATE : left > kept ? UFC_FA_CARRY_FULL : UFC_FA_DONE;
+    ar.merged_first = (uint32_t)mfirst;
+    ar.merged_count = p.merged;
+    ar.carried = p.ok ? kept : 0;
+    ar.dropped = left - kept;
+    ar.dud = p.dud ? 1 : 0;
+    a.ack_results[c] = ar;
+    ufc_frame_window O = W;
+    ufc_flush_ctl K = C;
+    if (p.ok) {
+      if (p.frames) O.sync_reply = 0;           // emit_cb, mod.rs:306-310
+      if (p.packed == p.merged) O.has_tail = 0;  // the deque is empty
+      K.carry_count = kept;
+    }
+    a.windows_out[c] = O;
+    a.ctl_out[c] = K;
+    if (a.flushes) a.flushes[c].flush_alloc = p.alloc_left;
+    if (a.flags)
+      a.flags[c] = (a.flags[c] & ~(uint32_t)UFC_RS_NO_DATA_FLUSH) |
+                   (p.stop == UFC_PACK_SIZE_LIMITED ? (uint32_t)UFC_RS_NO_DATA_FLUSH : 0u);
+  });
+}
+
+struct FsArgs {
+  const ufc_flush_ctl* ctl;
+  const ufc_rate_result* rate;
+  const ufc_flush_result* ack_results;
+  const ufc_resend_result* begin_results;
+  const ufc_flush_result* pack_results;
+  const ufc_resend_commit_result* commit_results;
+  const ufc_frame_queue* queues;
+  const ufc_sender* senders;
+  uint64_t n;
+  ufc_frame_info* infos;
+  uint64_t syncs_cap;
+  uint32_t* sync_index;
+  uint64_t* syncs_used;
+  ufc_flush_sync_result* results;
+  ufc_flush_ctl* ctl_out;
+  ufc_rate_tick* ticks_next;
+};
+inline bool fs_args_ok(const FsArgs& a) {
+  const bool bad = !a.ctl || !a.rate || !a.ack_results || !a.begin_results || !a.pack_results || !a.commit_results ||
+                   !a.queues || !a.senders || !a.sync_index || !a.syncs_used || !a.results || !a.ctl_out ||
+                   (!a.infos && a.syncs_cap) || a.n >= kCountLim;
+  return !bad;
+}
+constexpr uint64_t kMinSyncTimeoutMs = 2000;  // MIN_SYNC_TIMEOUT_MS
+constexpr int64_t kSyncFrameSize = 14;        // write_sync: id, mode, two ids, trailer
+
+// The ids a sync frame of connection c would carry: bit 0 / f0 next_frame_id (mod.rs:244-249), bit 1 / f1
+// next_packet_id (:257-263).
+UFC_HD uint32_t fs_ids(const FsArgs& a, uint64_t c, uint32_t& f0, uint32_t& f1) {
+  const ufc_frame_queue& Q = a.queues[c];
+  const ufc_sender& S = a.senders[c];
+  const ufc_resend_commit_result& M = a.commit_results[c];
+  const uint32_t next_frame = Q.log_next_id + a.pack_results[c].frame_count;
+  uint32_t mode = 0;
+  f0 = f1 = 0;
+  if (next_frame != Q.window_base_id) {
+    mode |= 1;
+    f0 = next_frame;
+  }
+  if (S.next_id != S.base_id && M.heap_len == 0 && M.pending_count == 0) {
+    mode |= 2;
+    f1 = S.next_id;
+  }
+  return mode;
+}
+// emit_frames behind emit_ack_frames for one connection (rules 1-10 of the header); returns whether a frame goes out.
+UFC_HD bool fs_decide(const FsArgs& a, uint64_t c) {
+  ufc_flush_ctl C = a.ctl[c];
+  const ufc_rate_result& R = a.rate[c];
+  const ufc_flush_result& P = a.pack_results[c];
+  const ufc_resend_commit_result& M = a.commit_results[c];
+  const uint32_t bstop = a.begin_results[c].stop;
+  ufc_flush_sync_result res{};
+  res.heap_len = M.heap_len;
+  res.pending_count = M.pending_count;
+  res.is_send_pending = (M.heap_len != 0 || M.pending_count != 0) ? 1 : 0;
+  uint32_t reason;
+  if (a.ack_results[c].stop == UFC_PACK_SIZE_LIMITED) {
+    reason = UFC_FS_ACK_LIMITED;  // mod.rs:218-221
+  } else {
+    if (P.frame_count) C.sync_timeout_base_ms = R.now_ms;  // emit_cb of emit_data_frames, :342-347
+    const uint64_t elapsed = R.now_ms - C.sync_timeout_base_ms;
+    uint32_t f0, f1;
+    if (bstop == UFC_RS_SIZE_LIMITED || P.stop == UFC_PACK_SIZE_LIMITED) {
+      reason = UFC_FS_DATA_LIMITED;  // :223-226
+    } else if (bstop == UFC_RS_REF_HANG || bstop == UFC_RS_BAD_STATE || M.stop == UFC_RS_REF_HANG ||
+               M.stop == UFC_RS_BAD_STATE || M.stop == UFC_RS_HEAP_FULL) {
+      reason = UFC_FS_UPSTREAM;
+    } else if (elapsed < (R.rto_ms > kMinSyncTimeoutMs ? R.rto_ms : kMinSyncTimeoutMs)) {
+      reason = UFC_FS_NOT_DUE;  // :235-238
+    } else if ((res.mode = (uint8_t)fs_ids(a, c, f0, f1)) == 0 &&
+               (!C.has_keepalive || elapsed < C.keepalive_interval_ms)) {
+      reason = UFC_FS_IDLE;  // :269-277
+    } else if (P.alloc_left < 0) {
+      reason = UFC_FS_NO_ALLOC;  // :279-281
+    } else {
+      reason = UFC_FS_SENT;
+      C.sync_timeout_base_ms = R.now_ms;  // :290
+    }
+  }
+  C.has_keepalive = C.has_keepalive ? 1 : 0;
+  if (!C.has_keepalive) C.keepalive_interval_ms = 0;
+  res.reason = reason;
+  res.sent = reason == UFC_FS_SENT ? 1 : 0;
+  if (!res.sent) res.mode = 0;
+  a.results[c] = res;
+  a.ctl_out[c] = C;
+  if (a.ticks_next) a.ticks_next[c].alloc_adjust = res.sent ? -kSyncFrameSize : 0;
+  return res.sent != 0;
+}
+// Connections [64 tile, 64 tile + 64): the decisions, a lane each; returns how many send a frame.
+template <class Wv>
+inline __host__ __device__ uint32_t fs_decide_tile(const Wv& wv, const FsArgs& a, uint64_t tile) {
+  return popc(wv.ballot([&](uint32_t lane) {
+    const uint64_t c = tile * 64 + lane;
+    return c < a.n && fs_decide(a, c);
+  }));
+}
+// The same tile behind the scan: `first` frames went out in the tiles before it.  The ballot over results[].sent is
+// the stage's one cross-lane read: a sending lane's frame index is `first` + the sending lanes below it.
+template <class Wv>
+inline __host__ __device__ void fs_write_tile(const Wv& wv, const FsArgs& a, uint64_t tile, uint64_t first) {
+  const unsigned long long m = wv.ballot([&](uint32_t lane) {
+    const uint64_t c = tile * 64 + lane;
+    return c < a.n && a.results[c].sent != 0;
+  });
+  wv.lanes([&](uint32_t lane) {
+    const uint64_t c = tile * 64 + lane;
+    if (c >= a.n) return;
+    if (!((m >> lane) & 1)) {
+      a.sync_index[c] = UFC_NO_PARENT;
+      return;
+    }
+    const uint64_t at = first + popc(m & ((1ull << lane) - 1));
+    a.sync_index[c] = (uint32_t)at;
+    if (at >= a.syncs_cap) return;
+    ufc_frame_info info{};
+    info.kind = UFC_FRAME_SYNC;
+    info.ok = 1;
+    info.aux = (uint8_t)fs_ids(a, c, info.f[0], info.f[1]);
+    a.infos[at] = info;
   });
 }
 

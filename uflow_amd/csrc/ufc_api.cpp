@@ -22,6 +22,7 @@
 #include "frame_parse.hpp"
 #include "frame_queue.hpp"
 #include "frame_window.hpp"
+#include "flush_ctl.hpp"
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
 #include "resend.hpp"
@@ -81,7 +82,9 @@ enum ScratchKind {
   kScratchPack = 7,
   kScratchEmit = 8,
   kScratchReceive = 9,
-  kScratchWindow = 10
+  kScratchWindow = 10,
+  kScratchFlushAcks = 11,
+  kScratchFlushSync = 12
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -1127,6 +1130,48 @@ int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_resul
   DeviceGuard g(ctx->device);
   hipError_t e;
   if ((e = ufc_dev::resend_commit_batch(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched flush control (flush_ctl.hip) ----
+int ufc_flush_acks_varlen(ufc_ctx* ctx, const ufc_flush_ctl* d_ctl, const ufc_frame_window* d_windows,
+                          const ufc_item* d_groups, size_t n_groups, const uint64_t* d_group_first,
+                          const ufc_receiver* d_receivers, const ufc_rate_result* d_rate, size_t n, ufc_item* d_carry,
+                          size_t n_carry, ufc_item* d_merged, size_t merged_cap, uint64_t* d_merged_first,
+                          uint64_t* d_merged_used, ufc_frame_info* d_infos, size_t frames_cap, uint64_t* d_frames_used,
+                          ufc_flush_result* d_results, ufc_flush_acks_result* d_ack_results,
+                          ufc_frame_window* d_windows_out, ufc_flush_ctl* d_ctl_out, ufc_flush* d_flushes,
+                          uint32_t* d_flags, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  const ufc_codec::FaArgs a{d_ctl, d_windows, d_groups, n_groups, d_group_first, d_receivers, d_rate, n, d_carry, n_carry,
+                            d_merged, merged_cap, d_merged_first, d_merged_used, d_infos, frames_cap, d_frames_used,
+                            d_results, d_ack_results, d_windows_out, d_ctl_out, d_flushes, d_flags};
+  if (!ufc_codec::fa_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  if ((e = ufc_dev::flush_acks_batch(a, {ctx, kScratchFlushAcks, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+int ufc_flush_sync_varlen(ufc_ctx* ctx, const ufc_flush_ctl* d_ctl, const ufc_rate_result* d_rate,
+                          const ufc_flush_result* d_ack_results, const ufc_resend_result* d_begin_results,
+                          const ufc_flush_result* d_pack_results, const ufc_resend_commit_result* d_commit_results,
+                          const ufc_frame_queue* d_queues, const ufc_sender* d_senders, size_t n,
+                          ufc_frame_info* d_infos, size_t syncs_cap, uint32_t* d_sync_index, uint64_t* d_syncs_used,
+                          ufc_flush_sync_result* d_results, ufc_flush_ctl* d_ctl_out, ufc_rate_tick* d_ticks_next,
+                          void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  if (n == 0) return UFC_OK;
+  const ufc_codec::FsArgs a{d_ctl, d_rate, d_ack_results, d_begin_results, d_pack_results, d_commit_results, d_queues,
+                            d_senders, n, d_infos, syncs_cap, d_sync_index, d_syncs_used, d_results, d_ctl_out,
+                            d_ticks_next};
+  if (!ufc_codec::fs_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  if ((e = ufc_dev::flush_sync_batch(a, {ctx, kScratchFlushSync, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
   return UFC_OK;
 }
 

@@ -1,4 +1,4 @@
-"""The record layouts of include/uflow_frame_codec.h, declared once for Python.
+"""The record layouts of include/uflow_frame_codec.h and include/uflow_flush_ctl.h, declared once for Python.
 
 Every batched call takes and returns arrays of these records: numpy structured arrays on the host
 (uflow_amd.frame), uint8[n, itemsize] rows on the device (uflow_amd.batch.rows / records).  FOO_BAR_DTYPE is the C
@@ -109,3 +109,17 @@ RESEND_COMMIT_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("pending_packed", "<u4"
 
 # C struct name -> dtype (ufc_item -> ITEM_DTYPE, ...).
 RECORDS = {"ufc_" + k[:-len("_DTYPE")].lower(): v for k, v in list(globals().items()) if k.endswith("_DTYPE")}
+
+# include/uflow_flush_ctl.h, the header of the batched flush control, has a table of its own (tests/test_flush_cpu.py
+# holds it to that header as tests/test_records_cpu.py holds RECORDS to uflow_frame_codec.h).
+# ufc_flush_ctl / ufc_flush_acks_result / ufc_flush_sync_result (batched flush control)
+FLUSH_CTL_DTYPE = np.dtype([("sync_timeout_base_ms", "<u8"), ("keepalive_interval_ms", "<u8"), ("carry_first", "<u8"),
+                            ("carry_cap", "<u4"), ("carry_count", "<u4"), ("has_keepalive", "u1"), ("reserved0", "u1"),
+                            ("reserved1", "<u2"), ("reserved2", "<u4")])
+FLUSH_ACKS_RESULT_DTYPE = np.dtype([("stop", "<u4"), ("merged_first", "<u4"), ("merged_count", "<u4"), ("carried", "<u4"),
+                                    ("dropped", "<u4"), ("dud", "u1"), ("reserved", "u1", (3,))])
+FLUSH_SYNC_RESULT_DTYPE = np.dtype([("sent", "<u4"), ("reason", "<u4"), ("heap_len", "<u4"), ("pending_count", "<u4"),
+                                    ("mode", "u1"), ("is_send_pending", "u1"), ("reserved", "<u2"),
+                                    ("reserved2", "<u4")])
+FLUSH_RECORDS = {"ufc_flush_ctl": FLUSH_CTL_DTYPE, "ufc_flush_acks_result": FLUSH_ACKS_RESULT_DTYPE,
+                 "ufc_flush_sync_result": FLUSH_SYNC_RESULT_DTYPE}
