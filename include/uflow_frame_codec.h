@@ -53,6 +53,11 @@
  *                                 (half_connection/mod.rs:296-333 over emit.rs:137-211), emit_sync_frame
  *                                 (mod.rs:234-294) and the early returns of emit_frames (:217-232), many
  *                                 connections per call, on the host and on the GPU
+ *   ufc_route_table_build_host, ufc_route_frames_* (declared in uflow_route.h, included at the end of this header)
+ *                              <- the address lookup and dispatch of Server::handle_frames (src/server/mod.rs:
+ *                                 591-602 over :492-589, clients: HashMap<SocketAddr, ..> :118) and of
+ *                                 Client::handle_frames (src/client/mod.rs:557-583) for State::Active clients:
+ *                                 the parse's frames grouped by connection, on the host and on the GPU
  *   ufc_datagram_is_valid, UFC_ITEM_VALID
  *                              <- src/half_connection/packet_receiver/mod.rs:12-30 `datagram_is_valid`,
  *                                 applied by handle_datagram (:147-150) to every received datagram
@@ -1254,5 +1259,9 @@ int ufc_resend_commit_varlen(ufc_ctx* ctx, const ufc_flush_result* d_flush_resul
 /* The batched flush control (ufc_flush_acks_*, ufc_flush_sync_*: the ack flush with dud and carry, the sync frame)
  * is declared in its own header, which this one brings along. */
 #include "uflow_flush_ctl.h"
+
+/* The batched frame routing (ufc_route_table_build_host, ufc_route_frames_*: a frame's source address to its
+ * connection, the batch grouped by connection) is declared in its own header as well. */
+#include "uflow_route.h"
 
 #endif /* UFLOW_FRAME_CODEC_H */

@@ -13,11 +13,12 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libuflowcrc.so")
 SOURCES = ["frame_crc.hip", "frame_crc_varlen8.hip", "frame_parse.hip", "frame_build.hip", "frame_pack.hip",
            "packet_emit.hip", "packet_receive.hip", "frame_window.hip", "frame_queue.hip", "send_rate.hip", "resend.hip",
-           "flush_ctl.hip", "hbm_probe.hip", "ufc_api.cpp", "ufc_shard.cpp", "crc_math.cpp", "frame_codec.cpp"]
+           "flush_ctl.hip", "route.hip", "hbm_probe.hip", "ufc_api.cpp", "ufc_shard.cpp", "crc_math.cpp",
+           "frame_codec.cpp"]
 HEADERS = ["frame_crc_dev.hpp", "frame_crc_kernels.hpp", "crc_math.hpp", "frame_codec_core.hpp", "frame_parse.hpp",
            "frame_parse_plan.hpp", "frame_build.hpp", "frame_build_piece.hpp", "frame_pack.hpp", "packet_emit.hpp",
            "packet_receive.hpp", "frame_window.hpp", "frame_queue.hpp", "send_rate.hpp", "resend.hpp", "flush_ctl.hpp",
-           "ufc_internal.hpp", "wave.hpp", "wave_dev.hpp", "scratch.hpp", "scan.hpp"]
+           "route.hpp", "ufc_internal.hpp", "wave.hpp", "wave_dev.hpp", "scratch.hpp", "scan.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -65,7 +66,8 @@ def _native_identity(defines=()):
     """(sources, hipcc flags, digest) of a native build from the sources in this tree."""
     sources = list(SOURCES)
     deps = [os.path.join(CSRC, s) for s in sources + HEADERS]
-    deps += [os.path.join(REPO_DIR, "include", h) for h in ("uflow_frame_crc.h", "uflow_frame_codec.h", "uflow_flush_ctl.h")]
+    deps += [os.path.join(REPO_DIR, "include", h)
+             for h in ("uflow_frame_crc.h", "uflow_frame_codec.h", "uflow_flush_ctl.h", "uflow_route.h")]
     # No atomic optimizer: the lean kernel's single-lane claim atomics must stay plain
     # global_atomic_add (the optimizer reads the result back at once, forcing a vmcnt(0) wait).
     flags = [HIPCC, "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall",

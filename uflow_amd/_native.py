@@ -71,6 +71,8 @@ UFC_RS_NO_DATA_FLUSH = 1
 UFC_FA_DONE, UFC_FA_BAD_STATE, UFC_FA_CARRY_FULL = 0, 1, 2
 (UFC_FS_SENT, UFC_FS_ACK_LIMITED, UFC_FS_DATA_LIMITED, UFC_FS_UPSTREAM, UFC_FS_NOT_DUE, UFC_FS_IDLE,
  UFC_FS_NO_ALLOC) = range(7)
+# the batched frame routing (include/uflow_route.h): a frame's class
+UFC_ROUTE_DROP, UFC_ROUTE_CONN, UFC_ROUTE_CONTROL, UFC_ROUTE_DEFERRED = range(4)
 
 # Every symbol the header declares, with its ctypes signature.
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -110,6 +112,11 @@ _FLUSH_ACKS_ARGS = [_V, _V, _V, _Z, _V, _V, _V, _Z, _V, _Z, _V, _Z, _V, _V, _V, 
 # ufc_flush_sync_*: ctl, rate, ack_results, begin_results, pack_results, commit_results, queues, senders, n, infos,
 # syncs_cap, sync_index, syncs_used, results, ctl_out, ticks_next
 _FLUSH_SYNC_ARGS = [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _Z, _V, _V, _V, _V, _V]
+# ufc_route_frames_*: infos, addrs, offsets, n, slots, n_slots, seed, max_probe, n_conns, conn_active, now_ms,
+# active_timeout_ms, timeout_in, route, cls, bucket_first, order, infos_out, src_base_out, results, timeout_out,
+# first_unknown_control
+_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
+_ROUTE_ARGS = [_V, _V, _V, _Z, _V, _Z, _U32, _U32, _Z, _V, _U64, _U64, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]
 _SIGNATURES = {
     "ufc_crc32_compute": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t]),
     "ufc_crc32_extend": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
@@ -231,6 +238,14 @@ _FLUSH_SIGNATURES = {
     "ufc_flush_sync_varlen": (_I, [_V] + _FLUSH_SYNC_ARGS + [_V]),
 }
 FLUSH_SYMBOLS = tuple(_FLUSH_SIGNATURES)
+# include/uflow_route.h: the batched frame routing's symbols, bound with the others in lib().
+_ROUTE_SIGNATURES = {
+    # addrs, n_conns, seed, slots, n_slots, max_probe, dup_index
+    "ufc_route_table_build_host": (_I, [_V, _Z, _U32, _V, _Z, _V, _V]),
+    "ufc_route_frames_host": (_I, _ROUTE_ARGS + [_I]),
+    "ufc_route_frames_varlen": (_I, [_V] + _ROUTE_ARGS + [_V]),
+}
+ROUTE_SYMBOLS = tuple(_ROUTE_SIGNATURES)
 
 
 # Structs of include/uflow_frame_codec.h the Python side instantiates (layouts checked against the
@@ -282,7 +297,8 @@ def lib():
             raise ImportError(f"libuflowcrc.so not found at {LIB_PATH}: run `python -m uflow_amd._build` "
                               "(the native library is required; there is no CPU fallback)")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_FLUSH_SIGNATURES.items()):
+        for name, (res, args) in (list(_SIGNATURES.items()) + list(_FLUSH_SIGNATURES.items()) +
+                                   list(_ROUTE_SIGNATURES.items())):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

@@ -17,13 +17,13 @@ import torch
 
 from ._native import lib, check
 from .frame import _RS_ARENA_DTYPE
-from .records import (FLUSH_ACKS_RESULT_DTYPE, FLUSH_CTL_DTYPE, FLUSH_DTYPE, FLUSH_RESULT_DTYPE,
+from .records import (ADDR_DTYPE, FLUSH_ACKS_RESULT_DTYPE, FLUSH_CTL_DTYPE, FLUSH_DTYPE, FLUSH_RESULT_DTYPE,
                       FLUSH_SYNC_RESULT_DTYPE, FRAME_INFO_DTYPE, FRAME_QUEUE_DTYPE, FRAME_QUEUE_RESULT_DTYPE,
                       FRAME_QUEUE_STEP_DTYPE, FRAME_WINDOW_DTYPE, FRAME_WINDOW_RESULT_DTYPE, ITEM_DTYPE, PACKET_DTYPE,
                       PACKET_RESULT_DTYPE, RATE_RESULT_DTYPE, RATE_STATE_DTYPE, RATE_TICK_DTYPE, RECEIVER_DTYPE,
                       RECEIVER_RESULT_DTYPE, RECV_RATE_ENTRY_DTYPE, RESEND_COMMIT_RESULT_DTYPE, RESEND_DTYPE,
-                      RESEND_RESULT_DTYPE, RX_PACKET_DTYPE, RX_SLOT_DTYPE, SENDER_DTYPE, SENDER_RESULT_DTYPE,
-                      SENT_FRAME_DTYPE)
+                      RESEND_RESULT_DTYPE, ROUTE_RESULT_DTYPE, ROUTE_SLOT_DTYPE, RX_PACKET_DTYPE, RX_SLOT_DTYPE,
+                      SENDER_DTYPE, SENDER_RESULT_DTYPE, SENT_FRAME_DTYPE)
 
 
 # Items of a flush whose frame chain one wave of the pack resolves in LDS at a time (kPackTile, csrc/frame_pack.hpp).
@@ -754,6 +754,46 @@ class FrameCrcEngine:
             self._stream(stream)), "ufc_flush_sync_varlen")
         return {"infos": infos, "sync_index": sync_index, "syncs_used": used, "results": results, "ctl_out": ctl_out,
                 "ticks_next": ticks_next}
+
+    # ---- the frame routing in front of the frame window, on the device (uflow_route.h) ----
+    def route_frames(self, infos, addrs, offsets, slots, seed, max_probe, conn_active, now_ms, active_timeout_ms,
+                     timeout_in, infos_out=None, src_base_out=None, timeout_out=None, stream=None):
+        """ufc_route_frames_varlen: the address lookup and dispatch of Server::handle_frames (server/mod.rs:591-602)
+        for every frame of a parsed batch, behind parse_varlen, in front of frame_window.  infos rows[n] as the parse
+        left them, addrs rows[n] (ADDR_DTYPE), offsets int64[n] or None (read as all zero), slots rows[n_slots]
+        (ROUTE_SLOT_DTYPE: uflow_amd.route.new_route_table's, uploaded) with its seed and max_probe, conn_active
+        uint8[n_conns], timeout_in int64[n_conns].  Returns a dict of device tensors: route int32[n], cls uint8[n],
+        bucket_first int64[n_conns + 3] (its first n_conns + 1 entries are the stages' frame_first), order int32[n],
+        infos_out rows[n] and src_base_out int64[n] (the stages' infos and src_base), results rows[n_conns]
+        (ROUTE_RESULT_DTYPE), timeout_out (may be given as `timeout_in`), first_unknown_control int32[1]."""
+        n = infos.shape[0]
+        n_conns = conn_active.numel()
+        self._rec("infos", infos, FRAME_INFO_DTYPE, n)
+        self._rec("addrs", addrs, ADDR_DTYPE, n)
+        self._check("offsets", offsets, (torch.int64,), n)
+        n_slots = self._rec("slots", slots, ROUTE_SLOT_DTYPE)
+        self._check("conn_active", conn_active, (torch.uint8,), n_conns)
+        self._check("timeout_in", timeout_in, (torch.int64,), n_conns)
+        self._rec("infos_out", infos_out, FRAME_INFO_DTYPE, n)
+        self._check("src_base_out", src_base_out, (torch.int64,), n)
+        self._check("timeout_out", timeout_out, (torch.int64,), n_conns)
+        with self._outputs(stream) as z:
+            infos_out, src_base_out = z(infos_out, n, FRAME_INFO_DTYPE), z(src_base_out, n, torch.int64)
+            timeout_out = z(timeout_out, n_conns, torch.int64)
+            route, cls, order = z(None, n, torch.int32), z(None, n, torch.uint8), z(None, n, torch.int32)
+            bucket_first = z(None, n_conns + 3, torch.int64)
+            results = z(None, n_conns, ROUTE_RESULT_DTYPE)
+            fuc = z(None, 1, torch.int32)
+        check(lib().ufc_route_frames_varlen(
+            self._ctx, _pn(infos, n), _pn(addrs, n), _pn(offsets, n), n, _pn(slots, n_slots), n_slots,
+            int(seed) & 0xFFFFFFFF, int(max_probe) & 0xFFFFFFFF, n_conns, _pn(conn_active, n_conns),
+            int(now_ms) & (2**64 - 1), int(active_timeout_ms) & (2**64 - 1), _pn(timeout_in, n_conns), _pn(route, n),
+            _pn(cls, n), _ptr(bucket_first), _pn(order, n), _pn(infos_out, n), _pn(src_base_out, n),
+            _pn(results, n_conns), _pn(timeout_out, n_conns), _ptr(fuc), self._stream(stream)),
+            "ufc_route_frames_varlen")
+        return {"route": route, "cls": cls, "bucket_first": bucket_first, "order": order, "infos_out": infos_out,
+                "src_base_out": src_base_out, "results": results, "timeout_out": timeout_out,
+                "first_unknown_control": fuc}
 
     # ---- host buffers (frames received into host memory) ----
     def seal_host_varlen(self, data: np.ndarray, offsets: np.ndarray):

@@ -828,4 +828,82 @@ int ufc_flush_sync_host(const ufc_flush_ctl* ctl, const ufc_rate_result* rate, c
   return UFC_OK;
 }
 
+// ---- batched host frame routing ----
+int ufc_route_table_build_host(const ufc_addr* addrs, size_t n_conns, uint32_t seed, ufc_route_slot* slots,
+                               size_t n_slots, uint32_t* max_probe, uint64_t* dup_index) {
+  if (!slots || !max_probe || (!addrs && n_conns) || !ufc_codec::rt_table_ok(n_slots, n_conns))
+    return UFC_ERR_INVALID_ARG;
+  std::memset(slots, 0, n_slots * sizeof(ufc_route_slot));
+  const uint32_t mask = (uint32_t)(n_slots - 1);
+  uint32_t longest = 0;
+  for (size_t c = 0; c < n_conns; c++) {
+    const ufc_codec::RtKey k = ufc_codec::rt_key(addrs[c]);
+    const uint32_t home = ufc_codec::rt_hash(seed, k.w) & mask;
+    // n_slots > n_conns: an empty slot is met before the probe comes round, and an equal key before that slot.
+    uint32_t p = 0;
+    for (;; p++) {
+      ufc_route_slot& s = slots[(home + p) & mask];
+      if (!s.used) {
+        s.key = addrs[c];
+        s.conn = (uint32_t)c;
+        s.used = 1;
+        break;
+      }
+      if (ufc_codec::rt_key_eq(ufc_codec::rt_key(s.key).w, k.w)) {
+        if (dup_index) *dup_index = c;
+        return UFC_ERR_INVALID_ARG;
+      }
+    }
+    longest = std::max(longest, p);
+  }
+  *max_probe = longest;
+  return UFC_OK;
+}
+
+int ufc_route_frames_host(const ufc_frame_info* infos, const ufc_addr* addrs, const uint64_t* offsets, size_t n,
+                          const ufc_route_slot* slots, size_t n_slots, uint32_t seed, uint32_t max_probe,
+                          size_t n_conns, const uint8_t* conn_active, uint64_t now_ms, uint64_t active_timeout_ms,
+                          const uint64_t* timeout_in, uint32_t* route, uint8_t* cls, uint64_t* bucket_first,
+                          uint32_t* order, ufc_frame_info* infos_out, uint64_t* src_base_out,
+                          ufc_route_result* results, uint64_t* timeout_out, uint32_t* first_unknown_control,
+                          int nthreads) {
+  const ufc_codec::RtArgs a{infos, addrs, offsets, n, slots, n_slots, seed, max_probe, n_conns, conn_active, now_ms,
+                            active_timeout_ms, timeout_in, route, cls, bucket_first, order, infos_out, src_base_out,
+                            results, timeout_out, first_unknown_control};
+  if (!ufc_codec::rt_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  for (size_t c = 0; c < n_conns; c++) results[c] = ufc_route_result{0, UFC_NO_PARENT, 0, 0};
+  *first_unknown_control = UFC_NO_PARENT;
+  std::fill(bucket_first, bucket_first + n_conns + 3, (uint64_t)0);
+  // The lookups; then the first control frames, in arrival order (the device takes the same minima).
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) route[i] = ufc_codec::rt_lookup(slots, n_slots, seed, max_probe, n_conns, addrs[i]);
+  });
+  for (size_t i = 0; i < n; i++) {
+    if (ufc_codec::rt_kind_class(infos[i]) != 1) continue;
+    uint32_t& first = route[i] == UFC_NO_PARENT ? *first_unknown_control : results[route[i]].first_control;
+    if (first == UFC_NO_PARENT) first = (uint32_t)i;
+  }
+  // The classes; the buckets' counts and their exclusive sum; the stable placement with a cursor per bucket.
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) cls[i] = (uint8_t)ufc_codec::rt_classify(a, i, ufc_codec::rt_kind_class(infos[i]));
+  });
+  for (size_t i = 0; i < n; i++) {
+    bucket_first[ufc_codec::rt_bucket(a, i, cls[i]) + 1]++;
+    if (cls[i] == UFC_ROUTE_DEFERRED && route[i] != UFC_NO_PARENT) results[route[i]].deferred++;
+  }
+  counts_to_firsts(bucket_first, n_conns + 2);
+  {
+    std::vector<uint64_t> cursor(bucket_first, bucket_first + n_conns + 2);
+    for (size_t i = 0; i < n; i++) order[cursor[ufc_codec::rt_bucket(a, i, cls[i])]++] = (uint32_t)i;
+  }
+  for_ranges(n, nthreads, kRecordGrain, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; k++) {
+      std::memcpy(&infos_out[k], &infos[order[k]], sizeof(ufc_frame_info));
+      src_base_out[k] = ufc_codec::rt_src_base(a, order[k]);
+    }
+  });
+  for (size_t c = 0; c < n_conns; c++) ufc_codec::rt_finish_conn(a, c);
+  return UFC_OK;
+}
+
 }  // extern "C"

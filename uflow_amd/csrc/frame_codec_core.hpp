@@ -3636,4 +3636,119 @@ inline __host__ __device__ void fs_write_tile(const Wv& wv, const FsArgs& a, uin
   });
 }
 
+// ---- batched frame routing (ufc_route_table_build_host, ufc_route_frames_*) ----
+// The address lookup and dispatch of Server::handle_frames (server/mod.rs:591-602 over :492-589; client/mod.rs:
+// 557-583) for the frames of State::Active clients; the rules are in include/uflow_route.h.  What a lane does for a
+// frame is written here once: the hash (rt_hash), the bounded probe (rt_lookup), the frame's kind class
+// (rt_kind_class) and, once every first control frame is known, its class and bucket (rt_classify, rt_bucket).  The
+// grouping itself is a stable sort of the frames by bucket number, which has one answer: the host counts and places
+// in arrival order (frame_codec.cpp), the device runs a radix placement (route.hip).
+struct RtArgs {
+  const ufc_frame_info* infos;
+  const ufc_addr* addrs;
+  const uint64_t* offsets;
+  uint64_t n;
+  const ufc_route_slot* slots;
+  uint64_t n_slots;
+  uint32_t seed, max_probe;
+  uint64_t n_conns;
+  const uint8_t* conn_active;
+  uint64_t now_ms, active_timeout_ms;
+  const uint64_t* timeout_in;
+  uint32_t* route;
+  uint8_t* cls;
+  uint64_t* bucket_first;
+  uint32_t* order;
+  ufc_frame_info* infos_out;
+  uint64_t* src_base_out;
+  ufc_route_result* results;
+  uint64_t* timeout_out;
+  uint32_t* first_unknown_control;
+};
+constexpr uint64_t kRouteConnLim = kCountLim - 2;  // n_conns + 2 bucket numbers and UFC_NO_PARENT stay apart in 32 bits
+// n_slots: a power of two above n_conns, and no more than 2^31 (the probe index is 32-bit).
+inline bool rt_table_ok(uint64_t n_slots, uint64_t n_conns) {
+  return n_conns < kRouteConnLim && n_slots > n_conns && (n_slots & (n_slots - 1)) == 0 &&
+         n_slots <= ((uint64_t)1 << 31);
+}
+inline bool rt_args_ok(const RtArgs& a) {
+  const bool bad = !a.slots || !a.bucket_first || !a.first_unknown_control || !rt_table_ok(a.n_slots, a.n_conns) ||
+                   a.n >= kCountLim ||
+                   (a.n && (!a.infos || !a.addrs || !a.route || !a.cls || !a.order || !a.infos_out || !a.src_base_out ||
+                            a.infos_out == a.infos || a.src_base_out == a.offsets)) ||
+                   (a.n_conns && (!a.conn_active || !a.timeout_in || !a.results || !a.timeout_out));
+  return !bad;
+}
+
+// The key's eight little-endian words (the host and the GPU are little-endian; a key is 4-byte aligned).
+struct RtKey {
+  uint32_t w[8];
+};
+UFC_HD RtKey rt_key(const ufc_addr& a) {
+  RtKey k;
+  __builtin_memcpy(k.w, &a, 32);
+  return k;
+}
+UFC_HD uint32_t rt_hash(uint32_t seed, const uint32_t* w) {
+  uint32_t h = seed;
+  for (int k = 0; k < 8; k++) {
+    h = (h ^ w[k]) * 0x9E3779B1u;
+    h ^= h >> 15;
+  }
+  h *= 0x85EBCA77u;
+  h ^= h >> 13;
+  return h;
+}
+UFC_HD bool rt_key_eq(const uint32_t* a, const uint32_t* b) {
+  uint32_t d = 0;
+  for (int k = 0; k < 8; k++) d |= a[k] ^ b[k];
+  return d == 0;
+}
+// e(i): the connection of a key, or UFC_NO_PARENT.  At most min(max_probe, n_slots - 1) + 1 slots are read, all of
+// them inside the table.
+UFC_HD uint32_t rt_lookup(const ufc_route_slot* slots, uint64_t n_slots, uint32_t seed, uint32_t max_probe,
+                          uint64_t n_conns, const ufc_addr& key) {
+  const RtKey kw = rt_key(key);
+  const uint32_t mask = (uint32_t)(n_slots - 1);
+  const uint32_t home = rt_hash(seed, kw.w) & mask;
+  const uint32_t last = max_probe < mask ? max_probe : mask;
+  for (uint32_t p = 0;; p++) {
+    const ufc_route_slot& s = slots[(home + p) & mask];
+    if (!s.used) return UFC_NO_PARENT;
+    if (s.conn < n_conns && rt_key_eq(rt_key(s.key).w, kw.w)) return s.conn;
+    if (p == last) return UFC_NO_PARENT;
+  }
+}
+// 1: control (handshake and disconnect frames), 2: session (data, sync, ack), 0: Frame::read gave None.
+UFC_HD uint32_t rt_kind_class(const ufc_frame_info& f) {
+  if (!f.ok) return 0;
+  if (f.kind <= UFC_FRAME_DISCONNECT_ACK) return 1;
+  return (f.kind == UFC_FRAME_DATA || f.kind == UFC_FRAME_SYNC || f.kind == UFC_FRAME_ACK) ? 2 : 0;
+}
+// Frame i's class, once route[] and every first control frame (results[].first_control, *first_unknown_control)
+// are final.  k: rt_kind_class of the frame.
+UFC_HD uint32_t rt_classify(const RtArgs& a, uint64_t i, uint32_t k) {
+  if (k == 1) return UFC_ROUTE_CONTROL;
+  if (k == 0) return UFC_ROUTE_DROP;
+  const uint32_t c = a.route[i];
+  if (c == UFC_NO_PARENT) return i > *a.first_unknown_control ? UFC_ROUTE_DEFERRED : UFC_ROUTE_DROP;
+  if (i > a.results[c].first_control) return UFC_ROUTE_DEFERRED;  // (UFC_NO_PARENT is above every index)
+  return a.conn_active[c] ? UFC_ROUTE_CONN : UFC_ROUTE_DROP;
+}
+UFC_HD uint32_t rt_bucket(const RtArgs& a, uint64_t i, uint32_t cls) {
+  if (cls == UFC_ROUTE_CONN) return a.route[i];
+  return (uint32_t)a.n_conns + (cls == UFC_ROUTE_DROP ? 1u : 0u);
+}
+// Grouped position k takes frame order[k]'s record and source offset.
+UFC_HD uint64_t rt_src_base(const RtArgs& a, uint32_t i) { return a.offsets ? a.offsets[i] : 0; }
+// Connection c behind the placement: its bucket's length, and the timeout refresh of handle_data / handle_sync /
+// handle_ack (server/mod.rs:507, :529, :551).  timeout_out may be timeout_in: entry c is read before it is written.
+UFC_HD void rt_finish_conn(const RtArgs& a, uint64_t c) {
+  const uint32_t frames = (uint32_t)(a.bucket_first[c + 1] - a.bucket_first[c]);
+  a.results[c].frames = frames;
+  a.results[c].reserved = 0;
+  const uint64_t t = a.timeout_in[c];
+  a.timeout_out[c] = frames ? a.now_ms + a.active_timeout_ms : t;
+}
+
 }  // namespace ufc_codec

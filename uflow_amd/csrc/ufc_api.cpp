@@ -26,6 +26,7 @@
 #include "packet_emit.hpp"
 #include "packet_receive.hpp"
 #include "resend.hpp"
+#include "route.hpp"
 #include "send_rate.hpp"
 #include "ufc_internal.hpp"
 
@@ -84,7 +85,8 @@ enum ScratchKind {
   kScratchReceive = 9,
   kScratchWindow = 10,
   kScratchFlushAcks = 11,
-  kScratchFlushSync = 12
+  kScratchFlushSync = 12,
+  kScratchRoute = 13
 };
 
 // The (kind, stream) scratch buffer of at least `need` bytes.  Growing waits for the work already
@@ -1171,6 +1173,27 @@ int ufc_flush_sync_varlen(ufc_ctx* ctx, const ufc_flush_ctl* d_ctl, const ufc_ra
   DeviceGuard g(ctx->device);
   hipError_t e;
   if ((e = ufc_dev::flush_sync_batch(a, {ctx, kScratchFlushSync, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
+    return hip_fail(ctx, e);
+  return UFC_OK;
+}
+
+// ---- batched frame routing (route.hip) ----
+int ufc_route_frames_varlen(ufc_ctx* ctx, const ufc_frame_info* d_infos, const ufc_addr* d_addrs,
+                            const uint64_t* d_offsets, size_t n, const ufc_route_slot* d_slots, size_t n_slots,
+                            uint32_t seed, uint32_t max_probe, size_t n_conns, const uint8_t* d_conn_active,
+                            uint64_t now_ms, uint64_t active_timeout_ms, const uint64_t* d_timeout_in,
+                            uint32_t* d_route, uint8_t* d_cls, uint64_t* d_bucket_first, uint32_t* d_order,
+                            ufc_frame_info* d_infos_out, uint64_t* d_src_base_out, ufc_route_result* d_results,
+                            uint64_t* d_timeout_out, uint32_t* d_first_unknown_control, void* stream) {
+  if (!ctx) return UFC_ERR_INVALID_ARG;
+  // (n == 0 is not a return here: the call still writes the empty batch's outputs.)
+  const ufc_codec::RtArgs a{d_infos, d_addrs, d_offsets, n, d_slots, n_slots, seed, max_probe, n_conns, d_conn_active,
+                            now_ms, active_timeout_ms, d_timeout_in, d_route, d_cls, d_bucket_first, d_order,
+                            d_infos_out, d_src_base_out, d_results, d_timeout_out, d_first_unknown_control};
+  if (!ufc_codec::rt_args_ok(a)) return UFC_ERR_INVALID_ARG;
+  DeviceGuard g(ctx->device);
+  hipError_t e;
+  if ((e = ufc_dev::route_frames_batch(a, {ctx, kScratchRoute, (hipStream_t)stream}, (hipStream_t)stream)) != hipSuccess)
     return hip_fail(ctx, e);
   return UFC_OK;
 }

@@ -1,4 +1,5 @@
-"""The record layouts of include/uflow_frame_codec.h and include/uflow_flush_ctl.h, declared once for Python.
+"""The record layouts of include/uflow_frame_codec.h, include/uflow_flush_ctl.h and include/uflow_route.h, declared
+once for Python.
 
 Every batched call takes and returns arrays of these records: numpy structured arrays on the host
 (uflow_amd.frame), uint8[n, itemsize] rows on the device (uflow_amd.batch.rows / records).  FOO_BAR_DTYPE is the C
@@ -123,3 +124,12 @@ FLUSH_SYNC_RESULT_DTYPE = np.dtype([("sent", "<u4"), ("reason", "<u4"), ("heap_l
                                     ("reserved2", "<u4")])
 FLUSH_RECORDS = {"ufc_flush_ctl": FLUSH_CTL_DTYPE, "ufc_flush_acks_result": FLUSH_ACKS_RESULT_DTYPE,
                  "ufc_flush_sync_result": FLUSH_SYNC_RESULT_DTYPE}
+
+# include/uflow_route.h, the header of the batched frame routing, has a table of its own as well
+# (tests/test_route_cpu.py holds it to that header).
+# ufc_addr / ufc_route_slot / ufc_route_result (batched frame routing)
+ADDR_DTYPE = np.dtype([("ip", "u1", (16,)), ("port", "<u2"), ("family", "u1"), ("reserved", "u1"), ("flowinfo", "<u4"),
+                       ("scope_id", "<u4"), ("reserved2", "<u4")])
+ROUTE_SLOT_DTYPE = np.dtype([("key", ADDR_DTYPE), ("conn", "<u4"), ("used", "u1"), ("reserved", "u1", (11,))])
+ROUTE_RESULT_DTYPE = np.dtype([("frames", "<u4"), ("first_control", "<u4"), ("deferred", "<u4"), ("reserved", "<u4")])
+ROUTE_RECORDS = {"ufc_addr": ADDR_DTYPE, "ufc_route_slot": ROUTE_SLOT_DTYPE, "ufc_route_result": ROUTE_RESULT_DTYPE}
